@@ -12,6 +12,13 @@ master weights, synthetic N(0,1) cutouts clipped at -3 (seed 1234), reference in
 One "step" = noise draw + forward + backward + (gradient all-reduce) + fused AdamW + cosine LR on
 one resident minibatch.  Secondary: cosine top-k queries/sec over a 1M x 768 fp32 bank
 (``search`` object).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).
+Everything else -- the GEMM-skip leg and the roofline, HBM phases, feeder, longer run, N > 1 schedule pricing, batch
+sweep, operand-format and placement A/Bs, fp32 mode, mim_19, search, CPU baselines and parity against the oracle --
+runs with --full.  --dump-outputs DIR writes what the last timed step computed (loss, reconstruction, mask and a seeded
+sample of the updated master weights) as DIR/<name>.npy; the inputs are seeded, so runs of two builds compare output
+for output.
 """
 import argparse
 import json
@@ -46,7 +53,12 @@ def parse():
     ap.add_argument("--skip-f32", action="store_true", help="skip the timing of the fp32 parity mode (extra.f32_mode)")
     ap.add_argument("--skip-mim19", action="store_true", help="skip the BASELINE configs[4] leg (SimMIM ViT-L/16, 5x128x128)")
     ap.add_argument("--skip-leg", action="store_true", help=argparse.SUPPRESS)   # internal: the GEMM-skip measurement (run_skip_leg)
-    ap.add_argument("--probe", action="store_true", help="also time every GEMM shape of the step alone (HIP-graph probe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (roofline, phases, A/Bs, mim_19, search, CPU baselines, "
+                         "parity); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--probe", action="store_true", help="with --full: also time every GEMM shape of the step alone (HIP-graph probe)")
     ap.add_argument("--bank-rows", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=10_000)
     ap.add_argument("--topk", type=int, default=100)
@@ -261,6 +273,8 @@ def bench_pretrain(args, rank, world, dev):
     for i in range(args.warmup):
         step(pool[i % 2])
     dt, gpu_ms, loss = timed(step, args.steps)
+    # (taken before anything else runs on the engine: its workspace and weights are those of the last timed step)
+    outputs = step_outputs(eng, step) if rank == 0 and args.dump_outputs else None
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -268,7 +282,7 @@ def bench_pretrain(args, rank, world, dev):
     executed, algorithmic = eng.flops_per_image(0.75)
     out = dict(fused_adamw=step.fused_adamw, adamw_side=getattr(step, "adamw_side", None), ms_per_step=1e3 * dt / args.steps, images_per_sec=world * B * args.steps / dt, gpu_ms_per_step=gpu_ms,
                loss=float(loss), flops_per_image_executed=executed, flops_per_image_reference=algorithmic, B=B)
-    if rank == 0:
+    if rank == 0 and args.full:
         # In-step time of the dominant kernel family: the same step with the MFMA GEMM launches left out (the C ABI's
         # measurement switch), HIP events over the same number of steps; the difference is what the GEMM launches take
         # INSIDE the step (cold weights, launch gaps and all) -- the figure rocprofv3's kernel_stats must agree with.
@@ -304,7 +318,33 @@ def bench_pretrain(args, rank, world, dev):
                                                                 "tiles_per_xcd=SKYEMB_GROUP_XCD_ORDER=1"] + os.environ.get("SKYEMB_BENCH_EXTRA_VARIANTS", "").split())
         if world == 1 and not args.skip_feeder:
             out["feeder"] = bench_feeder(args, dev, step, B)
-    return out, eng
+    return out, eng, outputs
+
+
+def step_outputs(eng, step):
+    """What a caller of the timed step receives from its last call, as float32 host arrays: the loss, the reconstruction
+    [B, L, patch_dim] and the mask [B, L] of that step's batch, and the fp32 master weights the step updated.  An array above
+    its cap (reconstruction 8 M elements, mask 1 M; the weights -- 112 M at ViT-B -- always) is replaced by a fixed, seeded
+    sample of its flattened elements in position order, so at most 40 MB are written whatever the batch."""
+    import numpy as np
+
+    def sample(t, cap, seed):
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        return t.float().cpu().numpy()
+
+    torch.cuda.synchronize()
+    return {"loss": sample(step.loss, 1, 0).reshape(-1), "pred": sample(step.pred, 8 << 20, 1),
+            "mask": sample(step.mask, 1 << 20, 2), "params_sample": sample(eng.store.p, 1 << 20, 3)}
+
+
+def write_outputs(out_dir, outputs):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def operand_format_ab(cfg, timed, B, pool, dev, step_timed, rounds=3, n=30):
@@ -865,32 +905,18 @@ def main():
             torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local))
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    pre, eng = bench_pretrain(args, rank, world, dev)
+    pre, eng, outputs = bench_pretrain(args, rank, world, dev)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     del eng
     torch.cuda.empty_cache()
     search = search_inputs = None
-    if not args.skip_search:
+    if args.full and not args.skip_search:
         search, search_inputs = bench_search(args, rank, world, dev)
     mim19 = None
-    if rank == 0 and world == 1 and not args.skip_mim19:
+    if args.full and rank == 0 and world == 1 and not args.skip_mim19:
         mim19 = bench_mim19(args, dev)
     if rank == 0:
-        executed = pre["flops_per_image_executed"]
-        ach = pre["images_per_sec"] / world * executed / 1e12   # per-GPU TFLOP/s, executed FLOPs
-        peak = PEAK_BF16_TFLOPS if args.dtype in ("bf16", "f16") else PEAK_F32_MFMA_TFLOPS
-        gi = pre["gemm_in_step"]
-        kernel = dict(kernel="gemm_pipe_kernel<BM,BN,A_KC,B_KC,NSTAGE,WM,WN,WK> (forward KC.KC, data gradient KC.RC; WK = 2 k-groups of waves "
-                             "on the <= 256-tile launches) + gemm_pipe_group_kernel<128,128,2,4,2,4> (encoder) / <128,64,3,4,2,4> (decoder): the "
-                             "four weight gradients of a block per launch (+ splitk_reduce_kernel)", **gi)
-        if "gemm_probe" in pre:
-            kernel["isolated_probe"] = pre["gemm_probe"]
-        if pre.get("fused_adamw") and "staged" in pre and "monolithic_separate_adamw" in pre["staged"]:
-            sep = pre["staged"]["monolithic_separate_adamw"]
-            if "gemm_ms_per_step" in sep:
-                kernel["with_separate_adamw_launch"] = dict(ms_per_step=sep["gemm_ms_per_step"], tflops=gi["flop_per_step"] / sep["gemm_ms_per_step"] / 1e9,
-                                                            frac=gi["flop_per_step"] / sep["gemm_ms_per_step"] / 1e9 / peak,
-                                                            note="the same GEMM family in the step that keeps AdamW as its own launch "
-                                                                 "(no optimiser traffic in the weight-gradient epilogues)")
         line = {
             "metric": "MAE pretrain images/sec (5x64x64, ViT-B)", "value": pre["images_per_sec"], "unit": "images/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": pre["ms_per_step"],
@@ -912,82 +938,108 @@ def main():
                        "adamw_placement": (f"policy {pre.get('adamw_side')}: epilogue of each block's own grouped weight-gradient launch at this size "
                                            "(side jobs of the next block's launch where launches leave compute units idle: ViT-L, extra.mim_19)"
                                            if pre.get("fused_adamw") else "separate launch")},
-            "roofline": {"bound": "mfma", "achieved": gi["tflops"], "peak": peak, "unit": "TFLOP/s", "frac": gi["tflops"] / peak,
-                         # the same family with AdamW as its own launch (no optimiser bytes in the weight-gradient epilogues): the figure
-                         # comparable with rounds 1-2, whose `frac` had no optimiser traffic in it
-                         "frac_gemm_only": kernel.get("with_separate_adamw_launch", {}).get("frac"),
-                         "traffic": gemm_pmc_traffic(),
-                         **traffic_ratio(),
-                         "note": "(one process: the AdamW step of the transformer blocks' weights runs INSIDE the grouped weight-gradient "
-                                 "launches, so the family's in-step time includes that HBM traffic -- 26 B per parameter; "
-                                 "extra.staged.monolithic_separate_adamw is the step with the separate optimiser launch) "
-                                 "dominant kernel family = the pipelined MFMA GEMM launches: algorithmic 2MNK FLOPs of every GEMM "
-                                 "launch of one step / their IN-STEP time = HIP-event time of the timed steps minus the same "
-                                 "steps replayed with the GEMM launches left out (kernel.step_without_gemm_ms); agrees with the "
-                                 "sum of the gemm_pipe_* rows of the rocprofv3 kernel_stats in profiles/.  step = whole-step rate "
-                                 "(executed fwd+bwd FLOPs x images / step time, all kernels + optimiser)",
-                         "kernel": kernel,
-                         "step": {"achieved": ach, "frac": ach / peak, "gpu_ms_per_step": pre["gpu_ms_per_step"],
-                                  "flops_per_image_executed": executed,
-                                  "flops_per_image_reference": pre["flops_per_image_reference"]}},
             "loss": pre["loss"],
-            "phases": pre.get("phases"),
-            "feeder": pre.get("feeder"),
         }
-        line["extra"] = {}
-        if mim19 is not None:
-            line["extra"]["mim_19"] = mim19
-        for key in ("long_run", "staged", "batch_sweep", "optimizer_placement", "operand_format_ab"):
-            if key in pre:
-                line["extra"][key] = pre[key]
-        if world == 1 and args.dtype in ("bf16", "f16") and not args.skip_f32:
-            line["extra"]["f32_mode"] = f32_mode_timing(dev, rank, pre["B"])
-        if search is not None:
-            ql, qs = search["q_large"], search["q_small"]
-            line["search"] = {
-                "metric": f"cosine top-k queries/sec over {args.bank_rows}x768", "value": ql["queries_per_sec"],
-                "unit": "queries/sec", "k": args.topk, "Q": ql["Q"], "dtype": "f32", "sharding": f"bank rows / {world}",
-                "q_large": ql, "q_small": qs, "q1": search["q1"],
-                "roofline": {"bound": "hbm", "achieved": qs["kernel_hbm_gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                             "frac": qs["kernel_hbm_gbs"] / PEAK_HBM_GBS, "traffic": pmc_traffic(args),
-                             "algorithmic_bytes": qs["kernel_bytes"],
-                             # the whole search as the caller sees it: query preparation, sample floor, bank pass, merge
-                             "frac_end_to_end": qs["kernel_bytes"] / qs["sec"] / 1e9 / PEAK_HBM_GBS,
-                             "frac_end_to_end_q1": search["q1"]["kernel_bytes"] / search["q1"]["sec"] / 1e9 / PEAK_HBM_GBS,
-                             "note": "Q=16 bank-streaming launch (HBM-bound regime): (bank shard + queries + partial "
-                                     "lists) bytes / kernel time; the Q=10k path: roofline_q_large"},
-                # BASELINE's own search config (10 000 queries: compute-bound): 2 Q N D algorithmic FLOPs over the END-TO-END time
-                # of the search (fp16 image of the queries, matrix pass, candidate selection, exact re-score), against the dense
-                # fp16 MFMA peak the first stage runs on
-                "roofline_q_large": {"bound": "mfma_f16", "achieved": ql["effective_tflops"], "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                                     "frac": ql["effective_tflops"] / PEAK_BF16_TFLOPS,
-                                     "note": "two-stage exact search (csrc/topk_prefilter.hip); the exact single-stage fp32 kernel on the "
-                                             "same inputs: q_large.kernel_tflops of the 157 TFLOP/s fp32-MFMA peak",
-                                     **search_pmc_record()},
-            }
-        if world == 1 and not args.skip_cpu:
-            cpre, csea = cpu_baselines(args, search_inputs)
-            line["parity"] = cpre.pop("parity")
-            line["parity"]["timed_mode"] = args.dtype
-            line["parity"]["note"] = ("north_star: loss and reconstructed pixels within 1e-3 relative of the fp32 reference.  f16 (IEEE half operands, "
-                                      "the default timed mode): inside it (pred_rel_l2 ~7e-4, loss ~1e-5; tests/test_f16_gpu.py holds B = 256 to 1e-3); "
-                                      "bf16 (BASELINE's named dtype, same kernels and rate): 6e-3 on the pixels -- the rounding of 8-bit "
-                                      "significands, measured operand class by operand class in profiles/r06_operand_rounding.json; f32 (exact "
-                                      "fp32 MFMA chains): ~1e-6")
-            pt = line["parity"].get("f16")
-            if pt is not None and "operand_format_ab" in line["extra"]:
-                ab = line["extra"]["operand_format_ab"]
-                line["extra"]["tol_mode"] = dict(dtype="f16", ms_per_step=ab["mean_ms"]["f16"], images_per_sec=ab["images_per_sec"]["f16"],
-                                                 pred_rel_l2=pt["pred_rel_l2"], loss_rel=pt["loss_rel"], grad_rel_l2_max=pt["grad_rel_l2_max"],
-                                                 is_headline=args.dtype == "f16",
-                                                 note="the 16-bit mode that meets the reference tolerance (1e-3 on loss and pixels)")
-            line["cpu_baseline"] = cpre
-            if search is not None and csea is not None:
-                line["search"]["cpu_baseline"] = csea
+        if args.full:
+            line.update(full_report(args, pre, world, rank, dev, search, search_inputs, mim19))
         print(json.dumps(line))
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def full_report(args, pre, world, rank, dev, search, search_inputs, mim19):
+    """The --full part of the result line: roofline of the GEMM family and of the step, phases, feeder, extra, search,
+    parity and CPU baselines."""
+    executed = pre["flops_per_image_executed"]
+    ach = pre["images_per_sec"] / world * executed / 1e12   # per-GPU TFLOP/s, executed FLOPs
+    peak = PEAK_BF16_TFLOPS if args.dtype in ("bf16", "f16") else PEAK_F32_MFMA_TFLOPS
+    gi = pre["gemm_in_step"]
+    kernel = dict(kernel="gemm_pipe_kernel<BM,BN,A_KC,B_KC,NSTAGE,WM,WN,WK> (forward KC.KC, data gradient KC.RC; WK = 2 k-groups of waves "
+                         "on the <= 256-tile launches) + gemm_pipe_group_kernel<128,128,2,4,2,4> (encoder) / <128,64,3,4,2,4> (decoder): the "
+                         "four weight gradients of a block per launch (+ splitk_reduce_kernel)", **gi)
+    if "gemm_probe" in pre:
+        kernel["isolated_probe"] = pre["gemm_probe"]
+    if pre.get("fused_adamw") and "staged" in pre and "monolithic_separate_adamw" in pre["staged"]:
+        sep = pre["staged"]["monolithic_separate_adamw"]
+        if "gemm_ms_per_step" in sep:
+            kernel["with_separate_adamw_launch"] = dict(ms_per_step=sep["gemm_ms_per_step"], tflops=gi["flop_per_step"] / sep["gemm_ms_per_step"] / 1e9,
+                                                        frac=gi["flop_per_step"] / sep["gemm_ms_per_step"] / 1e9 / peak,
+                                                        note="the same GEMM family in the step that keeps AdamW as its own launch "
+                                                             "(no optimiser traffic in the weight-gradient epilogues)")
+    line = {
+        "roofline": {"bound": "mfma", "achieved": gi["tflops"], "peak": peak, "unit": "TFLOP/s", "frac": gi["tflops"] / peak,
+                     # the same family with AdamW as its own launch (no optimiser bytes in the weight-gradient epilogues): the figure
+                     # comparable with rounds 1-2, whose `frac` had no optimiser traffic in it
+                     "frac_gemm_only": kernel.get("with_separate_adamw_launch", {}).get("frac"),
+                     "traffic": gemm_pmc_traffic(),
+                     **traffic_ratio(),
+                     "note": "(one process: the AdamW step of the transformer blocks' weights runs INSIDE the grouped weight-gradient "
+                             "launches, so the family's in-step time includes that HBM traffic -- 26 B per parameter; "
+                             "extra.staged.monolithic_separate_adamw is the step with the separate optimiser launch) "
+                             "dominant kernel family = the pipelined MFMA GEMM launches: algorithmic 2MNK FLOPs of every GEMM "
+                             "launch of one step / their IN-STEP time = HIP-event time of the timed steps minus the same "
+                             "steps replayed with the GEMM launches left out (kernel.step_without_gemm_ms); agrees with the "
+                             "sum of the gemm_pipe_* rows of the rocprofv3 kernel_stats in profiles/.  step = whole-step rate "
+                             "(executed fwd+bwd FLOPs x images / step time, all kernels + optimiser)",
+                     "kernel": kernel,
+                     "step": {"achieved": ach, "frac": ach / peak, "gpu_ms_per_step": pre["gpu_ms_per_step"],
+                              "flops_per_image_executed": executed,
+                              "flops_per_image_reference": pre["flops_per_image_reference"]}},
+        "phases": pre.get("phases"),
+        "feeder": pre.get("feeder"),
+    }
+    line["extra"] = {}
+    if mim19 is not None:
+        line["extra"]["mim_19"] = mim19
+    for key in ("long_run", "staged", "batch_sweep", "optimizer_placement", "operand_format_ab"):
+        if key in pre:
+            line["extra"][key] = pre[key]
+    if world == 1 and args.dtype in ("bf16", "f16") and not args.skip_f32:
+        line["extra"]["f32_mode"] = f32_mode_timing(dev, rank, pre["B"])
+    if search is not None:
+        ql, qs = search["q_large"], search["q_small"]
+        line["search"] = {
+            "metric": f"cosine top-k queries/sec over {args.bank_rows}x768", "value": ql["queries_per_sec"],
+            "unit": "queries/sec", "k": args.topk, "Q": ql["Q"], "dtype": "f32", "sharding": f"bank rows / {world}",
+            "q_large": ql, "q_small": qs, "q1": search["q1"],
+            "roofline": {"bound": "hbm", "achieved": qs["kernel_hbm_gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                         "frac": qs["kernel_hbm_gbs"] / PEAK_HBM_GBS, "traffic": pmc_traffic(args),
+                         "algorithmic_bytes": qs["kernel_bytes"],
+                         # the whole search as the caller sees it: query preparation, sample floor, bank pass, merge
+                         "frac_end_to_end": qs["kernel_bytes"] / qs["sec"] / 1e9 / PEAK_HBM_GBS,
+                         "frac_end_to_end_q1": search["q1"]["kernel_bytes"] / search["q1"]["sec"] / 1e9 / PEAK_HBM_GBS,
+                         "note": "Q=16 bank-streaming launch (HBM-bound regime): (bank shard + queries + partial "
+                                 "lists) bytes / kernel time; the Q=10k path: roofline_q_large"},
+            # BASELINE's own search config (10 000 queries: compute-bound): 2 Q N D algorithmic FLOPs over the END-TO-END time
+            # of the search (fp16 image of the queries, matrix pass, candidate selection, exact re-score), against the dense
+            # fp16 MFMA peak the first stage runs on
+            "roofline_q_large": {"bound": "mfma_f16", "achieved": ql["effective_tflops"], "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                                 "frac": ql["effective_tflops"] / PEAK_BF16_TFLOPS,
+                                 "note": "two-stage exact search (csrc/topk_prefilter.hip); the exact single-stage fp32 kernel on the "
+                                         "same inputs: q_large.kernel_tflops of the 157 TFLOP/s fp32-MFMA peak",
+                                 **search_pmc_record()},
+        }
+    if world == 1 and not args.skip_cpu:
+        cpre, csea = cpu_baselines(args, search_inputs)
+        line["parity"] = cpre.pop("parity")
+        line["parity"]["timed_mode"] = args.dtype
+        line["parity"]["note"] = ("north_star: loss and reconstructed pixels within 1e-3 relative of the fp32 reference.  f16 (IEEE half operands, "
+                                  "the default timed mode): inside it (pred_rel_l2 ~7e-4, loss ~1e-5; tests/test_f16_gpu.py holds B = 256 to 1e-3); "
+                                  "bf16 (BASELINE's named dtype, same kernels and rate): 6e-3 on the pixels -- the rounding of 8-bit "
+                                  "significands, measured operand class by operand class in profiles/r06_operand_rounding.json; f32 (exact "
+                                  "fp32 MFMA chains): ~1e-6")
+        pt = line["parity"].get("f16")
+        if pt is not None and "operand_format_ab" in line["extra"]:
+            ab = line["extra"]["operand_format_ab"]
+            line["extra"]["tol_mode"] = dict(dtype="f16", ms_per_step=ab["mean_ms"]["f16"], images_per_sec=ab["images_per_sec"]["f16"],
+                                             pred_rel_l2=pt["pred_rel_l2"], loss_rel=pt["loss_rel"], grad_rel_l2_max=pt["grad_rel_l2_max"],
+                                             is_headline=args.dtype == "f16",
+                                             note="the 16-bit mode that meets the reference tolerance (1e-3 on loss and pixels)")
+        line["cpu_baseline"] = cpre
+        if search is not None and csea is not None:
+            line["search"]["cpu_baseline"] = csea
+    return line
 
 
 def _pmc_load(names):

@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("SKYEMB_GOLDEN_OUT") or HERE      # the reproducibility test regenerates into a temporary directory
+OUT = os.environ.get("SKYEMB_GOLDEN_OUT") or HERE      # a scratch directory: regenerate there and compare with the committed fixtures
 
 
 # --------------------------------------------------------------------------

@@ -201,7 +201,8 @@ def test_tile_compressed_nulls_and_refusals(tmp_path):
             fits_lite.read_image_hdu(p, hdu=1)
 
 
-def test_committed_h5py_files_read_bit_exactly(tmp_path):
+def test_committed_h5py_files_read_bit_exactly(tmp_path, monkeypatch):
+    monkeypatch.setenv("SKYEMB_H5_CACHE", str(tmp_path))    # the contiguous copy of the chunked file, not beside the fixture
     exp = np.load(os.path.join(IO, "io_expected.npz"))
     assert "h5py 3.3.0" in list(exp["versions"])
     check_h5(IO, exp, tmp_path)

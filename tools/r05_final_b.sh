@@ -14,7 +14,7 @@ rm -f gpurun_out/r05x_search/pmc_*.csv gpurun_out/r05x_mim19/pmc_*.csv
 timeout -k 10 200 bash tools/r05_search_pmc.sh > $O/pmc_q16.txt 2>&1; echo "pmc q16 rc=$?"
 cp gpurun_out/r05spmc/r05_topk_stream_pmc.json $O/ 2>/dev/null
 rm -f gpurun_out/r05spmc/pmc_*.csv
-bash tools/prof_cmd.sh r05f/bench bench.py --skip-cpu > $O/bench_prof.txt 2>&1; echo "bench prof rc=$?"
+bash tools/prof_cmd.sh r05f/bench bench.py --full --skip-cpu > $O/bench_prof.txt 2>&1; echo "bench prof rc=$?"
 rm -rf $O/bench/prof
-python3 bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 300 $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 300 $O/bench.err
 du -sh gpurun_out | tail -1
