@@ -264,9 +264,13 @@ int skyemb_layernorm_bwd(const void *dy, int dy_is_f32, int dtype, const float *
                          float *part, float *dgamma, float *dbeta, int M, int D, void *stream);
 
 /* -------------------------------------------------------- attention -------
- * timm Attention core / F.scaled_dot_product_attention on tiny sequences (N = 5, 17, 65, 66):
+ * timm Attention core / F.scaled_dot_product_attention, no mask, 1 <= N <= SKYEMB_MHA_MAX_N tokens
+ * (the front end's 4096 patches + cls + RA/Dec), any head dim hd % 8 == 0 (hd <= 512 once a head outgrows LDS):
  * qkv dtype [B, N, 3, H, hd] -> out dtype [B, N, H*hd];  softmax(q k^T hd^-0.5) v in fp32.
- * Backward recomputes the probabilities from q, k. */
+ * bf16 / fp16 at hd 32 / 64 run on MFMA (N > 128: K/V streamed through LDS, online softmax); other shapes run fp32
+ * kernels.  Backward recomputes the probabilities from q, k; it needs no workspace and is deterministic.
+ * N > SKYEMB_MHA_MAX_N returns 1 before anything is launched. */
+#define SKYEMB_MHA_MAX_N 4098
 int skyemb_mha_fwd(const void *qkv, void *out, int dtype, int B, int N, int H, int hd, void *stream);
 int skyemb_mha_bwd(const void *qkv, const void *dout, void *dqkv, int dtype, int B, int N, int H, int hd,
                    void *stream);
@@ -452,6 +456,12 @@ int skyemb_attnpool_q(const float *latent, const float *Wq, const float *bq, flo
 int skyemb_attnpool_fwd(const float *q, const void *kv, int dtype, void *out, float *prob, int B, int N, int H, int hd, void *stream);
 int skyemb_attnpool_bwd(const float *q, const void *kv, int dtype, const void *dout, const float *prob, void *dkv, float *dq_part,
                         int B, int N, int H, int hd, void *stream);
+/* the same two calls for 1 <= N <= SKYEMB_MHA_MAX_N tokens (the plain ones take N <= 256): past 256 the token loop runs in chunks,
+ * the softmax statistics passing through prob */
+int skyemb_attnpool_fwd_long(const float *q, const void *kv, int dtype, void *out, float *prob, int B, int N, int H, int hd,
+                             void *stream);
+int skyemb_attnpool_bwd_long(const float *q, const void *kv, int dtype, const void *dout, const float *prob, void *dkv,
+                             float *dq_part, int B, int N, int H, int hd, void *stream);
 int skyemb_attnpool_q_bwd(const float *dq_part, int B, const float *latent, const float *Wq, float *dWq, float *dbq, float *dlatent,
                           float *ws, int D, void *stream);
 /* plain score matrix for the reference-shaped path with P>1 patches per sample

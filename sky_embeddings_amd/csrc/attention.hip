@@ -141,6 +141,204 @@ __global__ void mha_bwd_kernel(const T *__restrict__ qkv, const T *__restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Streaming fallback for the shapes whose whole head does not fit the LDS plan below (long sequences in the fp32 parity
+// mode, head dims other than the MFMA kernels' 32 / 64 -- the 512-wide single decoder head of maesimple): fp32 arithmetic
+// for every dtype, any N <= SKYEMB_MHA_MAX_N, any hd % 8 == 0 up to SH_MAXHD.  Built for correctness, not speed.
+//   forward : one wave per query row; keys in chunks of 64 (lane j scores key j), online softmax with the running max and
+//             sum in fp32, the output row rescaled when the max grows.
+//   backward: one workgroup per (sample, head), the three phases of the long MFMA kernel (attention_mfma.hip):
+//             A+C) per query row: a walk over the keys for lse_i and D_i = rowsum(P dP), then a second walk for dQ;
+//             B)   per key row: a walk over the queries for dK and dV, the statistics of every query out of LDS.
+//             Fixed summation order: deterministic.  LDS: 2 N floats of statistics + two [hd] rows and two [64] chunks
+//             per wave (49 KB at N = 4098, hd = 512).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int SH_MAXHD = 512, SH_C = SH_MAXHD / 64;
+
+template <typename T>
+__device__ __forceinline__ float dot_row(const float *lds_row, const T *g_row, int hd) {
+    float a0 = 0.f, a1 = 0.f;
+    for (int d = 0; d < hd; d += 8) {
+        a0 = dot4(*(const float4 *)&lds_row[d], load4<T>(g_row + d), a0);
+        a1 = dot4(*(const float4 *)&lds_row[d + 4], load4<T>(g_row + d + 4), a1);
+    }
+    return a0 + a1;
+}
+template <typename T>
+__device__ __forceinline__ void load_row(float *dst, const T *src, int hd, float scale, int lane) {
+    for (int d = 4 * lane; d < hd; d += 256) {
+        const float4 x = load4<T>(src + d);
+        *(float4 *)&dst[d] = make_float4(x.x * scale, x.y * scale, x.z * scale, x.w * scale);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mha_fwd_stream_kernel(const T *__restrict__ qkv, T *__restrict__ out, int B, int N,
+                                                             int H, int hd) {
+    __shared__ __attribute__((aligned(16))) float sq[4][SH_MAXHD];
+    __shared__ float sp[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.y * 4 + wave;
+    if (i >= N) return;
+    const int b = blockIdx.x / H, h = blockIdx.x - b * H, D = H * hd;
+    const int64_t rs = 3 * (int64_t)D;
+    const T *qb = qkv + (int64_t)b * N * rs + h * hd, *kb = qb + D, *vb = qb + 2 * D;
+    load_row<T>(sq[wave], qb + (int64_t)i * rs, hd, rsqrtf((float)hd), lane);
+    __builtin_amdgcn_wave_barrier();
+    float o[SH_C];
+#pragma unroll
+    for (int c = 0; c < SH_C; ++c) o[c] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    for (int j0 = 0; j0 < N; j0 += 64) {
+        const int j = j0 + lane;
+        const float s = j < N ? dot_row<T>(sq[wave], kb + (int64_t)j * rs, hd) : -INFINITY;
+        const float mn = fmaxf(m, wave_max(s)), alpha = __expf(m - mn);
+        const float p = j < N ? __expf(s - mn) : 0.f;
+        l = l * alpha + wave_sum(p);
+        m = mn;
+        sp[wave][lane] = p;
+        __builtin_amdgcn_wave_barrier();
+        const int nj = N - j0 < 64 ? N - j0 : 64;
+#pragma unroll
+        for (int c = 0; c < SH_C; ++c) o[c] *= alpha;
+        for (int jj = 0; jj < nj; ++jj) {
+            const float pj = sp[wave][jj];
+            const T *vr = vb + (int64_t)(j0 + jj) * rs;
+#pragma unroll
+            for (int c = 0; c < SH_C; ++c)
+                if (lane + 64 * c < hd) o[c] = fmaf(pj, to_f32<T>(vr[lane + 64 * c]), o[c]);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    const float inv = 1.0f / l;
+    T *orow = out + ((int64_t)b * N + i) * D + h * hd;
+#pragma unroll
+    for (int c = 0; c < SH_C; ++c)
+        if (lane + 64 * c < hd) orow[lane + 64 * c] = from_f32<T>(o[c] * inv);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mha_bwd_stream_kernel(const T *__restrict__ qkv, const T *__restrict__ dout,
+                                                             T *__restrict__ dqkv, int B, int N, int H, int hd) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *ra = lds + (size_t)threadIdx.x / 64 * 2 * SH_MAXHD, *rb = ra + SH_MAXHD;          // this wave's two rows
+    float *sa = lds + 8 * SH_MAXHD + (size_t)threadIdx.x / 64 * 128, *sb = sa + 64;           // this wave's two chunks
+    float *lse = lds + 8 * SH_MAXHD + 4 * 128, *dsum = lse + N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x / H, h = blockIdx.x - b * H, D = H * hd;
+    const int64_t rs = 3 * (int64_t)D;
+    const float scale = rsqrtf((float)hd);
+    const T *qb = qkv + (int64_t)b * N * rs + h * hd, *kb = qb + D, *vb = qb + 2 * D;
+    const T *ob = dout + (int64_t)b * N * D + h * hd;
+    T *dqb = dqkv + (int64_t)b * N * rs + h * hd;
+
+    // ---- phases A and C: one query row per wave
+    for (int i = wave; i < N; i += 4) {
+        load_row<T>(ra, qb + (int64_t)i * rs, hd, scale, lane);
+        load_row<T>(rb, ob + (int64_t)i * D, hd, 1.0f, lane);
+        __builtin_amdgcn_wave_barrier();
+        float m = -INFINITY, l = 0.f, dacc = 0.f;
+        for (int j0 = 0; j0 < N; j0 += 64) {
+            const int j = j0 + lane;
+            const float s = j < N ? dot_row<T>(ra, kb + (int64_t)j * rs, hd) : -INFINITY;
+            const float dp = j < N ? dot_row<T>(rb, vb + (int64_t)j * rs, hd) : 0.f;
+            const float mn = fmaxf(m, wave_max(s)), alpha = __expf(m - mn);
+            const float p = j < N ? __expf(s - mn) : 0.f;
+            l = l * alpha + wave_sum(p);
+            dacc = dacc * alpha + wave_sum(p * dp);
+            m = mn;
+        }
+        const float lse_i = m + logf(l), d_i = dacc / l;
+        if (lane == 0) {
+            lse[i] = lse_i;
+            dsum[i] = d_i;
+        }
+        float a[SH_C];
+#pragma unroll
+        for (int c = 0; c < SH_C; ++c) a[c] = 0.f;
+        for (int j0 = 0; j0 < N; j0 += 64) {
+            const int j = j0 + lane;
+            float ds = 0.f;
+            if (j < N) {
+                const float s = dot_row<T>(ra, kb + (int64_t)j * rs, hd), dp = dot_row<T>(rb, vb + (int64_t)j * rs, hd);
+                ds = __expf(s - lse_i) * (dp - d_i);
+            }
+            sa[lane] = ds;
+            __builtin_amdgcn_wave_barrier();
+            const int nj = N - j0 < 64 ? N - j0 : 64;
+            for (int jj = 0; jj < nj; ++jj) {
+                const float dsj = sa[jj];
+                const T *kr = kb + (int64_t)(j0 + jj) * rs;
+#pragma unroll
+                for (int c = 0; c < SH_C; ++c)
+                    if (lane + 64 * c < hd) a[c] = fmaf(dsj, to_f32<T>(kr[lane + 64 * c]), a[c]);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        T *dq = dqb + (int64_t)i * rs;
+#pragma unroll
+        for (int c = 0; c < SH_C; ++c)
+            if (lane + 64 * c < hd) dq[lane + 64 * c] = from_f32<T>(a[c] * scale);          // dq = scale dS k
+    }
+    __syncthreads();
+    // ---- phase B: one key row per wave
+    for (int j = wave; j < N; j += 4) {
+        load_row<T>(ra, kb + (int64_t)j * rs, hd, 1.0f, lane);
+        load_row<T>(rb, vb + (int64_t)j * rs, hd, 1.0f, lane);
+        __builtin_amdgcn_wave_barrier();
+        float ak[SH_C], av[SH_C];
+#pragma unroll
+        for (int c = 0; c < SH_C; ++c) ak[c] = av[c] = 0.f;
+        for (int i0 = 0; i0 < N; i0 += 64) {
+            const int i = i0 + lane;
+            float p = 0.f, ds = 0.f;
+            if (i < N) {
+                const float s = dot_row<T>(ra, qb + (int64_t)i * rs, hd) * scale, dp = dot_row<T>(rb, ob + (int64_t)i * D, hd);
+                p = __expf(s - lse[i]);
+                ds = p * (dp - dsum[i]);
+            }
+            sa[lane] = p;
+            sb[lane] = ds;
+            __builtin_amdgcn_wave_barrier();
+            const int ni = N - i0 < 64 ? N - i0 : 64;
+            for (int ii = 0; ii < ni; ++ii) {
+                const float pi = sa[ii], dsi = sb[ii];
+                const T *qr = qb + (int64_t)(i0 + ii) * rs, *orow = ob + (int64_t)(i0 + ii) * D;
+#pragma unroll
+                for (int c = 0; c < SH_C; ++c)
+                    if (lane + 64 * c < hd) {
+                        ak[c] = fmaf(dsi, to_f32<T>(qr[lane + 64 * c]), ak[c]);
+                        av[c] = fmaf(pi, to_f32<T>(orow[lane + 64 * c]), av[c]);
+                    }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        T *dk = dqb + (int64_t)j * rs + D, *dv = dk + D;
+#pragma unroll
+        for (int c = 0; c < SH_C; ++c)
+            if (lane + 64 * c < hd) {
+                dk[lane + 64 * c] = from_f32<T>(ak[c] * scale);                            // dk = dS^T (scale q)
+                dv[lane + 64 * c] = from_f32<T>(av[c]);                                    // dv = P^T dO
+            }
+    }
+}
+
+size_t stream_bwd_smem(int N) { return sizeof(float) * (8 * SH_MAXHD + 4 * 128 + 2 * (size_t)N); }
+
+template <typename T>
+void launch_stream(bool bwd, const void *qkv, const void *dout, void *out, int B, int N, int H, int hd, hipStream_t st) {
+    if (!bwd)
+        hipLaunchKernelGGL(mha_fwd_stream_kernel<T>, dim3(B * H, (N + 3) / 4), dim3(256), 0, st, (const T *)qkv, (T *)out, B, N, H, hd);
+    else
+        hipLaunchKernelGGL(mha_bwd_stream_kernel<T>, dim3(B * H), dim3(256), stream_bwd_smem(N), st, (const T *)qkv, (const T *)dout,
+                           (T *)out, B, N, H, hd);
+}
+void launch_stream_any(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, hipStream_t st) {
+    if (dtype == SKYEMB_BF16) launch_stream<bf16_t>(bwd, qkv, dout, out, B, N, H, hd, st);
+    else if (dtype == SKYEMB_F16) launch_stream<f16_t>(bwd, qkv, dout, out, B, N, H, hd, st);
+    else launch_stream<float>(bwd, qkv, dout, out, B, N, H, hd, st);
+}
+
 struct Plan {
     int waves, per_wave_floats;
     size_t smem;
@@ -178,17 +376,24 @@ int set_lds(K kern, size_t smem, const char *name) {
 
 }  // namespace
 
-// attention_mfma.hip: bf16, N <= 32, head dim 32 / 64 (the shapes of the MAE path); -1 = not handled
+// attention_mfma.hip: bf16 / fp16, head dim 32 / 64, any N <= SKYEMB_MHA_MAX_N; -1 = not handled
 int skyemb_mha_mfma_try(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, hipStream_t st);
 
 extern "C" int skyemb_mha_fwd(const void *qkv, void *out, int dtype, int B, int N, int H, int hd, void *stream) {
     SKY_CHECK_ARG(B > 0 && N > 0 && H > 0 && hd > 0 && hd % 8 == 0, "skyemb_mha_fwd: bad shape (head dim must be a multiple of 8)");
+    SKY_CHECK_ARG(N <= SKYEMB_MHA_MAX_N, "skyemb_mha_fwd: N = %d tokens, more than the supported %d", N, SKYEMB_MHA_MAX_N);
     hipStream_t st = (hipStream_t)stream;
     if (sky_is_lp(dtype) && skyemb_mha_mfma_try(false, qkv, nullptr, out, dtype, B, N, H, hd, st) == 0) {
         SKY_LAUNCH_CHECK("skyemb_mha_fwd");
         return 0;
     }
     const Plan p = make_plan(N, hd, false);
+    if (p.smem > 160 * 1024) {         // the head does not fit: the streaming kernel (hd <= SH_MAXHD)
+        SKY_CHECK_ARG(hd <= SH_MAXHD, "skyemb_mha_fwd: head dim %d with N = %d tokens: at most %d", hd, N, SH_MAXHD);
+        launch_stream_any(false, qkv, nullptr, out, dtype, B, N, H, hd, st);
+        SKY_LAUNCH_CHECK("skyemb_mha_fwd");
+        return 0;
+    }
     dim3 grid((B * H + p.waves - 1) / p.waves), block(64 * p.waves);
     int rc;
     if (dtype == SKYEMB_BF16) {
@@ -211,12 +416,19 @@ extern "C" int skyemb_mha_fwd(const void *qkv, void *out, int dtype, int B, int 
 extern "C" int skyemb_mha_bwd(const void *qkv, const void *dout, void *dqkv, int dtype, int B, int N, int H, int hd,
                               void *stream) {
     SKY_CHECK_ARG(B > 0 && N > 0 && H > 0 && hd > 0 && hd % 8 == 0, "skyemb_mha_bwd: bad shape (head dim must be a multiple of 8)");
+    SKY_CHECK_ARG(N <= SKYEMB_MHA_MAX_N, "skyemb_mha_bwd: N = %d tokens, more than the supported %d", N, SKYEMB_MHA_MAX_N);
     hipStream_t st = (hipStream_t)stream;
     if (sky_is_lp(dtype) && skyemb_mha_mfma_try(true, qkv, dout, dqkv, dtype, B, N, H, hd, st) == 0) {
         SKY_LAUNCH_CHECK("skyemb_mha_bwd");
         return 0;
     }
     const Plan p = make_plan(N, hd, true);
+    if (p.smem > 160 * 1024) {         // the head does not fit: the streaming kernel (hd <= SH_MAXHD)
+        SKY_CHECK_ARG(hd <= SH_MAXHD, "skyemb_mha_bwd: head dim %d with N = %d tokens: at most %d", hd, N, SH_MAXHD);
+        launch_stream_any(true, qkv, dout, dqkv, dtype, B, N, H, hd, st);
+        SKY_LAUNCH_CHECK("skyemb_mha_bwd");
+        return 0;
+    }
     dim3 grid((B * H + p.waves - 1) / p.waves), block(64 * p.waves);
     int rc;
     if (dtype == SKYEMB_BF16) {

@@ -612,6 +612,314 @@ int launch_strip(bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// 128 < N <= SKYEMB_MHA_MAX_N (finer patches on larger cutouts: 257 / 258 tokens at 128 x 128, patch 8): the key (or query)
+// operands STREAM through LDS in blocks of LB = 64 token rows, each block staged once with coalesced 16-byte loads and
+// shared by the workgroup's LW waves; the next block's loads are issued before the current one is consumed.
+//   forward : wave w owns query strip 32 (LW y + w); flash-style online softmax over the key blocks (running max and sum
+//             in fp32, O^T rescaled when the max grows, tail keys -inf, tail queries not stored).
+//   backward: one workgroup per (sample, head), no atomics, no workspace:
+//             A) per query strip, one walk over K/V blocks: running max / sum / sum_j p dP -> lse_i, D_i = rowsum(P dP)
+//                (kept in registers, and written to LDS for phase B);
+//             C) same strip, second walk over K/V blocks: dQ^T = K^T . dS^T with P = exp(s - lse_i);
+//             B) per key strip, one walk over Q/dO blocks: dK^T = Q^T . dS, dV^T = dO^T . P (statistics out of LDS).
+//             Every sum runs in a fixed order: the same call gives the same bits.
+// LDS: two [64][HD + 8] staging tiles (18.4 KB at hd 64) + 2 x round_up(N, 64) statistics floats in backward (32.8 KB
+// at N = 4098): under 64 KB, no hipFuncSetAttribute in the launch path.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int LB = 64, LW = 4;
+
+// two [LB][HD] operand blocks starting at token row0 held in registers (rows >= N zero), then written to two LDS tiles
+template <int HD>
+struct BlockStage {
+    static constexpr int PR = HD / 8, THREADS = 64 * LW, MAXP = (LB * PR + THREADS - 1) / THREADS;
+    lp8 v[2][MAXP];
+    __device__ __forceinline__ void load(const lp_t *b0, int64_t s0, const lp_t *b1, int64_t s1, int row0, int N, int tid) {
+#pragma unroll
+        for (int i = 0; i < MAXP; ++i) {
+            const int p = tid + i * THREADS, row = row0 + p / PR, c = p % PR;
+            const bool ok = p < LB * PR && row < N;
+            v[0][i] = ok ? *(const lp8 *)(b0 + (int64_t)row * s0 + 8 * c) : zero8();
+            v[1][i] = ok ? *(const lp8 *)(b1 + (int64_t)row * s1 + 8 * c) : zero8();
+        }
+    }
+    __device__ __forceinline__ void store(lp_t *t0, lp_t *t1, int tid) const {
+#pragma unroll
+        for (int i = 0; i < MAXP; ++i) {
+            const int p = tid + i * THREADS, row = p / PR, c = p % PR;
+            if (p < LB * PR) {
+                *(lp8 *)(t0 + row * (HD + 8) + 8 * c) = v[0][i];
+                *(lp8 *)(t1 + row * (HD + 8) + 8 * c) = v[1][i];
+            }
+        }
+    }
+};
+template <int HD>
+__device__ __forceinline__ lp8 tile_row(const lp_t *tile, int row, int g, int s) {
+    return *(const lp8 *)(tile + row * (HD + 8) + 16 * s + 8 * g);
+}
+
+template <int HD>
+__global__ __launch_bounds__(64 * LW) void mha_fwd_long_kernel(const lp_t *__restrict__ qkv, lp_t *__restrict__ out, int B, int N,
+                                                              int H) {
+    constexpr int KS = HD / 16, NB = (HD + 31) / 32, PITCH = HD + 8;
+    __shared__ __attribute__((aligned(16))) lp_t kt[LB * PITCH], vt[LB * PITCH];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
+    const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+    const int D = H * HD;
+    const int64_t rs = 3 * (int64_t)D;
+    const int r = lane & 31, g = lane >> 5;
+    const lp_t *qb = qkv + (int64_t)b * N * rs + h * HD, *kb = qb + D, *vb = qb + 2 * D;
+    const int q0 = 32 * (LW * blockIdx.y + wave), my = q0 + r;
+    const bool active = q0 < N;
+    const float scale = rsqrtf((float)HD);
+
+    lp8 qf[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) qf[s] = row_frag_at(qb, rs, my, g, s, N);
+    f32x16 ot[NB];
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk) ot[blk] = zero16();
+    float m = -INFINITY, l = 0.f;
+    BlockStage<HD> stg;
+    stg.load(kb, rs, vb, rs, 0, N, tid);
+    for (int j0 = 0; j0 < N; j0 += LB) {
+        __syncthreads();                                  // every wave is done with the previous block
+        stg.store(kt, vt, tid);
+        __syncthreads();
+        if (j0 + LB < N) stg.load(kb, rs, vb, rs, j0 + LB, N, tid);
+        if (!active) continue;
+        f32x16 st[2];
+        float bm = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            st[t] = zero16();
+            if (j0 + 32 * t < N) {
+#pragma unroll
+                for (int s = 0; s < KS; ++s) st[t] = mfma32(tile_row<HD>(kt, 32 * t + r, g, s), qf[s], st[t]);   // ST[j][i]
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                st[t][e] = j0 + 32 * t + acc_row(e, g) < N ? st[t][e] * scale : -INFINITY;
+                bm = fmaxf(bm, st[t][e]);
+            }
+        }
+        bm = fmaxf(bm, __shfl_xor(bm, 32));
+        const float mn = fmaxf(m, bm), alpha = __expf(m - mn);    // first block: exp(-inf) = 0
+        float ps = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                st[t][e] = __expf(st[t][e] - mn);
+                ps += st[t][e];
+            }
+        ps += __shfl_xor(ps, 32);
+        l = l * alpha + ps;
+        m = mn;
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) ot[blk][e] *= alpha;           // O^T[d][i]: column i is this lane's query
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    if (j0 + 32 * t + 16 * s < N)
+                        ot[blk] = mfma32(tok_frag_lds<HD>(vt + 32 * t * PITCH, blk, r, g, s), pack_regs(st[t], s), ot[blk]);
+        }
+    }
+    if (my < N) {
+        const float inv = 1.0f / l;
+        lp_t *orow = out + ((int64_t)b * N + my) * D + h * HD;
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk) store_tile<HD>(orow, ot[blk], blk, g, inv);
+    }
+}
+
+template <int HD>
+__global__ __launch_bounds__(64 * LW) void mha_bwd_long_kernel(const lp_t *__restrict__ qkv, const lp_t *__restrict__ dout,
+                                                              lp_t *__restrict__ dqkv, int B, int N, int H) {
+    constexpr int KS = HD / 16, NB = (HD + 31) / 32, PITCH = HD + 8;
+    extern __shared__ __attribute__((aligned(16))) float long_lds[];
+    const int NS = (N + LB - 1) / LB * LB;
+    lp_t *t0 = (lp_t *)long_lds, *t1 = t0 + LB * PITCH;
+    float *lse = (float *)(t1 + LB * PITCH), *dsum = lse + NS;     // per query token: log-sum-exp, rowsum(P dP)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
+    const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+    const int D = H * HD;
+    const int64_t rs = 3 * (int64_t)D;
+    const int r = lane & 31, g = lane >> 5;
+    const lp_t *qb = qkv + (int64_t)b * N * rs + h * HD, *kb = qb + D, *vb = qb + 2 * D;
+    const lp_t *ob = dout + (int64_t)b * N * D + h * HD;
+    lp_t *dqb = dqkv + (int64_t)b * N * rs + h * HD;
+    const float scale = rsqrtf((float)HD);
+    BlockStage<HD> stg;
+
+    // ---- phases A and C: query strips
+    for (int q0 = 32 * wave; q0 - 32 * wave < N; q0 += 32 * LW) {
+        const bool active = q0 < N;
+        const int my = q0 + r;
+        lp8 qf[KS], of[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            qf[s] = row_frag_at(qb, rs, my, g, s, N);
+            of[s] = row_frag_at(ob, D, my, g, s, N);
+        }
+        float m = -INFINITY, l = 0.f, dacc = 0.f, lse_i = 0.f, d_i = 0.f;
+        f32x16 tq[NB];
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk) tq[blk] = zero16();
+        for (int walk = 0; walk < 2; ++walk) {
+            stg.load(kb, rs, vb, rs, 0, N, tid);
+            for (int j0 = 0; j0 < N; j0 += LB) {
+                __syncthreads();
+                stg.store(t0, t1, tid);
+                __syncthreads();
+                if (j0 + LB < N) stg.load(kb, rs, vb, rs, j0 + LB, N, tid);
+                if (!active) continue;
+                f32x16 st[2], dpt[2];
+                float bm = -INFINITY;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    st[t] = zero16();
+                    dpt[t] = zero16();
+                    if (j0 + 32 * t < N) {
+#pragma unroll
+                        for (int s = 0; s < KS; ++s) {
+                            st[t] = mfma32(tile_row<HD>(t0, 32 * t + r, g, s), qf[s], st[t]);    // S^T[j][i]
+                            dpt[t] = mfma32(tile_row<HD>(t1, 32 * t + r, g, s), of[s], dpt[t]);  // dP^T[j][i]
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        st[t][e] = j0 + 32 * t + acc_row(e, g) < N ? st[t][e] * scale : -INFINITY;
+                        bm = fmaxf(bm, st[t][e]);
+                    }
+                }
+                if (walk == 0) {
+                    bm = fmaxf(bm, __shfl_xor(bm, 32));
+                    const float mn = fmaxf(m, bm), alpha = __expf(m - mn);
+                    float ps = 0.f, pd = 0.f;
+#pragma unroll
+                    for (int t = 0; t < 2; ++t)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) {
+                            const float p = __expf(st[t][e] - mn);
+                            ps += p;
+                            pd = fmaf(p, dpt[t][e], pd);
+                        }
+                    ps += __shfl_xor(ps, 32);
+                    pd += __shfl_xor(pd, 32);
+                    l = l * alpha + ps;
+                    dacc = dacc * alpha + pd;
+                    m = mn;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 2; ++t)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s)
+                            if (j0 + 32 * t + 16 * s < N) {
+                                lp8 df;
+#pragma unroll
+                                for (int e = 0; e < 8; ++e) {
+                                    const float p = __expf(st[t][8 * s + e] - lse_i);
+                                    df[e] = (lp_t)(p * (dpt[t][8 * s + e] - d_i));      // dS^T[j][i]
+                                }
+#pragma unroll
+                                for (int blk = 0; blk < NB; ++blk)
+                                    tq[blk] = mfma32(tok_frag_lds<HD>(t0 + 32 * t * PITCH, blk, r, g, s), df, tq[blk]);
+                            }
+                }
+            }
+            if (walk == 0) {
+                lse_i = m + logf(l);
+                d_i = dacc / l;
+                if (active && g == 0) {
+                    lse[my] = lse_i;
+                    dsum[my] = d_i;
+                }
+            }
+        }
+        if (my < N) {
+#pragma unroll
+            for (int blk = 0; blk < NB; ++blk) store_tile<HD>(dqb + (int64_t)my * rs, tq[blk], blk, g, scale);
+        }
+    }
+    // ---- phase B: key strips against streamed Q / dO blocks (lse, dsum of every query are in LDS after the barriers)
+    for (int k0 = 32 * wave; k0 - 32 * wave < N; k0 += 32 * LW) {
+        const bool active = k0 < N;
+        const int my = k0 + r;
+        lp8 kf[KS], vf[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            kf[s] = row_frag_at(kb, rs, my, g, s, N);
+            vf[s] = row_frag_at(vb, rs, my, g, s, N);
+        }
+        f32x16 tk[NB], tv[NB];
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk) {
+            tk[blk] = zero16();
+            tv[blk] = zero16();
+        }
+        stg.load(qb, rs, ob, D, 0, N, tid);
+        for (int i0 = 0; i0 < N; i0 += LB) {
+            __syncthreads();
+            stg.store(t0, t1, tid);
+            __syncthreads();
+            if (i0 + LB < N) stg.load(qb, rs, ob, D, i0 + LB, N, tid);
+            if (!active) continue;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                if (i0 + 32 * t >= N) break;
+                f32x16 sn = zero16(), dpn = zero16();
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    sn = mfma32(tile_row<HD>(t0, 32 * t + r, g, s), kf[s], sn);       // S[i][j]: rows i, column j = my
+                    dpn = mfma32(tile_row<HD>(t1, 32 * t + r, g, s), vf[s], dpn);     // dP[i][j]
+                }
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int i = i0 + 32 * t + acc_row(e, g);
+                    const bool ok = my < N && i < N;
+                    const float p = ok ? __expf(sn[e] * scale - lse[i]) : 0.f;
+                    dpn[e] = ok ? p * (dpn[e] - dsum[i]) : 0.f;     // dS[i][j]
+                    sn[e] = p;
+                }
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    if (i0 + 32 * t + 16 * s >= N) break;
+                    const lp8 pf = pack_regs(sn, s), df = pack_regs(dpn, s);
+#pragma unroll
+                    for (int blk = 0; blk < NB; ++blk) {
+                        tk[blk] = mfma32(tok_frag_lds<HD>(t0 + 32 * t * PITCH, blk, r, g, s), df, tk[blk]);   // dK^T[d][j] += Q[i][d] dS[i][j]
+                        tv[blk] = mfma32(tok_frag_lds<HD>(t1 + 32 * t * PITCH, blk, r, g, s), pf, tv[blk]);   // dV^T[d][j] += dO[i][d] P[i][j]
+                    }
+                }
+            }
+        }
+        if (my < N) {
+            lp_t *dk = dqb + (int64_t)my * rs + D, *dv = dk + D;
+#pragma unroll
+            for (int blk = 0; blk < NB; ++blk) {
+                store_tile<HD>(dk, tk[blk], blk, g, scale);
+                store_tile<HD>(dv, tv[blk], blk, g, 1.0f);
+            }
+        }
+    }
+}
+
+template <int HD>
+int launch_long(bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st) {
+    if (!bwd) {
+        hipLaunchKernelGGL((mha_fwd_long_kernel<HD>), dim3(B * H, (N + 32 * LW - 1) / (32 * LW)), dim3(64 * LW), 0, st, x, out, B, N, H);
+    } else {
+        const size_t smem = 2 * LB * (HD + 8) * sizeof(lp_t) + 2 * sizeof(float) * ((N + LB - 1) / LB * LB);
+        hipLaunchKernelGGL((mha_bwd_long_kernel<HD>), dim3(B * H), dim3(64 * LW), smem, st, x, dout, out, B, N, H);
+    }
+    return 0;
+}
+
 }  // namespace
 
 // returns -1 when the shape is outside this kernel's subset (caller falls back to the LDS kernel of attention.hip)
@@ -623,10 +931,14 @@ int SKY_TWIN(skyemb_mha_mfma_try)(bool bwd, const void *qkv, const void *dout, v
     if (dtype == SKYEMB_F16) return skyemb_mha_mfma_try_f16(bwd, qkv, dout, out, dtype, B, N, H, hd, st);
 #endif
     if (dtype != SKY_LP_DTYPE) return -1;
-    if (N > 32 * MAX_NT || (hd != 32 && hd != 64)) return -1;
+    if (hd != 32 && hd != 64) return -1;
     static const bool off = []() { const char *e = getenv("SKYEMB_MHA_MFMA"); return e && e[0] == '0'; }();
     if (off) return -1;
     const lp_t *x = (const lp_t *)qkv;
+    if (N > 32 * MAX_NT) {
+        if (hd == 32) return launch_long<32>(bwd, x, (const lp_t *)dout, (lp_t *)out, B, N, H, st);
+        return launch_long<64>(bwd, x, (const lp_t *)dout, (lp_t *)out, B, N, H, st);
+    }
     if (N > 32) {
         const int nt = (N + 31) / 32;
 #define STRIP(HD_, NT_) launch_strip<HD_, NT_>(bwd, x, (const lp_t *)dout, (lp_t *)out, B, N, H, st)

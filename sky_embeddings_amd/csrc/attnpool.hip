@@ -9,7 +9,7 @@
 
 namespace {
 
-constexpr int MAXN = 256;   // tokens per sample (cls + RA/Dec + patches)
+constexpr int MAXN = 256;   // tokens per sample held in LDS (cls + RA/Dec + patches); longer sequences stream in chunks
 constexpr int MAXHD = 512;  // columns per head (the downstream predictor pools with TWO heads: 384 at ViT-B, 512 at ViT-L)
 
 // q[o] = bq[o] + sum_i Wq[o][i] latent[i]; one wave per output
@@ -118,6 +118,127 @@ __global__ __launch_bounds__(256) void attnpool_bwd_kernel(const float *__restri
     }
 }
 
+// N > MAXN (finer patches on larger cutouts): the same sums with the token loop streamed in chunks of MAXN.  The raw
+// scores go through the caller's `prob` row (each lane re-reads only what it wrote), the probabilities / dS of one chunk
+// through LDS; the output (dq) columns d = lane + 64 c stay in registers.  Up to SKYEMB_MHA_MAX_N tokens.
+constexpr int MAXC = MAXHD / 64;
+template <typename T>
+__global__ __launch_bounds__(256) void attnpool_fwd_long_kernel(const float *__restrict__ q, const T *__restrict__ kv,
+                                                                T *__restrict__ out, float *__restrict__ prob, int B, int N,
+                                                                int H, int hd) {
+    __shared__ float sq[4][MAXHD], sp[4][MAXN];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bh = blockIdx.x * 4 + wave;
+    if (bh >= B * H) return;
+    const int b = bh / H, h = bh - b * H, D = H * hd;
+    const float scale = rsqrtf((float)hd);
+    for (int d = lane; d < hd; d += 64) sq[wave][d] = q[h * hd + d];
+    __builtin_amdgcn_wave_barrier();
+    const T *kb = kv + (int64_t)b * N * 2 * D + h * hd;
+    float *pr = prob + (int64_t)bh * N;
+    float mx = -INFINITY;
+    for (int j = lane; j < N; j += 64) {
+        const T *kr = kb + (int64_t)j * 2 * D;
+        float s = 0.f;
+        for (int d = 0; d < hd; d += 4) {
+            const float4 kk = load4<T>(kr + d);
+            s = fmaf(sq[wave][d], kk.x, fmaf(sq[wave][d + 1], kk.y, fmaf(sq[wave][d + 2], kk.z, fmaf(sq[wave][d + 3], kk.w, s))));
+        }
+        s *= scale;
+        pr[j] = s;
+        mx = fmaxf(mx, s);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < N; j += 64) sum += __expf(pr[j] - mx);
+    sum = wave_sum(sum);
+    const float inv = 1.0f / sum;
+    float o[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) o[c] = 0.f;
+    for (int j0 = 0; j0 < N; j0 += MAXN) {
+        const int nj = N - j0 < MAXN ? N - j0 : MAXN;
+        for (int j = j0 + lane; j < j0 + nj; j += 64) {
+            const float p = __expf(pr[j] - mx) * inv;
+            sp[wave][j - j0] = p;
+            pr[j] = p;
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int jj = 0; jj < nj; ++jj) {
+            const float p = sp[wave][jj];
+            const T *vr = kb + (int64_t)(j0 + jj) * 2 * D + D;
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (lane + 64 * c < hd) o[c] = fmaf(p, to_f32<T>(vr[lane + 64 * c]), o[c]);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (lane + 64 * c < hd) out[(int64_t)b * D + h * hd + lane + 64 * c] = from_f32<T>(o[c]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attnpool_bwd_long_kernel(const float *__restrict__ q, const T *__restrict__ kv,
+                                                                const T *__restrict__ dout, const float *__restrict__ prob,
+                                                                T *__restrict__ dkv, float *__restrict__ dq_part, int B, int N,
+                                                                int H, int hd) {
+    __shared__ float sq[4][MAXHD], sdo[4][MAXHD], sds[4][MAXN];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bh = blockIdx.x * 4 + wave;
+    if (bh >= B * H) return;
+    const int b = bh / H, h = bh - b * H, D = H * hd;
+    const float scale = rsqrtf((float)hd);
+    for (int d = lane; d < hd; d += 64) {
+        sq[wave][d] = q[h * hd + d];
+        sdo[wave][d] = to_f32<T>(dout[(int64_t)b * D + h * hd + d]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    const T *kb = kv + (int64_t)b * N * 2 * D + h * hd;
+    T *dkb = dkv + (int64_t)b * N * 2 * D + h * hd;
+    const float *pr = prob + (int64_t)bh * N;
+    auto dp_of = [&](int j) {
+        const T *vr = kb + (int64_t)j * 2 * D + D;
+        float dp = 0.f;
+        for (int d = 0; d < hd; d += 4) {
+            const float4 vv = load4<T>(vr + d);
+            dp = fmaf(sdo[wave][d], vv.x, fmaf(sdo[wave][d + 1], vv.y, fmaf(sdo[wave][d + 2], vv.z, fmaf(sdo[wave][d + 3], vv.w, dp))));
+        }
+        return dp;
+    };
+    float rs = 0.f;
+    for (int j = lane; j < N; j += 64) rs = fmaf(pr[j], dp_of(j), rs);
+    rs = wave_sum(rs);
+    float a[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) a[c] = 0.f;
+    for (int j0 = 0; j0 < N; j0 += MAXN) {
+        const int nj = N - j0 < MAXN ? N - j0 : MAXN;
+        for (int j = j0 + lane; j < j0 + nj; j += 64) {
+            const float p = pr[j];
+            const float ds = p * (dp_of(j) - rs);
+            sds[wave][j - j0] = ds * scale;
+            T *dk = dkb + (int64_t)j * 2 * D, *dv = dk + D;
+            for (int d = 0; d < hd; d += 4) {
+                store4<T>(dk + d, ds * scale * sq[wave][d], ds * scale * sq[wave][d + 1], ds * scale * sq[wave][d + 2], ds * scale * sq[wave][d + 3]);
+                store4<T>(dv + d, p * sdo[wave][d], p * sdo[wave][d + 1], p * sdo[wave][d + 2], p * sdo[wave][d + 3]);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int jj = 0; jj < nj; ++jj) {
+            const float dsj = sds[wave][jj];
+            const T *kr = kb + (int64_t)(j0 + jj) * 2 * D;
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c)
+                if (lane + 64 * c < hd) a[c] = fmaf(dsj, to_f32<T>(kr[lane + 64 * c]), a[c]);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (lane + 64 * c < hd) dq_part[(int64_t)b * D + h * hd + lane + 64 * c] = a[c];
+}
+
 // block o: dq[o] = sum_b dq_part[b][o] (fixed order);  dWq[o][:] = dq[o] latent;  dbq[o] = dq[o];  dqv[o] = dq[o]
 __global__ __launch_bounds__(256) void attnpool_q_bwd1_kernel(const float *__restrict__ dq_part, int B, const float *__restrict__ latent,
                                                               float *__restrict__ dWq, float *__restrict__ dbq,
@@ -158,12 +279,19 @@ extern "C" int skyemb_attnpool_q(const float *latent, const float *Wq, const flo
     return 0;
 }
 
-extern "C" int skyemb_attnpool_fwd(const float *q, const void *kv, int dtype, void *out, float *prob, int B, int N, int H, int hd,
-                                   void *stream) {
-    SKY_CHECK_ARG(q && kv && out && prob && B > 0 && N > 0 && N <= MAXN && H > 0 && hd > 0 && hd <= MAXHD && hd % 4 == 0,
-                  "skyemb_attnpool_fwd: bad shape B=%d N=%d H=%d hd=%d (N <= %d, hd <= %d, hd %% 4 == 0)", B, N, H, hd, MAXN, MAXHD);
+static int attnpool_fwd(const float *q, const void *kv, int dtype, void *out, float *prob, int B, int N, int H, int hd,
+                        void *stream, int max_n) {
+    SKY_CHECK_ARG(q && kv && out && prob && B > 0 && N > 0 && N <= max_n && H > 0 && hd > 0 && hd <= MAXHD && hd % 4 == 0,
+                  "skyemb_attnpool_fwd: bad shape B=%d N=%d H=%d hd=%d (N <= %d, hd <= %d, hd %% 4 == 0)", B, N, H, hd, max_n, MAXHD);
     const dim3 grid((B * H + 3) / 4), block(256);
-    if (dtype == SKYEMB_BF16)
+    if (N > MAXN) {
+        if (dtype == SKYEMB_BF16)
+            hipLaunchKernelGGL(attnpool_fwd_long_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, q, (const bf16_t *)kv, (bf16_t *)out, prob, B, N, H, hd);
+        else if (dtype == SKYEMB_F16)
+            hipLaunchKernelGGL(attnpool_fwd_long_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, q, (const f16_t *)kv, (f16_t *)out, prob, B, N, H, hd);
+        else
+            hipLaunchKernelGGL(attnpool_fwd_long_kernel<float>, grid, block, 0, (hipStream_t)stream, q, (const float *)kv, (float *)out, prob, B, N, H, hd);
+    } else if (dtype == SKYEMB_BF16)
         hipLaunchKernelGGL(attnpool_fwd_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, q, (const bf16_t *)kv, (bf16_t *)out, prob, B, N, H, hd);
     else if (dtype == SKYEMB_F16)
         hipLaunchKernelGGL(attnpool_fwd_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, q, (const f16_t *)kv, (f16_t *)out, prob, B, N, H, hd);
@@ -173,12 +301,22 @@ extern "C" int skyemb_attnpool_fwd(const float *q, const void *kv, int dtype, vo
     return 0;
 }
 
-extern "C" int skyemb_attnpool_bwd(const float *q, const void *kv, int dtype, const void *dout, const float *prob, void *dkv,
-                                   float *dq_part, int B, int N, int H, int hd, void *stream) {
-    SKY_CHECK_ARG(q && kv && dout && prob && dkv && dq_part && B > 0 && N > 0 && N <= MAXN && H > 0 && hd > 0 && hd <= MAXHD && hd % 4 == 0,
+static int attnpool_bwd(const float *q, const void *kv, int dtype, const void *dout, const float *prob, void *dkv,
+                        float *dq_part, int B, int N, int H, int hd, void *stream, int max_n) {
+    SKY_CHECK_ARG(q && kv && dout && prob && dkv && dq_part && B > 0 && N > 0 && N <= max_n && H > 0 && hd > 0 && hd <= MAXHD && hd % 4 == 0,
                   "skyemb_attnpool_bwd: bad shape B=%d N=%d H=%d hd=%d", B, N, H, hd);
     const dim3 grid((B * H + 3) / 4), block(256);
-    if (dtype == SKYEMB_BF16)
+    if (N > MAXN) {
+        if (dtype == SKYEMB_BF16)
+            hipLaunchKernelGGL(attnpool_bwd_long_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, q, (const bf16_t *)kv, (const bf16_t *)dout,
+                               prob, (bf16_t *)dkv, dq_part, B, N, H, hd);
+        else if (dtype == SKYEMB_F16)
+            hipLaunchKernelGGL(attnpool_bwd_long_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, q, (const f16_t *)kv, (const f16_t *)dout,
+                               prob, (f16_t *)dkv, dq_part, B, N, H, hd);
+        else
+            hipLaunchKernelGGL(attnpool_bwd_long_kernel<float>, grid, block, 0, (hipStream_t)stream, q, (const float *)kv, (const float *)dout,
+                               prob, (float *)dkv, dq_part, B, N, H, hd);
+    } else if (dtype == SKYEMB_BF16)
         hipLaunchKernelGGL(attnpool_bwd_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, q, (const bf16_t *)kv, (const bf16_t *)dout, prob,
                            (bf16_t *)dkv, dq_part, B, N, H, hd);
     else if (dtype == SKYEMB_F16)
@@ -189,6 +327,24 @@ extern "C" int skyemb_attnpool_bwd(const float *q, const void *kv, int dtype, co
                            (float *)dkv, dq_part, B, N, H, hd);
     SKY_LAUNCH_CHECK("skyemb_attnpool_bwd");
     return 0;
+}
+
+// skyemb_attnpool_fwd / _bwd keep their N <= MAXN contract; the _long entry points take any N <= SKYEMB_MHA_MAX_N
+extern "C" int skyemb_attnpool_fwd(const float *q, const void *kv, int dtype, void *out, float *prob, int B, int N, int H, int hd,
+                                   void *stream) {
+    return attnpool_fwd(q, kv, dtype, out, prob, B, N, H, hd, stream, MAXN);
+}
+extern "C" int skyemb_attnpool_fwd_long(const float *q, const void *kv, int dtype, void *out, float *prob, int B, int N, int H, int hd,
+                                        void *stream) {
+    return attnpool_fwd(q, kv, dtype, out, prob, B, N, H, hd, stream, SKYEMB_MHA_MAX_N);
+}
+extern "C" int skyemb_attnpool_bwd(const float *q, const void *kv, int dtype, const void *dout, const float *prob, void *dkv,
+                                   float *dq_part, int B, int N, int H, int hd, void *stream) {
+    return attnpool_bwd(q, kv, dtype, dout, prob, dkv, dq_part, B, N, H, hd, stream, MAXN);
+}
+extern "C" int skyemb_attnpool_bwd_long(const float *q, const void *kv, int dtype, const void *dout, const float *prob, void *dkv,
+                                        float *dq_part, int B, int N, int H, int hd, void *stream) {
+    return attnpool_bwd(q, kv, dtype, dout, prob, dkv, dq_part, B, N, H, hd, stream, SKYEMB_MHA_MAX_N);
 }
 
 extern "C" int skyemb_attnpool_q_bwd(const float *dq_part, int B, const float *latent, const float *Wq, float *dWq, float *dbq,

@@ -174,6 +174,17 @@ def attnpool_bwd(q, kv, dout, prob, dkv, dq_part, B, N, H, hd):
                                     _stream()), "skyemb_attnpool_bwd")
 
 
+def attnpool_fwd_long(q, kv, out, prob, B, N, H, hd):
+    """attnpool_fwd for any N <= 4098 tokens (attnpool_fwd takes N <= 256)."""
+    check(lib().skyemb_attnpool_fwd_long(_p(q), _p(kv), dtype_code(kv.dtype), _p(out), _p(prob), B, N, H, hd, _stream()),
+          "skyemb_attnpool_fwd_long")
+
+
+def attnpool_bwd_long(q, kv, dout, prob, dkv, dq_part, B, N, H, hd):
+    check(lib().skyemb_attnpool_bwd_long(_p(q), _p(kv), dtype_code(kv.dtype), _p(dout), _p(prob), _p(dkv), _p(dq_part), B, N, H, hd,
+                                         _stream()), "skyemb_attnpool_bwd_long")
+
+
 def attnpool_q_bwd(dq_part, latent, Wq, dWq, dbq, dlatent, ws):
     B, D = dq_part.shape
     check(lib().skyemb_attnpool_q_bwd(_p(dq_part), B, _p(latent), _p(Wq), _p(dWq), _p(dbq), _p(dlatent), _p(ws), D, _stream()),

@@ -158,7 +158,7 @@ class PredictorHead:
         M = B * Ne
         ops.gemm(x_lp, LP("attn_pool.kv.weight"), M=M, N=2 * D, K=D, bias=P("attn_pool.kv.bias"), out=w["kv"])
         ops.attnpool_q(P("attn_pool.latent"), P("attn_pool.q.weight"), P("attn_pool.q.bias"), w["q"])
-        ops.attnpool_fwd(w["q"], w["kv"], w["o"], w["prob"], B, Ne, H, D // H)
+        ops.attnpool_fwd_long(w["q"], w["kv"], w["o"], w["prob"], B, Ne, H, D // H)
         ops.gemm(w["o"], LP("attn_pool.proj.weight"), M=B, N=D, K=D, bias=P("attn_pool.proj.bias"), out_f32=w["y"])
         ops.layernorm_fwd(w["y"], P("attn_pool.norm.weight"), P("attn_pool.norm.bias"), w["ln"], w["mean"], w["rstd"], B, D, self.eps)
         ops.gemm(w["ln"], LP("attn_pool.mlp.fc1.weight"), M=B, N=hid, K=D, bias=P("attn_pool.mlp.fc1.bias"), act=ACT_GELU,
@@ -235,7 +235,7 @@ class PredictorHead:
                           G("attn_pool.norm.weight"), G("attn_pool.norm.bias"), B, D, self.code)
         # y = proj(pool(q, kv(tokens)))
         linear_bwd(w["gy_lp"], w["o"], "attn_pool.proj", D, D, B, out=w["do"])
-        ops.attnpool_bwd(w["q"], w["kv"], w["do"], w["prob"], w["dkv"], w["dq"], B, Ne, H, D // H)
+        ops.attnpool_bwd_long(w["q"], w["kv"], w["do"], w["prob"], w["dkv"], w["dq"], B, Ne, H, D // H)
         ops.attnpool_q_bwd(w["dq"], P("attn_pool.latent"), P("attn_pool.q.weight"), G("attn_pool.q.weight"), G("attn_pool.q.bias"),
                            G("attn_pool.latent"), w["dq_ws"])
         linear_bwd(w["dkv"], tokens_lp, "attn_pool.kv", 2 * D, D, M, out=dtokens_lp)

@@ -200,7 +200,7 @@ class SimMIMEngine(MAEEngine):
         ops.cast(x_last, w["ap_x"], M * D)
         ops.gemm(w["ap_x"], LP("attn_pool.kv.weight"), M=M, N=2 * D, K=D, bias=P("attn_pool.kv.bias"), out=w["ap_kv"])
         ops.attnpool_q(P("attn_pool.latent"), P("attn_pool.q.weight"), P("attn_pool.q.bias"), w["ap_q"])
-        ops.attnpool_fwd(w["ap_q"], w["ap_kv"], w["ap_o"], w["ap_prob"], B, Ne, H, D // H)
+        ops.attnpool_fwd_long(w["ap_q"], w["ap_kv"], w["ap_o"], w["ap_prob"], B, Ne, H, D // H)
         ops.gemm(w["ap_o"], LP("attn_pool.proj.weight"), M=B, N=D, K=D, bias=P("attn_pool.proj.bias"), out_f32=w["ap_y"])
         ops.layernorm_fwd(w["ap_y"], P("attn_pool.norm.weight"), P("attn_pool.norm.bias"), w["ap_ln"], w["ap_mean"], w["ap_rstd"],
                           B, D, cfg.ln_eps)
@@ -303,7 +303,7 @@ class SimMIMEngine(MAEEngine):
                      B, D, w)
         # y = proj(pool(q, kv(x)))
         self._linear_bwd(w["ap_gy_lp"], w["ap_o"], "attn_pool.proj.weight", "attn_pool.proj.bias", B, D, D, w, dx_out=w["ap_do"])
-        ops.attnpool_bwd(w["ap_q"], w["ap_kv"], w["ap_do"], w["ap_prob"], w["ap_dkv"], w["ap_dq"], B, Ne, H, D // H)
+        ops.attnpool_bwd_long(w["ap_q"], w["ap_kv"], w["ap_do"], w["ap_prob"], w["ap_dkv"], w["ap_dq"], B, Ne, H, D // H)
         ops.attnpool_q_bwd(w["ap_dq"], P("attn_pool.latent"), P("attn_pool.q.weight"), G("attn_pool.q.weight"), G("attn_pool.q.bias"),
                            G("attn_pool.latent"), w["ap_dq_ws"])
         self._wgrad(w["ap_dkv"], w["ap_x"], 2 * D, D, M, G("attn_pool.kv.weight"), G("attn_pool.kv.bias"), w)
