@@ -1274,6 +1274,21 @@ extern "C" int skyemb_gemm_group_plan(const skyemb_gemm_args *args, int n, int t
     return 0;
 }
 
+// the problems of a fused-optimiser group: plain weight gradients into the flat buffer -- a whole number of 8-element pieces per output
+// row, at an offset from g_base that is one too, no fused extras besides the bias gradient.  Stepped in the epilogue, or stored for a
+// later launch's side job to step as the slice of g_base they occupy.
+static bool flat_weight_gradients(const skyemb_gemm_args *args, int n, const skyemb_adamw_desc *adamw, const char *who) {
+    for (int i = 0; i < n; ++i) {
+        const skyemb_gemm_args &g = args[i];
+        if (!g.out_f32 || g.out || g.out2 || g.bias || g.table || g.resid || g.dst_row || g.act != SKYEMB_ACT_NONE || g.alpha != 1.0f ||
+            g.out_f32 < adamw->g_base || ((g.out_f32 - adamw->g_base) % 8) != 0 || (g.ldo32 ? g.ldo32 : g.N) % 8 != 0) {
+            skyemb_set_error("%s: problem %d is not a plain weight gradient into the flat buffer", who, i);
+            return false;
+        }
+    }
+    return true;
+}
+
 extern "C" int skyemb_gemm_group_plan_adamw(const skyemb_gemm_args *args, int n, int tile, const skyemb_adamw_desc *adamw, void *blob_host,
                                             int64_t blob_bytes, skyemb_gemm_group_info *info) {
     SKY_CHECK_ARG(adamw && adamw->g_base && adamw->p && adamw->m && adamw->v && adamw->p_lp && adamw->hyper,
@@ -1284,15 +1299,7 @@ extern "C" int skyemb_gemm_group_plan_adamw(const skyemb_gemm_args *args, int n,
         skyemb_set_error("skyemb_gemm_group_plan_adamw: weight-gradient (RC.RC) problems on the 64x64 / 128x64 / 128x128 / 256x256 tiles only");
         return -1;
     }
-    for (int i = 0; i < n; ++i) {
-        // a whole number of 8-element pieces per output row, inside the flat buffers, no fused extras besides the bias gradient
-        const skyemb_gemm_args &g = args[i];
-        if (!g.out_f32 || g.out || g.out2 || g.bias || g.table || g.resid || g.dst_row || g.act != SKYEMB_ACT_NONE || g.alpha != 1.0f ||
-            g.out_f32 < adamw->g_base || ((g.out_f32 - adamw->g_base) % 8) != 0 || (g.ldo32 ? g.ldo32 : g.N) % 8 != 0) {
-            skyemb_set_error("skyemb_gemm_group_plan_adamw: problem %d is not a plain weight gradient into the flat buffer", i);
-            return -1;
-        }
-    }
+    if (!flat_weight_gradients(args, n, adamw, "skyemb_gemm_group_plan_adamw")) return -1;
     skyemb_adamw_desc d = *adamw;
     d.enabled = 1;
     memcpy((char *)blob_host + GROUP_ADAMW_OFFSET, &d, sizeof d);
@@ -1316,6 +1323,8 @@ extern "C" int skyemb_gemm_group_plan_side_adamw(const skyemb_gemm_args *args, i
         skyemb_set_error("skyemb_gemm_group_plan_side_adamw: weight-gradient (RC.RC) problems on the 64x64 / 128x64 / 128x128 / 256x256 tiles only");
         return -1;
     }
+    // (own_step = 0: the stored gradients are what a later side job steps, so they obey the same rules as stepped ones)
+    if (!flat_weight_gradients(args, n, adamw, "skyemb_gemm_group_plan_side_adamw")) return -1;
     skyemb_adamw_desc d = *adamw;
     d.enabled = own_step ? 1 : 0;
     memcpy((char *)blob_host + GROUP_ADAMW_OFFSET, &d, sizeof d);

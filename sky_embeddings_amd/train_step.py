@@ -99,7 +99,9 @@ class TrainStep:
         engine.enable_wgrad_overlap(wgrad_overlap)   # weight-gradient GEMMs on a side stream (a parallel graph branch)
         # DDP mean of per-rank gradients, and the backward pass's static loss scale divided out again (fp16 mode)
         if hasattr(engine, "plan_loss_scale"):     # fp16 mode: the scale of THIS batch size, before anything bakes it into a launch
-            engine.plan_loss_scale(engine.expected_masked_elements(batch_size, mask_ratio))
+            # ... and pinned (the setter turns auto planning off): the captured loss kernel and the fused launches' grad_scale keep
+            # this value, so a forward pass the step does not own (an eager validation batch of another size) must not re-plan it
+            engine.loss_scale = engine.plan_loss_scale(engine.expected_masked_elements(batch_size, mask_ratio))
         optimizer.base_grad_scale = 1.0 / world_size
         # stage list: [(callable, [(start, end) slices of the flat gradient buffer final after it])]
         if n_encoder_groups is None:
@@ -291,12 +293,14 @@ class TrainStep:
         """Slices of the flat buffers the fused launches of THIS step's workspace do not update (the ordinary kernel takes them)."""
         if self._rest_ranges is None:
             eng = self.engine
-            w = eng._ws[eng._last_key()]                       # the workspace forward_train has just run on
+            w = eng._ws[self._ws_key]                          # the workspace this step's forward_train has just run on
             fused = eng.fused_adamw_ranges(w)
             bounds = [0] + [b for r in fused for b in r] + [eng.store.n]
             self._rest_ranges = [(bounds[i], bounds[i + 1]) for i in range(0, len(bounds), 2) if bounds[i] < bounds[i + 1]]
-            self._rest_key = eng._last_key()
-        assert self._rest_key == self.engine._last_key(), "TrainStep: the batch shape changed under a fused optimiser step"
+            self._rest_key = self._ws_key
+        # (keyed on the step's own forward, not on engine._last_key(): an eager forward_train on another batch shape between two
+        # steps moves the latter)
+        assert self._rest_key == self._ws_key, "TrainStep: the batch shape changed under a fused optimiser step"
         return self._rest_ranges
 
     def _forward(self):
@@ -309,11 +313,13 @@ class TrainStep:
                 ops.simmim_mask_from_noise(self.mask_noise, self.ratio_u, float(self.max_mask_ratio), cfg.grid, cfg.patch_size,
                                            self.pixel_mask)
             self.loss, self.pred, self.mask = self.engine.forward_train(self.imgs, mask=self.pixel_mask, ra_dec=self.ra_dec)
+            self._ws_key = self.engine._last_key()
             return
         # utils/mim_vit.py:363 draws the masking noise inside forward; keep it inside the step
         if not self.external_noise:
             self.noise.uniform_()
         self.loss, self.pred, self.mask = self.engine.forward_train(self.imgs, self.mask_ratio, self.noise, ra_dec=self.ra_dec)
+        self._ws_key = self.engine._last_key()                 # (the workspace of THIS step's batch: _rest())
 
     def load_batch(self, imgs, mask=None, ra_dec=None):
         """Stage the next minibatch (device or pinned host tensors) into the static input buffers."""
