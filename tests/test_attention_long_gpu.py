@@ -5,14 +5,18 @@ kernel read (the 16-bit operands rounded first):
   backward without atomics or workspace);
 - fp32, and every other head dim: the streaming fp32 kernels of csrc/attention.hip;
 - the attention pool past 256 tokens (csrc/attnpool.hip, token loop in chunks).
-Bars are those of tests/test_kernels_gpu.py::test_attention: relative L2 error 6e-3 for 16-bit, 3e-6 for fp32.
+Bars are those of tests/test_kernels_gpu.py::test_attention: relative L2 error 6e-3 for 16-bit, 3e-6 for fp32; on top of them
+every element of out, dq, dk and dv must meet the derived elementwise bar of tests/attention_reference.py, and the operands
+sit in the guarded buffers of tests/test_attention_core_gpu.py (NaN around the inputs, a sentinel around the outputs).
 """
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+from tests import attention_reference as ar
 from tests.helpers import record_parity
+from tests.test_attention_core_gpu import guarded_in, guarded_out, guards_intact
 
 DEV = "cuda"
 DTYPES = [torch.bfloat16, torch.float16, torch.float32]
@@ -48,27 +52,39 @@ def reference(qkv, dout, H, hd):
     return o.detach(), x.grad
 
 
-def run(ops, qkv, dout, H, hd, dtype):
+def run(ops, qkv, dout, H, hd, dtype, guards=None):
+    """Inputs inside NaN, outputs NaN inside a sentinel (guards[...] = whether the sentinel survived)."""
     B, N, _ = qkv.shape
     D = H * hd
-    qd, dd = qkv.to(DEV, dtype), dout.to(DEV, dtype)
-    out = torch.full((B, N, D), float("nan"), device=DEV, dtype=dtype)
-    dqkv = torch.full((B, N, 3 * D), float("nan"), device=DEV, dtype=dtype)
+    qd, dd = guarded_in(qkv, dtype, 3 * D), guarded_in(dout, dtype, D)
+    ob, out, po = guarded_out((B, N, D), dtype, D)
+    gb, dqkv, pg = guarded_out((B, N, 3 * D), dtype, 3 * D)
     ops.mha_fwd(qd, out, B, N, H, hd)
     ops.mha_bwd(qd, dd, dqkv, B, N, H, hd)
     torch.cuda.synchronize()
+    if guards is not None:
+        guards.update(out=guards_intact(ob, po, out.numel()), dqkv=guards_intact(gb, pg, dqkv.numel()))
     return qd, dd, out, dqkv
 
 
 def check(ops, name, qkv, dout, H, hd, dtype, f32_tol=None):
-    qd, dd, out, dqkv = run(ops, qkv, dout, H, hd, dtype)
+    guards = {}
+    qd, dd, out, dqkv = run(ops, qkv, dout, H, hd, dtype, guards)
+    assert all(guards.values()), (name, "write outside out / dqkv", guards)
     assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(dqkv).all()), f"{name}: inf / NaN or unwritten elements"
     o_r, g_r = reference(qd.cpu(), dd.cpu(), H, hd)
     e_o, e_g = relerr(out, o_r), relerr(dqkv, g_r)
-    record_parity(f"attention_long[{name}]", {"out": e_o, "dqkv": e_g})
+    c = ar.core(qd.cpu().float(), dd.cpu().float(), H, hd)
+    bars = ar.bars(c, dtype)
+    B, N, D = out.shape
+    g = dqkv.double().cpu().reshape(B, N, 3, D)
+    got = {"out": out.double().cpu(), "dq": g[:, :, 0], "dk": g[:, :, 1], "dv": g[:, :, 2]}
+    ratios = {n: ar.worst((got[n] - c["ref"][n]).abs(), bars[n]) for n in ar.NAMES}
+    record_parity(f"attention_long[{name}]", {"out": e_o, "dqkv": e_g, "err/bar": max(ratios.values())})
     bar = f32_tol if (f32_tol is not None and dtype == torch.float32) else tol(dtype)
     assert e_o < bar, (name, "out", e_o)
     assert e_g < bar, (name, "dqkv", e_g)
+    assert all(r <= 1.0 for r in ratios.values()), (name, "elementwise bar", ratios)
 
 
 def inputs(B, N, H, hd, seed):
