@@ -12,7 +12,6 @@
 //             dQ^T = K^T . dS^T (sum over j),   dK^T = Q^T . dS,   dV^T = dO^T . P  (sum over i)
 // qkv layout is the reference's [B, N, 3, H, hd] (timm Attention: qkv(x).reshape(B,N,3,H,hd)); softmax statistics,
 // probabilities and dS are fp32, rounded to bf16 only as MFMA operands.
-#include <mutex>
 #include "lp_twin.h"
 #include <stdlib.h>
 
@@ -590,22 +589,9 @@ template <int HD, int NT>
 int launch_strip(bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st) {
     const dim3 grid(B * H), block(64 * NT);
     const int smem = (bwd ? 4 : 2) * (((N + 3) & ~3) + 4) * (HD + 8) * 2;
-    if (smem > 65536) {
-        // one flag per instantiation AND device: the dynamic-LDS limit is an attribute of the function per device
-        static std::mutex attr_mutex;
-        static bool attr_done[64] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)mha_bwd_strip_kernel<HD, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               4 * (32 * NT + 4) * (HD + 8) * 2);     // the longest sequence of this instance
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_mha: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
+    if (smem > 65536) {   // (limit: the longest sequence of this instance)
+        if (const int rc = sky_set_lds_limit((const void *)mha_bwd_strip_kernel<HD, NT>, 4 * (32 * NT + 4) * (HD + 8) * 2, "skyemb_mha"))
+            return rc;
     }
     if (!bwd) hipLaunchKernelGGL((mha_fwd_strip_kernel<HD, NT>), grid, block, smem, st, x, out, B, N, H);
     else hipLaunchKernelGGL((mha_bwd_strip_kernel<HD, NT>), grid, block, smem, st, x, dout, out, B, N, H);

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <mutex>
+#include <set>
+#include <utility>
 
 #include "../../include/skyemb.h"
 
@@ -53,6 +56,24 @@ void skyemb_count_gemm(int slot);   // api.cpp: diagnostic launch counters, see 
             return 2;                                                                 \
         }                                                                             \
     } while (0)
+
+// Raises the dynamic-LDS limit of kernel `kern` to `bytes`, once per (kernel, device): the limit is an attribute of the function
+// PER DEVICE.  Thread-safe.  Returns 0, or 2 with "<who>: hipFuncSetAttribute(...)" as the library's error.
+inline int sky_set_lds_limit(const void *kern, int bytes, const char *who) {
+    static std::mutex mutex;
+    static std::set<std::pair<const void *, int>> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mutex);
+    if (done.count({kern, dev})) return 0;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        skyemb_set_error("%s: hipFuncSetAttribute(%d B LDS): %s", who, bytes, hipGetErrorString(e));
+        return 2;
+    }
+    done.insert({kern, dev});
+    return 0;
+}
 
 template <typename T>
 __device__ __forceinline__ float to_f32(T v);

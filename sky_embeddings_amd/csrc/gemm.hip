@@ -12,7 +12,6 @@
 //
 // Block = 256 threads = 4 waves (2x2), tile BM x BN in {128x128, 64x64}, BK = 64 (bf16) / 16 (f32),
 // register-staged global->LDS double buffer (one barrier per k-tile).
-#include <mutex>
 #include "lp_twin.h"
 #include <stdlib.h>
 
@@ -266,22 +265,7 @@ int launch(const skyemb_gemm_args &g, hipStream_t st) {
     constexpr size_t smem =
         2 * (size_t)(TileShape<T, A_KC, BM>::ELEMS + TileShape<T, B_KC, BN>::ELEMS) * sizeof(T);
     auto kern = gemm_kernel<T, BM, BN, A_KC, B_KC>;
-    // the dynamic-LDS limit is an attribute of the function PER DEVICE
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_gemm: hipFuncSetAttribute(%zu B LDS): %s", smem, hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
-    }
+    if (const int rc = sky_set_lds_limit((const void *)kern, (int)smem, "skyemb_gemm")) return rc;
     const int64_t tiles = ceil_div64(g.M, BM) * ceil_div64(g.N, BN);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), smem, st, g);
     skyemb_count_gemm(SKYEMB_GEMM_COUNT_FALLBACK);

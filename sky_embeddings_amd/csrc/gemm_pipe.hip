@@ -693,10 +693,28 @@ __global__ __launch_bounds__(WM * WN * WK * 64) void gemm_pipe_kernel(const skye
 // split-K or its reduce launch, and a small dgrad no longer leaves most CUs idle).  One tile shape per launch; the
 // problems may be of different operand-layout classes (CLASSES = bit mask of the classes compiled into this instance:
 // 1 KC.KC, 2 KC.RC, 4 RC.RC, 8 RC.KC).
-// blob = [int32 n, total_blocks, 6 x pad, start[0..n] (multiples of 8), ...pad to 256 B][n x skyemb_gemm_args]
-constexpr int GROUP_HEADER_BYTES = 256, GROUP_MAX = 32;
-constexpr int GROUP_ADAMW_OFFSET = 176;                  // skyemb_adamw_desc (80 bytes) ends the 256-byte header
-static_assert(sizeof(skyemb_adamw_desc) == 80, "the blob header reserves 80 bytes for the fused-AdamW descriptor");
+// blob = [GroupHeader, 256 B][n x skyemb_gemm_args][skyemb_ln_bwd_side, 128 B reserved].  The host plans write the header through
+// the struct; the kernels read it as int words (hdr[0], hdr[1], ...), which the static_assert pins to the struct.
+constexpr int GROUP_MAX = 32;
+struct GroupHeader {
+    int32_t n;                          // word 0: problem count
+    int32_t total;                      // word 1: workgroups of the launch (padded tiles + side workgroups) | GROUP_XCD_ORDER
+    int32_t side_first;                 // word 2: first side workgroup
+    int32_t side_adamw_wgs;             // word 3: side workgroups of the optimiser job
+    int64_t side_lo, side_hi;           // words 4-7: the optimiser job's slice [lo, hi) of the flat buffers
+    int32_t starts[GROUP_MAX + 1];      // words 8-40: first tile of each problem (multiples of 8); starts[n] = padded tile total
+    int32_t ln_count;                   // word 41: LayerNorm side workgroups
+    int32_t ln_offset;                  // word 42: byte offset of the skyemb_ln_bwd_side record in the blob
+    int32_t unused;
+    skyemb_adamw_desc adamw;            // the fused or side optimiser step
+};
+constexpr int GROUP_XCD_ORDER = 1 << 30;   // word 1: tiles in per-XCD order (gemm_pipe_group_kernel)
+constexpr int GROUP_HEADER_BYTES = sizeof(GroupHeader), GROUP_ADAMW_OFFSET = offsetof(GroupHeader, adamw);
+constexpr int GROUP_LN_COUNT_WORD = offsetof(GroupHeader, ln_count) / 4, GROUP_LN_OFFSET_WORD = offsetof(GroupHeader, ln_offset) / 4;
+static_assert(offsetof(GroupHeader, total) == 4 && offsetof(GroupHeader, side_first) == 8 && offsetof(GroupHeader, side_adamw_wgs) == 12 &&
+                  offsetof(GroupHeader, side_lo) == 16 && offsetof(GroupHeader, starts) == 32 && GROUP_LN_COUNT_WORD == 41 &&
+                  GROUP_LN_OFFSET_WORD == 42 && GROUP_ADAMW_OFFSET == 176 && GROUP_HEADER_BYTES == 256,
+              "the kernels read the header by these word indices and byte offsets");
 
 // SIDE job of a grouped weight-gradient launch (skyemb_gemm_group_plan_side_adamw): the workgroups behind the launch's tiles
 // (header words 2 / 3: first side workgroup, their count) stream the AdamW step of ANOTHER slice of the flat buffers -- [lo, hi),
@@ -709,7 +727,7 @@ static_assert(sizeof(skyemb_adamw_desc) == 80, "the blob header reserves 80 byte
 template <int THREADS, int U>
 __device__ __forceinline__ void side_adamw_job(const char *__restrict__ blob, const int wg, const int nwg) {
     const skyemb_adamw_desc *ad = (const skyemb_adamw_desc *)(blob + GROUP_ADAMW_OFFSET);
-    const long long *range = (const long long *)(blob + 16);
+    const long long *range = (const long long *)(blob + offsetof(GroupHeader, side_lo));
     const int64_t lo = range[0], hi = range[1];
     const float lr = ad->hyper[0], bc1 = ad->hyper[1], bc2 = ad->hyper[2];
     const SkyAdamScalars sc = sky_adam_scalars(lr, bc1, bc2, ad->beta1, ad->beta2, ad->eps, ad->weight_decay, ad->grad_scale);
@@ -755,7 +773,6 @@ __device__ __forceinline__ void side_adamw_job(const char *__restrict__ blob, co
 // block's norm1, which needs the qkv data gradient only -- taken by side workgroups (header word 41 = their count, word 42 = byte
 // offset of the skyemb_ln_bwd_side record in the blob; they come before the optimiser's).  A workgroup of W waves is W / 4 blocks of
 // the stand-alone kernel's partial-sum table (ln_bwd_body.h): same rows, same sums, same bits.
-constexpr int GROUP_LN_COUNT_WORD = 41, GROUP_LN_OFFSET_WORD = 42;
 __host__ __device__ inline int sky_ln_bwd_blocks(int M) {   // == skyemb_layernorm_bwd_blocks (layernorm.hip)
     int nb = (M + 3) / 4;
     if (nb < 1) nb = 1;
@@ -893,27 +910,100 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const skyemb_gemm_ar
     }
 }
 
+// ---- launch shapes ------------------------------------------------------------------------------------------------------------
+// One row per tile shape of the product: X(NAME, variant, BM, BN, NSTAGE, WM, WN, WK, FORMS, LN_MAX).  The tile's ABI code
+// (skyemb_gemm_args.tile, skyemb_gemm_group_info.tile) is NAME = variant * 1,000,000 + BM * 1000 + BN.  Every row is built for
+// single launches (skyemb_gemm) in the operand layouts its loader stages (dispatch); FORMS lists the grouped launches built on it:
+enum TileForm : int {
+    GROUPED = 1,   // grouped launches of one operand-layout class (class masks 1, 2, 4)
+    MIXED = 2,     // ... and of data gradients with weight gradients (mask 6: KC.RC + RC.RC)
+    ADAMW = 4,     // weight-gradient groups with the AdamW step in the epilogue (skyemb_gemm_group_plan_adamw)
+    SIDE = 8,      // weight-gradient groups with side jobs (skyemb_gemm_group_plan_side_adamw, _attach_ln_bwd)
+    OWN256 = 16,   // the 256 x 256 tile: kernels of its own (gemm_pipe256.h), 512 threads, all of the LDS
+};
+// LN_MAX = the widest LayerNorm row a side workgroup carries (side_job's MAXNV x 256 in the instance).
+// LDS per workgroup = NSTAGE * (BM + BN) * 128 B, which fixes the workgroups per CU (160 KiB): 64x64 x3 = 48 KB -> 3, x2 = 32 KB -> 5
+// (code 6064064, tuned table);
+// 128x64 x3 = 72 KB -> 2, x2 = 48 KB -> 3 (code 6128064: the decoder's [4352 x 2048] launches, tuned table);
+// 128x128 x3 = 96 KB -> 1, x2 = 64 KB -> 2; 256x128 x3 = 144 KB -> 1.  The 128x128 tile ships with the
+// 2-stage ring: two resident workgroups (16 waves) cover each other's barriers, which a third stage did not (ViT-L shapes,
+// tools/ubench/gemm_lab with LAB_VITL=1: [8320 x 3072 x 1024] 93 us on 128x64, 86 us on 128x128 x3, 74 us on 128x128 x2).
+// Variant 9 = two k-groups of waves per workgroup (WK = 2); the 144-row tiles step by tile_stride_m rows.
+#define SKY_GEMM_PRODUCT_TILES(X)                                                   \
+    X(T64x64, 0, 64, 64, 3, 2, 2, 1, GROUPED | MIXED | ADAMW | SIDE, 768)           \
+    X(T128x64, 0, 128, 64, 3, 4, 2, 1, GROUPED | MIXED | ADAMW | SIDE, 768)         \
+    X(T128x128, 0, 128, 128, 2, 4, 2, 1, GROUPED | MIXED | ADAMW | SIDE, 768)       \
+    X(T256x128, 2, 256, 128, 3, 4, 4, 1, 0, 0)                                      \
+    X(T128x64_2STAGE, 6, 128, 64, 2, 4, 2, 1, 0, 0)                                 \
+    X(T64x64_2STAGE, 6, 64, 64, 2, 2, 2, 1, 0, 0)                                   \
+    X(T64x64_WK2, 9, 64, 64, 3, 2, 2, 2, 0, 0)                                      \
+    X(T128x128_WK2, 9, 128, 128, 2, 4, 2, 2, GROUPED, 0)                            \
+    X(T144x64_WK2, 9, 144, 64, 3, 3, 2, 2, 0, 0)                                    \
+    X(T144x256, 13, 144, 256, 3, 3, 4, 1, 0, 0)                                     \
+    X(T256x256, 0, 256, 256, 0, 4, 2, 1, OWN256 | GROUPED | ADAMW | SIDE, 1024)
+// experiment builds (tools/ubench/gemm_lab.hip, -DSKY_GEMM_LAB) add single-launch rows X(variant, BM, BN, NSTAGE, WM, WN, WK)
+// through SKY_GEMM_LAB_VARIANTS
+
+enum TileCode : int {
+#define X(NAME, V, BM_, BN_, ...) NAME = V * 1000000 + BM_ * 1000 + BN_,
+    SKY_GEMM_PRODUCT_TILES(X)
+#undef X
+};
+constexpr int kLegacyTiles[][2] = {{64, T64x64}, {128, T128x128}, {12864, T128x64}};   // codes of the round-1 ABI
+
+struct TileDesc {
+    int code, bm, bn, stride_m, nstage, wm, wn, wk, forms, ln_max;
+    int threads() const { return wm * wn * wk * 64; }
+};
+constexpr TileDesc kTiles[] = {
+#define X(NAME, V, BM_, BN_, NS, WM_, WN_, WK_, FORMS, LN) {NAME, BM_, BN_, tile_stride_m(BM_, BN_), NS, WM_, WN_, WK_, FORMS, LN},
+    SKY_GEMM_PRODUCT_TILES(X)
+#undef X
+#ifdef SKY_GEMM_LAB
+#define X(V, BM_, BN_, NS, WM_, WN_, WK_) {V * 1000000 + BM_ * 1000 + BN_, BM_, BN_, tile_stride_m(BM_, BN_), NS, WM_, WN_, WK_, 0, 0},
+    SKY_GEMM_LAB_VARIANTS(X)
+#undef X
+#endif
+};
+
+int canonical_tile(int tile) {
+    for (const auto &a : kLegacyTiles)
+        if (tile == a[0]) return a[1];
+    return tile;
+}
+const TileDesc *find_tile(int code) {   // nullptr: no such tile
+    for (const TileDesc &d : kTiles)
+        if (d.code == code) return &d;
+    return nullptr;
+}
+
+// LDS of a ring-tile workgroup: the k-loop ring or the epilogue's output image (+ column sums of the two k-groups), the larger
+constexpr size_t ring_tile_lds(int bm, int bn, int nstage, int wk) {
+    const size_t ring = (size_t)nstage * (bm + bn) * BK * 2 * wk, image = (size_t)bm * (bn * 4 + 16) + (wk > 1 ? bm * 4 : 0);
+    return ring > image ? ring : image;
+}
+
+// The GEMM's environment switches (diagnostic switches), read once per process.  SKYEMB_GROUP_XCD_ORDER is read
+// per plan instead (skyemb_gemm_group_plan): bench.py builds both tile orders in one process for its interleaved A/B.
+struct GemmSwitches {
+    bool tuned, t256, tail, group256, prefetch_wgs;
+    int tile, group_tile;
+};
+const GemmSwitches &gemm_switches() {
+    static const GemmSwitches s = []() {
+        auto on = [](const char *name) { const char *e = getenv(name); return !(e && e[0] == '0'); };
+        auto code = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; };
+        return GemmSwitches{on("SKYEMB_GEMM_TUNED"), on("SKYEMB_GEMM_256"), on("SKYEMB_GEMM_TAIL"), on("SKYEMB_GROUP_256"),
+                            on("SKYEMB_PREFETCH_WGS"), code("SKYEMB_GEMM_TILE"), code("SKYEMB_GROUP_TILE")};
+    }();
+    return s;
+}
+
 template <int BM, int BN, bool A_KC, bool B_KC, int NSTAGE, int WM, int WN, int WK>
 int launch_n(const skyemb_gemm_args &g, hipStream_t st) {
-    constexpr size_t ring = (size_t)NSTAGE * (BM + BN) * BK * 2 * WK, image = (size_t)BM * (BN * 4 + 16) + (WK > 1 ? BM * 4 : 0);   // k-loop ring / epilogue tile (+ column sums)
-    constexpr size_t smem = ring > image ? ring : image;
+    constexpr size_t smem = ring_tile_lds(BM, BN, NSTAGE, WK);
     auto kern = gemm_pipe_kernel<BM, BN, A_KC, B_KC, NSTAGE, WM, WN, WK>;
-    // the dynamic-LDS limit is an attribute of the function PER DEVICE
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_gemm(pipe): hipFuncSetAttribute(%zu B LDS): %s", smem, hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
-    }
+    if (const int rc = sky_set_lds_limit((const void *)kern, (int)smem, "skyemb_gemm(pipe)")) return rc;
     const int64_t tiles = ceil_div64(g.M, tile_stride_m(BM, BN)) * ceil_div64(g.N, BN);
     const int S = g.split_k > 1 ? g.split_k : 1;
     // the prefetch hint goes to workgroups of its own where the tiles leave slots of the device free (prefetch_job), else it stays
@@ -921,10 +1011,12 @@ int launch_n(const skyemb_gemm_args &g, hipStream_t st) {
     skyemb_gemm_args gl = g;
     gl.prefetch_wgs = 0;
     if (g.prefetch != nullptr && g.prefetch_bytes >= 4) {
+        static std::mutex slots_mutex;
         static int slots[64] = {};
-        static const bool hint_wgs_on = []() { const char *e = getenv("SKYEMB_PREFETCH_WGS"); return !(e && e[0] == '0'); }();
+        int dev = 0;
+        (void)hipGetDevice(&dev);
         {
-            std::lock_guard<std::mutex> lock(attr_mutex);
+            std::lock_guard<std::mutex> lock(slots_mutex);
             if (slots[dev & 63] == 0) {
                 int per_cu = 0, cus = 0;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, WM * WN * WK * 64, smem) != hipSuccess) per_cu = 1;
@@ -933,7 +1025,7 @@ int launch_n(const skyemb_gemm_args &g, hipStream_t st) {
             }
         }
         const int64_t free_slots = slots[dev & 63] - tiles * S;
-        if (hint_wgs_on && free_slots >= 8) gl.prefetch_wgs = (int)(free_slots < 32 ? free_slots : 32);
+        if (gemm_switches().prefetch_wgs && free_slots >= 8) gl.prefetch_wgs = (int)(free_slots < 32 ? free_slots : 32);
     } else {
         gl.prefetch = nullptr;
         gl.prefetch_bytes = 0;
@@ -974,44 +1066,25 @@ int dispatch(const skyemb_gemm_args &g, hipStream_t st) {
     return 1;
 }
 
-// Launch shapes.  code = variant * 1,000,000 + BM * 1000 + BN; X(variant, BM, BN, NSTAGE, WM, WN, WK).
-// LDS per workgroup = NSTAGE * (BM + BN) * 128 B, which fixes the workgroups per CU (160 KiB): 64x64 x3 = 48 KB -> 3, x2 = 32 KB -> 5
-// (code 6064064, tuned table);
-// 128x64 x3 = 72 KB -> 2, x2 = 48 KB -> 3 (code 6128064: the decoder's [4352 x 2048] launches, tuned table);
-// 128x128 x3 = 96 KB -> 1, x2 = 64 KB -> 2; 256x128 x3 = 144 KB -> 1.  The 128x128 tile ships with the
-// 2-stage ring: two resident workgroups (16 waves) cover each other's barriers, which a third stage did not (ViT-L shapes,
-// tools/ubench/gemm_lab with LAB_VITL=1: [8320 x 3072 x 1024] 93 us on 128x64, 86 us on 128x128 x3, 74 us on 128x128 x2).
-#define SKY_GEMM_PRODUCT_VARIANTS(X) \
-    X(0, 64, 64, 3, 2, 2, 1)         \
-    X(0, 128, 64, 3, 4, 2, 1)        \
-    X(0, 128, 128, 2, 4, 2, 1)       \
-    X(2, 256, 128, 3, 4, 4, 1)       \
-    X(6, 128, 64, 2, 4, 2, 1)        \
-    X(6, 64, 64, 2, 2, 2, 1)         \
-    X(9, 64, 64, 3, 2, 2, 2)         \
-    X(9, 128, 128, 2, 4, 2, 2)       \
-    X(9, 144, 64, 3, 3, 2, 2)        \
-    X(13, 144, 256, 3, 3, 4, 1)
-#ifdef SKY_GEMM_LAB   // experiment builds (tools/ubench/gemm_lab.hip): every shape under study
-#define SKY_GEMM_VARIANTS(X) SKY_GEMM_PRODUCT_VARIANTS(X) SKY_GEMM_LAB_VARIANTS(X)
-#else
-#define SKY_GEMM_VARIANTS(X) SKY_GEMM_PRODUCT_VARIANTS(X)
-#endif
-
-int dispatch_code(int code, const skyemb_gemm_args &g, hipStream_t st) {
-#define X(V, BM_, BN_, NS, WM_, WN_, WK_) \
-    if (code == V * 1000000 + BM_ * 1000 + BN_) return dispatch<BM_, BN_, NS, WM_, WN_, WK_>(g, st);
-    SKY_GEMM_VARIANTS(X)
+int gemm256_launch(const skyemb_gemm_args &g, hipStream_t st);   // gemm_pipe256.h
+template <int BM, int BN, int NSTAGE, int WM, int WN, int WK, int FORMS = 0>
+int launch_tile(const skyemb_gemm_args &g, hipStream_t st) {
+    if constexpr (FORMS & OWN256) return gemm256_launch(g, st);
+    else return dispatch<BM, BN, NSTAGE, WM, WN, WK>(g, st);
+}
+int launch_code(int code, const skyemb_gemm_args &g, hipStream_t st) {
+#define X(NAME, V, BM_, BN_, NS, WM_, WN_, WK_, FORMS, LN) \
+    if (code == NAME) return launch_tile<BM_, BN_, NS, WM_, WN_, WK_, FORMS>(g, st);
+    SKY_GEMM_PRODUCT_TILES(X)
 #undef X
+#ifdef SKY_GEMM_LAB
+#define X(V, BM_, BN_, NS, WM_, WN_, WK_) \
+    if (code == V * 1000000 + BM_ * 1000 + BN_) return launch_tile<BM_, BN_, NS, WM_, WN_, WK_>(g, st);
+    SKY_GEMM_LAB_VARIANTS(X)
+#undef X
+#endif
     skyemb_set_error("skyemb_gemm(pipe): unknown tile code %d", code);
     return 1;
-}
-void tile_dims(int code, int &bm, int &bn) {   // bm = the row STRIDE of the tiles (136 for the 144-row image)
-    bn = code % 1000;
-    bm = tile_stride_m((code % 1000000) / 1000, bn);
-}
-int canonical_tile(int tile) {   // legacy codes of the round-1 ABI
-    return tile == 64 ? 64064 : tile == 128 ? 128128 : tile == 12864 ? 128064 : tile;
 }
 
 #include "gemm_pipe256.h"
@@ -1023,37 +1096,54 @@ const TunedGemm kTuned[] = {
 #include "gemm_tuned.h"
     {0, 0, 0, 0, 0, 0, 0}};
 
-}  // namespace
+// ---- single launches: a plan (host logic only), then its launches ------------------------------------------------------------
+struct GemmPart {
+    int tile, split_k, row0, rows;    // tile code, split-K factor, output rows [row0, row0 + rows)
+};
+struct GemmPlan {
+    int status = -1;                  // 0: launch part[0..n); -1: outside the pipelined subset (gemm.hip's kernel takes it); 1: refused
+    int n = 0;
+    GemmPart part[2];                 // the main launch and, where it pays, a row tail
+};
 
-// returns -1 when the problem is outside the fast-path subset (caller falls back to gemm.hip)
-int SKY_TWIN(skyemb_gemm_pipe_try)(const skyemb_gemm_args &g_in, hipStream_t st) {
-    skyemb_gemm_args g = g_in;
-    if (g.dtype != SKY_LP_DTYPE || g.K % BK != 0 || g.N % 8 != 0) return -1;
+// split-K for a launch of `tiles` tiles (deterministic slabs + a reduce launch that applies the epilogue): launches with too few
+// tiles to fill the chip.  want > 1 asks for that factor; the workspace bounds either.
+int split_factor(const skyemb_gemm_args &g, int64_t M, int64_t tiles, int want, int min_steps) {
+    const int KT = g.K / BK;
+    int S = want > 1 ? want : (int)(768 / tiles);
+    if (S > 8) S = 8;
+    if (want <= 1 && S > KT / min_steps) S = KT / min_steps;
+    if (S > KT) S = KT;
+    while (S > 1 && (int64_t)S * (M * g.N + M) * 4 > g.ws_bytes) --S;
+    return S < 1 ? 1 : S;
+}
+
+// Everything skyemb_gemm_pipe_try decides: which problems the pipelined kernels take, the tile, split-K and a row tail.  No HIP calls.
+GemmPlan plan_single(const skyemb_gemm_args &g) {
+    GemmPlan plan;
+    if (g.dtype != SKY_LP_DTYPE || g.K % BK != 0 || g.N % 8 != 0) return plan;
     // alignment of the vectorised epilogue operands
-    if ((g.ldo32 % 4) || (g.ldo % 8) || (g.ldo2 % 8) || (g.ldr % 4) || (g.ldt % 4) || (g.ldaux % 8)) return -1;
+    if ((g.ldo32 % 4) || (g.ldo % 8) || (g.ldo2 % 8) || (g.ldr % 4) || (g.ldt % 4) || (g.ldaux % 8)) return plan;
     if (!aligned16(g.out) || !aligned16(g.out2) || !aligned16(g.aux) || !aligned16(g.out_f32) || !aligned16(g.resid) ||
         !aligned16(g.bias) || !aligned16(g.table))
-        return -1;
-    if (g.a_layout == SKYEMB_KC ? g.M < 1 : (g.M % 8 != 0 || g.M < 8)) return -1;
-    if (g.b_layout == SKYEMB_KC ? g.N < 1 : (g.N % 8 != 0 || g.N < 8)) return -1;
+        return plan;
+    if (g.a_layout == SKYEMB_KC ? g.M < 1 : (g.M % 8 != 0 || g.M < 8)) return plan;
+    if (g.b_layout == SKYEMB_KC ? g.N < 1 : (g.N % 8 != 0 || g.N < 8)) return plan;
+    const GemmSwitches &sw = gemm_switches();
+    const bool a_kc = g.a_layout == SKYEMB_KC;
+    const int KT = g.K / BK;
     int tile = canonical_tile(g.tile);
     int want_split = g.split_k;
-    if (tile == 0 && want_split == 0) {
+    if (tile == 0 && want_split == 0 && sw.tuned) {
         // launch shapes tuned on hardware (tools/gemm_tune.py); anything else goes through the heuristic below
-        static const bool use_table = []() { const char *e = getenv("SKYEMB_GEMM_TUNED"); return !(e && e[0] == '0'); }();
-        if (use_table)
-            for (const TunedGemm *t = kTuned; t->M; ++t)
-                if (t->M == g.M && t->N == g.N && t->K == g.K && t->a_kc == (g.a_layout == SKYEMB_KC) &&
-                    t->b_kc == (g.b_layout == SKYEMB_KC) && (t->split == 1 || g.ws)) {
-                    tile = canonical_tile(t->tile);
-                    want_split = t->split;
-                    break;
-                }
+        for (const TunedGemm *t = kTuned; t->M; ++t)
+            if (t->M == g.M && t->N == g.N && t->K == g.K && t->a_kc == a_kc && t->b_kc == (g.b_layout == SKYEMB_KC) && (t->split == 1 || g.ws)) {
+                tile = canonical_tile(t->tile);
+                want_split = t->split;
+                break;
+            }
     }
-    if (tile == 0) {
-        static const int env_tile = []() { const char *e = getenv("SKYEMB_GEMM_TILE"); return e ? atoi(e) : 0; }();   // experiments
-        tile = canonical_tile(env_tile);
-    }
+    if (tile == 0) tile = canonical_tile(sw.tile);   // (experiments)
     // measured: the 64x64 tile (3 workgroups per CU) is the best all-round choice at ViT-B sizes; launches with several
     // full rounds of 128x64 tiles (ViT-L token counts) gain ~5 % from the larger tile's lower L2->LDS traffic
     // (from 4 rounds on with long k-loops: ViT-L data gradients and fc2, 12-19 % in tools/gemm_tune.py --model mim19)
@@ -1065,104 +1155,103 @@ int SKY_TWIN(skyemb_gemm_pipe_try)(const skyemb_gemm_args &g_in, hipStream_t st)
     // matrix pipe and load pipe side by side on every SIMD).  Taken when the tile count is within a sixth of whole rounds of 256 --
     // a few tiles over are cut off as a row tail below, a few under leave CUs idle for one round -- and the epilogue is one the
     // kernel has (no row maps, column sums or split-K).
-    static const bool t256_on = []() { const char *e = getenv("SKYEMB_GEMM_256"); return !(e && e[0] == '0'); }();
-    if (tile == 0 && t256_on && g_in.split_k <= 1 && gemm256_applicable(g)) {
+    if (tile == 0 && sw.t256 && g.split_k <= 1 && gemm256_applicable(g)) {
         const int64_t R = ceil_div64(g.M, 256), C = ceil_div64(g.N, 256), T = R * C;
         const int64_t over = T % 256;                     // tiles beyond whole rounds
         const bool tail_ok = over > 0 && over <= C && (R - 1) * C % 256 == 0 &&              // the last row block alone is the excess
-                             (g.ws || ((g.K / BK) % 2 == 0 && g.K <= 2048 && ceil_div64(g.M - (R - 1) * 256, 64) * ceil_div64(g.N, 64) <= 256));
-        if (T >= 512 && g.N % 256 == 0 && (over == 0 || over >= 214 || tail_ok)) tile = 256256;
+                             (g.ws || (KT % 2 == 0 && g.K <= 2048 && ceil_div64(g.M - (R - 1) * 256, 64) * ceil_div64(g.N, 64) <= 256));
+        if (T >= 512 && g.N % 256 == 0 && (over == 0 || over >= 214 || tail_ok)) tile = T256x256;
     }
-    if (tile == 0 && g.a_layout == SKYEMB_KC && ((t128 >= 512 && g.K >= 2048) || (t128 >= 2048 && g.N >= 4096))) tile = 2256128;
-    if (tile == 0 && (t128 >= 1024 || (t128 >= 512 && g.K >= 1024))) tile = 128128;   // >= 2 rounds of 2 workgroups per CU
-    if (tile == 0 && (t12864 >= 2048 || (t12864 >= 1024 && g.K >= 1024))) tile = 128064;
-    if (tile == 0) tile = 64064;
+    if (tile == 0 && a_kc && ((t128 >= 512 && g.K >= 2048) || (t128 >= 2048 && g.N >= 4096))) tile = T256x128;
+    if (tile == 0 && (t128 >= 1024 || (t128 >= 512 && g.K >= 1024))) tile = T128x128;   // >= 2 rounds of 2 workgroups per CU
+    if (tile == 0 && (t12864 >= 2048 || (t12864 >= 1024 && g.K >= 1024))) tile = T128x64;
+    if (tile == 0) tile = T64x64;
     // At most one 64x64 workgroup per CU: two k-groups of waves in the workgroup instead of an idle second wave slot per
     // SIMD (tools/ubench/gemm_lab: [1280 x 768] outputs 0.32 -> 0.20 us per k-step; K = 3072: 17.8 -> 14.3 us unsplit, where
     // the best one-group launch was a 2-way split-K plus its reduce launch).
-    static const bool wk2_on = []() { const char *e = getenv("SKYEMB_GEMM_WK2"); return !(e && e[0] == '0'); }();
-    if (wk2_on && tile == 64064 && g.tile == 0 && g_in.split_k <= 1 && g.a_layout == SKYEMB_KC && !g.colsum_a && (g.K / BK) % 2 == 0 &&
-        g.K / BK >= 4 && ceil_div64(g.M, 64) * ceil_div64(g.N, 64) <= 256) {
-        tile = 9064064;
+    if (tile == T64x64 && g.tile == 0 && g.split_k <= 1 && a_kc && !g.colsum_a && KT % 2 == 0 && KT >= 4 &&
+        ceil_div64(g.M, 64) * ceil_div64(g.N, 64) <= 256) {
+        tile = T64x64_WK2;
         want_split = 1;
     }
-    int bm, bn;
-    tile_dims(tile, bm, bn);
-    // split-K (deterministic slabs + a reduce launch that applies the epilogue) for launches with too few tiles to
-    // fill the chip.  The reduce launch costs ~5 us, so a split must leave >= 10-12 k-steps per workgroup.
-    int S = 1;
-    if (g.ws && want_split != 1) {
-        const int64_t tiles = ceil_div64(g.M, bm) * ceil_div64(g.N, bn);
-        const int KT = g.K / BK;
-        const int min_steps = (g.a_layout == SKYEMB_RC && g.b_layout == SKYEMB_RC) ? 10 : 12;
-        S = want_split > 1 ? want_split : (int)(768 / tiles);
-        if (S > 8) S = 8;
-        if (want_split <= 1 && S > KT / min_steps) S = KT / min_steps;
-        if (S > KT) S = KT;
-        while (S > 1 && (int64_t)S * ((int64_t)g.M * g.N + g.M) * 4 > g.ws_bytes) --S;
-        if (S < 1) S = 1;
+    const TileDesc *d = find_tile(tile);
+    if (!d) {
+        skyemb_set_error("skyemb_gemm(pipe): unknown tile code %d", tile);
+        plan.status = 1;
+        return plan;
     }
-    g.split_k = S;
+    // split-K: the reduce launch costs ~5 us, so a split must leave >= 10-12 k-steps per workgroup
+    int S = 1;
+    if (g.ws && want_split != 1)
+        S = split_factor(g, g.M, ceil_div64(g.M, d->stride_m) * ceil_div64(g.N, d->bn), want_split,
+                         (g.a_layout == SKYEMB_RC && g.b_layout == SKYEMB_RC) ? 10 : 12);
+    if (tile == T256x256) {
+        if (g.split_k > 1 || S > 1 || !(gemm256_applicable(g) || gemm256_wgrad_applicable(g))) {
+            skyemb_set_error("skyemb_gemm(256x256): the problem is outside this tile's subset (k-contiguous A, or a weight gradient of whole tiles; plain epilogue, K >= 128, no split-K)");
+            plan.status = 1;
+            return plan;
+        }
+    }
+    plan.status = 0;
+    plan.n = 1;
+    plan.part[0] = {tile, S, 0, g.M};
     // Row tail: with two 128x128 workgroups per CU a launch has 512 slots per round, and a few tiles more than whole rounds
     // (ViT-L: 65 row blocks of 128 token rows -> 520 / 1560 / 2080 tiles) cost a round of their own on 8-32 CUs while the
     // rest of the chip idles.  The row blocks that fill whole rounds go as one launch; the remaining rows as a second,
     // finely split launch (64x64 tiles, split-K) that is over in a fraction of a round.
-    static const bool tail_on = []() { const char *e = getenv("SKYEMB_GEMM_TAIL"); return !(e && e[0] == '0'); }();
-    if (tile == 256256 && (g_in.split_k > 1 || !(gemm256_applicable(g) || gemm256_wgrad_applicable(g)))) {
-        skyemb_set_error("skyemb_gemm(256x256): the problem is outside this tile's subset (k-contiguous A, or a weight gradient of whole tiles; plain epilogue, K >= 128, no split-K)");
-        return 1;
-    }
-    if (tile == 256256) S = g.split_k = 1;
     // (without a split-K workspace the tail must fit the one-launch two-k-group form)
-    const bool tail_wk2 = wk2_on && (g.K / BK) % 2 == 0 && g.K <= 2048;
-    if (tail_on && (tile == 128128 || tile == 2256128 || tile == 256256) && S == 1 && g.a_layout == SKYEMB_KC && (g.ws || tail_wk2) && !g.dst_row &&
-        !g.tab_row && !g.colsum_a) {
-        const int64_t bm_t = tile == 128128 ? 128 : 256, slots = tile == 128128 ? 512 : 256;   // 256x128, 256x256: one workgroup per CU
-        const int64_t R = ceil_div64(g.M, bm_t), C = ceil_div64(g.N, tile == 256256 ? 256 : 128);
-        const int64_t full = (R * C / slots) * slots;                 // tiles in whole rounds
-        const int64_t Rm = full / C;                                  // row blocks of the main launch
-        const int64_t tail_tiles = (R - Rm) * C;
-        // (measured on the ViT-L shapes: 118 -> 92 us at one round + 8 tiles; nothing gained at three or four rounds)
-        const int64_t t64_tail = ceil_div64(g.M - Rm * bm_t, 64) * ceil_div64(g.N, 64);
-        if (Rm >= 1 && Rm < R && tail_tiles <= 64 && full - Rm * C < C && (full <= 2 * slots || tile == 2256128 || tile == 256256) &&
-            (g.ws || t64_tail <= 256)) {
-            const int64_t r0 = Rm * bm_t;
-            skyemb_gemm_args gm = g, gt = g;
-            gm.M = (int)r0;
-            gt.M = g.M - (int)r0;
-            gt.A = (const char *)g.A + r0 * g.lda * 2;
-            if (g.out) gt.out = (char *)g.out + r0 * g.ldo * 2;
-            if (g.out2) gt.out2 = (char *)g.out2 + r0 * g.ldo2 * 2;
-            if (g.out_f32) gt.out_f32 = g.out_f32 + r0 * g.ldo32;
-            if (g.resid) gt.resid = g.resid + r0 * g.ldr;
-            if (g.aux) gt.aux = (const char *)g.aux + r0 * g.ldaux * 2;
-            const int64_t t64 = ceil_div64(gt.M, 64) * ceil_div64(gt.N, 64);
-            int St = (int)(768 / t64);
-            if (St > 8) St = 8;
-            if (St > g.K / BK / 4) St = g.K / BK / 4;
-            while (St > 1 && (int64_t)St * ((int64_t)gt.M * gt.N + gt.M) * 4 > g.ws_bytes) --St;
-            if (St < 1 || !g.ws) St = 1;
-            gt.tile = 64064;
-            gt.split_k = St;
-            gt.prefetch = nullptr;                          // (the main launch carries the hint)
-            gt.prefetch_bytes = 0;
-            // short k-loops: the tail as ONE launch of the two-k-group tile (at most one workgroup per CU, no slabs, no reduce
-            // launch -- mim_19 spent 145 reduce launches per step on its row tails)
-            if (wk2_on && (g.K / BK) % 2 == 0 && g.K <= 2048 && t64 <= 256) {
-                gt.tile = 9064064;
-                gt.split_k = 1;
-            }
-            const int rc = tile == 256256 ? gemm256_launch(gm, st) : dispatch_code(tile, gm, st);
-            if (rc != 0) return rc;
-            return SKY_TWIN(skyemb_gemm_pipe_try)(gt, st);
+    const bool tail_wk2 = KT % 2 == 0 && g.K <= 2048;
+    if (!(sw.tail && (tile == T128x128 || tile == T256x128 || tile == T256x256) && S == 1 && a_kc && (g.ws || tail_wk2) && !g.dst_row &&
+          !g.tab_row && !g.colsum_a))
+        return plan;
+    const int64_t bm_t = tile == T128x128 ? 128 : 256, slots = tile == T128x128 ? 512 : 256;   // 256x128, 256x256: one workgroup per CU
+    const int64_t R = ceil_div64(g.M, bm_t), C = ceil_div64(g.N, d->bn);
+    const int64_t full = (R * C / slots) * slots;                 // tiles in whole rounds
+    const int64_t Rm = full / C;                                  // row blocks of the main launch
+    const int64_t tail_tiles = (R - Rm) * C;
+    // (measured on the ViT-L shapes: 118 -> 92 us at one round + 8 tiles; nothing gained at three or four rounds)
+    const int64_t r0 = Rm * bm_t, t64 = ceil_div64(g.M - r0, 64) * ceil_div64(g.N, 64);
+    if (!(Rm >= 1 && Rm < R && tail_tiles <= 64 && full - Rm * C < C && (full <= 2 * slots || tile == T256x128 || tile == T256x256) &&
+          (g.ws || t64 <= 256)))
+        return plan;
+    plan.part[0].rows = (int)r0;
+    // short k-loops: the tail as ONE launch of the two-k-group tile (at most one workgroup per CU, no slabs, no reduce
+    // launch -- mim_19 spent 145 reduce launches per step on its row tails)
+    if (tail_wk2 && t64 <= 256) plan.part[1] = {T64x64_WK2, 1, (int)r0, g.M - (int)r0};
+    else plan.part[1] = {T64x64, g.ws ? split_factor(g, g.M - r0, t64, 0, 4) : 1, (int)r0, g.M - (int)r0};
+    plan.n = 2;
+    return plan;
+}
+
+}  // namespace
+
+// returns -1 when the problem is outside the fast-path subset (caller falls back to gemm.hip)
+int SKY_TWIN(skyemb_gemm_pipe_try)(const skyemb_gemm_args &g, hipStream_t st) {
+    const GemmPlan plan = plan_single(g);
+    if (plan.status != 0) return plan.status;
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmPart &p = plan.part[i];
+        skyemb_gemm_args gp = g;
+        gp.M = p.rows;
+        gp.split_k = p.split_k;
+        if (p.row0 > 0) {                                 // a row tail: its rows of A and of every per-row operand
+            const int64_t r0 = p.row0;
+            gp.tile = p.tile;
+            gp.A = (const char *)g.A + r0 * g.lda * 2;
+            if (g.out) gp.out = (char *)g.out + r0 * g.ldo * 2;
+            if (g.out2) gp.out2 = (char *)g.out2 + r0 * g.ldo2 * 2;
+            if (g.out_f32) gp.out_f32 = g.out_f32 + r0 * g.ldo32;
+            if (g.resid) gp.resid = g.resid + r0 * g.ldr;
+            if (g.aux) gp.aux = (const char *)g.aux + r0 * g.ldaux * 2;
+            gp.prefetch = nullptr;                        // (the main launch carries the hint)
+            gp.prefetch_bytes = 0;
         }
+        if (const int rc = launch_code(p.tile, gp, st)) return rc;
     }
-    if (tile == 256256) return gemm256_launch(g, st);
-    return dispatch_code(tile, g, st);
+    return 0;
 }
 
 // ---- grouped launch (see gemm_pipe_group_kernel) -------------------------------------------------------
-// [header 256 B][n problems][skyemb_ln_bwd_side, 128 B reserved]
 constexpr int GROUP_TAIL_BYTES = 128;
 static_assert(sizeof(skyemb_ln_bwd_side) <= GROUP_TAIL_BYTES, "the blob's tail holds the LayerNorm side job's record");
 // (the plans are host logic common to both 16-bit formats: built once, in the bf16 object; only the launch has a twin)
@@ -1175,56 +1264,59 @@ static int class_bit(const skyemb_gemm_args &g) {
     return a ? (b ? 1 : 2) : (b ? 8 : 4);
 }
 
+// what the grouped 256 x 256 kernel takes: weight gradients of whole tiles with a plain epilogue
+static bool group256_fits(const skyemb_gemm_args &g) {
+    return gemm256_wgrad_applicable(g) && !g.bias && !g.resid && g.act == SKYEMB_ACT_NONE && !g.out2;
+}
+
+// the tile of a grouped launch the caller leaves to the library (tile 0)
+static int group_tile(const skyemb_gemm_args *args, int n) {
+    int64_t t12864 = 0, t128 = 0, t256 = 0;
+    bool fit256 = true;
+    for (int i = 0; i < n; ++i) {
+        const skyemb_gemm_args &g = args[i];
+        t12864 += ceil_div64(g.M, 128) * ceil_div64(g.N, 64);
+        t128 += ceil_div64(g.M, 128) * ceil_div64(g.N, 128);
+        t256 += (g.M / 256) * (g.N / 256);
+        fit256 = fit256 && group256_fits(g) && g.K >= 2048;
+    }
+    // default: 128x64 tiles once they still give every CU two workgroups' worth of tiles, else 64x64
+    int tile = t12864 >= 320 ? T128x64 : T64x64;
+    // ViT-L weight gradients (>= 2.5 rounds of 128x128 tiles, K = thousands of token rows): 128x128 (mim_19: 35.8 -> 35.2 ms/step)
+    if (t128 >= 400) tile = T128x128;
+    // ViT-L weight gradients as ONE round of 256x256 tiles (mim_19: 192 tiles over 8320 token rows: 1.85 us per k-tile and
+    // workgroup against 4 x 0.82 on the 128x128 tile)
+    const GemmSwitches &sw = gemm_switches();
+    if (sw.group256 && fit256 && t256 >= 160 && t256 <= 256) tile = T256x256;
+    if (sw.group_tile) tile = canonical_tile(sw.group_tile);   // (experiments)
+    return tile;
+}
+
+// is the planned group one of weight gradients (RC.RC) on a tile built with `form` (ADAMW, SIDE)?
+static bool wgrad_group_has(const skyemb_gemm_group_info *info, int form, const char *who) {
+    const TileDesc *d = find_tile(info->tile);
+    if (info->class_mask == 4 && d && (d->forms & form)) return true;
+    skyemb_set_error("%s: weight-gradient (RC.RC) groups on a tile built with this form only (tile %d, class mask %d)", who, info->tile,
+                     info->class_mask);
+    return false;
+}
+
 extern "C" int skyemb_gemm_group_plan(const skyemb_gemm_args *args, int n, int tile, void *blob_host, int64_t blob_bytes,
                                       skyemb_gemm_group_info *info) {
     SKY_CHECK_ARG(args && blob_host && info && n >= 1 && n <= GROUP_MAX, "skyemb_gemm_group_plan: 1..%d problems", GROUP_MAX);
     SKY_CHECK_ARG(blob_bytes >= skyemb_gemm_group_blob_bytes(n), "skyemb_gemm_group_plan: blob too small");
     tile = canonical_tile(tile);
-    if (tile == 0) {
-        // default: 128x64 tiles once they still give every CU two workgroups' worth of tiles, else 64x64
-        int64_t t12864 = 0;
-        for (int i = 0; i < n; ++i) t12864 += ceil_div64(args[i].M, 128) * ceil_div64(args[i].N, 64);
-        tile = t12864 >= 320 ? 128064 : 64064;
-        // ViT-L weight gradients (>= 2.5 rounds of 128x128 tiles, K = thousands of token rows): 128x128 (mim_19: 35.8 -> 35.2 ms/step)
-        int64_t t128 = 0;
-        for (int i = 0; i < n; ++i) t128 += ceil_div64(args[i].M, 128) * ceil_div64(args[i].N, 128);
-        if (t128 >= 400) tile = 128128;
-        // at most one 128x128 workgroup per CU (the decoder's four weight gradients: 192 tiles, K = 4352 token rows): two k-groups
-        static const int wk2 = []() { const char *e = getenv("SKYEMB_GROUP_WK2"); return e ? atoi(e) : 0; }();
-        if (wk2 && t128 <= 256) {
-            bool even = true;
-            for (int i = 0; i < n; ++i) even = even && (args[i].K / BK) % 2 == 0 && args[i].K >= 4 * BK;
-            if (even) tile = 9128128;
-        }
-        // ViT-L weight gradients as ONE round of 256x256 tiles (mim_19: 192 tiles over 8320 token rows: 1.85 us per k-tile and
-        // workgroup against 4 x 0.82 on the 128x128 tile)
-        static const bool g256 = []() { const char *e = getenv("SKYEMB_GROUP_256"); return !(e && e[0] == '0'); }();
-        if (g256) {
-            int64_t t256 = 0;
-            bool ok = true;
-            for (int i = 0; i < n; ++i) {
-                ok = ok && gemm256_wgrad_applicable(args[i]) && args[i].K >= 2048 && !args[i].bias && !args[i].resid &&
-                     args[i].act == SKYEMB_ACT_NONE && !args[i].out2;
-                t256 += (args[i].M / 256) * (args[i].N / 256);
-            }
-            if (ok && t256 >= 160 && t256 <= 256) tile = 256256;
-        }
-        static const int env_tile = []() { const char *e = getenv("SKYEMB_GROUP_TILE"); return e ? atoi(e) : 0; }();   // experiments
-        if (env_tile) tile = canonical_tile(env_tile);
-    }
-    SKY_CHECK_ARG(tile == 64064 || tile == 128064 || tile == 128128 || tile == 9128128 || tile == 256256,
-                  "skyemb_gemm_group_plan: tile %d is not built for grouped launches", tile);
-    if (tile == 256256)
+    if (tile == 0) tile = group_tile(args, n);
+    const TileDesc *d = find_tile(tile);
+    SKY_CHECK_ARG(d && (d->forms & GROUPED), "skyemb_gemm_group_plan: tile %d is not built for grouped launches", tile);
+    if (d->forms & OWN256)
         for (int i = 0; i < n; ++i)
-            SKY_CHECK_ARG(gemm256_wgrad_applicable(args[i]) && !args[i].bias && !args[i].resid && args[i].act == SKYEMB_ACT_NONE && !args[i].out2,
-                          "skyemb_gemm_group_plan: the 256x256 tile takes weight gradients of whole tiles only (problem %d)", i);
-    if (tile == 9128128)
+            SKY_CHECK_ARG(group256_fits(args[i]), "skyemb_gemm_group_plan: the 256x256 tile takes weight gradients of whole tiles only (problem %d)", i);
+    if (d->wk == 2)
         for (int i = 0; i < n; ++i)
             SKY_CHECK_ARG((args[i].K / BK) % 2 == 0, "skyemb_gemm_group_plan: the two-k-group tile needs K %% 128 == 0 (problem %d)", i);
-    int bm, bn;
-    tile_dims(tile, bm, bn);
-    int *hdr = (int *)blob_host;
-    memset(blob_host, 0, GROUP_HEADER_BYTES);
+    GroupHeader *h = (GroupHeader *)blob_host;
+    memset(h, 0, sizeof *h);
     skyemb_gemm_args *out = (skyemb_gemm_args *)((char *)blob_host + GROUP_HEADER_BYTES);
     int start = 0, mask = 0;
     for (int i = 0; i < n; ++i) {
@@ -1244,8 +1336,8 @@ extern "C" int skyemb_gemm_group_plan(const skyemb_gemm_args *args, int n, int t
         g.prefetch_wgs = 0;                                // (a grouped launch's hint stays with its tiles' waves)
         out[i] = g;
         mask |= class_bit(g);
-        hdr[8 + i] = start;
-        const int64_t tiles = ceil_div64(g.M, bm) * ceil_div64(g.N, bn);
+        h->starts[i] = start;
+        const int64_t tiles = ceil_div64(g.M, d->stride_m) * ceil_div64(g.N, d->bn);
         start += (int)((tiles + 7) / 8 * 8);
     }
     // instances are built for: one class alone, and data-gradient (KC.RC) + weight-gradient (RC.RC) together
@@ -1253,9 +1345,9 @@ extern "C" int skyemb_gemm_group_plan(const skyemb_gemm_args *args, int n, int t
         skyemb_set_error("skyemb_gemm_group_plan: operand-layout mix %d is not built (single class, or KC.RC with RC.RC)", mask);
         return -1;
     }
-    hdr[8 + n] = start;
-    hdr[0] = n;
-    hdr[1] = start;
+    h->starts[n] = start;
+    h->n = n;
+    h->total = start;
     {
         // tile order across the group: an XCD takes consecutive tiles of the concatenated list.  Default: the 256 x 256 groups
         // (round 5: their L2 traffic 2.6x -> 1.35x of the operands).  For the ring-tile groups the same order was built in round 6
@@ -1265,7 +1357,7 @@ extern "C" int skyemb_gemm_group_plan(const skyemb_gemm_args *args, int n, int t
         // (read per plan, not once per process: bench.py builds both orders in one process for its interleaved A/B)
         const char *e = getenv("SKYEMB_GROUP_XCD_ORDER");
         const bool off = e && e[0] == '0', all = e && e[0] == '1';
-        if (!off && (tile == 256256 || all)) hdr[1] |= 1 << 30;
+        if (!off && ((d->forms & OWN256) || all)) h->total |= GROUP_XCD_ORDER;
     }
     info->total_blocks = start;
     info->tile = tile;
@@ -1291,18 +1383,14 @@ static bool flat_weight_gradients(const skyemb_gemm_args *args, int n, const sky
 
 extern "C" int skyemb_gemm_group_plan_adamw(const skyemb_gemm_args *args, int n, int tile, const skyemb_adamw_desc *adamw, void *blob_host,
                                             int64_t blob_bytes, skyemb_gemm_group_info *info) {
-    SKY_CHECK_ARG(adamw && adamw->g_base && adamw->p && adamw->m && adamw->v && adamw->p_lp && adamw->hyper,
-                  "skyemb_gemm_group_plan_adamw: incomplete descriptor");
+    const char *who = "skyemb_gemm_group_plan_adamw";
+    SKY_CHECK_ARG(adamw && adamw->g_base && adamw->p && adamw->m && adamw->v && adamw->p_lp && adamw->hyper, "%s: incomplete descriptor", who);
     const int rc = skyemb_gemm_group_plan(args, n, tile, blob_host, blob_bytes, info);
     if (rc != 0) return rc;
-    if (info->class_mask != 4 || !(info->tile == 64064 || info->tile == 128064 || info->tile == 128128 || info->tile == 256256)) {
-        skyemb_set_error("skyemb_gemm_group_plan_adamw: weight-gradient (RC.RC) problems on the 64x64 / 128x64 / 128x128 / 256x256 tiles only");
-        return -1;
-    }
-    if (!flat_weight_gradients(args, n, adamw, "skyemb_gemm_group_plan_adamw")) return -1;
-    skyemb_adamw_desc d = *adamw;
-    d.enabled = 1;
-    memcpy((char *)blob_host + GROUP_ADAMW_OFFSET, &d, sizeof d);
+    if (!wgrad_group_has(info, ADAMW, who) || !flat_weight_gradients(args, n, adamw, who)) return -1;
+    GroupHeader *h = (GroupHeader *)blob_host;
+    h->adamw = *adamw;
+    h->adamw.enabled = 1;
     info->reserved = (info->reserved & 4) | 1;
     return 0;
 }
@@ -1310,65 +1398,59 @@ extern "C" int skyemb_gemm_group_plan_adamw(const skyemb_gemm_args *args, int n,
 extern "C" int skyemb_gemm_group_plan_side_adamw(const skyemb_gemm_args *args, int n, int tile, const skyemb_adamw_desc *adamw, int own_step,
                                                  int64_t side_lo, int64_t side_hi, int side_blocks, void *blob_host, int64_t blob_bytes,
                                                  skyemb_gemm_group_info *info) {
-    SKY_CHECK_ARG(adamw && adamw->g_base && adamw->p && adamw->m && adamw->v && adamw->p_lp && adamw->hyper,
-                  "skyemb_gemm_group_plan_side_adamw: incomplete descriptor");
+    const char *who = "skyemb_gemm_group_plan_side_adamw";
+    SKY_CHECK_ARG(adamw && adamw->g_base && adamw->p && adamw->m && adamw->v && adamw->p_lp && adamw->hyper, "%s: incomplete descriptor", who);
     SKY_CHECK_ARG(side_lo >= 0 && side_hi >= side_lo && side_lo % 8 == 0 && side_hi % 8 == 0 && side_blocks >= 0 && side_blocks <= 65536 &&
                       (side_hi == side_lo) == (side_blocks == 0),
-                  "skyemb_gemm_group_plan_side_adamw: side range [%lld, %lld) must be whole 8-element pieces with >= 1 workgroup (or empty with none)",
+                  "%s: side range [%lld, %lld) must be whole 8-element pieces with >= 1 workgroup (or empty with none)", who,
                   (long long)side_lo, (long long)side_hi);
     int rc = own_step ? skyemb_gemm_group_plan_adamw(args, n, tile, adamw, blob_host, blob_bytes, info)
                       : skyemb_gemm_group_plan(args, n, tile, blob_host, blob_bytes, info);
     if (rc != 0) return rc;
-    if (info->class_mask != 4 || !(info->tile == 64064 || info->tile == 128064 || info->tile == 128128 || info->tile == 256256)) {
-        skyemb_set_error("skyemb_gemm_group_plan_side_adamw: weight-gradient (RC.RC) problems on the 64x64 / 128x64 / 128x128 / 256x256 tiles only");
-        return -1;
-    }
     // (own_step = 0: the stored gradients are what a later side job steps, so they obey the same rules as stepped ones)
-    if (!flat_weight_gradients(args, n, adamw, "skyemb_gemm_group_plan_side_adamw")) return -1;
-    skyemb_adamw_desc d = *adamw;
-    d.enabled = own_step ? 1 : 0;
-    memcpy((char *)blob_host + GROUP_ADAMW_OFFSET, &d, sizeof d);
-    int *hdr = (int *)blob_host;
-    hdr[2] = info->total_blocks;                          // first side workgroup
-    hdr[3] = side_blocks;
-    const long long range[2] = {(long long)side_lo, (long long)side_hi};
-    memcpy(hdr + 4, range, sizeof range);
+    if (!wgrad_group_has(info, SIDE, who) || !flat_weight_gradients(args, n, adamw, who)) return -1;
+    GroupHeader *h = (GroupHeader *)blob_host;
+    h->adamw = *adamw;
+    h->adamw.enabled = own_step ? 1 : 0;
+    h->side_first = info->total_blocks;
+    h->side_adamw_wgs = side_blocks;
+    h->side_lo = side_lo;
+    h->side_hi = side_hi;
     info->total_blocks += side_blocks;
-    hdr[1] = (hdr[1] & (1 << 30)) | info->total_blocks;
+    h->total = (h->total & GROUP_XCD_ORDER) | info->total_blocks;
     info->reserved = (info->reserved & 4) | (own_step ? 1 : 0) | 2;
     return 0;
 }
 
 extern "C" int skyemb_gemm_group_attach_ln_bwd(void *blob_host, int64_t blob_bytes, skyemb_gemm_group_info *info, const skyemb_ln_bwd_side *ln) {
-    SKY_CHECK_ARG(blob_host && info && ln && info->total_blocks > 0, "skyemb_gemm_group_attach_ln_bwd: bad arguments");
-    int *hdr = (int *)blob_host;
-    const int n = hdr[0];
-    SKY_CHECK_ARG(n >= 1 && n <= GROUP_MAX && blob_bytes >= skyemb_gemm_group_blob_bytes(n), "skyemb_gemm_group_attach_ln_bwd: not a planned blob");
-    SKY_CHECK_ARG(hdr[GROUP_LN_COUNT_WORD] == 0, "skyemb_gemm_group_attach_ln_bwd: the launch already carries a LayerNorm");
-    if (info->class_mask != 4 || !(info->tile == 64064 || info->tile == 128064 || info->tile == 128128 || info->tile == 256256)) {
-        skyemb_set_error("skyemb_gemm_group_attach_ln_bwd: weight-gradient (RC.RC) groups on the 64x64 / 128x64 / 128x128 / 256x256 tiles only");
-        return -1;
-    }
+    const char *who = "skyemb_gemm_group_attach_ln_bwd";
+    SKY_CHECK_ARG(blob_host && info && ln && info->total_blocks > 0, "%s: bad arguments", who);
+    GroupHeader *h = (GroupHeader *)blob_host;
+    const int n = h->n;
+    SKY_CHECK_ARG(n >= 1 && n <= GROUP_MAX && blob_bytes >= skyemb_gemm_group_blob_bytes(n), "%s: not a planned blob", who);
+    SKY_CHECK_ARG(h->ln_count == 0, "%s: the launch already carries a LayerNorm", who);
+    if (!wgrad_group_has(info, SIDE, who)) return -1;
     SKY_CHECK_ARG(ln->dy && ln->x && ln->gamma && ln->mean && ln->rstd && ln->g_out && ln->part && ln->M > 0 && ln->D > 0 && ln->D % 4 == 0 &&
                       aligned16(ln->dy) && aligned16(ln->x) && aligned16(ln->gamma) && aligned16(ln->g_out) && aligned16(ln->g_in) && aligned16(ln->g_lp) &&
                       aligned16(ln->part),
-                  "skyemb_gemm_group_attach_ln_bwd: bad LayerNorm record (M=%d D=%d; 16-byte aligned rows)", ln->M, ln->D);
-    if (ln->D > (info->tile == 256256 ? 1024 : 768)) {       // (not an error: the caller launches skyemb_layernorm_bwd itself)
-        skyemb_set_error("skyemb_gemm_group_attach_ln_bwd: rows of %d columns are wider than this tile's instance carries (1024 on 256 x 256 tiles, 768 on the others)", ln->D);
+                  "%s: bad LayerNorm record (M=%d D=%d; 16-byte aligned rows)", who, ln->M, ln->D);
+    const TileDesc *d = find_tile(info->tile);
+    if (ln->D > d->ln_max) {                                 // (not an error: the caller launches skyemb_layernorm_bwd itself)
+        skyemb_set_error("%s: rows of %d columns are wider than this tile's instance carries (%d)", who, ln->D, d->ln_max);
         return -1;
     }
-    const int per_wg = info->tile == 64064 ? 1 : 2;          // four-wave blocks of the partial-sum table per side workgroup (256 / 512 threads)
+    const int per_wg = d->threads() / 256;                   // four-wave blocks of the partial-sum table per side workgroup
     const int n_ln = (sky_ln_bwd_blocks(ln->M) + per_wg - 1) / per_wg;
     const int off = GROUP_HEADER_BYTES + n * (int)sizeof(skyemb_gemm_args);
     memcpy((char *)blob_host + off, ln, sizeof *ln);
     if (!(info->reserved & 2)) {                             // a launch without an optimiser side job: the side workgroups start behind its tiles
-        hdr[2] = info->total_blocks;
-        hdr[3] = 0;
+        h->side_first = info->total_blocks;
+        h->side_adamw_wgs = 0;
     }
-    hdr[GROUP_LN_COUNT_WORD] = n_ln;
-    hdr[GROUP_LN_OFFSET_WORD] = off;
+    h->ln_count = n_ln;
+    h->ln_offset = off;
     info->total_blocks += n_ln;
-    hdr[1] = (hdr[1] & (1 << 30)) | info->total_blocks;
+    h->total = (h->total & GROUP_XCD_ORDER) | info->total_blocks;
     info->reserved |= 2;
     return 0;
 }
@@ -1376,38 +1458,48 @@ extern "C" int skyemb_gemm_group_attach_ln_bwd(void *blob_host, int64_t blob_byt
 
 template <int BM, int BN, int NSTAGE, int WM, int WN, int CLASSES, int WK = 1, bool ADAM = false, bool SIDE = false>
 static int group_launch_n(const void *blob_dev, int total_blocks, hipStream_t st) {
-    constexpr size_t ring = (size_t)NSTAGE * (BM + BN) * BK * 2 * WK, image = (size_t)BM * (BN * 4 + 16) + (WK > 1 ? BM * 4 : 0);
-    constexpr size_t smem = ring > image ? ring : image;
+    constexpr size_t smem = ring_tile_lds(BM, BN, NSTAGE, WK);
     auto kern = gemm_pipe_group_kernel<BM, BN, NSTAGE, WM, WN, CLASSES, WK, ADAM, SIDE>;
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_gemm_group_launch: hipFuncSetAttribute(%zu B LDS): %s", smem, hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
-    }
+    if (const int rc = sky_set_lds_limit((const void *)kern, (int)smem, "skyemb_gemm_group_launch")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(WM * WN * WK * 64), smem, st, (const char *)blob_dev);
     skyemb_count_gemm(SKYEMB_GEMM_COUNT_GROUP);
     SKY_LAUNCH_CHECK("skyemb_gemm_group_launch");
     return 0;
 }
-template <int BM, int BN, int NSTAGE, int WM, int WN, int WK = 1>
-static int group_launch_classes(const void *blob_dev, int total_blocks, int mask, hipStream_t st) {
-    switch (mask) {
-        case 1: return group_launch_n<BM, BN, NSTAGE, WM, WN, 1, WK>(blob_dev, total_blocks, st);
-        case 2: return group_launch_n<BM, BN, NSTAGE, WM, WN, 2, WK>(blob_dev, total_blocks, st);
-        case 4: return group_launch_n<BM, BN, NSTAGE, WM, WN, 4, WK>(blob_dev, total_blocks, st);
-        case 6: if constexpr (WK == 1) return group_launch_n<BM, BN, NSTAGE, WM, WN, 6, WK>(blob_dev, total_blocks, st); else break;
+
+// the grouped launch of one tile row in one MODE: 0 plain, 1 the optimiser step in the epilogue, 2 side jobs (skyemb_gemm_group_info.reserved:
+// bit 0 = the tiles' own gradients are stepped, bit 1 = side jobs)
+template <int MODE, int BM, int BN, int NSTAGE, int WM, int WN, int WK, int FORMS>
+static int group_launch_tile(const void *blob_dev, const skyemb_gemm_group_info *info, hipStream_t st) {
+    const int total = info->total_blocks;
+    const bool own = info->reserved & 1;
+    constexpr bool g256 = FORMS & OWN256;
+    if constexpr (MODE == 2 && (FORMS & SIDE)) {
+        if constexpr (g256) return own ? gemm256_group_launch<true, true>(blob_dev, total, st) : gemm256_group_launch<false, true>(blob_dev, total, st);
+        else return own ? group_launch_n<BM, BN, NSTAGE, WM, WN, 4, WK, true, true>(blob_dev, total, st)
+                        : group_launch_n<BM, BN, NSTAGE, WM, WN, 4, WK, false, true>(blob_dev, total, st);
+    } else if constexpr (MODE == 1 && (FORMS & ADAMW)) {
+        if constexpr (g256) return gemm256_group_launch<true>(blob_dev, total, st);
+        else return group_launch_n<BM, BN, NSTAGE, WM, WN, 4, WK, true>(blob_dev, total, st);
+    } else if constexpr (MODE == 0 && (FORMS & GROUPED)) {
+        if constexpr (g256) return gemm256_group_launch<false>(blob_dev, total, st);
+        else switch (info->class_mask) {
+            case 1: return group_launch_n<BM, BN, NSTAGE, WM, WN, 1, WK>(blob_dev, total, st);
+            case 2: return group_launch_n<BM, BN, NSTAGE, WM, WN, 2, WK>(blob_dev, total, st);
+            case 4: return group_launch_n<BM, BN, NSTAGE, WM, WN, 4, WK>(blob_dev, total, st);
+            case 6: if constexpr ((FORMS & MIXED) != 0) return group_launch_n<BM, BN, NSTAGE, WM, WN, 6, WK>(blob_dev, total, st); else break;
+        }
     }
-    skyemb_set_error("skyemb_gemm_group_launch: class mask %d not built", mask);
+    skyemb_set_error("skyemb_gemm_group_launch: tile %d is not built for this group (mode %d, class mask %d)", info->tile, MODE, info->class_mask);
+    return 1;
+}
+template <int MODE>
+static int group_launch_mode(const void *blob_dev, const skyemb_gemm_group_info *info, hipStream_t st) {
+#define X(NAME, V, BM_, BN_, NS, WM_, WN_, WK_, FORMS, LN) \
+    if (info->tile == NAME) return group_launch_tile<MODE, BM_, BN_, NS, WM_, WN_, WK_, FORMS>(blob_dev, info, st);
+    SKY_GEMM_PRODUCT_TILES(X)
+#undef X
+    skyemb_set_error("skyemb_gemm_group_launch: tile %d not built", info->tile);
     return 1;
 }
 
@@ -1418,39 +1510,9 @@ extern "C" SKY_TWIN_VIS int SKY_TWIN(skyemb_gemm_group_launch)(const void *blob_
 #endif
     if (skyemb_skip_mask() & 1) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int mode = info->reserved & 3;
-    if (mode == 2 || mode == 3) {          // side optimiser job (plan_side_adamw), own tiles stored (2) or stepped (3)
-        const bool own = mode == 3;
-        switch (info->tile) {
-            case 64064: return own ? group_launch_n<64, 64, 3, 2, 2, 4, 1, true, true>(blob_dev, info->total_blocks, st)
-                                   : group_launch_n<64, 64, 3, 2, 2, 4, 1, false, true>(blob_dev, info->total_blocks, st);
-            case 128064: return own ? group_launch_n<128, 64, 3, 4, 2, 4, 1, true, true>(blob_dev, info->total_blocks, st)
-                                    : group_launch_n<128, 64, 3, 4, 2, 4, 1, false, true>(blob_dev, info->total_blocks, st);
-            case 128128: return own ? group_launch_n<128, 128, 2, 4, 2, 4, 1, true, true>(blob_dev, info->total_blocks, st)
-                                    : group_launch_n<128, 128, 2, 4, 2, 4, 1, false, true>(blob_dev, info->total_blocks, st);
-            case 256256: return own ? gemm256_group_launch<true, true>(blob_dev, info->total_blocks, st)
-                                    : gemm256_group_launch<false, true>(blob_dev, info->total_blocks, st);
-        }
-        skyemb_set_error("skyemb_gemm_group_launch: tile %d not built with a side optimiser job", info->tile);
-        return 1;
+    switch (info->reserved & 3) {
+        case 2: case 3: return group_launch_mode<2>(blob_dev, info, st);
+        case 1: return group_launch_mode<1>(blob_dev, info, st);
+        default: return group_launch_mode<0>(blob_dev, info, st);
     }
-    if (mode == 1) {                                 // optimiser step fused into the epilogue (plan_adamw: class 4 only)
-        switch (info->tile) {
-            case 64064: return group_launch_n<64, 64, 3, 2, 2, 4, 1, true>(blob_dev, info->total_blocks, st);
-            case 128064: return group_launch_n<128, 64, 3, 4, 2, 4, 1, true>(blob_dev, info->total_blocks, st);
-            case 128128: return group_launch_n<128, 128, 2, 4, 2, 4, 1, true>(blob_dev, info->total_blocks, st);
-            case 256256: return gemm256_group_launch<true>(blob_dev, info->total_blocks, st);
-        }
-        skyemb_set_error("skyemb_gemm_group_launch: tile %d not built with the fused optimiser step", info->tile);
-        return 1;
-    }
-    switch (info->tile) {
-        case 64064: return group_launch_classes<64, 64, 3, 2, 2>(blob_dev, info->total_blocks, info->class_mask, st);
-        case 128064: return group_launch_classes<128, 64, 3, 4, 2>(blob_dev, info->total_blocks, info->class_mask, st);
-        case 128128: return group_launch_classes<128, 128, 2, 4, 2>(blob_dev, info->total_blocks, info->class_mask, st);
-        case 9128128: return group_launch_classes<128, 128, 2, 4, 2, 2>(blob_dev, info->total_blocks, info->class_mask, st);
-        case 256256: return gemm256_group_launch<false>(blob_dev, info->total_blocks, st);
-    }
-    skyemb_set_error("skyemb_gemm_group_launch: tile %d not built", info->tile);
-    return 1;
 }

@@ -458,21 +458,7 @@ template <bool ADAM, bool SIDE = false>
 int gemm256_group_launch(const void *blob_dev, int total_blocks, hipStream_t st) {
     constexpr int smem = G256_RING * G256_HT;
     auto kern = gemm256_group_kernel<ADAM, SIDE>;
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_gemm_group_launch(256x256): hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
-    }
+    if (const int rc = sky_set_lds_limit((const void *)kern, smem, "skyemb_gemm_group_launch(256x256)")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(512), smem, st, (const char *)blob_dev);
     skyemb_count_gemm(SKYEMB_GEMM_COUNT_GROUP256);
     SKY_LAUNCH_CHECK("skyemb_gemm_group_launch(256x256)");
@@ -490,29 +476,14 @@ template <bool B_KC>
 int gemm256_launch_n(const skyemb_gemm_args &g, hipStream_t st) {
     constexpr int smem = G256_RING * G256_HT;             // all 160 KiB
     auto kern = gemm256_kernel<B_KC>;
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_gemm(256x256): hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
-    }
+    if (const int rc = sky_set_lds_limit((const void *)kern, smem, "skyemb_gemm(256x256)")) return rc;
     const int64_t tiles = ceil_div64(g.M, 256) * ceil_div64(g.N, 256);
     static const int ncu = []() {
         int dev_ = 0, n = 256;
         if (hipGetDevice(&dev_) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev_);
         return n > 0 ? n : 256;
     }();
-    static const bool persist = []() { const char *e = getenv("SKYEMB_GEMM_256_PERSIST"); return !(e && e[0] == '0'); }();
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < ncu || !persist ? tiles : ncu)), dim3(512), smem, st, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < ncu ? tiles : ncu)), dim3(512), smem, st, g);
     skyemb_count_gemm(SKYEMB_GEMM_COUNT_256);
     SKY_LAUNCH_CHECK("skyemb_gemm(256x256)");
     return 0;
@@ -520,21 +491,7 @@ int gemm256_launch_n(const skyemb_gemm_args &g, hipStream_t st) {
 
 int gemm256_wgrad_launch(const skyemb_gemm_args &g, hipStream_t st) {
     constexpr int smem = G256_RING * G256_HT;
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done[dev & 63]) {
-            hipError_t e = hipFuncSetAttribute((const void *)gemm256_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) {
-                skyemb_set_error("skyemb_gemm(256x256, weight gradient): hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
-                return 2;
-            }
-            attr_done[dev & 63] = true;
-        }
-    }
+    if (const int rc = sky_set_lds_limit((const void *)gemm256_wgrad_kernel, smem, "skyemb_gemm(256x256, weight gradient)")) return rc;
     hipLaunchKernelGGL(gemm256_wgrad_kernel, dim3((unsigned)((g.M / 256) * (g.N / 256))), dim3(512), smem, st, g);
     skyemb_count_gemm(SKYEMB_GEMM_COUNT_256);
     SKY_LAUNCH_CHECK("skyemb_gemm(256x256, weight gradient)");

@@ -31,7 +31,6 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
-#include <mutex>
 
 namespace {
 
@@ -1033,28 +1032,15 @@ extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, 
     const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
     hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
                        w.qpar, w.tau, w.cnt, w.overflow, (int)first_rows);
-    // the dynamic-LDS limit is a per-DEVICE attribute of the function: one flag per device, set under a mutex
-    static std::mutex attr_mutex;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
     const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
     constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
-    std::lock_guard<std::mutex> attr_lock(attr_mutex);
-    bool &attr_set = attr_done[dev & 63];
-    if (!attr_set) {
-        hipError_t e = hipSuccess;
-#define PF_ATTR(M, L) if (e == hipSuccess) e = hipFuncSetAttribute((const void *)prefilter_kernel<M, L>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_max)
-        PF_ATTR(0, false); PF_ATTR(1, false); PF_ATTR(2, false); PF_ATTR(0, true); PF_ATTR(1, true); PF_ATTR(2, true);
+    const char *who = "skyemb_cosine_topk_prefiltered";
+    int rc = 0;
+#define PF_ATTR(M, L) if (rc == 0) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L>, smem_max, who)
+    PF_ATTR(0, false); PF_ATTR(1, false); PF_ATTR(2, false); PF_ATTR(0, true); PF_ATTR(1, true); PF_ATTR(2, true);
 #undef PF_ATTR
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void *)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8192 * 4 + 272 * 4);
-        if (e != hipSuccess) {
-            skyemb_set_error("skyemb_cosine_topk_prefiltered: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return 2;
-        }
-        attr_set = true;
-    }
+    if (rc == 0) rc = sky_set_lds_limit((const void *)select_kernel, 2 * 8192 * 4 + 272 * 4, who);
+    if (rc != 0) return rc;
     // (the slice right after the first one meets a threshold that still passes ~5 % of the pairs -- k of the ~2000 rows seen --
     // so it is kept short, to ~96 k rows or 1/128 of the tiles, and appends directly; from then on the threshold passes ~1 %
     // or less and a workgroup's candidates fit its staging list and region)

@@ -32,6 +32,8 @@
     X(2, 144, 64, 4, 3, 2, 1)    \
     X(14, 144, 256, 2, 3, 4, 1)
 #include "../../sky_embeddings_amd/csrc/gemm_pipe.hip"
+// (the library's fp16 twin of the grouped launch is not part of the lab)
+extern "C" __attribute__((visibility("hidden"))) int skyemb_gemm_group_launch_f16(const void *, const skyemb_gemm_group_info *, void *) { return 1; }
 
 #include <stdarg.h>
 #include <algorithm>
@@ -40,7 +42,6 @@
 #include <tuple>
 
 static char g_err[512];
-int skyemb_skip_mask(void) { return 0; }
 void skyemb_count_gemm(int) {}
 void skyemb_set_error(const char *fmt, ...) {
     va_list ap;
@@ -126,11 +127,14 @@ int main(int argc, char **argv) {
         shapes.push_back({nm("fc2", "wgrad"), D, 4 * D, M, 0, 0, cnt, 4});
     }
     std::vector<int> codes;
-    for (int i = 1; i < argc; ++i) codes.push_back(atoi(argv[i]));
+    for (int i = 1; i < argc; ++i) {
+        const int code = canonical_tile(atoi(argv[i]));
+        if (find_tile(code)) codes.push_back(code);
+        else printf("unknown tile code %s\n", argv[i]);
+    }
     if (codes.empty()) {
-#define X(V, BM_, BN_, NS, WM_, WN_, WK_) codes.push_back(V * 1000000 + BM_ * 1000 + BN_);
-        SKY_GEMM_VARIANTS(X)
-#undef X
+        for (const TileDesc &d : kTiles)
+            if (!(d.forms & OWN256)) codes.push_back(d.code);
     }
     const int ROT = 6;
     size_t max_a = (size_t)Md * 3072, max_b = (size_t)3072 * 4352, max_o = (size_t)Md * 2048;
@@ -400,8 +404,7 @@ int main(int argc, char **argv) {
         // weight-gradient launches (both operands row-contiguous, contraction over token rows): time vs the token count
         for (int code : codes) {
             if (code / 1000000 >= 9) continue;
-            int bm, bn;
-            tile_dims(code, bm, bn);
+            const int bm = find_tile(code)->stride_m, bn = find_tile(code)->bn;
             std::vector<std::pair<int, int>> wmn = {{2048, 512}, {512, 2048}, {1536, 512}, {3072, 768}, {768, 3072}, {2304, 768}};
             std::vector<int> wk = {256, 1088, 2176, 4352};
             if (vitl) {       // mim_19: the four weight gradients of a ViT-L block over 8320 token rows
@@ -436,8 +439,7 @@ int main(int argc, char **argv) {
         const int epi = atoi(getenv("LAB_KSWEEP"));
         const int bkc = getenv("LAB_BKC") ? atoi(getenv("LAB_BKC")) : 1;      // 0: B operand row-contiguous (the dgrad layout)
         for (int code : codes) {
-            int bm, bn;
-            tile_dims(code, bm, bn);
+            const int bm = find_tile(code)->stride_m, bn = find_tile(code)->bn;
             std::vector<std::pair<int, int>> mns = {{1280, 3072}, {1280, 768}, {4352, 2048}, {4352, 512}};
             if (vitl) mns = {{8320, 4096}, {8320, 3072}, {8320, 1024}, {8192, 4096}, {8192, 1024}};
             for (auto mn : mns) {
@@ -466,8 +468,7 @@ int main(int argc, char **argv) {
         std::vector<R> res;
         const float base = time_us(s, 0, 0);    // current product choice (tuned table / heuristic)
         for (int code : codes) {
-            int bm, bn;
-            tile_dims(code, bm, bn);
+            const int bm = find_tile(code)->stride_m, bn = find_tile(code)->bn;
             const int64_t tiles = ceil_div64(s.M, bm) * ceil_div64(s.N, bn);
             for (int split : {1, 2, 3, 4, 6, 8}) {
                 if (split > 1 && (tiles * split > 1100 || s.K / 64 / split < 4)) continue;
