@@ -16,19 +16,78 @@ Memory layout (HBM, per process):
 from __future__ import annotations
 
 import math
+import os
 from collections import OrderedDict
+from contextlib import contextmanager
 
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import ACT_DGELU, ACT_GELU, BF16, F32, KC, RC
+from ._lib import ACT_DGELU, ACT_GELU, BF16, F32, KC, RC, AdamwDesc
 from .model_config import (FROZEN, SH_FEATURES, SIREN_HIDDEN, MAEConfig, not_optimised, sincos_pos_embed, state_layout,
                            weight_decay_split, xavier_bound)
 
 
 def _pad8(n):
     return (n + 7) // 8 * 8
+
+
+def merge_spans(spans):
+    """[lo, hi) spans of the flat buffers (disjoint, any order) -> ascending, touching neighbours joined."""
+    out = []
+    for lo, hi in sorted(spans):
+        if out and out[-1][1] == lo:
+            out[-1] = (out[-1][0], hi)
+        else:
+            out.append((lo, hi))
+    return out
+
+
+def subtract_spans(spans, holes):
+    """[(lo, hi), ...] minus [(lo, hi), ...] (both ascending, disjoint) -> what remains, ascending."""
+    out = []
+    for s, e in spans:
+        cur = s
+        for hs, he in holes:
+            if he <= cur or hs >= e:
+                continue
+            if hs > cur:
+                out.append((cur, hs))
+            cur = max(cur, he)
+        if cur < e:
+            out.append((cur, e))
+    return out
+
+
+# Workgroups of a grouped weight-gradient launch that one compute unit holds at a time, by tile code (they follow from the tile's
+# LDS ring: one 256 x 256, two 128 x 128 / 128 x 64, three 64 x 64), and the share of those slots a launch may fill and still
+# carry a side job under "auto": it must leave a quarter of them free.
+WGRAD_SLOTS_PER_CU = {256256: 1, 128128: 2, 9128128: 1, 128064: 2, 64064: 3}
+SIDE_CARRIER_MAX_FILL = 0.76
+ADAMW_SIDE_MODES = ("auto", "0", "1", "dec", "enc")
+# workspace key of each variant's {block prefix: ops.GemmGroup} (MAEEngine._build_wgrad_groups, wgrad_variant)
+WGRAD_GROUPS_KEY = {"plain": "wgrad_groups", "adamw": "wgrad_groups_adamw", "g16": "wgrad_groups_g16"}
+
+
+def plan_wgrad_schedule(prefixes, tiles, ncu, mode):
+    """Where the AdamW step of each block's weights runs, for the grouped weight-gradient launches of one backward pass.
+    prefixes: the blocks in launch order; tiles: per launch (tile code, workgroups that compute tiles); ncu: compute units;
+    mode: "auto" = a launch carries the step of the PREVIOUS launch's block as a side job where its tiles leave a quarter of
+    the device's workgroup slots free, "1" / "0" = every launch that can / none, "dec" / "enc" = the decoder's / encoder's
+    launches only (experiments).  -> per launch (carries, stores): `carries` the previous block's step as a side job; `stores`
+    its own gradients (the next launch steps them) instead of stepping them in its epilogue.  Launch 0 has no predecessor."""
+    assert mode in ADAMW_SIDE_MODES, mode
+    carry = [False] * len(prefixes)
+    for k in range(1, len(prefixes)):
+        tile, count = tiles[k]
+        # Measured (bench.py extra.optimizer_placement): ViT-L, 192 tiles of 256 x 256 on 256 units: 26.5 -> 25.5 ms per step;
+        # ViT-B decoder, 384 tiles of 128 x 64 on 512 slots: 5.24 -> 5.21; ViT-B encoder, 440 of 512: side jobs LOSE (5.24 -> 5.47
+        # with every launch carrying one: they start when the tiles end, and move 34 instead of 26 bytes per parameter)
+        slots = ncu * WGRAD_SLOTS_PER_CU.get(tile, 1)
+        carry[k] = (mode == "1" or (mode == "auto" and count <= SIDE_CARRIER_MAX_FILL * slots) or
+                    (mode == "dec" and prefixes[k].startswith("decoder_blocks")) or (mode == "enc" and prefixes[k].startswith("blocks")))
+    return [(carry[k], k + 1 < len(carry) and carry[k + 1]) for k in range(len(carry))]
 
 
 class ParamStore:
@@ -63,6 +122,11 @@ class ParamStore:
         o = self.offsets[name]
         return buf[o:o + int(np.prod(self.shapes[name]))].view(self.shapes[name])
 
+    def span(self, name):
+        """[lo, hi) of tensor `name` in the flat buffers, its padding included."""
+        o = self.offsets[name]
+        return o, o + _pad8(int(np.prod(self.shapes[name])))
+
     def param(self, name):
         return self.frozen[name] if name in self.frozen else self._view(self.p, name)
 
@@ -85,7 +149,7 @@ def stage_gradient_ranges(store: ParamStore, cfg: MAEConfig, n_encoder_groups: i
     off = store.offsets
     # decoder_embed.weight, the first tensor of the decoder's run, goes with the TOP ENCODER stage: its gradient may be a problem of
     # blocks.{depth-1}'s grouped weight-gradient launch (MAEEngine._extra_wgrad_layers), i.e. written after the decoder stage ended
-    dec0 = off["decoder_embed.weight"] + _pad8(int(np.prod(store.shapes["decoder_embed.weight"])))
+    dec0 = store.span("decoder_embed.weight")[1]
     ranges = [[(dec0, store.n_decay)]]
     bounds = sorted({round(cfg.depth * k / n_encoder_groups) for k in range(n_encoder_groups + 1)}, reverse=True)
     groups = []
@@ -120,7 +184,6 @@ class MAEEngine:
         # mim_19's B = 128 -- profiles/r06_operand_rounding.json: with it fp16 gradients sit at the format's rounding floor, 1e-3;
         # without, 2.6e-2 -- 2^11 at B = 8: a fixed 2^16 would put d loss / d pred of a four-image batch at ~10 and the products
         # behind it past fp16's 65504).  SKYEMB_LOSS_SCALE or assigning `engine.loss_scale` fixes it by hand.
-        import os
         env = os.environ.get("SKYEMB_LOSS_SCALE")
         self._loss_scale_auto = compute_dtype == torch.float16 and env is None
         self._loss_scale = float(env) if (env is not None and compute_dtype == torch.float16) else (65536.0 if compute_dtype == torch.float16 else 1.0)
@@ -130,9 +193,17 @@ class MAEEngine:
         self._ws = {}
         self._last = None
         # fp32 scratch for split-K GEMM launches (partial slabs; every launch on the stream reuses it)
-        self._splitk_ws = torch.zeros(8 * 1024 * 1024, device=self.device, dtype=torch.float32)
+        self.splitk_ws = torch.zeros(8 * 1024 * 1024, device=self.device, dtype=torch.float32)
         self._side, self._pending, self._group_done = None, {}, None
+        self._splitk_ws_side = None              # the side stream's own scratch (enable_wgrad_overlap)
         self._ln_first = self._ln_count = 0      # LayerNorms of the running backward stage awaiting their batched reduce
+        self._pf_maps = None                     # prefetch-hint chains, built on first use (_pf)
+        self._graph_captures = 0                 # HIP graphs holding pointers into self._ws (note_graph_capture)
+        # variants of the blocks' grouped weight-gradient launches beside the plain one: what each is built with (None = not
+        # enabled: enable_fused_adamw's descriptor, enable_grad_mirror's buffer), and the one backward launches (wgrad_variant)
+        self._variant_args = {"adamw": None, "g16": None}
+        self._variant = "plain"
+        self._adamw_side, self._adamw_side_blocks = "0", 0
         self.initialize_weights(seed)
 
     # ------------------------------------------------------------------ parameters
@@ -241,20 +312,13 @@ class MAEEngine:
         w["pe_dst"] = (torch.arange(B, device=dev)[:, None] * Ne + E + torch.arange(keep, device=dev)[None, :]).to(torch.int32).contiguous()
         w["patches"] = torch.empty(B * keep, pv, **lp)
         w["latent32"] = torch.empty(Me, D, **f32)
-
-        def block_bufs(M, dim):
-            return dict(ln1=torch.empty(M, dim, **lp), mean1=torch.empty(M, **f32), rstd1=torch.empty(M, **f32),
-                        qkv=torch.empty(M, 3 * dim, **lp), att=torch.empty(M, dim, **lp), xmid=torch.empty(M, dim, **f32),
-                        ln2=torch.empty(M, dim, **lp), mean2=torch.empty(M, **f32), rstd2=torch.empty(M, **f32),
-                        hpre=torch.empty(M, int(dim * cfg.mlp_ratio), **lp), hact=torch.empty(M, int(dim * cfg.mlp_ratio), **lp))
-
         n_enc_sets = cfg.depth if train else 1
-        w["enc"] = [block_bufs(Me, D) for _ in range(n_enc_sets)]
+        w["enc"] = [self._block_bufs(Me, D) for _ in range(n_enc_sets)]
         w["xs"] = [torch.empty(Me, D, **f32) for _ in range((cfg.depth + 1) if train else 2)]
         w["lat_lp"] = torch.empty(Me, D, **lp)
         w["lat_mean"], w["lat_rstd"] = torch.empty(Me, **f32), torch.empty(Me, **f32)
         if train:
-            w["dec"] = [block_bufs(Md, Dd) for _ in range(cfg.decoder_depth)]
+            w["dec"] = [self._block_bufs(Md, Dd) for _ in range(cfg.decoder_depth)]
             w["xd"] = [torch.empty(Md, Dd, **f32) for _ in range(cfg.decoder_depth + 1)]
             w["dlat_lp"] = torch.empty(Md, Dd, **lp)
             w["dlat_mean"], w["dlat_rstd"] = torch.empty(Md, **f32), torch.empty(Md, **f32)
@@ -263,20 +327,7 @@ class MAEEngine:
             w["loss_ws"] = torch.empty(4 * B * L + 4, **f32)
             w["dpred"] = torch.empty(Md, pv, **lp)
             # backward temporaries (sized for the larger of encoder / decoder)
-            Mx = max(Me, Md)
-            Dx = max(D, Dd)
-            Hx = max(Me * int(D * cfg.mlp_ratio), Md * int(Dd * cfg.mlp_ratio))
-            w["g"] = torch.empty(Mx * Dx, **f32)
-            w["g_lp"] = torch.empty(Mx * Dx, **lp)
-            w["g_lp2"] = torch.empty(Mx * Dx, **lp)   # d(xmid) copy: keeps g_lp (fc2's dy) alive for the grouped wgrad launch
-            # second set of the four dy buffers a block's grouped weight-gradient launch reads: consecutive blocks
-            # alternate between the sets, so that launch can run on the side stream under the NEXT block's dgrad chain
-            w["g_lp_b"], w["g_lp2_b"] = torch.empty(Mx * Dx, **lp), torch.empty(Mx * Dx, **lp)
-            w["dh_b"], w["dqkv_b"] = torch.empty(Hx, **lp), torch.empty(3 * Mx * Dx, **lp)
-            w["dln"] = torch.empty(Mx * Dx, **lp)
-            w["datt"] = torch.empty(Mx * Dx, **lp)
-            w["dh"] = torch.empty(Hx, **lp)
-            w["dqkv"] = torch.empty(3 * Mx * Dx, **lp)
+            self._bwd_scratch(w, max(Me, Md) * max(D, Dd), max(Me * int(D * cfg.mlp_ratio), Md * int(Dd * cfg.mlp_ratio)))
             # LayerNorm dgamma/dbeta: every LN keeps its own partial sums; ONE batched launch per backward stage
             # finishes them (42 reduce launches -> 3-6).  Table order = the order backward visits the LNs.
             order = [("ln", "decoder_norm", Md, Dd)]
@@ -287,25 +338,53 @@ class MAEEngine:
                 order.append(("block", f"blocks.{i}", w["enc"][i], Me, D))
             self._build_reduce_table(w, order)
             w["dE"] = torch.empty(Me, Dd, **lp)
-            # the four weight-gradient GEMMs of a block as ONE grouped launch (ops.GemmGroup): together they fill the
-            # chip, so none needs split-K slabs or a reduce launch.  bf16 path only; pointers are fixed from here on.
-            # (the block's norm1 backward rides in the same launch as a side job: _make_wgrad_group)
-            w["splitk_ws"] = self._splitk_ws
-            w["wgrad_groups"] = {}
-            if self.dtype in ops.LP_DTYPES:
-                for tag, blocks, M_, dim in (("blocks", w["enc"], Me, D), ("decoder_blocks", w["dec"], Md, Dd)):
-                    for i, bufs in enumerate(blocks):
-                        w["wgrad_groups"][f"{tag}.{i}"] = self._make_wgrad_group(f"{tag}.{i}", bufs, M_, dim, w)
+            self._build_wgrad_groups(w, (("blocks", w["enc"], Me, D), ("decoder_blocks", w["dec"], Md, Dd)))
             w["dT"] = torch.empty(B * keep, D, **lp)
             w["drows"] = torch.empty(B * keep, pv, **f32)
             w["pmv_part"] = torch.empty(B, pv, **f32)
             w["rs_part"] = torch.empty(256, max(D, Dd), **f32)
-        if train and getattr(self, "_fused_adamw", None) is not None and w.get("wgrad_groups"):
-            self._build_adamw_groups(w)
-        if train and getattr(self, "_g16", None) is not None and w.get("wgrad_groups"):
-            self._build_variant_groups(w, "g16")
         self._ws[key] = w
         return w
+
+    def _block_bufs(self, M, dim):
+        """What a transformer block's forward leaves for its backward (M token rows of width dim)."""
+        f32, lp = dict(device=self.device, dtype=torch.float32), dict(device=self.device, dtype=self.dtype)
+        hidden = int(dim * self.cfg.mlp_ratio)
+        return dict(ln1=torch.empty(M, dim, **lp), mean1=torch.empty(M, **f32), rstd1=torch.empty(M, **f32),
+                    qkv=torch.empty(M, 3 * dim, **lp), att=torch.empty(M, dim, **lp), xmid=torch.empty(M, dim, **f32),
+                    ln2=torch.empty(M, dim, **lp), mean2=torch.empty(M, **f32), rstd2=torch.empty(M, **f32),
+                    hpre=torch.empty(M, hidden, **lp), hact=torch.empty(M, hidden, **lp))
+
+    def _bwd_scratch(self, w, n, n_hidden):
+        """Backward temporaries of the transformer blocks: n = rows x width, n_hidden = rows x MLP width (of the larger stack)."""
+        f32, lp = dict(device=self.device, dtype=torch.float32), dict(device=self.device, dtype=self.dtype)
+        w["g"] = torch.empty(n, **f32)
+        w["g_lp"] = torch.empty(n, **lp)
+        w["g_lp2"] = torch.empty(n, **lp)   # d(xmid) copy: keeps g_lp (fc2's dy) alive for the grouped wgrad launch
+        # second set of the four dy buffers a block's grouped weight-gradient launch reads: consecutive blocks
+        # alternate between the sets, so that launch can run on the side stream under the NEXT block's dgrad chain
+        w["g_lp_b"], w["g_lp2_b"] = torch.empty(n, **lp), torch.empty(n, **lp)
+        w["dh_b"], w["dqkv_b"] = torch.empty(n_hidden, **lp), torch.empty(3 * n, **lp)
+        w["dln"] = torch.empty(n, **lp)
+        w["datt"] = torch.empty(n, **lp)
+        w["dh"] = torch.empty(n_hidden, **lp)
+        w["dqkv"] = torch.empty(3 * n, **lp)
+
+    def _build_wgrad_groups(self, w, stacks):
+        """The four weight-gradient GEMMs of a block as ONE grouped launch (ops.GemmGroup): together they fill the
+        chip, so none needs split-K slabs or a reduce launch.  16-bit paths only; pointers are fixed from here on.
+        (the block's norm1 backward rides in the same launch as a side job: _make_wgrad_group -- so the reduce table and
+        every buffer a folded problem reads exist by now.)  stacks: (tag, per-block buffers, rows, width) per block stack.
+        w[WGRAD_GROUPS_KEY[variant]][prefix]: 'plain' always (None where a block cannot be grouped), then every enabled variant."""
+        w["splitk_ws"] = self.splitk_ws
+        plain = w["wgrad_groups"] = {}
+        if self.dtype in ops.LP_DTYPES:
+            for tag, blocks, M, dim in stacks:
+                for i, bufs in enumerate(blocks):
+                    plain[f"{tag}.{i}"] = self._make_wgrad_group(f"{tag}.{i}", bufs, M, dim, w)
+        for kind, arg in self._variant_args.items():
+            if arg is not None and plain:
+                self._build_variant_groups(w, kind)
 
     def _build_reduce_table(self, w, order):
         """Device table of the batched column reduces of backward (ops.layernorm_bwd_reduce_batch), in the order backward visits
@@ -365,19 +444,17 @@ class MAEEngine:
     def _pf(self, direction, wname, rows=0):
         """The bf16 weights the GEMM after the one reading `wname` will read (forward chain / backward's data-gradient chain), or None.
         rows: token rows of the naming launch."""
-        import os
         if rows >= int(os.environ.get("SKYEMB_PF_MAX_ROWS", self.PF_MAX_ROWS)):
             return None
-        maps = getattr(self, "_pf_maps", None)
-        if maps is None:
+        if self._pf_maps is None:
             chain = self._weight_chain()
-            maps = self._pf_maps = {"fwd": dict(zip(chain[:-1], chain[1:])), "bwd": dict(zip(chain[1:], chain[:-1]))}
+            self._pf_maps = {"fwd": dict(zip(chain[:-1], chain[1:])), "bwd": dict(zip(chain[1:], chain[:-1]))}
         if self.dtype not in ops.LP_DTYPES:
             return None
         only = os.environ.get("SKYEMB_PF_ONLY", "")        # (bench.py's A/B: hints in one direction only)
         if only and only != direction:
             return None
-        nxt = maps[direction].get(wname)
+        nxt = self._pf_maps[direction].get(wname)
         return None if nxt is None else self.store.lp(nxt)
 
     # ------------------------------------------------------------------ forward pieces
@@ -396,6 +473,13 @@ class MAEEngine:
         ops.gemm(w["patches"], st.lp("patch_embed.proj.weight"), M=B * keep, N=D, K=pv,
                  bias=st.param("patch_embed.proj.bias"), table=pos[E:], tab_row=w["ids_keep"], ldt=D,
                  dst_row=w["pe_dst"], out_f32=x0, ldo32=D, prefetch=self._pf("fwd", "patch_embed.proj.weight", B * keep))
+        self._extra_tokens_fwd(x0, pos, B, Ne, ra_dec, w)
+        return x0
+
+    def _extra_tokens_fwd(self, x0, pos, B, Ne, ra_dec, w):
+        """The rows in front of every sample's patch tokens: cls (, RA/Dec)."""
+        cfg, st = self.cfg, self.store
+        D = cfg.embed_dim
         # cls_token + pos_embed[:, :1] (utils/mim_vit.py:417-419): B tiny row copies (host glue)
         x0.view(B, Ne, D)[:, 0, :] = st.param("cls_token").view(D) + pos[0]
         if cfg.ra_dec:
@@ -405,7 +489,6 @@ class MAEEngine:
                                 P("ra_dec_embed.neural_network.layers.0.bias"), P("ra_dec_embed.neural_network.last_layer.weight"),
                                 P("ra_dec_embed.neural_network.last_layer.bias"), pos[1], x0.view(-1)[D:], Ne * D, B, D,
                                 w["sh"], w["z"])
-        return x0
 
     def _block_fwd(self, x_in, x_out, bufs, prefix, M, dim, heads, Bsz, N):
         st, eps = self.store, self.cfg.ln_eps
@@ -419,13 +502,25 @@ class MAEEngine:
                  out=bufs["qkv"], prefetch=PF("attn.qkv"))
         ops.mha_fwd(bufs["qkv"], bufs["att"], Bsz, N, heads, hd)
         ops.gemm(bufs["att"], LP(f"{prefix}.attn.proj.weight"), M=M, N=dim, K=dim, bias=P(f"{prefix}.attn.proj.bias"),
-                 resid=x_in, ldr=dim, out_f32=bufs["xmid"], ws=self._splitk_ws, prefetch=PF("attn.proj"))
+                 resid=x_in, ldr=dim, out_f32=bufs["xmid"], ws=self.splitk_ws, prefetch=PF("attn.proj"))
         ops.layernorm_fwd(bufs["xmid"], P(f"{prefix}.norm2.weight"), P(f"{prefix}.norm2.bias"), bufs["ln2"],
                           bufs["mean2"], bufs["rstd2"], M, dim, eps)
         ops.gemm(bufs["ln2"], LP(f"{prefix}.mlp.fc1.weight"), M=M, N=hidden, K=dim, bias=P(f"{prefix}.mlp.fc1.bias"),
                  act=ACT_GELU, out=bufs["hact"], out2=bufs["hpre"], prefetch=PF("mlp.fc1"))
         ops.gemm(bufs["hact"], LP(f"{prefix}.mlp.fc2.weight"), M=M, N=dim, K=hidden, bias=P(f"{prefix}.mlp.fc2.bias"),
-                 resid=bufs["xmid"], ldr=dim, out_f32=x_out, ws=self._splitk_ws, prefetch=PF("mlp.fc2"))
+                 resid=bufs["xmid"], ldr=dim, out_f32=x_out, ws=self.splitk_ws, prefetch=PF("mlp.fc2"))
+
+    def _blocks_fwd(self, w, B, Ne, train):
+        """The encoder blocks over w['xs'][0]: training keeps every block's stream and activations, inference alternates between
+        two streams and one buffer set.  -> the last block's output stream."""
+        cfg, xs = self.cfg, w["xs"]
+        M, D = B * Ne, cfg.embed_dim
+        for i in range(cfg.depth):
+            if train:
+                self._block_fwd(xs[i], xs[i + 1], w["enc"][i], f"blocks.{i}", M, D, cfg.num_heads, B, Ne)
+            else:
+                self._block_fwd(xs[i % 2], xs[(i + 1) % 2], w["enc"][0], f"blocks.{i}", M, D, cfg.num_heads, B, Ne)
+        return xs[cfg.depth] if train else xs[cfg.depth % 2]
 
     def _encoder_fwd(self, imgs, noise, keep, w, train, ra_dec=None):
         cfg, st = self.cfg, self.store
@@ -433,29 +528,28 @@ class MAEEngine:
         D, Ne = cfg.embed_dim, cfg.num_extra_tokens + keep
         Me = B * Ne
         self._embed(imgs, noise, keep, w, ra_dec)
-        xs = w["xs"]
-        for i in range(cfg.depth):
-            if train:
-                self._block_fwd(xs[i], xs[i + 1], w["enc"][i], f"blocks.{i}", Me, D, cfg.num_heads, B, Ne)
-            else:
-                self._block_fwd(xs[i % 2], xs[(i + 1) % 2], w["enc"][0], f"blocks.{i}", Me, D, cfg.num_heads, B, Ne)
-        x_last = xs[cfg.depth] if train else xs[cfg.depth % 2]
+        x_last = self._blocks_fwd(w, B, Ne, train)
         ops.layernorm_fwd(x_last, st.param("norm.weight"), st.param("norm.bias"), w["lat_lp"], w["lat_mean"],
                           w["lat_rstd"], Me, D, cfg.ln_eps, y32=w["latent32"])
         return x_last
 
     # ------------------------------------------------------------------ public forward paths
-    def _check_ra_dec(self, imgs, ra_dec):
+    def check_ra_dec(self, imgs, ra_dec):
         if not self.cfg.ra_dec:
             return None
         assert ra_dec is not None and tuple(ra_dec.shape) == (imgs.shape[0], 2), "ra_dec=True models need ra_dec [B,2] (degrees)"
         return ra_dec.to(device=imgs.device, dtype=torch.float32).contiguous()
 
-    def _check_inputs(self, imgs, noise):
+    def _check_cutouts(self, imgs):
         cfg = self.cfg
         assert imgs.is_cuda and imgs.dtype == torch.float32 and imgs.is_contiguous()
         B, C, H, W = imgs.shape
         assert (C, H, W) == (cfg.in_chans, cfg.img_size, cfg.img_size), f"bad cutout shape {tuple(imgs.shape)}"
+        return B
+
+    def _check_inputs(self, imgs, noise):
+        cfg = self.cfg
+        B = self._check_cutouts(imgs)
         if noise is None:
             noise = torch.rand(B, cfg.num_patches, device=imgs.device)  # utils/mim_vit.py:363
         assert noise.shape == (B, cfg.num_patches) and noise.is_cuda and noise.dtype == torch.float32
@@ -465,19 +559,27 @@ class MAEEngine:
         """utils/mim_vit.py:381-438 (MAE mode): -> (latent fp32 [B, E+keep, D], mask [B,L], ids_restore [B,L])."""
         cfg = self.cfg
         noise = self._check_inputs(imgs, noise)
-        ra_dec = self._check_ra_dec(imgs, ra_dec)
+        ra_dec = self.check_ra_dec(imgs, ra_dec)
         B = imgs.shape[0]
         keep = int(cfg.num_patches * (1 - mask_ratio))
         w = self._workspace(B, keep, False)
         self._encoder_fwd(imgs, noise, keep, w, False, ra_dec)
         return w["latent32"].view(B, cfg.num_extra_tokens + keep, cfg.embed_dim), w["mask"], w["ids_restore"]
 
+    def encoder_forward_train(self, imgs, noise, keep, ra_dec=None):
+        """The encoder alone in training mode (activations kept), recorded as the last forward: a caller with a head of its own
+        (utils.vit) continues from the returned workspace and enters backward through start_backward_at()."""
+        w = self._workspace(imgs.shape[0], keep, True)
+        self._encoder_fwd(imgs, noise, keep, w, True, ra_dec)
+        self._last = (imgs, imgs.shape[0], keep)
+        return w
+
     def forward_train(self, imgs, mask_ratio=0.75, noise=None, ra_dec=None):
         """utils/mim_vit.py:552-559: -> (loss [1] device tensor, pred fp32 view [B, L, pv], mask [B, L]).
         Activations are saved for :meth:`backward`."""
         cfg, st = self.cfg, self.store
         noise = self._check_inputs(imgs, noise)
-        ra_dec = self._check_ra_dec(imgs, ra_dec)
+        ra_dec = self.check_ra_dec(imgs, ra_dec)
         B = imgs.shape[0]
         L, D, Dd, pv, E = cfg.num_patches, cfg.embed_dim, cfg.decoder_embed_dim, cfg.patch_dim, cfg.num_extra_tokens
         keep = int(L * (1 - mask_ratio))
@@ -527,7 +629,7 @@ class MAEEngine:
         if bool(on) != (self._side is not None):
             # workspaces are planned for one of the two schedules (side workgroups and folded problems of the grouped launches exist
             # only without the side stream: _norm1_side_record, _extra_wgrad_layers): rebuild them on the next forward
-            if self._ws and getattr(self, "_graph_captures", 0):
+            if self._ws and self._graph_captures:
                 # HIP graphs captured by an earlier TrainStep hold raw pointers into those workspaces (group blobs, scratch):
                 # dropping them would leave that step replaying freed memory
                 raise RuntimeError("enable_wgrad_overlap: the weight-gradient schedule cannot change while HIP graphs captured on this "
@@ -535,26 +637,33 @@ class MAEEngine:
             self._ws, self._last = {}, None
         if on and self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
-            self._splitk_ws_side = torch.zeros_like(self._splitk_ws)
+            self._splitk_ws_side = torch.zeros_like(self.splitk_ws)
         elif not on:
             self._side = None
         self._pending = {}
 
+    def note_graph_capture(self):
+        """A caller has captured HIP graphs on this engine's workspaces (enable_wgrad_overlap refuses to re-plan under them)."""
+        self._graph_captures += 1
+
     def _wgrad(self, dy, x_in, M, N, K, dW, db, w):
-        side = self._side
-        if side is None:
-            ops.gemm(dy, x_in, M=M, N=N, K=K, a_layout=RC, b_layout=RC, lda=M, ldb=N, out_f32=dW, colsum_a=db,
-                     ws=w["splitk_ws"])
-            return
+        def launch(ws):
+            ops.gemm(dy, x_in, M=M, N=N, K=K, a_layout=RC, b_layout=RC, lda=M, ldb=N, out_f32=dW, colsum_a=db, ws=ws)
+        if self._side is None:
+            launch(w["splitk_ws"])
+        else:
+            self._pending[dy.data_ptr()] = self._on_side(lambda: launch(self._splitk_ws_side))
+
+    def _on_side(self, launch):
+        """Run `launch` on the weight-gradient stream, behind everything enqueued so far -> the event recorded after it."""
         ready = torch.cuda.Event()
         ready.record()
-        side.wait_event(ready)
-        with torch.cuda.stream(side):
-            ops.gemm(dy, x_in, M=M, N=N, K=K, a_layout=RC, b_layout=RC, lda=M, ldb=N, out_f32=dW, colsum_a=db,
-                     ws=self._splitk_ws_side)
+        self._side.wait_event(ready)
+        with torch.cuda.stream(self._side):
+            launch()
             done = torch.cuda.Event()
             done.record()
-        self._pending[dy.data_ptr()] = done
+        return done
 
     def _before_write(self, buf):
         if self._side is not None:
@@ -612,9 +721,8 @@ class MAEEngine:
             if g16 is None:
                 return dict(out_f32=st.grad(f"{name}.weight"))
             o = st.offsets[f"{name}.weight"]
-            return dict(out=g16[o:o + n_out * k_in].view(n_out, k_in))
+            return dict(out=g16[o:o + n_out * k_in].view(n_out, k_in))       # (the tensor itself: span() includes its padding)
         layers = self._wgrad_layers(prefix, bufs, M, dim, w) + self._extra_wgrad_layers(prefix, M, w)
-        import os
         # (experiments: SKYEMB_WGRAD_TILE_ENC / _DEC force the grouped launch's tile code for one stack)
         tile = int(os.environ.get("SKYEMB_WGRAD_TILE_DEC" if prefix.startswith("decoder") else "SKYEMB_WGRAD_TILE_ENC", "0"))
         # (the launch sits between the data-gradient chains of two blocks: its first problem touches the weights the next chain starts
@@ -635,7 +743,6 @@ class MAEEngine:
         (same token rows = same contraction length; round 5): `decoder_pred` into the first decoder block's launch, `decoder_embed`
         into the first encoder block's.  As launches of their own (a split-K GEMM + its reduce each) they were 25 and 14 us of the
         step's dependent chain.  -> [(dy, x_in, layer name, n_out, k_in)]; the names are recorded in w['folded_wgrads']."""
-        import os
         if (os.environ.get("SKYEMB_FOLD_WGRADS", "1") == "0" or self._side is not None or "dpred" not in w
                 or not self.fold_decoder_wgrads):
             # (fold_decoder_wgrads = False: a caller that runs backward_encoder / backward_embed WITHOUT backward_decoder -- the
@@ -660,7 +767,6 @@ class MAEEngine:
         of its own it sat BEHIND the grouped launch, 7-11 us at ViT-B and 29 us at ViT-L per block on the step's critical path.
         Same buffers _block_bwd would hand ops.layernorm_bwd; None when the schedule cannot take it (weight gradients on a side
         stream: the next block would read the residual gradient before this launch is done; SKYEMB_LN_SIDE=0)."""
-        import os
         if self._side is not None or os.environ.get("SKYEMB_LN_SIDE", "1") == "0" or "ln_parts" not in w:
             return None
         s = self._bwd_set(prefix)
@@ -681,18 +787,16 @@ class MAEEngine:
         384 tiles for 512 slots), the epilogue form elsewhere (the ViT-B encoder's launches fill the chip and the side form
         LOSES there).  Either way fused_adamw_ranges(workspace) are the slices of the flat buffers these launches update -- the
         caller runs the ordinary AdamW on the rest (embeddings, biases, LayerNorms, the single weight gradients)."""
-        self._fused_adamw = None
+        self._variant_args["adamw"] = None
         if not on:
             return
-        import os
         # placement policy: "auto" (default) = side jobs where the carrying launch leaves compute units idle (256 x 256 tiles:
         # ViT-L), epilogue elsewhere; "1" / True = side jobs everywhere; "0" / False = epilogue everywhere; "dec" / "enc" =
         # side jobs carried by the decoder's / encoder's launches only (experiments)
         self._adamw_side = os.environ.get("SKYEMB_ADAMW_SIDE", "auto") if side is None else ("1" if side is True else "0" if side is False else str(side))
-        assert self._adamw_side in ("auto", "0", "1", "dec", "enc"), self._adamw_side
+        assert self._adamw_side in ADAMW_SIDE_MODES, self._adamw_side
         self._adamw_side_blocks = int(os.environ.get("SKYEMB_SIDE_BLOCKS", "256"))
         assert self.dtype in ops.LP_DTYPES, "the fused optimiser step exists on the 16-bit paths (grouped weight gradients)"
-        from ._lib import AdamwDesc
         st = self.store
         b1, b2 = optimizer.defaults["betas"]
         d = AdamwDesc()
@@ -701,19 +805,42 @@ class MAEEngine:
         d.n_decay = st.n_decay
         d.beta1, d.beta2, d.eps = b1, b2, optimizer.defaults["eps"]
         d.weight_decay, d.grad_scale = optimizer.param_groups[1]["weight_decay"], optimizer.grad_scale
-        self._fused_adamw = d
+        self._enable_variant("adamw", d)
+
+    def _enable_variant(self, kind, arg):
+        self._variant_args[kind] = arg
         for w in self._ws.values():                           # workspaces built before the switch
             if "wgrad_groups" in w:
-                self._build_adamw_groups(w)
+                self._build_variant_groups(w, kind)
+
+    @property
+    def adamw_side(self):
+        """Placement policy of the fused optimiser step: 'auto' | '0' | '1' | 'dec' | 'enc' (enable_fused_adamw)."""
+        return self._adamw_side
+
+    @property
+    def fused_adamw_desc(self):
+        """The _lib.AdamwDesc the fused launches were planned with (None: enable_fused_adamw not called, or turned off)."""
+        return self._variant_args["adamw"]
+
+    @contextmanager
+    def wgrad_variant(self, kind):
+        """backward() inside this context launches the blocks' weight-gradient groups of variant `kind` ('adamw': the launches
+        carry the optimiser step; 'g16': they write the bf16 mirror; 'plain') where that variant is enabled and has a group
+        for the block.  Only a TrainStep that owns the optimiser step / the mirror enters it around ITS launches, so that
+        engine.backward() called by anybody else -- loss.backward() of the module API, tests -- stores plain gradients."""
+        assert kind in WGRAD_GROUPS_KEY, kind
+        prev, self._variant = self._variant, kind
+        try:
+            yield
+        finally:
+            self._variant = prev
 
     # -- data-parallel runs with bf16 gradient communication: the block weights' gradients go straight into the bf16 mirror --
     def enable_grad_mirror(self, g16):
         """The grouped weight-gradient launches write bf16 into `g16` (the flat mirror the all-reduce sums) instead of fp32 into
         the gradient buffer; grad_mirror_ranges(workspace) are the slices they cover -- the caller casts only the rest."""
-        self._g16 = g16
-        for w in self._ws.values():
-            if "wgrad_groups" in w:
-                self._build_variant_groups(w, "g16")
+        self._enable_variant("g16", g16)
 
     def grad_mirror_ranges(self, w):
         return list(w.get("g16_ranges", []))
@@ -722,9 +849,6 @@ class MAEEngine:
         """Slices of the flat buffers the fused launches of workspace `w` update (merged, ascending)."""
         return list(w.get("fused_ranges", []))
 
-    def _build_adamw_groups(self, w):
-        self._build_variant_groups(w, "adamw")
-
     def _wgrad_launch_order(self, w):
         """Prefixes of the blocks in the order backward() launches their grouped weight gradients."""
         order = [f"decoder_blocks.{i}" for i in reversed(range(len(w.get("dec", []))))]
@@ -732,74 +856,43 @@ class MAEEngine:
 
     def _block_weight_span(self, prefix):
         """[lo, hi) of the flat buffers holding a block's four weight matrices (layout order keeps them together)."""
-        st = self.store
-        spans = sorted((st.offsets[f"{prefix}.{n}.weight"], st.offsets[f"{prefix}.{n}.weight"] + _pad8(int(np.prod(st.shapes[f"{prefix}.{n}.weight"]))))
-                       for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"))
-        assert all(a[1] == b[0] for a, b in zip(spans, spans[1:])), "a block's weight matrices are not contiguous in the flat buffers"
-        return spans[0][0], spans[-1][1]
+        spans = merge_spans(self.store.span(f"{prefix}.{n}.weight") for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"))
+        assert len(spans) == 1, "a block's weight matrices are not contiguous in the flat buffers"
+        return spans[0]
 
     def _build_variant_groups(self, w, kind):
         """A second set of the blocks' grouped weight-gradient launches: kind 'adamw' (optimiser step carried by the launches -- in
-        the epilogue, or as the side job of the following launch: enable_fused_adamw; ranges in w['fused_ranges']) or 'g16' (bf16
-        output into the communication mirror; w['g16_ranges'])."""
-        st = self.store
+        the epilogue, or as the side job of the following launch: enable_fused_adamw, plan_wgrad_schedule; ranges in
+        w['fused_ranges']) or 'g16' (bf16 output into the communication mirror; w['g16_ranges'])."""
+        st, arg = self.store, self._variant_args[kind]
+        plain = w["wgrad_groups"]
         groups, spans = {}, []
-        order = [p for p in self._wgrad_launch_order(w) if w["wgrad_groups"].get(p) is not None]
-        # carry[k]: launch k carries the step of launch k-1's block as a side job (launch k-1 then STORES its gradients)
-        carry = [False] * len(order)
+        order = [p for p in self._wgrad_launch_order(w) if plain.get(p) is not None]
+        plan = [(False, False)] * len(order)
         if kind == "adamw":
-            mode = getattr(self, "_adamw_side", "0")
             ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
-            for k in range(1, len(order)):
-                grp0 = w["wgrad_groups"][order[k]]
-                info = grp0.info
-                # "auto": the carrying launch must leave a quarter of the device's workgroup slots free (slots per compute unit
-                # follow from the tile's LDS ring: one 256 x 256, two 128 x 128 / 128 x 64, three 64 x 64).  Measured (bench.py
-                # extra.optimizer_placement): ViT-L, 192 tiles of 256 x 256 on 256 units: 26.5 -> 25.5 ms per step; ViT-B decoder,
-                # 384 tiles of 128 x 64 on 512 slots: 5.24 -> 5.21; ViT-B encoder, 440 of 512: side jobs LOSE (5.24 -> 5.47 with
-                # every launch carrying one: they start when the tiles end, and move 34 instead of 26 bytes per parameter)
-                slots = ncu * {256256: 1, 128128: 2, 9128128: 1, 128064: 2, 64064: 3}.get(info.tile, 1)
-                carry[k] = (mode == "1" or (mode == "auto" and grp0.tile_blocks <= 0.76 * slots) or
-                            (mode == "dec" and order[k].startswith("decoder_blocks")) or (mode == "enc" and order[k].startswith("blocks")))
-        w["adamw_side_launches"] = sum(carry)
-        for k, prefix in enumerate(order):
+            plan = plan_wgrad_schedule(order, [(plain[p].info.tile, plain[p].tile_blocks) for p in order], ncu, self._adamw_side)
+            w["adamw_side_launches"] = sum(carries for carries, _ in plan)
+        for k, (prefix, (carries, stores)) in enumerate(zip(order, plan)):
             tag, i = prefix.rsplit(".", 1)
             bufs = (w["enc"] if tag == "blocks" else w["dec"])[int(i)]
             M, dim = bufs["ln1"].shape
-            stores = k + 1 < len(order) and carry[k + 1]
-            if kind == "adamw" and (carry[k] or stores):
-                lo, hi = self._block_weight_span(order[k - 1]) if carry[k] else (0, 0)
+            side = None
+            if carries or stores:
+                lo, hi = self._block_weight_span(order[k - 1]) if carries else (0, 0)
                 side = (not stores, lo, hi, self._adamw_side_blocks if hi > lo else 0)
-                grp = self._make_wgrad_group(prefix, bufs, M, dim, w, adamw=self._fused_adamw, side=side)
-                side_mode = True
-            elif kind == "adamw":
-                grp = self._make_wgrad_group(prefix, bufs, M, dim, w, adamw=self._fused_adamw)
-                side_mode = False
-            else:
-                grp = self._make_wgrad_group(prefix, bufs, M, dim, w, g16=self._g16)
-                side_mode = False
+            grp = self._make_wgrad_group(prefix, bufs, M, dim, w, side=side, **{kind: arg})
             if grp is None:
-                assert not side_mode, f"side optimiser jobs: the grouped launch of {prefix} could not be planned"
+                assert side is None, f"side optimiser jobs: the grouped launch of {prefix} could not be planned"
                 continue
             groups[prefix] = grp
-            for name in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2"):
-                o = st.offsets[f"{prefix}.{name}.weight"]
-                spans.append((o, o + _pad8(int(np.prod(st.shapes[f"{prefix}.{name}.weight"])))))
+            spans += [st.span(f"{prefix}.{name}.weight") for name in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
             # folded single weight gradients: written to the mirror / stepped in the epilogue with the launch's own tiles; where the
             # launch only STORES gradients they stay with the ordinary AdamW launch like every tensor outside the blocks
-            if kind != "adamw" or not stores:
-                for name in getattr(grp, "extra_layers", []):
-                    o = st.offsets[f"{name}.weight"]
-                    spans.append((o, o + _pad8(int(np.prod(st.shapes[f"{name}.weight"])))))
-        spans.sort()
-        merged = []
-        for s_, e_ in spans:
-            if merged and merged[-1][1] == s_:
-                merged[-1] = (merged[-1][0], e_)
-            else:
-                merged.append((s_, e_))
-        w["wgrad_groups_adamw" if kind == "adamw" else "wgrad_groups_g16"] = groups
-        w["fused_ranges" if kind == "adamw" else "g16_ranges"] = merged
+            if not stores:
+                spans += [st.span(f"{name}.weight") for name in grp.extra_layers]
+        w[WGRAD_GROUPS_KEY[kind]] = groups
+        w["fused_ranges" if kind == "adamw" else "g16_ranges"] = merge_spans(spans)
 
     def _block_bwd(self, x_in, bufs, prefix, M, dim, heads, Bsz, N, g, g_lp, w):
         """g holds d(block output) on entry and d(block input) on exit (fp32); its compute-dtype copy is read from the
@@ -813,13 +906,9 @@ class MAEEngine:
         dqkv = self._scratch(w, "dqkv", s, 3 * M * dim).view(M, 3 * dim)
         dln = w["dln"][:M * dim].view(M, dim)
         datt = w["datt"][:M * dim].view(M, dim)
-        # (only inside a TrainStep that owns the optimiser step: `_fused_active` is raised around ITS launches, so that
-        # engine.backward() called by anybody else -- loss.backward() of the module API, tests -- stores plain gradients)
-        fused = (getattr(self, "_fused_active", False) and getattr(self, "_fused_adamw", None) is not None
-                 and prefix in w.get("wgrad_groups_adamw", {}))
-        mirror = (not fused and getattr(self, "_g16_active", False) and getattr(self, "_g16", None) is not None
-                  and prefix in w.get("wgrad_groups_g16", {}))
-        group = (w["wgrad_groups_adamw"] if fused else w["wgrad_groups_g16"] if mirror else w["wgrad_groups"]).get(prefix)
+        group = w["wgrad_groups"].get(prefix)
+        if self._variant_args.get(self._variant) is not None:        # (wgrad_variant: a TrainStep around its own launches)
+            group = w.get(WGRAD_GROUPS_KEY[self._variant], {}).get(prefix, group)
         single = group is None                      # weight gradients launch by launch (fp32 mode)
         g_mid = g_lp if single else self._scratch(w, "g_lp2", s, M * dim).view(M, dim)
         # MLP: x_out = xmid + fc2(gelu(fc1(ln2(xmid))))
@@ -843,13 +932,7 @@ class MAEEngine:
             if self._side is None:
                 group.launch()
             else:
-                ready = torch.cuda.Event()
-                ready.record()
-                self._side.wait_event(ready)
-                with torch.cuda.stream(self._side):
-                    group.launch()
-                    self._group_done = torch.cuda.Event()
-                    self._group_done.record()
+                self._group_done = self._on_side(group.launch)
         if prev_done is not None:
             torch.cuda.current_stream().wait_event(prev_done)   # the previous block's launch still reads g_lp_next
         if group is not None and group.ln_side:
@@ -860,10 +943,19 @@ class MAEEngine:
         else:
             self._ln_bwd(dln, x_in, f"{prefix}.norm1", bufs["mean1"], bufs["rstd1"], g, g, g_lp_next, M, dim, w)
 
-    def _last_key(self):
-        """Workspace key of the last forward_train() call."""
+    def last_key(self):
+        """Workspace key (B, keep, True) of the last forward_train() call."""
         assert self._last is not None, "no forward_train() yet"
         return (self._last[1], self._last[2], True)
+
+    def last_workspace(self):
+        """The workspace the last forward_train() ran on (the one backward() will use)."""
+        return self._ws[self.last_key()]
+
+    def start_backward_at(self, ln_name):
+        """Backward enters below the loss, at LayerNorm `ln_name`: the batched dgamma / dbeta reduce of the stage starts with its
+        table entry (callers with a head of their own: utils.vit; backward_decoder() starts at the table's top itself)."""
+        self._ln_first, self._ln_count = self.last_workspace()["ln_index"][ln_name], 0
 
     def _bwd_ctx(self):
         assert self._last is not None, "backward() without forward_train()"
@@ -916,10 +1008,17 @@ class MAEEngine:
     def backward_embed(self):
         """Last stage: cls token, patch embedding, patch_mask_values (g = d xs[0])."""
         imgs, B, keep, Ne, Nd, w = self._bwd_ctx()
+        self._embed_bwd(B, Ne, keep, w)
+        ops.patch_gather_bwd_pmv(imgs, w["ids_keep"], w["drows"], w["pmv_part"], self.store.grad("patch_mask_values"),
+                                 self.cfg.patch_size, keep)
+        self._end_stage(w, last=True)
+
+    def _embed_bwd(self, B, Ne, n_patch, w):
+        """g = d xs[0] [B * Ne, D] -> gradients of the cls token, the RA/Dec encoder and the patch embedding; leaves the gradient of
+        the n_patch embedded patch rows per sample in w['drows'] (for patch_mask_values)."""
         cfg, st = self.cfg, self.store
         D, pv = cfg.embed_dim, cfg.patch_dim
-        Me = B * Ne
-        g = w["g"][:Me * D].view(Me, D)
+        g = w["g"][:B * Ne * D].view(B * Ne, D)
         ops.rowsum_select(g, D, None, 0, 1, Ne, B, D, w["rs_part"], st.grad("cls_token").view(D))
         if cfg.ra_dec:
             G = st.grad
@@ -927,14 +1026,11 @@ class MAEEngine:
                                 w["z"], w["dz"], G("ra_dec_embed.neural_network.layers.0.weight"),
                                 G("ra_dec_embed.neural_network.layers.0.bias"), G("ra_dec_embed.neural_network.last_layer.weight"),
                                 G("ra_dec_embed.neural_network.last_layer.bias"), B, D)
-        ops.gather_rows(g, w["pe_dst"], None, w["dT"], B * keep, D)
-        self._wgrad(w["dT"], w["patches"], D, pv, B * keep, st.grad("patch_embed.proj.weight"),
+        ops.gather_rows(g, w["pe_dst"], None, w["dT"], B * n_patch, D)
+        self._wgrad(w["dT"], w["patches"], D, pv, B * n_patch, st.grad("patch_embed.proj.weight"),
                     st.grad("patch_embed.proj.bias"), w)
-        ops.gemm(w["dT"], st.lp("patch_embed.proj.weight"), M=B * keep, N=pv, K=D, a_layout=KC, b_layout=RC, lda=D,
+        ops.gemm(w["dT"], st.lp("patch_embed.proj.weight"), M=B * n_patch, N=pv, K=D, a_layout=KC, b_layout=RC, lda=D,
                  ldb=pv, out_f32=w["drows"])
-        ops.patch_gather_bwd_pmv(imgs, w["ids_keep"], w["drows"], w["pmv_part"], st.grad("patch_mask_values"),
-                                 cfg.patch_size, keep)
-        self._end_stage(w, last=True)
 
     def backward(self):
         """Gradients of the last :meth:`forward_train` loss into the flat ``g`` buffer (every
@@ -946,13 +1042,15 @@ class MAEEngine:
     def backward_stages(self, n_encoder_groups=3):
         """Backward cut into stages for gradient all-reduce overlap (one process per GPU): a list of
         (callable, [(start, end), ...]) -- see :func:`stage_gradient_ranges`."""
-        cfg = self.cfg
-        groups, ranges = stage_gradient_ranges(self.store, cfg, n_encoder_groups)
+        groups, ranges = self._stage_ranges(n_encoder_groups)
         stages = [(self.backward_decoder, ranges[0])]
         for k, (hi, lo) in enumerate(groups):
             stages.append(((lambda h=hi, l=lo, top=(k == 0): self.backward_encoder(None if top else h, l)), ranges[1 + k]))
         stages.append((self.backward_embed, ranges[-1]))
         return stages
+
+    def _stage_ranges(self, n_encoder_groups):
+        return stage_gradient_ranges(self.store, self.cfg, n_encoder_groups)
 
     # ------------------------------------------------------------------ accounting
     def flops_per_image(self, mask_ratio=0.75):

@@ -14,7 +14,8 @@ one "patch" the size of the image).
 """
 from __future__ import annotations
 
-import numpy as np
+import os
+
 import torch
 
 from . import ops
@@ -30,7 +31,7 @@ def simmim_stage_ranges(store, cfg: MAEConfig, n_encoder_groups: int = 3):
     # (layout order: the pool precedes the head.  Without the pool the head's weight gradient may be a problem of the last block's
     # grouped launch -- _extra_wgrad_layers -- so it belongs to the top encoder stage and the head stage finishes no decayed tensor)
     head0 = off["attn_pool.latent"] if cfg.attn_pool else store.n_decay
-    assert cfg.attn_pool or off["decoder.0.weight"] + int(np.prod(store.shapes["decoder.0.weight"])) <= store.n_decay
+    assert cfg.attn_pool or store.span("decoder.0.weight")[1] <= store.n_decay
     ranges = [[(head0, store.n_decay)] if head0 < store.n_decay else []]
     bounds = sorted({round(cfg.depth * k / n_encoder_groups) for k in range(n_encoder_groups + 1)}, reverse=True)
     groups = []
@@ -67,14 +68,7 @@ class SimMIMEngine(MAEEngine):
         w["patches"] = torch.empty(B * L, pv, **lp)
         w["latent32"] = torch.empty(M, D, **f32)
         hidden = int(D * cfg.mlp_ratio)
-
-        def block_bufs():
-            return dict(ln1=torch.empty(M, D, **lp), mean1=torch.empty(M, **f32), rstd1=torch.empty(M, **f32),
-                        qkv=torch.empty(M, 3 * D, **lp), att=torch.empty(M, D, **lp), xmid=torch.empty(M, D, **f32),
-                        ln2=torch.empty(M, D, **lp), mean2=torch.empty(M, **f32), rstd2=torch.empty(M, **f32),
-                        hpre=torch.empty(M, hidden, **lp), hact=torch.empty(M, hidden, **lp))
-
-        w["enc"] = [block_bufs() for _ in range(cfg.depth if train else 1)]
+        w["enc"] = [self._block_bufs(M, D) for _ in range(cfg.depth if train else 1)]
         w["xs"] = [torch.empty(M, D, **f32) for _ in range((cfg.depth + 1) if train else 2)]
         w["lat_lp"] = torch.empty(M, D, **lp)
         w["lat_mean"], w["lat_rstd"] = torch.empty(M, **f32), torch.empty(M, **f32)
@@ -110,49 +104,26 @@ class SimMIMEngine(MAEEngine):
                 w["ap_do"] = torch.empty(B, D, **lp)
                 w["ap_dkv"] = torch.empty(M, 2 * D, **lp)
                 w["ap_dq"], w["ap_dq_ws"] = torch.empty(B, D, **f32), torch.empty(D, **f32)
-            w["g"] = torch.empty(M * D, **f32)
-            w["g_lp"] = torch.empty(M * D, **lp)
-            w["g_lp2"] = torch.empty(M * D, **lp)
-            w["dln"] = torch.empty(M * D, **lp)
-            w["datt"] = torch.empty(M * D, **lp)
-            w["dh"] = torch.empty(M * hidden, **lp)
-            w["dqkv"] = torch.empty(3 * M * D, **lp)
-            # second scratch set (see MAEEngine._workspace): consecutive blocks alternate between the two
-            w["g_lp_b"], w["g_lp2_b"] = torch.empty(M * D, **lp), torch.empty(M * D, **lp)
-            w["dh_b"], w["dqkv_b"] = torch.empty(M * hidden, **lp), torch.empty(3 * M * D, **lp)
+            self._bwd_scratch(w, M * D, M * hidden)
             w["dT"] = torch.empty(B * L, D, **lp)
             w["drows"] = torch.empty(B * L, pv, **f32)
             w["pmv_part"] = torch.empty(B, pv, **f32)
             w["rs_part"] = torch.empty(256, D, **f32)
-            w["splitk_ws"] = self._splitk_ws
             order = [("ln", "norm", R, D)] + ([("ln", "attn_pool.norm", B, D)] if pool else [])
             for i in reversed(range(cfg.depth)):
                 order.append(("block", f"blocks.{i}", w["enc"][i], M, D))
             self._build_reduce_table(w, order)
-            w["wgrad_groups"] = {}            # (built after the reduce table: every group carries its block's norm1 backward)
-            if self.dtype in ops.LP_DTYPES:
-                for i, bufs in enumerate(w["enc"]):
-                    w["wgrad_groups"][f"blocks.{i}"] = self._make_wgrad_group(f"blocks.{i}", bufs, M, D, w)
-        if train and getattr(self, "_fused_adamw", None) is not None and w.get("wgrad_groups"):
-            self._build_adamw_groups(w)
-        if train and getattr(self, "_g16", None) is not None and w.get("wgrad_groups"):
-            self._build_variant_groups(w, "g16")
+            self._build_wgrad_groups(w, (("blocks", w["enc"], M, D),))
         self._ws[key] = w
         return w
 
     # ------------------------------------------------------------------ forward
     def _check_simmim_inputs(self, imgs, mask, ra_dec):
-        cfg = self.cfg
-        assert imgs.is_cuda and imgs.dtype == torch.float32 and imgs.is_contiguous()
-        B, C, H, W = imgs.shape
-        assert (C, H, W) == (cfg.in_chans, cfg.img_size, cfg.img_size), f"bad cutout shape {tuple(imgs.shape)}"
+        self._check_cutouts(imgs)
         if mask is not None:
             assert mask.shape == imgs.shape and mask.is_cuda, "SimMIM pixel mask must be [B,C,H,W] on the device"
             mask = mask.to(torch.float32).contiguous()
-        if cfg.ra_dec:
-            assert ra_dec is not None and tuple(ra_dec.shape) == (B, 2), "ra_dec=True models need ra_dec [B,2] (degrees)"
-            ra_dec = ra_dec.to(device=imgs.device, dtype=torch.float32).contiguous()
-        return mask, ra_dec
+        return mask, self.check_ra_dec(imgs, ra_dec)
 
     def _encoder_fwd_simmim(self, imgs, mask, ra_dec, w, train):
         """utils/mim_vit.py:381-429 with simmim=True: blend, embed all L patches, (RA/Dec,) cls, blocks, norm."""
@@ -163,25 +134,13 @@ class SimMIMEngine(MAEEngine):
         M = B * Ne
         ops.patch_gather_blend(imgs, st.param("patch_mask_values"), None, mask, w["patches"], cfg.patch_size, L,
                                cfg.pixel_mean, cfg.pixel_std)
-        xs = w["xs"]
-        x0 = xs[0]
+        x0 = w["xs"][0]
         pos = st.frozen["pos_embed"].view(-1, D)
         ops.gemm(w["patches"], st.lp("patch_embed.proj.weight"), M=B * L, N=D, K=pv, bias=st.param("patch_embed.proj.bias"),
                  table=pos[E:], tab_row=w["pe_tab"], ldt=D, dst_row=w["pe_dst"], out_f32=x0, ldo32=D,
                  prefetch=self._pf("fwd", "patch_embed.proj.weight", B * L))
-        x0.view(B, Ne, D)[:, 0, :] = st.param("cls_token").view(D) + pos[0]        # utils/mim_vit.py:417-419 (host glue)
-        if cfg.ra_dec:
-            P = st.param
-            ops.radec_token_fwd(ra_dec, P("ra_dec_embed.neural_network.layers.0.weight"),
-                                P("ra_dec_embed.neural_network.layers.0.bias"), P("ra_dec_embed.neural_network.last_layer.weight"),
-                                P("ra_dec_embed.neural_network.last_layer.bias"), pos[1], x0.view(-1)[D:], Ne * D, B, D,
-                                w["sh"], w["z"])
-        for i in range(cfg.depth):
-            if train:
-                self._block_fwd(xs[i], xs[i + 1], w["enc"][i], f"blocks.{i}", M, D, cfg.num_heads, B, Ne)
-            else:
-                self._block_fwd(xs[i % 2], xs[(i + 1) % 2], w["enc"][0], f"blocks.{i}", M, D, cfg.num_heads, B, Ne)
-        x_last = xs[cfg.depth] if train else xs[cfg.depth % 2]
+        self._extra_tokens_fwd(x0, pos, B, Ne, ra_dec, w)
+        x_last = self._blocks_fwd(w, B, Ne, train)
         if cfg.attn_pool:
             self._pool_fwd(x_last, w, B, Ne)
             ops.layernorm_fwd(w["ap_z"], st.param("norm.weight"), st.param("norm.bias"), w["lat_lp"], w["lat_mean"], w["lat_rstd"],
@@ -207,7 +166,7 @@ class SimMIMEngine(MAEEngine):
         ops.gemm(w["ap_ln"], LP("attn_pool.mlp.fc1.weight"), M=B, N=hidden, K=D, bias=P("attn_pool.mlp.fc1.bias"), act=ops.ACT_GELU,
                  out=w["ap_hact"], out2=w["ap_hpre"])
         ops.gemm(w["ap_hact"], LP("attn_pool.mlp.fc2.weight"), M=B, N=D, K=hidden, bias=P("attn_pool.mlp.fc2.bias"), resid=w["ap_y"],
-                 ldr=D, out_f32=w["ap_z"], ws=self._splitk_ws)
+                 ldr=D, out_f32=w["ap_z"], ws=self.splitk_ws)
 
     def forward_features(self, imgs, mask_ratio=0.0, noise=None, mask=None, ra_dec=None):
         """utils/mim_vit.py:381-438 (reshape_out=False): -> (latent fp32 [B, E+L, D], mask, None); tokens keep their order."""
@@ -261,7 +220,6 @@ class SimMIMEngine(MAEEngine):
         """The pixel head's weight gradient (Conv2d 1x1 = a linear over the token rows, utils/mim_vit.py:244-249) as a fifth problem
         of the last block's grouped weight-gradient launch -- the first grouped launch of backward, same token rows (engine.py
         _extra_wgrad_layers).  Not with the pooled head: its rows are the images, not the tokens."""
-        import os
         cfg = self.cfg
         if (os.environ.get("SKYEMB_FOLD_WGRADS", "1") == "0" or self._side is not None or cfg.attn_pool or "dpred" not in w
                 or prefix != f"blocks.{cfg.depth - 1}" or w["dpred"].shape[0] != M):
@@ -323,38 +281,15 @@ class SimMIMEngine(MAEEngine):
     def backward_embed(self):
         """Last stage: cls token, RA/Dec encoder, patch embedding, patch_mask_values (g = d xs[0])."""
         imgs, B, mask, w = self._ctx()
-        cfg, st = self.cfg, self.store
-        L, D, pv, E = cfg.num_patches, cfg.embed_dim, cfg.patch_dim, cfg.num_extra_tokens
-        Ne = E + L
-        M = B * Ne
-        g = w["g"][:M * D].view(M, D)
-        ops.rowsum_select(g, D, None, 0, 1, Ne, B, D, w["rs_part"], st.grad("cls_token").view(D))
-        if cfg.ra_dec:
-            G = st.grad
-            ops.radec_token_bwd(g.view(-1)[D:], Ne * D, st.param("ra_dec_embed.neural_network.last_layer.weight"), w["sh"],
-                                w["z"], w["dz"], G("ra_dec_embed.neural_network.layers.0.weight"),
-                                G("ra_dec_embed.neural_network.layers.0.bias"), G("ra_dec_embed.neural_network.last_layer.weight"),
-                                G("ra_dec_embed.neural_network.last_layer.bias"), B, D)
-        ops.gather_rows(g, w["pe_dst"], None, w["dT"], B * L, D)
-        self._wgrad(w["dT"], w["patches"], D, pv, B * L, st.grad("patch_embed.proj.weight"), st.grad("patch_embed.proj.bias"), w)
-        ops.gemm(w["dT"], st.lp("patch_embed.proj.weight"), M=B * L, N=pv, K=D, a_layout=KC, b_layout=RC, lda=D, ldb=pv,
-                 out_f32=w["drows"])
-        ops.patch_gather_bwd_pmv_blend(imgs, None, mask, w["drows"], w["pmv_part"], st.grad("patch_mask_values"),
+        cfg = self.cfg
+        L = cfg.num_patches
+        self._embed_bwd(B, cfg.num_extra_tokens + L, L, w)
+        ops.patch_gather_bwd_pmv_blend(imgs, None, mask, w["drows"], w["pmv_part"], self.store.grad("patch_mask_values"),
                                        cfg.patch_size, L)
         self._end_stage(w, last=True)
 
-    def backward(self):
-        self.backward_decoder()
-        self.backward_encoder()
-        self.backward_embed()
-
-    def backward_stages(self, n_encoder_groups=3):
-        groups, ranges = simmim_stage_ranges(self.store, self.cfg, n_encoder_groups)
-        stages = [(self.backward_decoder, ranges[0])]
-        for k, (hi, lo) in enumerate(groups):
-            stages.append(((lambda h=hi, l=lo: self.backward_encoder(h, l)), ranges[1 + k]))
-        stages.append((self.backward_embed, ranges[-1]))
-        return stages
+    def _stage_ranges(self, n_encoder_groups):          # (backward(), backward_stages(): MAEEngine's, over these stages)
+        return simmim_stage_ranges(self.store, self.cfg, n_encoder_groups)
 
     # ------------------------------------------------------------------ accounting
     def flops_per_image(self, mask_ratio=0.0):

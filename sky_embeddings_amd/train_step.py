@@ -24,24 +24,9 @@ import os
 import torch
 
 from . import ops
-from .distributed import all_gather_range, bucket_bounds, reduce_scatter_range
+from .distributed import all_gather_range, bucket_bounds, reduce_scatter_range, shard_chunk
+from .engine import subtract_spans
 from .optim import CosineLR, FusedAdamW
-
-
-def _subtract_ranges(ranges, holes):
-    """[(s, e), ...] minus [(s, e), ...] (both ascending, disjoint) -> what remains, ascending."""
-    out = []
-    for s, e in ranges:
-        cur = s
-        for hs, he in holes:
-            if he <= cur or hs >= e:
-                continue
-            if hs > cur:
-                out.append((cur, hs))
-            cur = max(cur, he)
-        if cur < e:
-            out.append((cur, e))
-    return out
 
 
 class TrainStep:
@@ -98,10 +83,10 @@ class TrainStep:
             wgrad_overlap = os.environ.get("SKYEMB_WGRAD_OVERLAP", "0") == "1"
         engine.enable_wgrad_overlap(wgrad_overlap)   # weight-gradient GEMMs on a side stream (a parallel graph branch)
         # DDP mean of per-rank gradients, and the backward pass's static loss scale divided out again (fp16 mode)
-        if hasattr(engine, "plan_loss_scale"):     # fp16 mode: the scale of THIS batch size, before anything bakes it into a launch
-            # ... and pinned (the setter turns auto planning off): the captured loss kernel and the fused launches' grad_scale keep
-            # this value, so a forward pass the step does not own (an eager validation batch of another size) must not re-plan it
-            engine.loss_scale = engine.plan_loss_scale(engine.expected_masked_elements(batch_size, mask_ratio))
+        # fp16 mode: the scale of THIS batch size, before anything bakes it into a launch ... and pinned (the setter turns auto
+        # planning off): the captured loss kernel and the fused launches' grad_scale keep this value, so a forward pass the step
+        # does not own (an eager validation batch of another size) must not re-plan it
+        engine.loss_scale = engine.plan_loss_scale(engine.expected_masked_elements(batch_size, mask_ratio))
         optimizer.base_grad_scale = 1.0 / world_size
         # stage list: [(callable, [(start, end) slices of the flat gradient buffer final after it])]
         if n_encoder_groups is None:
@@ -118,7 +103,7 @@ class TrainStep:
             # bf16 gradient communication: the blocks' grouped weight-gradient launches write their bf16 gradients straight
             # into the mirror (98 % of the bytes: no fp32 store + cast pass for them); each stage ends with the cast of whatever
             # else it has finalised (embeddings, biases, LayerNorms, the three single weight gradients)
-            direct = os.environ.get("SKYEMB_G16_DIRECT", "1") == "1" and hasattr(engine, "enable_grad_mirror")
+            direct = os.environ.get("SKYEMB_G16_DIRECT", "1") == "1"
             if direct:
                 engine.enable_grad_mirror(self.g16)
 
@@ -126,16 +111,13 @@ class TrainStep:
                 todo = []
 
                 def run():
-                    engine._g16_active = direct
-                    try:
+                    with engine.wgrad_variant("g16" if direct else "plain"):
                         fn()
-                    finally:
-                        engine._g16_active = False
                     if not todo:                              # (the first call has just built the workspace and its groups)
                         holes = []
                         if direct:
-                            holes = engine.grad_mirror_ranges(engine._ws[engine._last_key()])   # the workspace this step ran on
-                        todo.append(_subtract_ranges(ranges, holes))
+                            holes = engine.grad_mirror_ranges(engine.last_workspace())   # the workspace this step ran on
+                        todo.append(subtract_spans(ranges, holes))
                     for (s, e) in todo[0]:
                         ops.cast(engine.store.g[s:e], self.g16[s:e], e - s)
                 return run
@@ -173,7 +155,6 @@ class TrainStep:
         self.shard_optimizer = bool(shard_optimizer and self.staged and (self.shard_world > 1 or forced_one) and not self.optimizer_overlap)
         self._own = {}
         if self.shard_optimizer:
-            from .distributed import shard_chunk
             gdt = engine.store.g.dtype if self.g16 is None else self.g16.dtype
             for k, (_, ranges) in enumerate(self.stages[:-1]):
                 for (s_, e_) in ranges:
@@ -184,7 +165,7 @@ class TrainStep:
         if fused_adamw is None:
             fused_adamw = os.environ.get("SKYEMB_FUSED_ADAMW", "1") == "1"
         self.fused_adamw = bool(fused_adamw and world_size == 1 and not self.staged and not self.optimizer_overlap
-                                and engine.dtype in ops.LP_DTYPES and hasattr(engine, "enable_fused_adamw"))
+                                and engine.dtype in ops.LP_DTYPES)
         self._rest_ranges = None
         snap = None
         if self.fused_adamw:
@@ -192,7 +173,7 @@ class TrainStep:
             # (adamw_side: the step of a block's weights as a side job of the NEXT block's weight-gradient launch instead of its own
             # launch's epilogue -- engine.enable_fused_adamw; None = the default, SKYEMB_ADAMW_SIDE)
             engine.enable_fused_adamw(optimizer, side=adamw_side)
-            self.adamw_side = engine._adamw_side          # placement policy: 'auto' | '0' | '1' | 'dec' | 'enc'
+            self.adamw_side = engine.adamw_side           # placement policy: 'auto' | '0' | '1' | 'dec' | 'enc'
             # (the warm-up launches below would already step the fused tensors: restore them afterwards)
             st = engine.store
             snap = [t.clone() for t in (st.p, st.m, st.v, st.p_lp)]
@@ -203,11 +184,8 @@ class TrainStep:
 
             def owning(fn):
                 def run():
-                    engine._fused_active = True          # these launches carry the optimiser step
-                    try:
+                    with engine.wgrad_variant("adamw"):  # these launches carry the optimiser step
                         fn()
-                    finally:
-                        engine._fused_active = False
                     # ... and the ordinary kernel updates the rest (embeddings, biases, LayerNorms, the single weight gradients)
                     # right behind them, inside the same graph: as separate launches after the replay they started 8.6 us late
                     # (the host's launch latency on the critical path of every step)
@@ -234,7 +212,7 @@ class TrainStep:
                     fn()
                 pool = g.pool()
                 self.graphs.append(g)
-            engine._graph_captures = getattr(engine, "_graph_captures", 0) + 1     # (engine.enable_wgrad_overlap refuses to re-plan under them)
+            engine.note_graph_capture()                 # (engine.enable_wgrad_overlap refuses to re-plan under them)
         if snap is not None:
             if not use_graph:                                  # (graph mode ran the warm-up above: the workspace exists)
                 self.stages[0][0]()
@@ -245,7 +223,6 @@ class TrainStep:
     def _sharded_update(self):
         """AdamW on this rank's chunk of every sharded range (gradients: the reduce-scatter's output) and on the replicated rest,
         then the all-gather of the 16-bit shadow; the next forward waits for it on the stream."""
-        from .distributed import shard_chunk
         opt, st = self.optimizer, self.engine.store
         r, W = self.shard_rank, self.shard_world
         opt.begin_step()
@@ -293,12 +270,10 @@ class TrainStep:
         """Slices of the flat buffers the fused launches of THIS step's workspace do not update (the ordinary kernel takes them)."""
         if self._rest_ranges is None:
             eng = self.engine
-            w = eng._ws[self._ws_key]                          # the workspace this step's forward_train has just run on
-            fused = eng.fused_adamw_ranges(w)
-            bounds = [0] + [b for r in fused for b in r] + [eng.store.n]
-            self._rest_ranges = [(bounds[i], bounds[i + 1]) for i in range(0, len(bounds), 2) if bounds[i] < bounds[i + 1]]
+            assert eng.last_key() == self._ws_key              # the workspace this step's forward_train has just run on
+            self._rest_ranges = subtract_spans([(0, eng.store.n)], eng.fused_adamw_ranges(eng.last_workspace()))
             self._rest_key = self._ws_key
-        # (keyed on the step's own forward, not on engine._last_key(): an eager forward_train on another batch shape between two
+        # (keyed on the step's own forward, not on engine.last_key(): an eager forward_train on another batch shape between two
         # steps moves the latter)
         assert self._rest_key == self._ws_key, "TrainStep: the batch shape changed under a fused optimiser step"
         return self._rest_ranges
@@ -313,13 +288,13 @@ class TrainStep:
                 ops.simmim_mask_from_noise(self.mask_noise, self.ratio_u, float(self.max_mask_ratio), cfg.grid, cfg.patch_size,
                                            self.pixel_mask)
             self.loss, self.pred, self.mask = self.engine.forward_train(self.imgs, mask=self.pixel_mask, ra_dec=self.ra_dec)
-            self._ws_key = self.engine._last_key()
+            self._ws_key = self.engine.last_key()
             return
         # utils/mim_vit.py:363 draws the masking noise inside forward; keep it inside the step
         if not self.external_noise:
             self.noise.uniform_()
         self.loss, self.pred, self.mask = self.engine.forward_train(self.imgs, self.mask_ratio, self.noise, ra_dec=self.ra_dec)
-        self._ws_key = self.engine._last_key()                 # (the workspace of THIS step's batch: _rest())
+        self._ws_key = self.engine.last_key()                 # (the workspace of THIS step's batch: _rest())
 
     def load_batch(self, imgs, mask=None, ra_dec=None):
         """Stage the next minibatch (device or pinned host tensors) into the static input buffers."""

@@ -84,7 +84,7 @@ class VisionTransformer:
         # mlp_ratio, norm_layer) (utils/vit.py:303-309)
         self.pool_heads = 2
         self._head_mod = PredictorHead(D, cfg.mlp_ratio, cfg.ln_eps, global_pool, self.num_classes, dev, compute_dtype, gen,
-                                       splitk_ws=self.engine._splitk_ws)
+                                       splitk_ws=self.engine.splitk_ws)
         self.head = self._head_mod.tensors
         self.training = False
         self.frozen_encoder = False                # linear probe: only norm / fc_norm / head receive gradients
@@ -168,7 +168,7 @@ class VisionTransformer:
         B, L = x.shape[0], self.cfg.num_patches
         if self._ramp is None or self._ramp.shape[0] != B:
             self._ramp = torch.arange(L, device=x.device, dtype=torch.float32).repeat(B, 1).contiguous() / L
-        return x, self.engine._check_ra_dec(x, ra_dec)
+        return x, self.engine.check_ra_dec(x, ra_dec)
 
     def forward_features(self, x, ra_dec=None, mask=None, reshape_out=False):
         """utils/vit.py:344-388 -> (tokens [B, extra+L, D], None, None); extra = cls (+ the RA/Dec token)."""
@@ -192,9 +192,7 @@ class VisionTransformer:
         has no classifier)."""
         eng, cfg, hd = self.engine, self.cfg, self._head_mod
         B, L = x.shape[0], cfg.num_patches
-        w = eng._workspace(B, L, True)
-        eng._encoder_fwd(x, self._ramp, L, w, True, ra_dec)
-        eng._last = (x, B, L)
+        w = eng.encoder_forward_train(x, self._ramp, L, ra_dec)
         Ne, D = cfg.num_extra_tokens + L, cfg.embed_dim
         if self.global_pool == 'map':
             out = hd.forward(B, Ne, tokens_lp=w["lat_lp"])          # the final norm's output in the compute dtype: every token
@@ -208,8 +206,8 @@ class VisionTransformer:
 
     def _predict_backward(self, dpred):
         eng, cfg, hd = self.engine, self.cfg, self._head_mod
-        x, B, L = eng._last
-        w = eng._ws[(B, L, True)]
+        B, L, _ = eng.last_key()
+        w = eng.last_workspace()
         Ne, D = cfg.num_extra_tokens + L, cfg.embed_dim
         Me = B * Ne
         st = eng.store
@@ -224,7 +222,7 @@ class VisionTransformer:
             g.zero_()
             g[:, 1:] = (dfeat / (Ne - 1)).unsqueeze(1)
             w["g_lp"][:Me * D].view(B, Ne, D).copy_(g)
-            eng._ln_first, eng._ln_count = w["ln_index"][f"blocks.{cfg.depth - 1}.norm2"], 0
+            eng.start_backward_at(f"blocks.{cfg.depth - 1}.norm2")
             eng.backward_encoder(hi=cfg.depth, lo=0)   # (hi given: the final norm is not part of this configuration)
             eng.backward_embed()
             return
@@ -237,7 +235,7 @@ class VisionTransformer:
             ops.layernorm_bwd(dlat, w["xs"][cfg.depth], st.param("norm.weight"), w["lat_mean"], w["lat_rstd"], None, tmp, None,
                               w["ln_parts"]["norm"], st.grad("norm.weight"), st.grad("norm.bias"), Me, D, eng.code)
             return
-        eng._ln_first, eng._ln_count = w["ln_index"]["norm"], 0
+        eng.start_backward_at("norm")
         eng.backward_encoder()
         eng.backward_embed()
 

@@ -261,6 +261,64 @@ def test_simmim_stage_ranges_put_the_head_weight_with_the_top_encoder_stage():
             assert owner == [0 if cfg.attn_pool else 1]
 
 
+def test_span_helpers_and_param_store_spans():
+    """merge_spans / subtract_spans on hand cases; ParamStore.span tiles [0, n) in store.order (MAE and SimMIM layouts)."""
+    from sky_embeddings_amd.engine import ParamStore, merge_spans, subtract_spans
+    assert merge_spans([]) == [] and subtract_spans([], []) == [] and subtract_spans([], [(0, 8)]) == []
+    assert merge_spans([(8, 16), (0, 8)]) == [(0, 16)]                              # touching: joined, whatever the input order
+    assert merge_spans([(0, 8), (16, 24)]) == [(0, 8), (16, 24)]                    # a gap stays a gap
+    assert merge_spans([(0, 8), (8, 16), (24, 32), (32, 40), (48, 56)]) == [(0, 16), (24, 40), (48, 56)]
+    assert subtract_spans([(0, 32)], []) == [(0, 32)]
+    assert subtract_spans([(0, 32)], [(8, 16)]) == [(0, 8), (16, 32)]
+    assert subtract_spans([(0, 32)], [(0, 8), (24, 32)]) == [(8, 24)]               # holes at both ends
+    assert subtract_spans([(0, 8), (16, 24), (32, 40)], [(8, 32)]) == [(0, 8), (32, 40)]     # a hole covering a whole span
+    assert subtract_spans([(0, 8), (16, 24)], [(0, 8), (16, 24)]) == []
+    assert subtract_spans([(0, 16), (24, 40)], [(8, 32)]) == [(0, 8), (32, 40)]     # one hole across two spans
+    assert subtract_spans([(0, 8)], [(16, 24)]) == [(0, 8)]                         # a hole outside
+    for n, x in ((64, [(8, 16), (24, 40)]), (64, []), (64, [(0, 64)]), (40, [(0, 8), (32, 40)])):
+        assert merge_spans(subtract_spans([(0, n)], x) + x) == [(0, n)]
+    tiny = mc.config_for("tiny", img_size=64, patch_size=16, in_chans=5, embed_dim=192)
+    simmim = mc.config_for("simmim", img_size=128, patch_size=16, in_chans=5, embed_dim=64, depth=4, num_heads=4)
+    for cfg in (tiny, simmim):
+        st = ParamStore(cfg, "cpu", torch.bfloat16)
+        spans = [st.span(name) for name in st.order]
+        assert spans[0][0] == 0 and spans[-1][1] == st.n
+        assert all(a[1] == b[0] and a[0] < a[1] for a, b in zip(spans, spans[1:]))
+        for name, (lo, hi) in zip(st.order, spans):
+            assert lo == st.offsets[name] and 0 <= hi - lo - int(np.prod(st.shapes[name])) < 8 and (hi - lo) % 8 == 0
+        assert merge_spans(spans) == [(0, st.n)]
+
+
+def test_wgrad_schedule_plan_places_side_jobs_by_mode():
+    """plan_wgrad_schedule: launch 0 never carries; '0' / '1' / 'dec' / 'enc' by their rule; 'auto' by the free workgroup slots --
+    the three cases the engine records as measured; a launch stores its gradients exactly when the next one carries."""
+    from sky_embeddings_amd.engine import ADAMW_SIDE_MODES, plan_wgrad_schedule
+    order = ["decoder_blocks.1", "decoder_blocks.0", "blocks.2", "blocks.1", "blocks.0"]
+    tiles = [(128064, 384), (128064, 384), (128064, 440), (128064, 440), (256256, 192)]
+    for mode in ADAMW_SIDE_MODES:
+        plan = plan_wgrad_schedule(order, tiles, 256, mode)
+        carries = [c for c, _ in plan]
+        assert len(plan) == len(order) and carries[0] is False
+        assert [s for _, s in plan] == carries[1:] + [False]            # stores <=> the next launch carries
+        assert plan_wgrad_schedule([], [], 256, mode) == [] and plan_wgrad_schedule(order[:1], tiles[:1], 256, mode) == [(False, False)]
+        want = {"0": [False] * 5, "1": [False] + [True] * 4, "dec": [False, True, False, False, False],
+                "enc": [False, False, True, True, True], "auto": [False, True, False, False, True]}[mode]
+        assert carries == want, (mode, carries)
+    with pytest.raises(AssertionError):
+        plan_wgrad_schedule(order, tiles, 256, "always")
+
+    def auto(tile, count, ncu=256):
+        return plan_wgrad_schedule(["blocks.1", "blocks.0"], [(tile, count)] * 2, ncu, "auto")[1][0]
+    assert auto(256256, 192)            # ViT-L: 192 tiles of 256 x 256 on 256 units (one slot each)
+    assert auto(128064, 384)            # ViT-B decoder: 384 of 512 slots
+    assert not auto(128064, 440)        # ViT-B encoder: 440 of 512 -- side jobs lose there
+    for tile, per_cu in ((256256, 1), (128128, 2), (9128128, 1), (128064, 2), (64064, 3)):
+        got = [auto(tile, c) for c in range(1, 256 * per_cu + 2)]
+        assert got[0] and not got[-1] and got == sorted(got, reverse=True)          # monotone: never again once the launch is too full
+        assert sum(got) == int(0.76 * 256 * per_cu)                                 # three quarters (and a tile's rounding) of the slots
+    assert auto(128064, 120, ncu=80) and not auto(128064, 125, ncu=80)              # the slots follow the device's unit count
+
+
 def test_native_host_gather_rows():
     """skyemb_gather_rows_host (the feeder's minibatch gather; a HOST function of the C ABI) against numpy indexing."""
     import ctypes

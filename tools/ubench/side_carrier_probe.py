@@ -50,7 +50,7 @@ def main():
     opt = FusedAdamW(eng, lr=1e-4, weight_decay=0.05)
     opt.use_device_scalars(dev)
     eng.enable_fused_adamw(opt, True)
-    ad = eng._fused_adamw
+    ad = eng.fused_adamw_desc
     opt.begin_step()
     st = eng.store
     M, D, H = 1280, 768, 3072
