@@ -468,6 +468,30 @@ int skyemb_attnpool_q_bwd(const float *dq_part, int B, const float *latent, cons
  * (utils/similarity.py:262-267 combine over patches happens on these): scores [Q, N]. */
 int skyemb_cosine_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
                          int D, float eps, float *scores, void *stream);
+/* Patch-token bank search (utils/similarity.py:214-268 with max_pool = False: every patch token of a test image is scored,
+ * then the P token scores are combined per image): the bank is [N, P, D] fp32, viewed as N * P rows with weighted norms
+ * xn [N * P] (skyemb_weighted_norms); tw / qn as for skyemb_cosine_topk.  One pass over the bank: token score = the contract's
+ * fma chain + the same last step as skyemb_cosine_topk (NaN -> -inf), combined in registers, in fp32:
+ *   MIN / MAX  exact;  MEAN  (((0 + s[0]) + s[1]) + ... + s[P-1]) / (float)P -- token order, one IEEE division, independent of
+ *   launch geometry and of Q.  A -inf token gives -inf for MIN and MEAN and is ignored by MAX.
+ * Shapes: Q <= 16, D % 64 == 0, D <= 1024, 1 <= P <= 4096 with 16 % P == 0 or P % 16 == 0, N * P < 2^31 and, for the lists,
+ * 1 <= k <= 512 with 64 D + 32 Q k <= 163840 (A image + four waves' lists in LDS); skyemb_cosine_token_applicable says so without
+ * touching the device (0 leaves the limits and the refused shape as skyemb_last_error), everything else returns 1 before any launch.  bank and tw 16-byte aligned.
+ *   skyemb_cosine_token_scores   scores [Q, N]: the combined score of every image.
+ *   skyemb_cosine_token_topk     part_s f32 / part_i i64 [Q, nlists, k] (nlists = skyemb_cosine_token_topk_chunks(N, P, Q, D, k)):
+ *                                one sorted list per wavefront, ONE insertion attempt per image, (score desc, image asc),
+ *                                idx = idx_offset + image, thr0 and the (-inf, -1) terminator as in skyemb_cosine_topk; images
+ *                                whose combined score is -inf are never listed.  Then skyemb_topk_merge. */
+#define SKYEMB_COMBINE_MIN 0
+#define SKYEMB_COMBINE_MEAN 1
+#define SKYEMB_COMBINE_MAX 2
+int skyemb_cosine_token_applicable(int Q, int P, int D, int k);
+int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, int k);
+int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N, int P, int D,
+                               int combine, float eps, float *scores, void *stream);
+int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N, int P, int D,
+                             int k, int combine, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s,
+                             int64_t *part_i, void *stream);
 
 #ifdef __cplusplus
 }

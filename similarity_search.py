@@ -8,7 +8,9 @@ Differences: figures are not drawn (matplotlib/LaTeX plotting is out of scope, S
 the 64x target augmentation (``-aug True``, the reference's default) runs on the device
 (sky_embeddings_amd.augment: torchvision's parameter draws, one HIP launch per batch).  ``--bank`` (extension) encodes the
 test set ONCE into a resident embedding bank and runs the fused cosine top-k kernel over it
-instead of re-scoring streamed batches (requires -mp True or -ct True, i.e. one vector per sample).
+instead of re-scoring streamed batches: one vector per sample with -mp True or -ct True, or, with both False, the
+patch tokens of every sample scored one by one and combined per image (-c min | mean | max) by the fused token kernel.
+Cosine metric only.
 """
 import argparse
 import ast
@@ -93,17 +95,30 @@ def main():
                                               remove_cls=False)
     if args.bank:
         from sky_embeddings_amd import search
-        assert args.metric == 'cosine' and (max_pool or cls_token), "--bank scores one vector per sample"
+        if args.metric != 'cosine':
+            raise SystemExit("--bank runs the weighted cosine metric only (-m cosine)")
         mod = model.module
         tl = target_latent.to(device)
-        tl = tl[:, :1] if cls_token else tl[:, mod.num_extra_tokens:].max(dim=1, keepdim=True).values
-        bank = build_embedding_bank(model, test_dataloader, device, pool='cls' if cls_token else 'max')
-        first = bank[:args.batch_size]   # the reference standardises with the first batch (utils/similarity.py:98-100)
-        mean_feats, std_feats = first.mean(dim=0), first.std(dim=0, unbiased=True)
-        tl = (tl - mean_feats) / (std_feats + 1e-8)
-        search.standardise_(bank, mean_feats, std_feats)
-        avg, w = determine_target_features(tl)
-        scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(args.n_save, bank.shape[0]), weights=w)
+        k = args.n_save
+        if max_pool or cls_token:                # one vector per sample
+            tl = tl[:, :1] if cls_token else tl[:, mod.num_extra_tokens:].max(dim=1, keepdim=True).values
+            bank = build_embedding_bank(model, test_dataloader, device, pool='cls' if cls_token else 'max')
+            first = bank[:args.batch_size]   # the reference standardises with the first batch (utils/similarity.py:98-100)
+            mean_feats, std_feats = first.mean(dim=0), first.std(dim=0, unbiased=True)
+            tl = (tl - mean_feats) / (std_feats + 1e-8)
+            search.standardise_(bank, mean_feats, std_feats)
+            avg, w = determine_target_features(tl)
+            scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w)
+        else:                                    # every patch token scored, combined per image (-c min | mean | max)
+            tl = tl[:, mod.num_extra_tokens:]
+            bank = build_embedding_bank(model, test_dataloader, device, pool='tokens')
+            first = bank[:args.batch_size]   # mean / unbiased std over (batch, patch) of the first batch (utils/similarity.py:98-100)
+            mean_feats, std_feats = first.mean(dim=(0, 1)), first.std(dim=(0, 1), unbiased=True)
+            tl = (tl - mean_feats) / (std_feats + 1e-8)
+            search.standardise_(bank.view(-1, bank.shape[2]), mean_feats, std_feats)
+            avg, w = determine_target_features(tl)
+            scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
+                                                    weights=w)
         test_scores, order = scores[0], idx[0].cpu().numpy()
         ds = test_dataloader.dataset
         items = [ds[int(j)] for j in order if j >= 0]

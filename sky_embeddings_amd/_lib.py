@@ -19,9 +19,10 @@ SO_PATH = os.environ.get("SKYEMB_LIB") or os.path.join(_HERE, "libskyemb.so")   
 CSRC = os.path.join(_HERE, "csrc")
 
 BF16, F32, F16 = 0, 1, 2
-ABI_VERSION = 110          # skyemb_version() of the library this binding was written against (csrc/api.cpp)
+ABI_VERSION = 111          # skyemb_version() of the library this binding was written against (csrc/api.cpp)
 KC, RC = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU = 0, 1, 2
+COMBINE_MIN, COMBINE_MEAN, COMBINE_MAX = 0, 1, 2       # SKYEMB_COMBINE_*: how the token scores of an image are combined
 
 
 class SkyembLibraryError(RuntimeError):
@@ -138,6 +139,11 @@ PROTOTYPES = {
     "skyemb_cosine_topk_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_i64, c_vp,
                                                c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
+    "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "skyemb_cosine_token_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    "skyemb_cosine_token_topk": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_i32, c_vp,
+                                         c_vp, c_vp, c_vp]),
 }
 
 _LIB = None

@@ -1,0 +1,249 @@
+// Patch-token bank search for Q <= 16 queries: the bank holds P consecutive rows (patch tokens) per image, every token is
+// scored with the contract's fp32 fma chain (same arithmetic as cosine_topk_stream_kernel: rows straight from HBM into
+// registers, v_mfma_f32_16x16x4_f32), the P token scores of an image are combined in registers (min | mean | max,
+// utils/similarity.py:262-267) and ONE candidate per image goes to the wave's private sorted lists.  The [Q, N * P] token score
+// matrix never reaches memory.
+//
+// P divides 16 (an image is P neighbouring lanes of a 16-row tile) or is a multiple of 16 (an image is P / 16 consecutive tiles
+// of ONE wave: rows per wave are a multiple of lcm(P, 16), so no image straddles two waves).
+//
+// Combine order (fp32): min and max are exact.  mean = (((0 + s[0]) + s[1]) + ... + s[P-1]) / (float)P: token order
+// p = 0 .. P-1, one IEEE division; every lane of an image's lane group runs the same chain, tiles of a long image are folded in
+// ascending order, so the result does not depend on the launch geometry, on the wave or on Q.  A -inf token score (NaN scores
+// rank as -inf) gives -inf for min and mean and is ignored by max; an image whose combined score is -inf never enters a list.
+#include "topk_stream.h"
+
+namespace {
+
+template <int COMBINE>
+__device__ __forceinline__ float combine_start() {
+    return COMBINE == SKYEMB_COMBINE_MIN ? INFINITY : (COMBINE == SKYEMB_COMBINE_MAX ? -INFINITY : 0.f);
+}
+
+// folds the token scores `s` of the tp (1, 2, 4, 8 or 16) lanes this image has in the current tile into `carry`
+template <int COMBINE>
+__device__ __forceinline__ float combine_tile(float s, float carry, int lane, int tp) {
+    if (COMBINE == SKYEMB_COMBINE_MEAN) {
+        const int base = lane & ~(tp - 1);
+        float acc = carry;
+        for (int j = 0; j < tp; ++j) acc = acc + __shfl(s, base + j, 64);
+        return acc;
+    }
+    float v = s;
+    for (int o = 1; o < tp; o <<= 1) {
+        const float u = __shfl_xor(v, o, 64);
+        v = COMBINE == SKYEMB_COMBINE_MIN ? fminf(v, u) : fmaxf(v, u);
+    }
+    return COMBINE == SKYEMB_COMBINE_MIN ? fminf(carry, v) : fmaxf(carry, v);
+}
+
+// LISTS: part_s / part_i [Q, nlists, k] as cosine_topk_stream_kernel writes them (idx = idx_offset + image).
+// !LISTS: scores [Q, n_img] combined scores.
+template <int WAVES, int COMBINE, bool LISTS>
+__global__ __launch_bounds__(WAVES * 64) void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
+                                                                  const float *__restrict__ bank, const float *__restrict__ xn,
+                                                                  int Q, int64_t R, int P, int D, int k, float eps,
+                                                                  int64_t idx_offset, int64_t rows_per_wave,
+                                                                  float *__restrict__ part_s, int64_t *__restrict__ part_i,
+                                                                  const float *__restrict__ thr0, float *__restrict__ scores,
+                                                                  int64_t n_img) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nchunk = D >> 4;
+    float4 *imgA = (float4 *)lds;                                   // [nchunk][64]: A fragments of every k-step
+    float *ls_all = lds + (size_t)nchunk * 64 * 4;                  // [WAVES][Q][k]
+    int *li_all = (int *)(ls_all + (size_t)WAVES * Q * k);         // [WAVES][Q][k]
+    build_imgA<WAVES>(imgA, tw, Q, D, nchunk, tid);
+    __syncthreads();
+    float *ls = ls_all + (size_t)wave * Q * k;
+    int *li = li_all + (size_t)wave * Q * k;
+    const int wid = blockIdx.x * WAVES + wave;
+    const int64_t r_begin = (int64_t)wid * rows_per_wave;           // a multiple of lcm(P, 16): the first row of an image
+    int64_t r_end = r_begin + rows_per_wave;
+    if (r_end > R) r_end = R;                                       // R = images x P: whole images only
+    const int n_lane = lane & 15, g = lane >> 4;
+    const int tp = P < 16 ? P : 16;                                 // lanes of one image in a tile
+    const int tiles_per_image = P < 16 ? 1 : P >> 4;
+    // per-query list sizes / thresholds live in registers of ALL lanes (wave-uniform arrays of 16)
+    int n_in[16];
+    float thr[16], floor_thr[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        n_in[q] = 0;
+        thr[q] = (LISTS && thr0 && q < Q) ? thr0[q] : -INFINITY;
+        floor_thr[q] = thr[q];                                      // valid lower bound of the global k-th best (or -inf)
+    }
+    float qn4[4], carry[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        qn4[r] = (4 * g + r) < Q ? qn[4 * g + r] : 0.f;
+        carry[r] = combine_start<COMBINE>();
+    }
+    const float fP = (float)P;
+    int tile_in_image = 0;
+
+    for (int64_t n0 = r_begin; n0 < r_end; n0 += 16) {
+        int64_t row = n0 + n_lane;
+        const bool row_ok = row < r_end;
+        if (!row_ok) row = r_end - 1;                                // clamp: masked below
+        const float *src = bank + row * D + 4 * g;
+        const f32x4 acc = stream_dot16(src, imgA, nchunk, lane);
+        // C/D: col = lane&15 -> bank row n0 + n_lane, row = 4g + r -> query
+        const float xnv = xn[row];
+        const bool last_tile = ++tile_in_image == tiles_per_image;
+        if (last_tile) tile_in_image = 0;
+        // the image's first lane speaks for it (a row past r_end belongs to an image past r_end)
+        const bool lead = last_tile && (n_lane & (tp - 1)) == 0 && row_ok;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int q_mine = 4 * g + r;
+            const float s = (row_ok && q_mine < Q) ? finish_score(acc[r], qn4[r], xnv, eps) : -INFINITY;
+            float c = combine_tile<COMBINE>(s, carry[r], lane, tp);
+            carry[r] = last_tile ? combine_start<COMBINE>() : c;
+            if (COMBINE == SKYEMB_COMBINE_MEAN && last_tile) {          // wave-uniform: the sum is complete
+                c = __fdiv_rn(c, fP);
+                c = c == c ? c : -INFINITY;
+            }
+            if (!LISTS) {
+                if (lead && q_mine < Q) scores[(int64_t)q_mine * n_img + (int64_t)((unsigned)(n0 + n_lane) / (unsigned)P)] = c;
+                continue;
+            }
+            // candidates of the 4 queries {r, 4+r, 8+r, 12+r} (one per lane group), images ascending within a group
+            float my_thr = -INFINITY;
+#pragma unroll
+            for (int gg = 0; gg < 4; ++gg) my_thr = (g == gg) ? thr[4 * gg + r] : my_thr;
+            unsigned long long m = __ballot(lead && q_mine < Q && c > my_thr);
+            while (m) {
+                const int srcl = __builtin_ctzll(m);
+                m &= m - 1;
+                const float cv = __shfl(c, srcl, 64);
+                const int q = 4 * (srcl >> 4) + r;
+                float *lsq = ls + q * k;
+                int *liq = li + q * k;
+                // wave-uniform per-query state (static indexing through the unrolled select)
+                int nq = 0;
+                float tq = -INFINITY;
+#pragma unroll
+                for (int gg = 0; gg < 4; ++gg)
+                    if (q == 4 * gg + r) { nq = n_in[4 * gg + r]; tq = thr[4 * gg + r]; }
+                if (!(cv > tq)) continue;
+                const int image = (int)((unsigned)(n0 + (srcl & 15)) / (unsigned)P);
+                const int new_n = stream_list_insert(lsq, liq, nq, k, cv, image, lane);
+                const float kth = new_n == k ? lsq[k - 1] : -INFINITY;
+#pragma unroll
+                for (int gg = 0; gg < 4; ++gg)
+                    if (q == 4 * gg + r) {
+                        n_in[4 * gg + r] = new_n;
+                        thr[4 * gg + r] = new_n == k ? kth : floor_thr[4 * gg + r];
+                    }
+            }
+        }
+    }
+    if (!LISTS) return;
+    // write this wave's lists: part[q][wid][k], the entries and ONE terminator (-inf, -1) as cosine_topk_stream_kernel does
+    const int nlists = gridDim.x * WAVES;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        if (q >= Q) continue;
+        const int64_t o = ((int64_t)q * nlists + wid) * k;
+        const int n_out = n_in[q] < k ? n_in[q] + 1 : k;
+        for (int e = lane; e < n_out; e += 64) {
+            const bool have = e < n_in[q];
+            part_s[o + e] = have ? ls[q * k + e] : -INFINITY;
+            part_i[o + e] = have ? idx_offset + (int64_t)li[q * k + e] : -1;
+        }
+    }
+}
+
+constexpr int LDS_BYTES = 160 * 1024;
+
+size_t image_bytes(int D) { return (size_t)(D >> 4) * 64 * 16; }   // the A operand image: 64 D bytes
+
+// 8 waves per workgroup when their private lists (Q x k entries of 8 bytes each) fit next to the A image, else 4
+int token_waves(int Q, int D, int k) { return image_bytes(D) + (size_t)8 * 8 * Q * k <= (size_t)LDS_BYTES ? 8 : 4; }
+
+int64_t image_unit(int P) { return P < 16 ? 16 : P; }              // lcm(P, 16) for the accepted P
+
+bool combine_ok(int combine) { return combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MEAN || combine == SKYEMB_COMBINE_MAX; }
+
+template <int WAVES, bool LISTS>
+int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
+                  const float *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
+                  int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img) {
+    auto go = [&](auto kern) {
+        if (smem > 64 * 1024) {
+            const int rc = sky_set_lds_limit((const void *)kern, LDS_BYTES, who);
+            if (rc != 0) return rc;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), smem, st, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
+                           rows_per_wave, part_s, part_i, thr0, scores, n_img);
+        SKY_LAUNCH_CHECK(who);
+        return 0;
+    };
+    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<WAVES, SKYEMB_COMBINE_MIN, LISTS>);
+    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<WAVES, SKYEMB_COMBINE_MEAN, LISTS>);
+    return go(cosine_token_kernel<WAVES, SKYEMB_COMBINE_MAX, LISTS>);
+}
+
+}  // namespace
+
+#define TOKEN_SHAPE_MSG                                                                                                        \
+    "needs Q <= 16, D %% 64 == 0, D <= 1024, 1 <= P <= 4096 with 16 %% P == 0 or P %% 16 == 0, 1 <= k <= 512 and "             \
+    "64 D + 32 Q k <= 163840 bytes of LDS (Q=%d P=%d D=%d k=%d)"
+
+// The one statement of the shape limits: a refusal leaves it as the library's error text (skyemb_last_error), which the callers
+// -- the two entry points below and the Python layer -- pass on instead of restating it.
+extern "C" int skyemb_cosine_token_applicable(int Q, int P, int D, int k) {
+    // k <= 512: the list capacity skyemb_topk_merge sorts; four waves' lists next to the A image: 64 D + 32 Q k <= 160 KiB
+    const bool ok = Q >= 1 && Q <= 16 && D >= 64 && D % (16 * UNROLL) == 0 && D <= 1024 && P >= 1 && P <= 4096 &&
+                    (16 % P == 0 || P % 16 == 0) && k >= 1 && k <= 512 &&
+                    image_bytes(D) + (size_t)4 * 8 * Q * k <= (size_t)LDS_BYTES;
+    if (!ok) skyemb_set_error("patch-token search " TOKEN_SHAPE_MSG, Q, P, D, k);
+    return ok ? 1 : 0;
+}
+
+extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, int k) {
+    if (N < 1 || !skyemb_cosine_token_applicable(Q, P, D, k)) return 0;
+    const int waves = token_waves(Q, D, k);
+    const int64_t per_wave = image_unit(P) < 64 ? 64 : image_unit(P);   // at least 64 rows and one whole image per wave
+    int64_t blocks = 256;
+    while (blocks > 1 && blocks * waves * per_wave > N * P) blocks >>= 1;
+    return (int)(blocks * waves);
+}
+
+extern "C" int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
+                                        int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
+                                        const float *thr0, float *part_s, int64_t *part_i, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "skyemb_cosine_token_topk: bad arguments");
+    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "skyemb_cosine_token_topk: " TOKEN_SHAPE_MSG, Q, P, D, k);
+    SKY_CHECK_ARG(combine_ok(combine), "skyemb_cosine_token_topk: unknown combine code %d", combine);
+    SKY_CHECK_ARG(N * P < (1ll << 31), "skyemb_cosine_token_topk: shard too large (N * P < 2^31 rows per call)");
+    SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k),
+                  "skyemb_cosine_token_topk: nlists must come from skyemb_cosine_token_topk_chunks");
+    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "skyemb_cosine_token_topk: bank and tw must be 16-byte aligned");
+    const int waves = token_waves(Q, D, k);
+    const int64_t R = N * P, unit = image_unit(P);
+    const int64_t rows_per_wave = ceil_div64(ceil_div64(R, nlists), unit) * unit;
+    const size_t smem = image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
+    const char *who = "skyemb_cosine_token_topk";
+    if (waves == 8)
+        return launch_tokens<8, true>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
+                                      idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
+    return launch_tokens<4, true>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
+                                  idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
+}
+
+extern "C" int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
+                                          int P, int D, int combine, float eps, float *scores, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "skyemb_cosine_token_scores: bad arguments");
+    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "skyemb_cosine_token_scores: " TOKEN_SHAPE_MSG, Q, P, D, 1);
+    SKY_CHECK_ARG(combine_ok(combine), "skyemb_cosine_token_scores: unknown combine code %d", combine);
+    SKY_CHECK_ARG(N * P < (1ll << 31), "skyemb_cosine_token_scores: bank too large (N * P < 2^31 rows per call)");
+    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "skyemb_cosine_token_scores: bank and tw must be 16-byte aligned");
+    const int64_t R = N * P, unit = image_unit(P);
+    int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), 4);
+    if (blocks > 2048) blocks = 2048;
+    const int64_t rows_per_wave = ceil_div64(ceil_div64(R, blocks * 4), unit) * unit;
+    return launch_tokens<4, false>(combine, (int)blocks, image_bytes(D), (hipStream_t)stream, "skyemb_cosine_token_scores", tw, qn,
+                                   bank, xn, Q, R, P, D, 1, eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N);
+}

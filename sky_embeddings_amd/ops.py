@@ -11,7 +11,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ACT_DGELU, ACT_GELU, ACT_NONE, BF16, F16, F32, KC, RC, AdamwDesc, GemmArgs, GemmGroupInfo, LnBwdSide, check, lib
+from ._lib import (ACT_DGELU, ACT_GELU, ACT_NONE, BF16, COMBINE_MAX, COMBINE_MEAN, COMBINE_MIN, F16, F32, KC, RC, AdamwDesc,
+                   GemmArgs, GemmGroupInfo, LnBwdSide, check, lib)
 
 TORCH_DTYPE = {BF16: torch.bfloat16, F32: torch.float32, F16: torch.float16}
 LP_DTYPES = (torch.bfloat16, torch.float16)     # the two 16-bit operand formats of the MFMA kernels (SKYEMB_BF16 / SKYEMB_F16)
@@ -408,3 +409,36 @@ def cosine_scores(tw, qn, bank, xn, eps, scores):
     N = bank.shape[0]
     check(lib().skyemb_cosine_scores(_p(tw), _p(qn), _p(bank), _p(xn), Q, N, D, eps, _p(scores), _stream()),
           "skyemb_cosine_scores")
+
+
+COMBINE_CODES = {"min": COMBINE_MIN, "mean": COMBINE_MEAN, "max": COMBINE_MAX}
+
+
+def cosine_token_applicable(Q, P, D, k):
+    """The library's shape predicate of the patch-token search (no device work): see include/skyemb.h."""
+    return bool(lib().skyemb_cosine_token_applicable(Q, P, D, k))
+
+
+def cosine_token_refusal(Q, P, D, k):
+    """None when the shape is taken, else the library's own statement of the limits (the predicate leaves it as its error text)."""
+    L = lib()
+    return None if L.skyemb_cosine_token_applicable(Q, P, D, k) else L.skyemb_last_error().decode()
+
+
+def cosine_token_topk_chunks(N, P, Q, D, k):
+    return lib().skyemb_cosine_token_topk_chunks(N, P, Q, D, k)
+
+
+def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores):
+    """bank [N, P, D], xn [N * P], combine: a COMBINE_* code -> scores [Q, N]."""
+    Q, D = tw.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_cosine_token_scores(_p(tw), _p(qn), _p(bank), _p(xn), Q, N, P, D, combine, eps, _p(scores), _stream()),
+          "skyemb_cosine_token_scores")
+
+
+def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None):
+    Q, D = tw.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_cosine_token_topk(_p(tw), _p(qn), _p(bank), _p(xn), Q, N, P, D, k, combine, eps, idx_offset, nlists, _p(thr0),
+                                         _p(part_s), _p(part_i), _stream()), "skyemb_cosine_token_topk")

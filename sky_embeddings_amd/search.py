@@ -169,3 +169,132 @@ def cosine_scores(queries: torch.Tensor, bank, weights: torch.Tensor | None = No
     out = torch.empty(q.shape[0], pb.bank.shape[0], device=q.device)
     ops.cosine_scores(tw, qn, pb.bank, pb.norms, eps, out)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# patch-token banks: P tokens per image, scored token by token and combined per image (min | mean | max)
+# ------------------------------------------------------------------------------------------------
+class TokenBank:
+    """Patch tokens [N, P, D] of N images + the weighted norms of the N * P rows (recomputed only when the weights change)."""
+
+    def __init__(self, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
+        assert bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous() and bank.dim() == 3
+        self.bank, self.idx_offset = bank, int(idx_offset)
+        self.norms = torch.empty(bank.shape[0] * bank.shape[1], device=bank.device)
+        self._sample = None
+        self.set_weights(weights)
+
+    def set_weights(self, weights):
+        self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
+        ops.weighted_norms(self.bank.view(-1, self.bank.shape[2]), self.weights, self.norms)
+        self._sample = None
+
+    def sample(self, images: int):
+        """A strided sample of WHOLE images (tokens [S, P, D] + the norms of their S * P rows) used to derive the pruning
+        floor of a search."""
+        N, P, _ = self.bank.shape
+        images = min(images, N)
+        if self._sample is None or self._sample[0].shape[0] != images:
+            idx = torch.arange(images, device=self.bank.device) * (N // images)
+            self._sample = (self.bank.index_select(0, idx).contiguous(),
+                            self.norms.view(N, P).index_select(0, idx).contiguous().view(-1))
+        return self._sample
+
+
+def _combine_code(combine, who):
+    if combine not in ops.COMBINE_CODES:
+        raise ValueError(f"{who}: combine = {combine!r}, expected one of {sorted(ops.COMBINE_CODES)}")
+    return ops.COMBINE_CODES[combine]
+
+
+def _token_scores(tw, qn, tokens, norms, code, eps):
+    """[Q, N] combined scores of Q <= 16 prepared queries."""
+    out = torch.empty(tw.shape[0], tokens.shape[0], device=tw.device)
+    ops.cosine_token_scores(tw, qn, tokens, norms, code, eps, out)
+    return out
+
+
+def token_pruning_floor(tw, qn, tb: "TokenBank", k: int, combine: str = 'min', eps: float = 1e-6, sample_images: int | None = None):
+    """Per-query floor for the token search: the k-th best COMBINED score over a sample of whole images, one ulp lower
+    (``pruning_floor``'s argument, with images for rows).  None under the same size rule: N < 8 x the sample."""
+    N = tb.bank.shape[0]
+    if sample_images is None:
+        sample_images = 256 * k
+    if N < 8 * sample_images:
+        return None
+    st, sn = tb.sample(sample_images)
+    sc = _token_scores(tw, qn, st, sn, _combine_code(combine, "token_pruning_floor"), eps)
+    floor = torch.empty(tw.shape[0], device=tw.device)
+    ops.kth_largest_floor(sc, k, floor)
+    return floor
+
+
+def _check_token_shape(who, Q, P, D, k):
+    why = ops.cosine_token_refusal(max(1, min(Q, 16)), P, D, k)       # Q: queries per launch
+    if why is not None:
+        raise ValueError(f"{who}: {why}")
+
+
+def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min', weights: torch.Tensor | None = None,
+                       eps: float = 1e-6, process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None):
+    """-> (scores f32 [Q,k], image indices i64 [Q,k]): exact top-k images by the combined score of their P patch tokens
+    (reference: compute_similarity with max_pool = False, utils/similarity.py:214-268, + update_best_scores), order
+    (score desc, image asc).  ``bank`` is a [N,P,D] tensor or a TokenBank (this rank's shard of images; ``idx_offset`` = first
+    global image of the shard).  One pass over the bank per group of at most 16 queries (Q > 16 runs ceil(Q / 16) passes: a
+    many-query prefilter for token banks is out of scope).  Images whose combined score is -inf (a NaN token under min / mean)
+    are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
+    carries its own (``TokenBank.set_weights``), and the argument is then ignored, as ``cosine_topk`` does with a PreparedBank."""
+    tokens = bank.bank if isinstance(bank, TokenBank) else bank
+    Q, D = queries.shape
+    N, P = tokens.shape[0], tokens.shape[1]
+    assert tokens.dim() == 3 and D == tokens.shape[2]
+    code = _combine_code(combine, "cosine_topk_tokens")
+    if k < 1:
+        raise ValueError(f"cosine_topk_tokens: k = {k}")
+    if world_size == 1 and k > N:
+        raise ValueError(f"cosine_topk_tokens: k = {k} exceeds the {N} images of the bank")
+    _check_token_shape("cosine_topk_tokens", Q, P, D, k)     # every refusal above and here: before the first launch
+    tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
+    q = queries.to(tb.bank.device, torch.float32).contiguous()
+    out_s = torch.empty(Q, k, device=q.device)
+    out_i = torch.empty(Q, k, device=q.device, dtype=torch.int64)
+    if Q == 0:                                      # nothing to search for: empty result, no launch
+        return out_s, out_i
+    tw_all, qn_all = prepare_queries(q, tb.weights)
+    pruned = False
+    for lo in range(0, Q, 16):
+        tw, qn = tw_all[lo:lo + 16], qn_all[lo:lo + 16]
+        Qg = tw.shape[0]
+        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps) if prune else None
+        pruned = pruned or thr0 is not None
+        nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
+        ps = torch.empty(Qg, nl, k, device=q.device)
+        pi = torch.empty(Qg, nl, k, device=q.device, dtype=torch.int64)
+        ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, tb.idx_offset, nl, ps, pi, thr0)
+        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + 16], out_i[lo:lo + 16], torch.empty(Qg, device=q.device, dtype=torch.int32))
+    if stats is not None:
+        stats.update(path="tokens", groups=(Q + 15) // 16, pruned=pruned)
+    if world_size > 1:
+        from .distributed import gather_topk
+        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
+        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    return out_s, out_i
+
+
+def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weights: torch.Tensor | None = None, eps: float = 1e-6):
+    """[Q, N] combined score of every image of a [N,P,D] token bank (or TokenBank), in groups of at most 16 queries.
+    ``weights`` is ignored when ``bank`` is a TokenBank (it carries its own)."""
+    tokens = bank.bank if isinstance(bank, TokenBank) else bank
+    Q, D = queries.shape
+    assert tokens.dim() == 3 and D == tokens.shape[2]
+    code = _combine_code(combine, "cosine_token_scores")
+    _check_token_shape("cosine_token_scores", Q, tokens.shape[1], D, 1)
+    tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
+    q = queries.to(tb.bank.device, torch.float32).contiguous()
+    out = torch.empty(Q, tb.bank.shape[0], device=q.device)
+    if Q == 0:
+        return out
+    tw, qn = prepare_queries(q, tb.weights)
+    for lo in range(0, Q, 16):
+        out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps)
+    return out

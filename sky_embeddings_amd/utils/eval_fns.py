@@ -85,11 +85,16 @@ def mae_latent(model, dataloader, device, n_batches=None, return_images=False, v
 def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None):
     """Encode a dataset ONCE into a resident [N, D] fp32 bank (cls token, or max / mean pool over
     the patch tokens -- all permutation invariant, so the reference's shuffled token order does not
-    matter).  The reference re-encodes every test image per search (utils/similarity.py:81)."""
+    matter).  The reference re-encodes every test image per search (utils/similarity.py:81).
+    ``pool='tokens'`` keeps the patch tokens themselves (extra tokens removed): a [N, P, D] bank for
+    ``search.cosine_topk_tokens``.  The encoder returns them in shuffled order at mask_ratio = 0; the three combines
+    over an image's tokens (min | mean | max of the token scores) do not depend on that order as sets -- min and max exactly,
+    mean up to the rounding of its fixed-order fp32 sum."""
     model.eval()
     net = _net(model)
     reduce = {'cls': lambda t: t[:, 0].clone(), 'max': lambda t: t[:, net.num_extra_tokens:].amax(dim=1),
-              'mean': lambda t: t[:, net.num_extra_tokens:].mean(dim=1)}
+              'mean': lambda t: t[:, net.num_extra_tokens:].mean(dim=1),
+              'tokens': lambda t: t[:, net.num_extra_tokens:].to(torch.float32)}
     if pool not in reduce:
         raise ValueError(pool)
     rows = []

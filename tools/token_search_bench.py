@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Patch-token bank search: the fused pass (search.cosine_topk_tokens) against the best the one-vector API offers for the same
+answer (search.cosine_scores over the token rows in chunks the streaming score kernel takes, then torch amin + topk), and the
+one-vector streaming top-k over a bank of the same byte size.  HIP-event timing, the variants interleaved in one process.
+
+usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim 768] [--k 100] [--iters 10] [--out FILE]
+"fused_equals_baseline" compares the fused result with the baseline's torch.topk, whose order among equal scores is unspecified:
+False may come from exact ties alone and is not by itself a mismatch (the tests compare against the CPU restatement).
+Bytes counted per pass: images x tokens x dim x 4 (the bank; norms and lists are under 0.2 % of it).  Peak: 8.0 TB/s (spec)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sky_embeddings_amd import search  # noqa: E402
+
+HBM_PEAK = 8.0e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=250_000)
+    ap.add_argument("--tokens", type=int, default=16)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--combine", default="min")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("token_search_bench.py needs a GPU")
+    N, P, D, k = a.images, a.tokens, a.dim, a.k
+    g = torch.Generator(device="cuda").manual_seed(2024)
+    bank = torch.empty(N, P, D, device="cuda")
+    for s in range(0, N, 5_000):
+        bank[s:s + 5_000] = torch.randn(min(5_000, N - s), P, D, device="cuda", generator=g)
+    w = 1.0 / (torch.rand(D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)) + 0.5) ** 2
+    w = w / w.sum()
+    rows = bank.view(N * P, D)
+    tb = search.TokenBank(bank, w)
+    pb = search.PreparedBank(rows, w)                       # the same bytes as a one-vector bank of N * P rows
+    chunk = (1 << 20) // P * P                              # rows per cosine_scores call (streaming score kernel: <= 2^20 rows)
+    chunks = [search.PreparedBank(rows[s:s + chunk], w) for s in range(0, N * P, chunk)]
+    reduce = {"min": torch.amin, "max": torch.amax, "mean": torch.mean}[a.combine]
+    nbytes = N * P * D * 4
+    results = []
+    for Q in (1, 16):
+        q = torch.randn(Q, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2025 + Q))
+
+        def baseline():
+            parts = [reduce(search.cosine_scores(q, c).view(Q, -1, P), dim=2) for c in chunks]
+            return torch.topk(torch.cat(parts, dim=1), k, dim=1)
+
+        variants = {
+            "baseline_scores_amin_topk": baseline,
+            "fused_tokens": lambda: search.cosine_topk_tokens(q, tb, k, a.combine),
+            "fused_tokens_no_floor": lambda: search.cosine_topk_tokens(q, tb, k, a.combine, prune=False),
+            "one_vector_stream_same_bytes": lambda: search.cosine_topk(q, pb, k),
+            "one_vector_stream_no_floor": lambda: search.cosine_topk(q, pb, k, prune=False),
+        }
+        bs, bi = baseline()
+        fs, fi = variants["fused_tokens"]()
+        same = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
+        times = {name: [] for name in variants}
+        for it in range(a.warmup + a.iters):
+            for name, fn in variants.items():                # interleaved: every variant once per round
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if it >= a.warmup:
+                    times[name].append(e0.elapsed_time(e1))
+        for name, ts in times.items():
+            ts = sorted(ts)
+            med = ts[len(ts) // 2]
+            results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, combine=a.combine, variant=name, ms_median=round(med, 4),
+                                ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), bank_bytes=nbytes,
+                                tb_per_s=round(nbytes / (med * 1e-3) / 1e12, 3), hbm_peak_fraction=round(nbytes / (med * 1e-3) / HBM_PEAK, 4),
+                                fused_equals_baseline=same))
+            print(json.dumps(results[-1]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
