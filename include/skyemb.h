@@ -492,6 +492,26 @@ int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *ba
 int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N, int P, int D,
                              int k, int combine, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s,
                              int64_t *part_i, void *stream);
+/* Half-precision resident banks (additive to ABI version 111: nothing above changes).  A 16-bit bank IS the fp32 bank obtained by
+ * widening every stored element exactly (fp16 subnormals included, fp16 inf stays inf): after the load the `_lp` calls run the
+ * arithmetic of their fp32 namesakes -- the same fma chain, last step, combine order, lists -- so their results are bit-identical
+ * to the fp32 calls on the widened bank, at half the bytes per pass.  The only approximation is the rounding when the bank is
+ * stored.  bank_dtype / dtype / out_dtype: SKYEMB_BF16 or SKYEMB_F16; SKYEMB_F32 and every other code are refused before any
+ * launch.  Shapes, alignment (16 bytes for bank and tw) and the remaining arguments as for the calls above;
+ * skyemb_cosine_token_applicable and skyemb_cosine_token_topk_chunks hold unchanged for 16-bit banks.
+ *   skyemb_weighted_norms_lp   norms [N] of 16-bit rows x [N, D] (D % 4 == 0, x 8-byte aligned): fp32 on the widened values in
+ *                              skyemb_weighted_norms' operation order, bit-equal to that call on the widened array.
+ *   skyemb_standardise_lp      x fp32 [N, D] -> out 16-bit [N, D] (D % 4 == 0): skyemb_standardise's value, then ONE rounding to
+ *                              nearest-even (fp16: overflow -> +-inf, subnormals kept; NaN stays NaN), so a 16-bit bank can be
+ *                              built batch by batch without its fp32 image ever existing at full size. */
+int skyemb_cosine_token_scores_lp(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                  int64_t N, int P, int D, int combine, float eps, float *scores, void *stream);
+int skyemb_cosine_token_topk_lp(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                int64_t N, int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
+                                const float *thr0, float *part_s, int64_t *part_i, void *stream);
+int skyemb_weighted_norms_lp(const void *x, int dtype, const float *w, float *norms, int64_t N, int D, void *stream);
+int skyemb_standardise_lp(const float *x, const float *mu, const float *sigma, void *out, int out_dtype, int64_t N, int D,
+                          void *stream);
 
 #ifdef __cplusplus
 }

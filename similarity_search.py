@@ -9,8 +9,9 @@ the 64x target augmentation (``-aug True``, the reference's default) runs on the
 (sky_embeddings_amd.augment: torchvision's parameter draws, one HIP launch per batch).  ``--bank`` (extension) encodes the
 test set ONCE into a resident embedding bank and runs the fused cosine top-k kernel over it
 instead of re-scoring streamed batches: one vector per sample with -mp True or -ct True, or, with both False, the
-patch tokens of every sample scored one by one and combined per image (-c min | mean | max) by the fused token kernel.
-Cosine metric only.
+patch tokens of every sample scored one by one and combined per image (-c min | mean | max) by the fused token kernel;
+``--bank-dtype f16 | bf16`` keeps that token bank in 16 bits (half the memory and half the bytes per search; the standardised
+features are rounded once when stored).  Cosine metric only.
 """
 import argparse
 import ast
@@ -26,6 +27,9 @@ from utils.mim_vit import build_model as build_mim
 from utils.misc import h5_snr, str2bool
 from utils.similarity import determine_target_features, mae_simsearch
 from utils.vit import build_model as build_vit
+
+
+BANK_DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 
 
 def parseArguments():
@@ -47,6 +51,8 @@ def parseArguments():
     parser.add_argument("-dd", "--data_dir", help="Data directory if different from sky_embeddings/data/", type=str,
                         default=None)
     parser.add_argument("--bank", action="store_true", help="encode once into a resident bank + fused top-k kernel")
+    parser.add_argument("--bank-dtype", choices=sorted(BANK_DTYPES), default="f32",
+                        help="element type of the resident patch-token bank (--bank -mp False -ct False)")
     return parser
 
 
@@ -97,6 +103,8 @@ def main():
         from sky_embeddings_amd import search
         if args.metric != 'cosine':
             raise SystemExit("--bank runs the weighted cosine metric only (-m cosine)")
+        if args.bank_dtype != "f32" and (max_pool or cls_token):
+            raise SystemExit("--bank-dtype f16 / bf16 applies to the patch-token bank (-mp False -ct False)")
         mod = model.module
         tl = target_latent.to(device)
         k = args.n_save
@@ -111,11 +119,17 @@ def main():
             scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w)
         else:                                    # every patch token scored, combined per image (-c min | mean | max)
             tl = tl[:, mod.num_extra_tokens:]
-            bank = build_embedding_bank(model, test_dataloader, device, pool='tokens')
-            first = bank[:args.batch_size]   # mean / unbiased std over (batch, patch) of the first batch (utils/similarity.py:98-100)
-            mean_feats, std_feats = first.mean(dim=(0, 1)), first.std(dim=(0, 1), unbiased=True)
+            if args.bank_dtype == "f32":
+                bank = build_embedding_bank(model, test_dataloader, device, pool='tokens')
+                first = bank[:args.batch_size]   # mean / unbiased std over (batch, patch) of the first batch (utils/similarity.py:98-100)
+                mean_feats, std_feats = first.mean(dim=(0, 1)), first.std(dim=(0, 1), unbiased=True)
+                search.standardise_(bank.view(-1, bank.shape[2]), mean_feats, std_feats)
+            else:                                # the same statistics; every batch standardised, rounded once and kept in 16 bits
+                bank, mean_feats, std_feats = build_embedding_bank(model, test_dataloader, device, pool='tokens',
+                                                                   bank_dtype=BANK_DTYPES[args.bank_dtype],
+                                                                   standardise_with_first_batch=True)
+            print(f'Token bank: {bank.numel() * bank.element_size() / 1e9:.3f} GB, {bank.dtype}')
             tl = (tl - mean_feats) / (std_feats + 1e-8)
-            search.standardise_(bank.view(-1, bank.shape[2]), mean_feats, std_feats)
             avg, w = determine_target_features(tl)
             scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
                                                     weights=w)

@@ -144,6 +144,12 @@ PROTOTYPES = {
     "skyemb_cosine_token_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_topk": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_i32, c_vp,
                                          c_vp, c_vp, c_vp]),
+    # half-precision resident banks: additive to ABI version 111 (nothing above changed, so the version did not)
+    "skyemb_cosine_token_scores_lp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp]),
+    "skyemb_cosine_token_topk_lp": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_i32,
+                                            c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_weighted_norms_lp": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "skyemb_standardise_lp": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
 }
 
 _LIB = None

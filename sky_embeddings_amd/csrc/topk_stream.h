@@ -1,7 +1,7 @@
 // Device pieces shared by the bank-streaming kernels (topk_stream.hip: one vector per row; topk_tokens.hip: P rows per image):
 // the 16-row MFMA dot product fed straight from HBM, the A operand image, the score's last step and the wave-owned sorted list.
 //
-// Lane (n = lane&15, g = lane>>4) loads bank[row0+n][16c + 4g .. 4g+3]; the MFMA B operand of k-step m
+// Lane (n = lane&15, g = lane>>4) loads bank[row0+n][16c + 4g .. 4g+3] (fp32 rows; 16-bit rows: BankSet); the MFMA B operand of k-step m
 // must hold bank[row0+n][16c + 4m + g], i.e. the 4x4 transpose of (lane group g) x (element s):
 // two v_permlane32_swap (lanes +-32) and two v_permlane16_swap (lanes +-16) per float4.
 #pragma once
@@ -103,6 +103,87 @@ __device__ __forceinline__ f32x4 stream_dot16(const float *__restrict__ src, con
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b1[u].z, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b1[u].w, acc, 0, 0, 0);
             }
+        }
+    }
+    return acc;
+}
+
+// ---- 16-bit bank rows (bf16_t | f16_t): a half-precision bank IS the fp32 bank its elements widen to, so the chain above is fed
+// the same operands in the same order from half the bytes.
+
+// the two floats a 32-bit word of a 16-bit row widens to, exactly (lower address first)
+template <typename T>
+__device__ __forceinline__ void widen2(unsigned w, float &a, float &b);
+template <>
+__device__ __forceinline__ void widen2<bf16_t>(unsigned w, float &a, float &b) {
+    a = __uint_as_float(w << 16);                 // bf16 is the upper half of the fp32 with the same value
+    b = __uint_as_float(w & 0xffff0000u);
+}
+template <>
+__device__ __forceinline__ void widen2<f16_t>(unsigned w, float &a, float &b) {
+    typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+    const f16x2 h = __builtin_bit_cast(f16x2, w);
+    a = (float)h[0];                              // v_cvt_f32_f16: exact, subnormals included, inf stays inf
+    b = (float)h[1];
+}
+
+// elements of a row that one lane's 16-byte load covers: `src` of stream_dot16 = row + lane_elems<T>() * g
+template <typename T>
+__host__ __device__ constexpr int lane_elems() { return 16 / (int)sizeof(T); }
+
+// One 16-byte load `r` of lane (n, g) = elements 32 c' + 8 g .. 8 g + 7 -> the MFMAs of the 32 elements 32 c' .. 32 c' + 31
+// (A fragments a0 = imgA[2 c'], a1 = imgA[2 c' + 1]).  Widened, lo = elements 8 g .. 8 g + 3 and hi = 8 g + 4 .. 8 g + 7; after
+// transpose4 component m of lo / hi is element 8 m + g / 8 m + 4 + g, so the order lo.x hi.x lo.y hi.y | lo.z hi.z lo.w hi.w
+// walks the k-steps 4 m' + g, m' = 0 .. 7: the fp32 rows' d-ascending chain, A image unchanged, the same permlane swaps per
+// element.
+template <typename T>
+__device__ __forceinline__ f32x4 mfma32_lp(f32x4 acc, const uint4 r, const float4 a0, const float4 a1) {
+    float4 lo, hi;
+    widen2<T>(r.x, lo.x, lo.y);
+    widen2<T>(r.y, lo.z, lo.w);
+    widen2<T>(r.z, hi.x, hi.y);
+    widen2<T>(r.w, hi.z, hi.w);
+    transpose4(lo);
+    transpose4(hi);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, lo.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, hi.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, lo.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, hi.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, lo.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, hi.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, lo.w, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, hi.w, acc, 0, 0, 0);
+    return acc;
+}
+
+// stream_dot16 for 16-bit rows (`src` = row + 8 g).  The same two register sets of 16 UNROLL = 64 elements each, i.e. LP_LOADS
+// 16-byte loads per set (nchunk % UNROLL == 0 as above, so D = 64 and D = 192 work).
+constexpr int LP_LOADS = UNROLL / 2;
+
+template <typename T>
+__device__ __forceinline__ f32x4 stream_dot16(const T *__restrict__ src, const float4 *__restrict__ imgA, int nchunk, int lane) {
+    static_assert(sizeof(T) == 2, "16-bit bank rows");
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    uint4 b0[LP_LOADS], b1[LP_LOADS];
+#pragma unroll
+    for (int j = 0; j < LP_LOADS; ++j) b0[j] = *(const uint4 *)(src + 32 * j);
+    for (int c0 = 0; c0 < nchunk; c0 += 2 * UNROLL) {
+        const bool more1 = c0 + UNROLL < nchunk, more2 = c0 + 2 * UNROLL < nchunk;
+        if (more1) {
+#pragma unroll
+            for (int j = 0; j < LP_LOADS; ++j) b1[j] = *(const uint4 *)(src + 16 * (c0 + UNROLL) + 32 * j);
+        }
+#pragma unroll
+        for (int j = 0; j < LP_LOADS; ++j)
+            acc = mfma32_lp<T>(acc, b0[j], imgA[(c0 + 2 * j) * 64 + lane], imgA[(c0 + 2 * j + 1) * 64 + lane]);
+        if (more2) {
+#pragma unroll
+            for (int j = 0; j < LP_LOADS; ++j) b0[j] = *(const uint4 *)(src + 16 * (c0 + 2 * UNROLL) + 32 * j);
+        }
+        if (more1) {
+#pragma unroll
+            for (int j = 0; j < LP_LOADS; ++j)
+                acc = mfma32_lp<T>(acc, b1[j], imgA[(c0 + UNROLL + 2 * j) * 64 + lane], imgA[(c0 + UNROLL + 2 * j + 1) * 64 + lane]);
         }
     }
     return acc;

@@ -11,6 +11,10 @@
 // p = 0 .. P-1, one IEEE division; every lane of an image's lane group runs the same chain, tiles of a long image are folded in
 // ascending order, so the result does not depend on the launch geometry, on the wave or on Q.  A -inf token score (NaN scores
 // rank as -inf) gives -inf for min and mean and is ignored by max; an image whose combined score is -inf never enters a list.
+//
+// Bank element type T: float, or bf16_t / f16_t for a half-precision resident bank (the `_lp` entry points).  A 16-bit row is
+// widened exactly on its way into the MFMA operands (mfma32_lp, topk_stream.h); everything after the load is the same code, so a
+// 16-bit bank gives the fp32 kernel's result on the widened bank bit for bit, for half the bytes.
 #include "topk_stream.h"
 
 namespace {
@@ -39,9 +43,9 @@ __device__ __forceinline__ float combine_tile(float s, float carry, int lane, in
 
 // LISTS: part_s / part_i [Q, nlists, k] as cosine_topk_stream_kernel writes them (idx = idx_offset + image).
 // !LISTS: scores [Q, n_img] combined scores.
-template <int WAVES, int COMBINE, bool LISTS>
+template <typename T, int WAVES, int COMBINE, bool LISTS>
 __global__ __launch_bounds__(WAVES * 64) void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
-                                                                  const float *__restrict__ bank, const float *__restrict__ xn,
+                                                                  const T *__restrict__ bank, const float *__restrict__ xn,
                                                                   int Q, int64_t R, int P, int D, int k, float eps,
                                                                   int64_t idx_offset, int64_t rows_per_wave,
                                                                   float *__restrict__ part_s, int64_t *__restrict__ part_i,
@@ -86,7 +90,7 @@ __global__ __launch_bounds__(WAVES * 64) void cosine_token_kernel(const float *_
         int64_t row = n0 + n_lane;
         const bool row_ok = row < r_end;
         if (!row_ok) row = r_end - 1;                                // clamp: masked below
-        const float *src = bank + row * D + 4 * g;
+        const T *src = bank + row * D + lane_elems<T>() * g;
         const f32x4 acc = stream_dot16(src, imgA, nchunk, lane);
         // C/D: col = lane&15 -> bank row n0 + n_lane, row = 4g + r -> query
         const float xnv = xn[row];
@@ -166,9 +170,9 @@ int64_t image_unit(int P) { return P < 16 ? 16 : P; }              // lcm(P, 16)
 
 bool combine_ok(int combine) { return combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MEAN || combine == SKYEMB_COMBINE_MAX; }
 
-template <int WAVES, bool LISTS>
+template <typename T, int WAVES, bool LISTS>
 int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
-                  const float *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
+                  const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
                   int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img) {
     auto go = [&](auto kern) {
         if (smem > 64 * 1024) {
@@ -180,9 +184,9 @@ int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const ch
         SKY_LAUNCH_CHECK(who);
         return 0;
     };
-    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<WAVES, SKYEMB_COMBINE_MIN, LISTS>);
-    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<WAVES, SKYEMB_COMBINE_MEAN, LISTS>);
-    return go(cosine_token_kernel<WAVES, SKYEMB_COMBINE_MAX, LISTS>);
+    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS>);
+    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS>);
+    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS>);
 }
 
 }  // namespace
@@ -211,39 +215,77 @@ extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, i
     return (int)(blocks * waves);
 }
 
-extern "C" int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
-                                        int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
-                                        const float *thr0, float *part_s, int64_t *part_i, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "skyemb_cosine_token_topk: bad arguments");
-    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "skyemb_cosine_token_topk: " TOKEN_SHAPE_MSG, Q, P, D, k);
-    SKY_CHECK_ARG(combine_ok(combine), "skyemb_cosine_token_topk: unknown combine code %d", combine);
-    SKY_CHECK_ARG(N * P < (1ll << 31), "skyemb_cosine_token_topk: shard too large (N * P < 2^31 rows per call)");
-    SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k),
-                  "skyemb_cosine_token_topk: nlists must come from skyemb_cosine_token_topk_chunks");
-    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "skyemb_cosine_token_topk: bank and tw must be 16-byte aligned");
+// Argument checks and launch geometry of the two calls, for every bank element type (`who`: the entry point's name in error texts).
+template <typename T>
+int token_topk(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D, int k,
+               int combine, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i,
+               void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "%s: bad arguments", who);
+    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
+    SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
+    SKY_CHECK_ARG(N * P < (1ll << 31), "%s: shard too large (N * P < 2^31 rows per call)", who);
+    SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
+                  who);
+    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
     const int waves = token_waves(Q, D, k);
     const int64_t R = N * P, unit = image_unit(P);
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, nlists), unit) * unit;
     const size_t smem = image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
-    const char *who = "skyemb_cosine_token_topk";
     if (waves == 8)
-        return launch_tokens<8, true>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                      idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
-    return launch_tokens<4, true>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                  idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
+        return launch_tokens<T, 8, true>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
+                                         idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
+    return launch_tokens<T, 4, true>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
+                                     idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
 }
 
-extern "C" int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
-                                          int P, int D, int combine, float eps, float *scores, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "skyemb_cosine_token_scores: bad arguments");
-    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "skyemb_cosine_token_scores: " TOKEN_SHAPE_MSG, Q, P, D, 1);
-    SKY_CHECK_ARG(combine_ok(combine), "skyemb_cosine_token_scores: unknown combine code %d", combine);
-    SKY_CHECK_ARG(N * P < (1ll << 31), "skyemb_cosine_token_scores: bank too large (N * P < 2^31 rows per call)");
-    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "skyemb_cosine_token_scores: bank and tw must be 16-byte aligned");
+template <typename T>
+int token_scores(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D,
+                 int combine, float eps, float *scores, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "%s: bad arguments", who);
+    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, 1);
+    SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
+    SKY_CHECK_ARG(N * P < (1ll << 31), "%s: bank too large (N * P < 2^31 rows per call)", who);
+    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
     const int64_t R = N * P, unit = image_unit(P);
     int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), 4);
     if (blocks > 2048) blocks = 2048;
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, blocks * 4), unit) * unit;
-    return launch_tokens<4, false>(combine, (int)blocks, image_bytes(D), (hipStream_t)stream, "skyemb_cosine_token_scores", tw, qn,
-                                   bank, xn, Q, R, P, D, 1, eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N);
+    return launch_tokens<T, 4, false>(combine, (int)blocks, image_bytes(D), (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, 1,
+                                      eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N);
+}
+
+extern "C" int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
+                                        int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
+                                        const float *thr0, float *part_s, int64_t *part_i, void *stream) {
+    return token_topk("skyemb_cosine_token_topk", tw, qn, bank, xn, Q, N, P, D, k, combine, eps, idx_offset, nlists, thr0, part_s,
+                      part_i, stream);
+}
+
+extern "C" int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
+                                          int P, int D, int combine, float eps, float *scores, void *stream) {
+    return token_scores("skyemb_cosine_token_scores", tw, qn, bank, xn, Q, N, P, D, combine, eps, scores, stream);
+}
+
+// Half-precision resident banks: the same two calls on a bf16 / fp16 bank (include/skyemb.h).  The dtype is checked first, so a
+// refused code never reaches a launch.
+#define LP_DTYPE_MSG "bank_dtype must be SKYEMB_BF16 (0) or SKYEMB_F16 (2), got %d (an fp32 bank takes the call without _lp)"
+
+extern "C" int skyemb_cosine_token_topk_lp(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                           int64_t N, int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
+                                           const float *thr0, float *part_s, int64_t *part_i, void *stream) {
+    const char *who = "skyemb_cosine_token_topk_lp";
+    SKY_CHECK_ARG(sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_lp: " LP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, eps, idx_offset, nlists, thr0, part_s, part_i,
+                          stream);
+    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, eps, idx_offset, nlists, thr0, part_s, part_i,
+                      stream);
+}
+
+extern "C" int skyemb_cosine_token_scores_lp(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn,
+                                             int Q, int64_t N, int P, int D, int combine, float eps, float *scores, void *stream) {
+    const char *who = "skyemb_cosine_token_scores_lp";
+    SKY_CHECK_ARG(sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_lp: " LP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_BF16) return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, eps, scores, stream);
+    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, eps, scores, stream);
 }

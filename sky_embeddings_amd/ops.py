@@ -340,6 +340,30 @@ def weighted_norms(x, w, norms, xw_out=None):
     check(lib().skyemb_weighted_norms(_p(x), _p(w), _p(norms), _p(xw_out), N, D, _stream()), "skyemb_weighted_norms")
 
 
+BANK_DTYPES = (torch.float32, torch.float16, torch.bfloat16)     # element types of a resident token bank
+
+
+def bank_dtype_code(t: torch.dtype, who: str) -> int:
+    """SKYEMB_* code of a token bank's element type; anything but fp32 / fp16 / bf16 is a ValueError naming the three."""
+    if t not in BANK_DTYPES:
+        raise ValueError(f"{who}: bank dtype {t} is not supported, expected one of torch.float32, torch.float16, torch.bfloat16")
+    return dtype_code(t)
+
+
+def weighted_norms_lp(x, w, norms):
+    """weighted_norms of fp16 / bf16 rows: fp32 on the exactly widened values, bit-equal to weighted_norms(x.float(), ...)."""
+    N, D = x.shape
+    check(lib().skyemb_weighted_norms_lp(_p(x), bank_dtype_code(x.dtype, "weighted_norms_lp"), _p(w), _p(norms), N, D, _stream()),
+          "skyemb_weighted_norms_lp")
+
+
+def standardise_lp(x, mu, sigma, out):
+    """standardise, then one rounding to nearest-even into ``out`` (fp16 or bf16)."""
+    N, D = x.shape
+    check(lib().skyemb_standardise_lp(_p(x), _p(mu), _p(sigma), _p(out), bank_dtype_code(out.dtype, "standardise_lp"), N, D, _stream()),
+          "skyemb_standardise_lp")
+
+
 def cosine_topk_chunks(N, Q, D, k):
     return lib().skyemb_cosine_topk_chunks(N, Q, D, k)
 
@@ -430,9 +454,13 @@ def cosine_token_topk_chunks(N, P, Q, D, k):
 
 
 def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores):
-    """bank [N, P, D], xn [N * P], combine: a COMBINE_* code -> scores [Q, N]."""
+    """bank [N, P, D] fp32, fp16 or bf16, xn [N * P], combine: a COMBINE_* code -> scores [Q, N]."""
     Q, D = tw.shape
     N, P = bank.shape[0], bank.shape[1]
+    if bank.dtype != torch.float32:
+        check(lib().skyemb_cosine_token_scores_lp(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_scores"), _p(xn),
+                                                  Q, N, P, D, combine, eps, _p(scores), _stream()), "skyemb_cosine_token_scores_lp")
+        return
     check(lib().skyemb_cosine_token_scores(_p(tw), _p(qn), _p(bank), _p(xn), Q, N, P, D, combine, eps, _p(scores), _stream()),
           "skyemb_cosine_token_scores")
 
@@ -440,5 +468,10 @@ def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores):
 def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None):
     Q, D = tw.shape
     N, P = bank.shape[0], bank.shape[1]
+    if bank.dtype != torch.float32:
+        check(lib().skyemb_cosine_token_topk_lp(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_topk"), _p(xn), Q, N,
+                                                P, D, k, combine, eps, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i), _stream()),
+              "skyemb_cosine_token_topk_lp")
+        return
     check(lib().skyemb_cosine_token_topk(_p(tw), _p(qn), _p(bank), _p(xn), Q, N, P, D, k, combine, eps, idx_offset, nlists, _p(thr0),
                                          _p(part_s), _p(part_i), _stream()), "skyemb_cosine_token_topk")

@@ -56,6 +56,20 @@ def standardise_(bank: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, out:
     return out
 
 
+def standardise_to(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, dtype: torch.dtype):
+    """(x - mean) / (std + 1e-8) of fp32 rows ``x`` [..., D], rounded ONCE to nearest-even into a new ``dtype`` tensor
+    (torch.float16 or torch.bfloat16): ``standardise_``'s value, then the storage rounding of a half-precision bank (fp16:
+    overflow -> +-inf, subnormals kept; NaN stays NaN).  Lets a 16-bit bank be built batch by batch."""
+    if dtype not in ops.LP_DTYPES:
+        raise ValueError(f"standardise_to: dtype {dtype} is not supported, expected torch.float16 or torch.bfloat16")
+    x = x.contiguous()
+    out = torch.empty(x.shape, device=x.device, dtype=dtype)
+    D = x.shape[-1]
+    ops.standardise_lp(x.view(-1, D), mean.to(x.device, torch.float32).contiguous(), std.to(x.device, torch.float32).contiguous(),
+                       out.view(-1, D))
+    return out
+
+
 def prepare_queries(queries: torch.Tensor, weights: torch.Tensor | None):
     Q, D = queries.shape
     tw = torch.empty(Q, D, device=queries.device)
@@ -132,7 +146,14 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     """-> (scores f32 [Q,k], indices i64 [Q,k]).  ``bank`` is a [N,D] tensor or a PreparedBank
     (this rank's shard; ``idx_offset`` = first global row of the shard).  More than 16 queries take the two-stage
     path (fp16 matrix-core prefilter with a proven error bound, exact fp32 re-score of the survivors: same results bit
-    for bit); SKYEMB_TOPK_PREFILTER=0 keeps every search on the exact fp32 kernels."""
+    for bit); SKYEMB_TOPK_PREFILTER=0 keeps every search on the exact fp32 kernels.
+
+    A 2-D fp16 / bf16 tensor is a half-precision resident bank: it is served as a token bank with one token per row
+    (``cosine_topk_tokens`` on ``bank.unsqueeze(1)``, ``stats['path'] == 'tokens'``) under that search's limits -- k <= 512,
+    more than 16 queries in groups of 16 -- with the results of the fp32 search on the widened bank, bit for bit.  The
+    many-query prefilter over a 16-bit flat bank is out of scope.  fp32 banks take exactly the paths described above."""
+    if isinstance(bank, torch.Tensor) and bank.dim() == 2 and bank.dtype in ops.LP_DTYPES:
+        return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats)
     pb = bank if isinstance(bank, PreparedBank) else PreparedBank(bank, weights)
     q = queries.to(pb.bank.device, torch.float32).contiguous()
     Q, D = q.shape
@@ -175,23 +196,32 @@ def cosine_scores(queries: torch.Tensor, bank, weights: torch.Tensor | None = No
 # patch-token banks: P tokens per image, scored token by token and combined per image (min | mean | max)
 # ------------------------------------------------------------------------------------------------
 class TokenBank:
-    """Patch tokens [N, P, D] of N images + the weighted norms of the N * P rows (recomputed only when the weights change)."""
+    """Patch tokens [N, P, D] of N images + the weighted norms of the N * P rows (recomputed only when the weights change).
+
+    ``bank`` is fp32, or fp16 / bf16 for a half-precision resident bank (``dtype``): such a bank IS the fp32 bank its elements
+    widen to -- norms (fp32) and scores are those of the widened bank bit for bit, for half the memory and half the bytes per
+    pass.  The only approximation is the rounding when the bank was stored (``standardise_to``)."""
 
     def __init__(self, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
-        assert bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous() and bank.dim() == 3
-        self.bank, self.idx_offset = bank, int(idx_offset)
+        ops.bank_dtype_code(bank.dtype, "TokenBank")          # ValueError for anything but fp32 / fp16 / bf16
+        assert bank.is_cuda and bank.is_contiguous() and bank.dim() == 3
+        self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self.norms = torch.empty(bank.shape[0] * bank.shape[1], device=bank.device)
         self._sample = None
         self.set_weights(weights)
 
     def set_weights(self, weights):
         self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
-        ops.weighted_norms(self.bank.view(-1, self.bank.shape[2]), self.weights, self.norms)
+        rows = self.bank.view(-1, self.bank.shape[2])
+        if self.dtype == torch.float32:
+            ops.weighted_norms(rows, self.weights, self.norms)
+        else:
+            ops.weighted_norms_lp(rows, self.weights, self.norms)
         self._sample = None
 
     def sample(self, images: int):
-        """A strided sample of WHOLE images (tokens [S, P, D] + the norms of their S * P rows) used to derive the pruning
-        floor of a search."""
+        """A strided sample of WHOLE images (tokens [S, P, D] in the bank's dtype + the norms of their S * P rows) used to
+        derive the pruning floor of a search."""
         N, P, _ = self.bank.shape
         images = min(images, N)
         if self._sample is None or self._sample[0].shape[0] != images:
@@ -239,8 +269,8 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
                        eps: float = 1e-6, process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None):
     """-> (scores f32 [Q,k], image indices i64 [Q,k]): exact top-k images by the combined score of their P patch tokens
     (reference: compute_similarity with max_pool = False, utils/similarity.py:214-268, + update_best_scores), order
-    (score desc, image asc).  ``bank`` is a [N,P,D] tensor or a TokenBank (this rank's shard of images; ``idx_offset`` = first
-    global image of the shard).  One pass over the bank per group of at most 16 queries (Q > 16 runs ceil(Q / 16) passes: a
+    (score desc, image asc).  ``bank`` is a [N,P,D] tensor (fp32, or fp16 / bf16: see TokenBank) or a TokenBank (this rank's
+    shard of images; ``idx_offset`` = first global image of the shard).  One pass over the bank per group of at most 16 queries (Q > 16 runs ceil(Q / 16) passes: a
     many-query prefilter for token banks is out of scope).  Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
     carries its own (``TokenBank.set_weights``), and the argument is then ignored, as ``cosine_topk`` does with a PreparedBank."""
@@ -282,7 +312,8 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
 
 
 def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weights: torch.Tensor | None = None, eps: float = 1e-6):
-    """[Q, N] combined score of every image of a [N,P,D] token bank (or TokenBank), in groups of at most 16 queries.
+    """[Q, N] combined score of every image of a [N,P,D] token bank (fp32, fp16 or bf16; or a TokenBank), in groups of at most
+    16 queries.
     ``weights`` is ignored when ``bank`` is a TokenBank (it carries its own)."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape

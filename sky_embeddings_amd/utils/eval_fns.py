@@ -82,14 +82,30 @@ def mae_latent(model, dataloader, device, n_batches=None, return_images=False, v
     return (latents, torch.cat(images)) if return_images else latents
 
 
-def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None):
+def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None, bank_dtype=torch.float32,
+                         standardise_with_first_batch=False):
     """Encode a dataset ONCE into a resident [N, D] fp32 bank (cls token, or max / mean pool over
     the patch tokens -- all permutation invariant, so the reference's shuffled token order does not
     matter).  The reference re-encodes every test image per search (utils/similarity.py:81).
     ``pool='tokens'`` keeps the patch tokens themselves (extra tokens removed): a [N, P, D] bank for
     ``search.cosine_topk_tokens``.  The encoder returns them in shuffled order at mask_ratio = 0; the three combines
     over an image's tokens (min | mean | max of the token scores) do not depend on that order as sets -- min and max exactly,
-    mean up to the rounding of its fixed-order fp32 sum."""
+    mean up to the rounding of its fixed-order fp32 sum.
+
+    ``pool='tokens', bank_dtype=torch.float16 | torch.bfloat16, standardise_with_first_batch=True`` builds a half-precision
+    resident bank without its fp32 image ever existing at full size: mean / unbiased std over (batch, patch) of the FIRST batch
+    (as mae_simsearch takes them, utils/similarity.py:98-100), every batch standardised and rounded once to nearest-even
+    (``search.standardise_to``), the 16-bit batches concatenated -> ``(bank, mean, std)``.  A 16-bit bank is stored
+    standardised only: rounding raw features first would let ``standardise_`` amplify the rounding error.  The defaults
+    return what they always returned."""
+    from .. import search
+    lp = bank_dtype != torch.float32
+    if bank_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"build_embedding_bank: bank_dtype {bank_dtype} is not supported, expected torch.float32, torch.float16 or "
+                         "torch.bfloat16")
+    if lp != bool(standardise_with_first_batch) or (lp and pool != 'tokens'):
+        raise ValueError("build_embedding_bank: a 16-bit bank_dtype and standardise_with_first_batch=True go together, with "
+                         "pool='tokens'")
     model.eval()
     net = _net(model)
     reduce = {'cls': lambda t: t[:, 0].clone(), 'max': lambda t: t[:, net.num_extra_tokens:].amax(dim=1),
@@ -100,9 +116,16 @@ def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None):
     rows = []
     with torch.no_grad():
         for done, (samples, _masks, ra_decs) in enumerate(dataloader, 1):
-            rows.append(reduce[pool](net.forward_features(samples.to(device, non_blocking=True), ra_dec=ra_decs, reshape_out=False)[0]))
+            feats = reduce[pool](net.forward_features(samples.to(device, non_blocking=True), ra_dec=ra_decs, reshape_out=False)[0])
+            if lp:
+                if done == 1:
+                    mean, std = feats.mean(dim=(0, 1)), feats.std(dim=(0, 1), unbiased=True)
+                feats = search.standardise_to(feats, mean, std, bank_dtype)
+            rows.append(feats)
             if n_batches is not None and done >= n_batches:
                 break
+    if lp:
+        return torch.cat(rows).contiguous(), mean, std
     return torch.cat(rows).contiguous()
 
 

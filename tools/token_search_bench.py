@@ -4,9 +4,14 @@ answer (search.cosine_scores over the token rows in chunks the streaming score k
 one-vector streaming top-k over a bank of the same byte size.  HIP-event timing, the variants interleaved in one process.
 
 usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim 768] [--k 100] [--iters 10] [--out FILE]
+                                         [--bank-dtype f32 | f16 | bf16 | a comma list, e.g. f32,f16,bf16]
+--bank-dtype: element type(s) of the resident token bank the fused pass runs on (16-bit banks: the fp32 bank rounded to nearest);
+the fused variants of every listed type run interleaved in the same rounds, named fused_tokens[f16] etc.; the comparison variants
+(baseline and one-vector) need the fp32 bank and run when f32 is listed.
 "fused_equals_baseline" compares the fused result with the baseline's torch.topk, whose order among equal scores is unspecified:
 False may come from exact ties alone and is not by itself a mismatch (the tests compare against the CPU restatement).
-Bytes counted per pass: images x tokens x dim x 4 (the bank; norms and lists are under 0.2 % of it).  Peak: 8.0 TB/s (spec)."""
+Bytes counted per pass: images x tokens x dim x element size (the bank; norms and lists are under 0.4 % of it).  Peak: 8.0 TB/s
+(spec)."""
 import argparse
 import json
 import os
@@ -18,6 +23,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sky_embeddings_amd import search  # noqa: E402
 
 HBM_PEAK = 8.0e12
+BANK_DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+
+
+def bank_dtypes(text):
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    if not names or any(n not in BANK_DTYPES for n in names) or len(set(names)) != len(names):
+        raise argparse.ArgumentTypeError(f"expected f32, f16, bf16 or a comma list of them, got {text!r}")
+    return names
 
 
 def main():
@@ -30,6 +43,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--combine", default="min")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bank-dtype", type=bank_dtypes, default=["f32"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("token_search_bench.py needs a GPU")
@@ -41,12 +55,23 @@ def main():
     w = 1.0 / (torch.rand(D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)) + 0.5) ** 2
     w = w / w.sum()
     rows = bank.view(N * P, D)
-    tb = search.TokenBank(bank, w)
-    pb = search.PreparedBank(rows, w)                       # the same bytes as a one-vector bank of N * P rows
+    with_f32 = "f32" in a.bank_dtype
+    lp_banks = {}
+    for name in a.bank_dtype:
+        if name != "f32":
+            lp = torch.empty(N, P, D, device="cuda", dtype=BANK_DTYPES[name])
+            for s in range(0, N, 5_000):
+                lp[s:s + 5_000] = bank[s:s + 5_000]         # rounds to nearest-even
+            lp_banks[name] = search.TokenBank(lp, w)
     chunk = (1 << 20) // P * P                              # rows per cosine_scores call (streaming score kernel: <= 2^20 rows)
-    chunks = [search.PreparedBank(rows[s:s + chunk], w) for s in range(0, N * P, chunk)]
+    if with_f32:
+        tb = search.TokenBank(bank, w)
+        pb = search.PreparedBank(rows, w)                   # the same bytes as a one-vector bank of N * P rows
+        chunks = [search.PreparedBank(rows[s:s + chunk], w) for s in range(0, N * P, chunk)]
+    else:
+        del bank, rows
     reduce = {"min": torch.amin, "max": torch.amax, "mean": torch.mean}[a.combine]
-    nbytes = N * P * D * 4
+    elems = N * P * D
     results = []
     for Q in (1, 16):
         q = torch.randn(Q, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2025 + Q))
@@ -55,16 +80,22 @@ def main():
             parts = [reduce(search.cosine_scores(q, c).view(Q, -1, P), dim=2) for c in chunks]
             return torch.topk(torch.cat(parts, dim=1), k, dim=1)
 
-        variants = {
-            "baseline_scores_amin_topk": baseline,
-            "fused_tokens": lambda: search.cosine_topk_tokens(q, tb, k, a.combine),
-            "fused_tokens_no_floor": lambda: search.cosine_topk_tokens(q, tb, k, a.combine, prune=False),
-            "one_vector_stream_same_bytes": lambda: search.cosine_topk(q, pb, k),
-            "one_vector_stream_no_floor": lambda: search.cosine_topk(q, pb, k, prune=False),
-        }
-        bs, bi = baseline()
-        fs, fi = variants["fused_tokens"]()
-        same = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
+        variants, nbytes, same = {}, {}, None
+        if with_f32:
+            variants = {
+                "baseline_scores_amin_topk": baseline,
+                "fused_tokens": lambda: search.cosine_topk_tokens(q, tb, k, a.combine),
+                "fused_tokens_no_floor": lambda: search.cosine_topk_tokens(q, tb, k, a.combine, prune=False),
+                "one_vector_stream_same_bytes": lambda: search.cosine_topk(q, pb, k),
+                "one_vector_stream_no_floor": lambda: search.cosine_topk(q, pb, k, prune=False),
+            }
+            bs, bi = baseline()
+            fs, fi = variants["fused_tokens"]()
+            same = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
+        for name, lpb in lp_banks.items():
+            variants[f"fused_tokens[{name}]"] = lambda lpb=lpb: search.cosine_topk_tokens(q, lpb, k, a.combine)
+            variants[f"fused_tokens_no_floor[{name}]"] = lambda lpb=lpb: search.cosine_topk_tokens(q, lpb, k, a.combine, prune=False)
+            nbytes[f"fused_tokens[{name}]"] = nbytes[f"fused_tokens_no_floor[{name}]"] = elems * lpb.bank.element_size()
         times = {name: [] for name in variants}
         for it in range(a.warmup + a.iters):
             for name, fn in variants.items():                # interleaved: every variant once per round
@@ -78,9 +109,10 @@ def main():
         for name, ts in times.items():
             ts = sorted(ts)
             med = ts[len(ts) // 2]
+            nb = nbytes.get(name, elems * 4)
             results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, combine=a.combine, variant=name, ms_median=round(med, 4),
-                                ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), bank_bytes=nbytes,
-                                tb_per_s=round(nbytes / (med * 1e-3) / 1e12, 3), hbm_peak_fraction=round(nbytes / (med * 1e-3) / HBM_PEAK, 4),
+                                ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), bank_bytes=nb,
+                                tb_per_s=round(nb / (med * 1e-3) / 1e12, 3), hbm_peak_fraction=round(nb / (med * 1e-3) / HBM_PEAK, 4),
                                 fused_equals_baseline=same))
             print(json.dumps(results[-1]), flush=True)
     if a.out:
