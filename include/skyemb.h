@@ -512,6 +512,25 @@ int skyemb_cosine_token_topk_lp(const float *tw, const float *qn, const void *ba
 int skyemb_weighted_norms_lp(const void *x, int dtype, const float *w, float *norms, int64_t N, int D, void *stream);
 int skyemb_standardise_lp(const float *x, const float *mu, const float *sigma, void *out, int out_dtype, int64_t N, int D,
                           void *stream);
+/* Top-t combine (additive to ABI version 111: nothing above changes): the reference's n_top_sims.  Only the top_t best token
+ * scores of an image count.  With d[0] >= d[1] >= ... >= d[P-1] the image's token scores in descending order (-inf, which a
+ * NaN score ranks as, last -- torch.topk would rank NaN largest):
+ *   MAX   d[0], the plain MAX bit for bit (any top_t);
+ *   MIN   d[top_t-1]; top_t == P is the plain MIN bit for bit;
+ *   MEAN  (((0 + d[0]) + d[1]) + ... + d[top_t-1]) / (float)top_t: one fp32 rounding per add, LARGEST FIRST, one IEEE division,
+ *         NaN -> -inf.  Equal values are interchangeable, so the sum does not depend on how ties are ordered, nor on launch
+ *         geometry, Q or bank dtype.  top_t == P is NOT the plain MEAN, which sums in token order.
+ * An image with fewer than top_t scores above -inf gives -inf under MIN and MEAN and is never listed.
+ * top_t: 1 .. min(P, 16), or 0 = all tokens: then the call IS the plain call for that bank type (same kernel, same bits, one
+ * launch).  bank_dtype: SKYEMB_F32, SKYEMB_F16 or SKYEMB_BF16 (`bank` points to that element type).  Everything else -- shapes
+ * (skyemb_cosine_token_applicable), nlists (skyemb_cosine_token_topk_chunks), alignment, thr0, idx_offset, list format -- as
+ * for skyemb_cosine_token_scores / skyemb_cosine_token_topk.  A bad dtype, an unknown combine, a top_t out of range or a bad
+ * shape returns 1 before any launch with the cause as skyemb_last_error. */
+int skyemb_cosine_token_scores_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                   int64_t N, int P, int D, int combine, int top_t, float eps, float *scores, void *stream);
+int skyemb_cosine_token_topk_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                 int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset, int nlists,
+                                 const float *thr0, float *part_s, int64_t *part_i, void *stream);
 
 #ifdef __cplusplus
 }

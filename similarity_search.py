@@ -11,7 +11,9 @@ test set ONCE into a resident embedding bank and runs the fused cosine top-k ker
 instead of re-scoring streamed batches: one vector per sample with -mp True or -ct True, or, with both False, the
 patch tokens of every sample scored one by one and combined per image (-c min | mean | max) by the fused token kernel;
 ``--bank-dtype f16 | bf16`` keeps that token bank in 16 bits (half the memory and half the bytes per search; the standardised
-features are rounded once when stored).  Cosine metric only.
+features are rounded once when stored).  Cosine metric only.  ``-nts / --n_top_sims T`` (extension) combines only the T best
+patch scores of a sample (compute_similarity's n_top_sims): streamed without --bank, and with ``--bank -mp False -ct False``
+inside the fused token kernel (1 <= T <= min(patches, 16)).
 """
 import argparse
 import ast
@@ -50,6 +52,8 @@ def parseArguments():
     parser.add_argument("-ns", "--n_save", type=int, default=300)
     parser.add_argument("-dd", "--data_dir", help="Data directory if different from sky_embeddings/data/", type=str,
                         default=None)
+    parser.add_argument("-nts", "--n_top_sims", type=int, default=None,
+                        help="combine only the n best patch scores of a sample (-mp False -ct False)")
     parser.add_argument("--bank", action="store_true", help="encode once into a resident bank + fused top-k kernel")
     parser.add_argument("--bank-dtype", choices=sorted(BANK_DTYPES), default="f32",
                         help="element type of the resident patch-token bank (--bank -mp False -ct False)")
@@ -60,6 +64,8 @@ def main():
     args = parseArguments().parse_args()
     target_indices = ast.literal_eval(args.target_indices) if args.target_indices != 'None' else None
     max_pool, cls_token = str2bool(args.max_pool), str2bool(args.cls_token)
+    if (max_pool or cls_token) and args.n_top_sims not in (None, 1):
+        raise SystemExit("-mp True / -ct True score one vector per sample: --n_top_sims must be 1 or left out")
     snr_range = ast.literal_eval(args.snr_range)
     cur_dir = os.path.dirname(os.path.abspath(__file__))
     config_dir, model_dir = os.path.join(cur_dir, 'configs/'), os.path.join(cur_dir, 'models/')
@@ -132,7 +138,7 @@ def main():
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             avg, w = determine_target_features(tl)
             scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
-                                                    weights=w)
+                                                    weights=w, top_t=args.n_top_sims)
         test_scores, order = scores[0], idx[0].cpu().numpy()
         ds = test_dataloader.dataset
         items = [ds[int(j)] for j in order if j >= 0]
@@ -142,7 +148,7 @@ def main():
     else:
         test_images, test_latent, test_ra_decs, test_scores = mae_simsearch(
             model, target_latent, test_dataloader, device, metric=args.metric, combine=args.combine, use_weights=True,
-            max_pool=max_pool, cls_token=cls_token, nested_batches=False, n_save=args.n_save)
+            max_pool=max_pool, cls_token=cls_token, nested_batches=False, n_save=args.n_save, n_top_sims=args.n_top_sims)
     out = os.path.join(results_dir, f'{args.model_name}_{args.target_fn[:-3]}_simsearch_results_f.npz')
     np.savez(out, test_ra_decs=test_ra_decs.cpu().numpy(), test_scores=test_scores.cpu().numpy(),
              target_images=target_images.cpu().numpy(), target_features=target_latent.cpu().numpy(),

@@ -150,6 +150,11 @@ PROTOTYPES = {
                                             c_vp, c_vp, c_vp, c_vp]),
     "skyemb_weighted_norms_lp": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "skyemb_standardise_lp": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
+    # top-t combine (n_top_sims): additive again
+    "skyemb_cosine_token_scores_top": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp,
+                                               c_vp]),
+    "skyemb_cosine_token_topk_top": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
+                                             c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _LIB = None

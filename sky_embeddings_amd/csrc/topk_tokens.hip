@@ -15,6 +15,15 @@
 // Bank element type T: float, or bf16_t / f16_t for a half-precision resident bank (the `_lp` entry points).  A 16-bit row is
 // widened exactly on its way into the MFMA operands (mfma32_lp, topk_stream.h); everything after the load is the same code, so a
 // 16-bit bank gives the fp32 kernel's result on the widened bank bit for bit, for half the bytes.
+//
+// Top-t combine (TOPT, the `_top` entry points; the reference's n_top_sims): only the top_t (1 .. min(P, 16)) best token scores
+// of an image count.  d[0] >= d[1] >= ... the image's scores in descending order, -inf last: min = d[top_t-1],
+// mean = (((0 + d[0]) + d[1]) + ... + d[top_t-1]) / (float)top_t, largest first (NOT the plain mean's token order, also for
+// top_t == P); max is d[0], the plain max kernel.  The image's lane group sorts its scores with a bitonic network over
+// DPP lane permutes; a long image keeps its 16 best as one float per lane in `carry` (the plain combine's registers): per tile
+// max(carry[i], new[15 - i]) is the 16 largest of the union as a bitonic sequence, which a bitonic merge sorts again.  Equal
+// values are interchangeable, so neither result depends on how the network orders ties.  An image with fewer than top_t
+// scores above -inf gives -inf.  No LDS and no global scratch beyond the plain kernel's.
 #include "topk_stream.h"
 
 namespace {
@@ -41,16 +50,75 @@ __device__ __forceinline__ float combine_tile(float s, float carry, int lane, in
     return COMBINE == SKYEMB_COMBINE_MIN ? fminf(carry, v) : fmaxf(carry, v);
 }
 
+// the value of lane (lane ^ j), j in {1, 2, 4, 8, 15} (a constant once the callers' loops are unrolled), with every lane active:
+// DPP quad / row permutes and, for 4, a swizzle -- no address register, which __shfl_xor's bpermute would keep live per j
+__device__ __forceinline__ float lane_xor(float v, int j) {
+    const int x = __float_as_int(v);
+    switch (j) {
+    case 1: return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false));    // quad_perm:[1,0,3,2]
+    case 2: return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false));    // quad_perm:[2,3,0,1]
+    case 4: return __int_as_float(__builtin_amdgcn_ds_swizzle(x, 0x101F));                      // bit mode: and 0x1f, or 0, xor 4
+    case 8: return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false));   // row_ror:8
+    default: return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false));  // 15: row_mirror
+    }
+}
+
+// bitonic sort, descending, of the tp (1, 2, 4, 8 or 16) values an image's lane group holds; i = this lane's place in the group
+__device__ __forceinline__ float sort_desc(float v, int i, int tp) {
+#pragma unroll
+    for (int k = 2; k <= 16; k <<= 1) {
+        if (k <= tp) {                                              // wave-uniform
+#pragma unroll
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                const float u = lane_xor(v, j);
+                v = (((i & k) == 0) == ((i & j) == 0)) ? fmaxf(v, u) : fminf(v, u);   // k == tp: i & k == 0, every block descends
+            }
+        }
+    }
+    return v;
+}
+
+// bitonic merge, descending, of a bitonic sequence over the 16 lanes of a tile
+__device__ __forceinline__ float merge_desc16(float v, int i) {
+#pragma unroll
+    for (int j = 8; j > 0; j >>= 1) {
+        const float u = lane_xor(v, j);
+        v = (i & j) == 0 ? fmaxf(v, u) : fminf(v, u);
+    }
+    return v;
+}
+
+// top-t combine of one tile: -> the image's best min(P, 16) scores so far, descending over its lane group (`carry`: those of
+// the image's earlier tiles, unused on its first tile)
+__device__ __forceinline__ float top_tile(float s, float carry, int n_lane, int tp, bool first_tile) {
+    float v = sort_desc(s, n_lane & (tp - 1), tp);
+    if (!first_tile) v = merge_desc16(fmaxf(carry, lane_xor(v, 15)), n_lane);   // wave-uniform; only P >= 32 gets here
+    return v;
+}
+
+// the combined score from the sorted scores `v` of a finished image: lanes base .. base + top_t - 1 hold d[0] .. d[top_t-1]
+template <int COMBINE>
+__device__ __forceinline__ float top_finish(float v, int lane, int tp, int top_t) {
+    const int base = lane & ~(tp - 1);
+    if (COMBINE == SKYEMB_COMBINE_MIN) return __shfl(v, base + top_t - 1, 64);
+    float acc = 0.f;
+    for (int j = 0; j < top_t; ++j) acc = acc + __shfl(v, base + j, 64);
+    const float c = __fdiv_rn(acc, (float)top_t);
+    return c == c ? c : -INFINITY;
+}
+
 // LISTS: part_s / part_i [Q, nlists, k] as cosine_topk_stream_kernel writes them (idx = idx_offset + image).
 // !LISTS: scores [Q, n_img] combined scores.
-template <typename T, int WAVES, int COMBINE, bool LISTS>
-__global__ __launch_bounds__(WAVES * 64) void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
+// TOPT: the top-t combine with 1 <= top_t <= min(P, 16) (MIN and MEAN only); !TOPT ignores top_t.
+template <typename T, int WAVES, int COMBINE, bool LISTS, bool TOPT>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(TOPT && WAVES == 8 ? 4 : 1)))
+void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
                                                                   const T *__restrict__ bank, const float *__restrict__ xn,
                                                                   int Q, int64_t R, int P, int D, int k, float eps,
                                                                   int64_t idx_offset, int64_t rows_per_wave,
                                                                   float *__restrict__ part_s, int64_t *__restrict__ part_i,
                                                                   const float *__restrict__ thr0, float *__restrict__ scores,
-                                                                  int64_t n_img) {
+                                                                  int64_t n_img, int top_t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nchunk = D >> 4;
@@ -94,6 +162,7 @@ __global__ __launch_bounds__(WAVES * 64) void cosine_token_kernel(const float *_
         const f32x4 acc = stream_dot16(src, imgA, nchunk, lane);
         // C/D: col = lane&15 -> bank row n0 + n_lane, row = 4g + r -> query
         const float xnv = xn[row];
+        const bool first_tile = tile_in_image == 0;
         const bool last_tile = ++tile_in_image == tiles_per_image;
         if (last_tile) tile_in_image = 0;
         // the image's first lane speaks for it (a row past r_end belongs to an image past r_end)
@@ -102,11 +171,17 @@ __global__ __launch_bounds__(WAVES * 64) void cosine_token_kernel(const float *_
         for (int r = 0; r < 4; ++r) {
             const int q_mine = 4 * g + r;
             const float s = (row_ok && q_mine < Q) ? finish_score(acc[r], qn4[r], xnv, eps) : -INFINITY;
-            float c = combine_tile<COMBINE>(s, carry[r], lane, tp);
-            carry[r] = last_tile ? combine_start<COMBINE>() : c;
-            if (COMBINE == SKYEMB_COMBINE_MEAN && last_tile) {          // wave-uniform: the sum is complete
-                c = __fdiv_rn(c, fP);
-                c = c == c ? c : -INFINITY;
+            float c;
+            if (TOPT) {
+                carry[r] = top_tile(s, carry[r], n_lane, tp, first_tile);
+                c = last_tile ? top_finish<COMBINE>(carry[r], lane, tp, top_t) : -INFINITY;   // wave-uniform
+            } else {
+                c = combine_tile<COMBINE>(s, carry[r], lane, tp);
+                carry[r] = last_tile ? combine_start<COMBINE>() : c;
+                if (COMBINE == SKYEMB_COMBINE_MEAN && last_tile) {      // wave-uniform: the sum is complete
+                    c = __fdiv_rn(c, fP);
+                    c = c == c ? c : -INFINITY;
+                }
             }
             if (!LISTS) {
                 if (lead && q_mine < Q) scores[(int64_t)q_mine * n_img + (int64_t)((unsigned)(n0 + n_lane) / (unsigned)P)] = c;
@@ -173,21 +248,29 @@ bool combine_ok(int combine) { return combine == SKYEMB_COMBINE_MIN || combine =
 template <typename T, int WAVES, bool LISTS>
 int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
                   const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
-                  int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img) {
+                  int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
+                  int top_t) {
     auto go = [&](auto kern) {
         if (smem > 64 * 1024) {
             const int rc = sky_set_lds_limit((const void *)kern, LDS_BYTES, who);
             if (rc != 0) return rc;
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), smem, st, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
-                           rows_per_wave, part_s, part_i, thr0, scores, n_img);
+                           rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t);
         SKY_LAUNCH_CHECK(who);
         return 0;
     };
-    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS>);
-    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS>);
-    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS>);
+    // top_t == 0: all tokens, the plain kernels; max is d[0] for every top_t, the plain max kernel
+    if (top_t != 0 && combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true>);
+    if (top_t != 0 && combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true>);
+    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false>);
+    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false>);
+    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false>);
 }
+
+bool top_t_ok(int top_t, int P) { return top_t >= 0 && top_t <= (P < 16 ? P : 16); }
+
+#define TOP_T_MSG "top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)"
 
 }  // namespace
 
@@ -218,11 +301,12 @@ extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, i
 // Argument checks and launch geometry of the two calls, for every bank element type (`who`: the entry point's name in error texts).
 template <typename T>
 int token_topk(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D, int k,
-               int combine, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i,
+               int combine, int top_t, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i,
                void *stream) {
     SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "%s: bad arguments", who);
     SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
     SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
+    SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
     SKY_CHECK_ARG(N * P < (1ll << 31), "%s: shard too large (N * P < 2^31 rows per call)", who);
     SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
                   who);
@@ -233,17 +317,18 @@ int token_topk(const char *who, const float *tw, const float *qn, const T *bank,
     const size_t smem = image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
     if (waves == 8)
         return launch_tokens<T, 8, true>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                         idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
+                                         idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t);
     return launch_tokens<T, 4, true>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                     idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N);
+                                     idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t);
 }
 
 template <typename T>
 int token_scores(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D,
-                 int combine, float eps, float *scores, void *stream) {
+                 int combine, int top_t, float eps, float *scores, void *stream) {
     SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "%s: bad arguments", who);
     SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, 1);
     SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
+    SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
     SKY_CHECK_ARG(N * P < (1ll << 31), "%s: bank too large (N * P < 2^31 rows per call)", who);
     SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
     const int64_t R = N * P, unit = image_unit(P);
@@ -251,19 +336,19 @@ int token_scores(const char *who, const float *tw, const float *qn, const T *ban
     if (blocks > 2048) blocks = 2048;
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, blocks * 4), unit) * unit;
     return launch_tokens<T, 4, false>(combine, (int)blocks, image_bytes(D), (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, 1,
-                                      eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N);
+                                      eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N, top_t);
 }
 
 extern "C" int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
                                         int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
                                         const float *thr0, float *part_s, int64_t *part_i, void *stream) {
-    return token_topk("skyemb_cosine_token_topk", tw, qn, bank, xn, Q, N, P, D, k, combine, eps, idx_offset, nlists, thr0, part_s,
+    return token_topk("skyemb_cosine_token_topk", tw, qn, bank, xn, Q, N, P, D, k, combine, 0, eps, idx_offset, nlists, thr0, part_s,
                       part_i, stream);
 }
 
 extern "C" int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
                                           int P, int D, int combine, float eps, float *scores, void *stream) {
-    return token_scores("skyemb_cosine_token_scores", tw, qn, bank, xn, Q, N, P, D, combine, eps, scores, stream);
+    return token_scores("skyemb_cosine_token_scores", tw, qn, bank, xn, Q, N, P, D, combine, 0, eps, scores, stream);
 }
 
 // Half-precision resident banks: the same two calls on a bf16 / fp16 bank (include/skyemb.h).  The dtype is checked first, so a
@@ -276,9 +361,9 @@ extern "C" int skyemb_cosine_token_topk_lp(const float *tw, const float *qn, con
     const char *who = "skyemb_cosine_token_topk_lp";
     SKY_CHECK_ARG(sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_lp: " LP_DTYPE_MSG, bank_dtype);
     if (bank_dtype == SKYEMB_BF16)
-        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, eps, idx_offset, nlists, thr0, part_s, part_i,
+        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, 0, eps, idx_offset, nlists, thr0, part_s, part_i,
                           stream);
-    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, eps, idx_offset, nlists, thr0, part_s, part_i,
+    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, 0, eps, idx_offset, nlists, thr0, part_s, part_i,
                       stream);
 }
 
@@ -286,6 +371,37 @@ extern "C" int skyemb_cosine_token_scores_lp(const float *tw, const float *qn, c
                                              int Q, int64_t N, int P, int D, int combine, float eps, float *scores, void *stream) {
     const char *who = "skyemb_cosine_token_scores_lp";
     SKY_CHECK_ARG(sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_lp: " LP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_BF16) return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, eps, scores, stream);
-    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, eps, scores, stream);
+    if (bank_dtype == SKYEMB_BF16) return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, 0, eps, scores, stream);
+    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, 0, eps, scores, stream);
+}
+
+// Top-t combine (include/skyemb.h): one pair of calls for the three bank element types.  top_t == 0 is the plain call of that
+// type: the same checks, the same kernel, the same launch.
+#define TOP_DTYPE_MSG "bank_dtype must be SKYEMB_BF16 (0), SKYEMB_F32 (1) or SKYEMB_F16 (2), got %d"
+
+extern "C" int skyemb_cosine_token_topk_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                            int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset,
+                                            int nlists, const float *thr0, float *part_s, int64_t *part_i, void *stream) {
+    const char *who = "skyemb_cosine_token_topk_top";
+    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_top: " TOP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_F32)
+        return token_topk(who, tw, qn, (const float *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
+                          part_i, stream);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
+                          part_i, stream);
+    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s, part_i,
+                      stream);
+}
+
+extern "C" int skyemb_cosine_token_scores_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn,
+                                              int Q, int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
+                                              void *stream) {
+    const char *who = "skyemb_cosine_token_scores_top";
+    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_top: " TOP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_F32)
+        return token_scores(who, tw, qn, (const float *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
+    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
 }

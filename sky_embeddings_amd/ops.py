@@ -453,10 +453,16 @@ def cosine_token_topk_chunks(N, P, Q, D, k):
     return lib().skyemb_cosine_token_topk_chunks(N, P, Q, D, k)
 
 
-def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores):
-    """bank [N, P, D] fp32, fp16 or bf16, xn [N * P], combine: a COMBINE_* code -> scores [Q, N]."""
+def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores, top_t=0):
+    """bank [N, P, D] fp32, fp16 or bf16, xn [N * P], combine: a COMBINE_* code -> scores [Q, N].  top_t: 0 = all tokens (the
+    plain calls), else only the top_t best token scores of an image count (skyemb_cosine_token_scores_top)."""
     Q, D = tw.shape
     N, P = bank.shape[0], bank.shape[1]
+    if top_t != 0:
+        check(lib().skyemb_cosine_token_scores_top(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_scores"), _p(xn),
+                                                   Q, N, P, D, combine, top_t, eps, _p(scores), _stream()),
+              "skyemb_cosine_token_scores_top")
+        return
     if bank.dtype != torch.float32:
         check(lib().skyemb_cosine_token_scores_lp(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_scores"), _p(xn),
                                                   Q, N, P, D, combine, eps, _p(scores), _stream()), "skyemb_cosine_token_scores_lp")
@@ -465,9 +471,14 @@ def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores):
           "skyemb_cosine_token_scores")
 
 
-def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None):
+def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None, top_t=0):
     Q, D = tw.shape
     N, P = bank.shape[0], bank.shape[1]
+    if top_t != 0:
+        check(lib().skyemb_cosine_token_topk_top(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_topk"), _p(xn), Q,
+                                                 N, P, D, k, combine, top_t, eps, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i),
+                                                 _stream()), "skyemb_cosine_token_topk_top")
+        return
     if bank.dtype != torch.float32:
         check(lib().skyemb_cosine_token_topk_lp(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_topk"), _p(xn), Q, N,
                                                 P, D, k, combine, eps, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i), _stream()),

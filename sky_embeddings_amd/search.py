@@ -237,23 +237,35 @@ def _combine_code(combine, who):
     return ops.COMBINE_CODES[combine]
 
 
-def _token_scores(tw, qn, tokens, norms, code, eps):
+def _top_t_arg(top_t, P, who):
+    """``top_t`` (None: all tokens) -> the library's argument (0: all tokens); ValueError outside 1 .. min(P, 16)."""
+    if top_t is None:
+        return 0
+    if isinstance(top_t, bool) or int(top_t) != top_t or not 1 <= top_t <= min(P, 16):
+        raise ValueError(f"{who}: top_t = {top_t!r}, expected None (all tokens) or an integer 1 .. min(P, 16) = {min(P, 16)} (P = {P})")
+    return int(top_t)
+
+
+def _token_scores(tw, qn, tokens, norms, code, eps, top_t=0):
     """[Q, N] combined scores of Q <= 16 prepared queries."""
     out = torch.empty(tw.shape[0], tokens.shape[0], device=tw.device)
-    ops.cosine_token_scores(tw, qn, tokens, norms, code, eps, out)
+    ops.cosine_token_scores(tw, qn, tokens, norms, code, eps, out, top_t)
     return out
 
 
-def token_pruning_floor(tw, qn, tb: "TokenBank", k: int, combine: str = 'min', eps: float = 1e-6, sample_images: int | None = None):
+def token_pruning_floor(tw, qn, tb: "TokenBank", k: int, combine: str = 'min', eps: float = 1e-6, sample_images: int | None = None,
+                        top_t: int | None = None):
     """Per-query floor for the token search: the k-th best COMBINED score over a sample of whole images, one ulp lower
-    (``pruning_floor``'s argument, with images for rows).  None under the same size rule: N < 8 x the sample."""
+    (``pruning_floor``'s argument, with images for rows).  None under the same size rule: N < 8 x the sample.  ``top_t``: the
+    search's own, so that the sample is scored as the search scores it and the floor stays a lower bound of its k-th best."""
+    t = _top_t_arg(top_t, tb.bank.shape[1], "token_pruning_floor")
     N = tb.bank.shape[0]
     if sample_images is None:
         sample_images = 256 * k
     if N < 8 * sample_images:
         return None
     st, sn = tb.sample(sample_images)
-    sc = _token_scores(tw, qn, st, sn, _combine_code(combine, "token_pruning_floor"), eps)
+    sc = _token_scores(tw, qn, st, sn, _combine_code(combine, "token_pruning_floor"), eps, t)
     floor = torch.empty(tw.shape[0], device=tw.device)
     ops.kth_largest_floor(sc, k, floor)
     return floor
@@ -266,19 +278,28 @@ def _check_token_shape(who, Q, P, D, k):
 
 
 def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min', weights: torch.Tensor | None = None,
-                       eps: float = 1e-6, process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None):
+                       eps: float = 1e-6, process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None,
+                       top_t: int | None = None):
     """-> (scores f32 [Q,k], image indices i64 [Q,k]): exact top-k images by the combined score of their P patch tokens
     (reference: compute_similarity with max_pool = False, utils/similarity.py:214-268, + update_best_scores), order
     (score desc, image asc).  ``bank`` is a [N,P,D] tensor (fp32, or fp16 / bf16: see TokenBank) or a TokenBank (this rank's
     shard of images; ``idx_offset`` = first global image of the shard).  One pass over the bank per group of at most 16 queries (Q > 16 runs ceil(Q / 16) passes: a
     many-query prefilter for token banks is out of scope).  Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
-    carries its own (``TokenBank.set_weights``), and the argument is then ignored, as ``cosine_topk`` does with a PreparedBank."""
+    carries its own (``TokenBank.set_weights``), and the argument is then ignored, as ``cosine_topk`` does with a PreparedBank.
+
+    ``top_t`` (the reference's ``n_top_sims``; None: all tokens, the search above unchanged): an integer 1 .. min(P, 16); only
+    the top_t best token scores of an image count.  With d[0] >= d[1] >= ... the image's scores in descending order (-inf, which
+    a NaN score ranks as, last -- torch.topk would rank NaN largest): max is d[0] (unchanged), min is d[top_t-1], mean is
+    (((0 + d[0]) + d[1]) + ... + d[top_t-1]) / float32(top_t), summed largest first.  ``top_t == P`` with 'min' is the plain min
+    bit for bit; with 'mean' it is NOT the plain mean, which sums in token order.  An image with fewer than top_t scores above
+    -inf scores -inf under min and mean and is never returned.  ValueError outside the range, before the first launch."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
     N, P = tokens.shape[0], tokens.shape[1]
     assert tokens.dim() == 3 and D == tokens.shape[2]
     code = _combine_code(combine, "cosine_topk_tokens")
+    t = _top_t_arg(top_t, P, "cosine_topk_tokens")
     if k < 1:
         raise ValueError(f"cosine_topk_tokens: k = {k}")
     if world_size == 1 and k > N:
@@ -295,15 +316,17 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     for lo in range(0, Q, 16):
         tw, qn = tw_all[lo:lo + 16], qn_all[lo:lo + 16]
         Qg = tw.shape[0]
-        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps) if prune else None
+        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps, top_t=top_t) if prune else None
         pruned = pruned or thr0 is not None
         nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
         ps = torch.empty(Qg, nl, k, device=q.device)
         pi = torch.empty(Qg, nl, k, device=q.device, dtype=torch.int64)
-        ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, tb.idx_offset, nl, ps, pi, thr0)
+        ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, tb.idx_offset, nl, ps, pi, thr0, t)
         ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + 16], out_i[lo:lo + 16], torch.empty(Qg, device=q.device, dtype=torch.int32))
     if stats is not None:
         stats.update(path="tokens", groups=(Q + 15) // 16, pruned=pruned)
+        if top_t is not None:
+            stats.update(top_t=t)
     if world_size > 1:
         from .distributed import gather_topk
         gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
@@ -311,14 +334,18 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     return out_s, out_i
 
 
-def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weights: torch.Tensor | None = None, eps: float = 1e-6):
+def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weights: torch.Tensor | None = None, eps: float = 1e-6,
+                        top_t: int | None = None):
     """[Q, N] combined score of every image of a [N,P,D] token bank (fp32, fp16 or bf16; or a TokenBank), in groups of at most
     16 queries.
-    ``weights`` is ignored when ``bank`` is a TokenBank (it carries its own)."""
+    ``weights`` is ignored when ``bank`` is a TokenBank (it carries its own).  ``top_t``: as for ``cosine_topk_tokens`` (None:
+    all tokens; else only the top_t best token scores of an image count, mean summed largest first -- so 'mean' with
+    ``top_t == P`` is not the plain mean)."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
     assert tokens.dim() == 3 and D == tokens.shape[2]
     code = _combine_code(combine, "cosine_token_scores")
+    t = _top_t_arg(top_t, tokens.shape[1], "cosine_token_scores")
     _check_token_shape("cosine_token_scores", Q, tokens.shape[1], D, 1)
     tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
     q = queries.to(tb.bank.device, torch.float32).contiguous()
@@ -327,5 +354,5 @@ def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weigh
         return out
     tw, qn = prepare_queries(q, tb.weights)
     for lo in range(0, Q, 16):
-        out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps)
+        out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps, t)
     return out

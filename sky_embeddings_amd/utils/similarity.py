@@ -159,10 +159,12 @@ def _pick_tokens(latent, num_extra_tokens, cls_token, max_pool):
 
 
 def mae_simsearch(model, target_latent, dataloader, device, n_batches=None, metric='cosine', combine='min',
-                  use_weights=True, max_pool=False, cls_token=False, nested_batches=True, n_save=256, verbose=100):
+                  use_weights=True, max_pool=False, cls_token=False, nested_batches=True, n_save=256, verbose=100,
+                  n_top_sims=None):
     """utils/similarity.py:37-132: stream the test set through the encoder, score every batch against the
     target set, keep the best ``n_save``; returns (samples, latents, ra_decs, scores).  ``n_batches`` limits
-    flat loaders only, as in the reference."""
+    flat loaders only, as in the reference.  ``n_top_sims`` (extension: the reference's driver does not pass it on) goes to
+    ``compute_similarity``: only the n_top_sims best patch scores of a sample are combined."""
     net = getattr(model, 'module', model)
     model.eval()
     limit = None if nested_batches else (len(dataloader) if n_batches is None else n_batches)
@@ -187,7 +189,7 @@ def mae_simsearch(model, target_latent, dataloader, device, n_batches=None, metr
             rows = feats.reshape(-1, feats.shape[-1]).to(torch.float32).contiguous()
             feats = search.standardise_(rows, *scale).view(feats.shape)
             pool.push(samples, ra_decs, compute_similarity(target, feats, metric=metric, combine=combine,
-                                                           use_weights=use_weights))
+                                                           use_weights=use_weights, n_top_sims=n_top_sims))
             if verbose and seen % verbose == 0:
                 print(f'  {seen} batches scored, {(time.time() - started) / seen:0.3f} s per batch', end='\r')
             if limit is not None and seen >= limit:

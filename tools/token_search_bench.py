@@ -5,9 +5,13 @@ one-vector streaming top-k over a bank of the same byte size.  HIP-event timing,
 
 usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim 768] [--k 100] [--iters 10] [--out FILE]
                                          [--bank-dtype f32 | f16 | bf16 | a comma list, e.g. f32,f16,bf16]
+                                         [--combine min | mean | max | a comma list] [--top-t T | a comma list, e.g. 4,16]
 --bank-dtype: element type(s) of the resident token bank the fused pass runs on (16-bit banks: the fp32 bank rounded to nearest);
 the fused variants of every listed type run interleaved in the same rounds, named fused_tokens[f16] etc.; the comparison variants
 (baseline and one-vector) need the fp32 bank and run when f32 is listed.
+--top-t: for every listed T and every listed bank type the fused pass with top_t=T (fused_tokens_top4 etc.: only the T best
+token scores of an image count) and, with f32 listed, the unfused route to the same result (unfused_top4: cosine_scores over the
+token rows, torch.topk over the P scores of every image, the reduce, torch.topk), in the same interleaved rounds.
 "fused_equals_baseline" compares the fused result with the baseline's torch.topk, whose order among equal scores is unspecified:
 False may come from exact ties alone and is not by itself a mismatch (the tests compare against the CPU restatement).
 Bytes counted per pass: images x tokens x dim x element size (the bank; norms and lists are under 0.4 % of it).  Peak: 8.0 TB/s
@@ -33,6 +37,23 @@ def bank_dtypes(text):
     return names
 
 
+def int_list(text):
+    try:
+        vals = [int(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        vals = []
+    if not vals or min(vals) < 1:
+        raise argparse.ArgumentTypeError(f"expected a positive integer or a comma list of them, got {text!r}")
+    return vals
+
+
+def combines(text):
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    if not names or any(n not in ("min", "mean", "max") for n in names):
+        raise argparse.ArgumentTypeError(f"expected min, mean, max or a comma list of them, got {text!r}")
+    return names
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=250_000)
@@ -41,7 +62,8 @@ def main():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--combine", default="min")
+    ap.add_argument("--combine", type=combines, default=["min"])
+    ap.add_argument("--top-t", type=int_list, default=[])
     ap.add_argument("--out", default=None)
     ap.add_argument("--bank-dtype", type=bank_dtypes, default=["f32"])
     a = ap.parse_args()
@@ -70,32 +92,51 @@ def main():
         chunks = [search.PreparedBank(rows[s:s + chunk], w) for s in range(0, N * P, chunk)]
     else:
         del bank, rows
-    reduce = {"min": torch.amin, "max": torch.amax, "mean": torch.mean}[a.combine]
+    reducers = {"min": torch.amin, "max": torch.amax, "mean": torch.mean}
     elems = N * P * D
     results = []
     for Q in (1, 16):
         q = torch.randn(Q, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2025 + Q))
 
-        def baseline():
-            parts = [reduce(search.cosine_scores(q, c).view(Q, -1, P), dim=2) for c in chunks]
+        def baseline(combine, top_t=None):
+            parts = []
+            for c in chunks:
+                sc = search.cosine_scores(q, c).view(Q, -1, P)
+                if top_t is not None:
+                    sc = torch.topk(sc, top_t, dim=2).values
+                parts.append(reducers[combine](sc, dim=2))
             return torch.topk(torch.cat(parts, dim=1), k, dim=1)
 
-        variants, nbytes, same = {}, {}, None
-        if with_f32:
-            variants = {
-                "baseline_scores_amin_topk": baseline,
-                "fused_tokens": lambda: search.cosine_topk_tokens(q, tb, k, a.combine),
-                "fused_tokens_no_floor": lambda: search.cosine_topk_tokens(q, tb, k, a.combine, prune=False),
-                "one_vector_stream_same_bytes": lambda: search.cosine_topk(q, pb, k),
-                "one_vector_stream_no_floor": lambda: search.cosine_topk(q, pb, k, prune=False),
-            }
-            bs, bi = baseline()
-            fs, fi = variants["fused_tokens"]()
-            same = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
-        for name, lpb in lp_banks.items():
-            variants[f"fused_tokens[{name}]"] = lambda lpb=lpb: search.cosine_topk_tokens(q, lpb, k, a.combine)
-            variants[f"fused_tokens_no_floor[{name}]"] = lambda lpb=lpb: search.cosine_topk_tokens(q, lpb, k, a.combine, prune=False)
-            nbytes[f"fused_tokens[{name}]"] = nbytes[f"fused_tokens_no_floor[{name}]"] = elems * lpb.bank.element_size()
+        variants, nbytes, same, combine_of = {}, {}, {}, {}
+        for combine in a.combine:
+            tag = "" if len(a.combine) == 1 else f"/{combine}"
+            mine = {}
+            if with_f32:
+                mine = {
+                    "baseline_scores_amin_topk": lambda c=combine: baseline(c),
+                    "fused_tokens": lambda c=combine: search.cosine_topk_tokens(q, tb, k, c),
+                    "fused_tokens_no_floor": lambda c=combine: search.cosine_topk_tokens(q, tb, k, c, prune=False),
+                }
+                if combine == a.combine[0]:
+                    mine["one_vector_stream_same_bytes"] = lambda: search.cosine_topk(q, pb, k)
+                    mine["one_vector_stream_no_floor"] = lambda: search.cosine_topk(q, pb, k, prune=False)
+                for t in a.top_t:
+                    mine[f"unfused_top{t}"] = lambda c=combine, t=t: baseline(c, t)
+                    mine[f"fused_tokens_top{t}"] = lambda c=combine, t=t: search.cosine_topk_tokens(q, tb, k, c, top_t=t)
+                bs, bi = baseline(combine)
+                fs, fi = mine["fused_tokens"]()
+                same[combine] = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
+            for name, lpb in lp_banks.items():
+                lp = {f"fused_tokens[{name}]": lambda lpb=lpb, c=combine: search.cosine_topk_tokens(q, lpb, k, c),
+                      f"fused_tokens_no_floor[{name}]": lambda lpb=lpb, c=combine: search.cosine_topk_tokens(q, lpb, k, c, prune=False)}
+                for t in a.top_t:
+                    lp[f"fused_tokens_top{t}[{name}]"] = lambda lpb=lpb, c=combine, t=t: search.cosine_topk_tokens(q, lpb, k, c, top_t=t)
+                for v in lp:
+                    nbytes[v + tag] = elems * lpb.bank.element_size()
+                mine.update(lp)
+            for v, fn in mine.items():
+                variants[v + tag] = fn
+                combine_of[v + tag] = combine
         times = {name: [] for name in variants}
         for it in range(a.warmup + a.iters):
             for name, fn in variants.items():                # interleaved: every variant once per round
@@ -110,10 +151,10 @@ def main():
             ts = sorted(ts)
             med = ts[len(ts) // 2]
             nb = nbytes.get(name, elems * 4)
-            results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, combine=a.combine, variant=name, ms_median=round(med, 4),
+            results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, combine=combine_of[name], variant=name, ms_median=round(med, 4),
                                 ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), bank_bytes=nb,
                                 tb_per_s=round(nb / (med * 1e-3) / 1e12, 3), hbm_peak_fraction=round(nb / (med * 1e-3) / HBM_PEAK, 4),
-                                fused_equals_baseline=same))
+                                fused_equals_baseline=same.get(combine_of[name])))
             print(json.dumps(results[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
