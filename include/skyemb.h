@@ -531,6 +531,24 @@ int skyemb_cosine_token_scores_top(const float *tw, const float *qn, const void 
 int skyemb_cosine_token_topk_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
                                  int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset, int nlists,
                                  const float *thr0, float *part_s, int64_t *part_i, void *stream);
+/* Selection (additive to ABI version 111: nothing above changes): the `_top` calls restricted to a selection of the bank's
+ * images.  `select` is a packed bitmask on the device: bit (i & 31) of 32-bit word (i >> 5) is image i, ceil(N / 32) words, the
+ * padding bits of the last word zero (skyemb_pack_select writes exactly that); it is only read.  The result is that of the same
+ * call over the compacted bank (the selected images in their order), every image index mapped back to the whole bank and then
+ * offset by idx_offset: scores bit-equal, order (score desc, image asc).  Deselected images contribute nothing -- a NaN or inf in
+ * their tokens changes no output -- and, for 16 | P, none of their rows or norms is loaded (P | 16: a 16-row tile is passed over
+ * when every image in it is deselected).  skyemb_cosine_token_scores_sel writes all [Q, N] slots: -inf for a deselected image.
+ * Fewer than k selected images: the lists end with the (-inf, -1) terminator as ever.  Launch geometry, nlists and every limit
+ * are those of the whole bank; one selection serves all queries of the call.  select == NULL IS the `_top` call.  Refusals
+ * before any launch: those of the `_top` calls, and a `select` that is not 4-byte aligned.
+ *   skyemb_pack_select   flags u8 [N] on the device (non-zero = selected) -> words u32 [ceil(N / 32)]; one short launch. */
+int skyemb_cosine_token_scores_sel(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                   int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
+                                   const uint32_t *select, void *stream);
+int skyemb_cosine_token_topk_sel(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                 int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset, int nlists,
+                                 const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
+int skyemb_pack_select(const uint8_t *flags, int64_t N, uint32_t *words, void *stream);
 
 #ifdef __cplusplus
 }

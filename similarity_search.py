@@ -13,7 +13,13 @@ patch tokens of every sample scored one by one and combined per image (-c min | 
 ``--bank-dtype f16 | bf16`` keeps that token bank in 16 bits (half the memory and half the bytes per search; the standardised
 features are rounded once when stored).  Cosine metric only.  ``-nts / --n_top_sims T`` (extension) combines only the T best
 patch scores of a sample (compute_similarity's n_top_sims): streamed without --bank, and with ``--bank -mp False -ct False``
-inside the fused token kernel (1 <= T <= min(patches, 16)).
+inside the fused token kernel (1 <= T <= min(patches, 16)).  ``--bank-select-snr`` (extension, only with ``--bank``) encodes
+EVERY row of the test file once and turns the ``-snr`` window into a selection of the resident bank (search.Selection) instead
+of filtering before the encoder: another S/N range is then another search over the same bank, not another encoding.  The
+standardisation statistics are those of the first ``-bs`` SELECTED images (the reference's first batch of the filtered set; for
+a 16-bit bank those images are encoded first to get them), results are looked up in the full test file.  It works in all three
+--bank modes; the pooled ones (-mp True / -ct True) then run as the token search with one token per sample, under its limits:
+-ns <= 512 and a feature width that is a multiple of 64, at most 1024.
 """
 import argparse
 import ast
@@ -57,6 +63,8 @@ def parseArguments():
     parser.add_argument("--bank", action="store_true", help="encode once into a resident bank + fused top-k kernel")
     parser.add_argument("--bank-dtype", choices=sorted(BANK_DTYPES), default="f32",
                         help="element type of the resident patch-token bank (--bank -mp False -ct False)")
+    parser.add_argument("--bank-select-snr", action="store_true",
+                        help="with --bank: encode every test row once and apply -snr as a selection of the resident bank")
     return parser
 
 
@@ -66,6 +74,8 @@ def main():
     max_pool, cls_token = str2bool(args.max_pool), str2bool(args.cls_token)
     if (max_pool or cls_token) and args.n_top_sims not in (None, 1):
         raise SystemExit("-mp True / -ct True score one vector per sample: --n_top_sims must be 1 or left out")
+    if args.bank_select_snr and not args.bank:
+        raise SystemExit("--bank-select-snr selects images of the resident bank: it needs --bank")
     snr_range = ast.literal_eval(args.snr_range)
     cur_dir = os.path.dirname(os.path.abspath(__file__))
     config_dir, model_dir = os.path.join(cur_dir, 'configs/'), os.path.join(cur_dir, 'models/')
@@ -101,7 +111,9 @@ def main():
                   patch_size=int(mae_config['ARCHITECTURE']['patch_size']),
                   num_channels=int(mae_config['ARCHITECTURE']['num_channels']), max_mask_ratio=None, shuffle=False)
     target_dataloader = build_h5_dataloader(os.path.join(data_dir, args.target_fn), indices=target_indices, **common)
-    test_dataloader = build_h5_dataloader(os.path.join(data_dir, args.test_fn), indices=test_indices, **common)
+    # --bank-select-snr: every row is encoded, the S/N window becomes a selection of the bank
+    test_dataloader = build_h5_dataloader(os.path.join(data_dir, args.test_fn),
+                                          indices=None if args.bank_select_snr else test_indices, **common)
     target_latent, target_images = mae_latent(model, target_dataloader, device, return_images=True,
                                               apply_augmentations=str2bool(args.augment_targets), num_augmentations=64,
                                               remove_cls=False)
@@ -114,31 +126,46 @@ def main():
         mod = model.module
         tl = target_latent.to(device)
         k = args.n_save
+        select, first_rows = None, slice(args.batch_size)
+        if args.bank_select_snr:
+            flags = torch.zeros(len(test_snr), dtype=torch.bool)
+            flags[torch.from_numpy(test_indices)] = True
+            select = search.Selection(flags, device)
+            first_rows = torch.from_numpy(test_indices[:args.batch_size]).to(device)   # the first batch of the filtered set
+            print(f'Selection: {select.count} of {select.N} test images inside the S/N window')
+            if select.count == 0:
+                raise SystemExit(f"--bank-select-snr: no test image has an S/N inside {snr_range}: nothing to search")
+            k = min(k, select.count)         # the saved arrays line up: no (-inf, -1) tail
         if max_pool or cls_token:                # one vector per sample
             tl = tl[:, :1] if cls_token else tl[:, mod.num_extra_tokens:].max(dim=1, keepdim=True).values
             bank = build_embedding_bank(model, test_dataloader, device, pool='cls' if cls_token else 'max')
-            first = bank[:args.batch_size]   # the reference standardises with the first batch (utils/similarity.py:98-100)
+            first = bank[first_rows]         # the reference standardises with the first batch (utils/similarity.py:98-100)
             mean_feats, std_feats = first.mean(dim=0), first.std(dim=0, unbiased=True)
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             search.standardise_(bank, mean_feats, std_feats)
             avg, w = determine_target_features(tl)
-            scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w)
+            scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w, select=select)
         else:                                    # every patch token scored, combined per image (-c min | mean | max)
             tl = tl[:, mod.num_extra_tokens:]
             if args.bank_dtype == "f32":
                 bank = build_embedding_bank(model, test_dataloader, device, pool='tokens')
-                first = bank[:args.batch_size]   # mean / unbiased std over (batch, patch) of the first batch (utils/similarity.py:98-100)
+                first = bank[first_rows]         # mean / unbiased std over (batch, patch) of the first batch (utils/similarity.py:98-100)
                 mean_feats, std_feats = first.mean(dim=(0, 1)), first.std(dim=(0, 1), unbiased=True)
                 search.standardise_(bank.view(-1, bank.shape[2]), mean_feats, std_feats)
             else:                                # the same statistics; every batch standardised, rounded once and kept in 16 bits
+                stats = None
+                if select is not None:           # the first batch of the filtered set is encoded first, for its statistics
+                    head = build_h5_dataloader(os.path.join(data_dir, args.test_fn), indices=test_indices[:args.batch_size], **common)
+                    first = build_embedding_bank(model, head, device, pool='tokens', n_batches=1)
+                    stats = (first.mean(dim=(0, 1)), first.std(dim=(0, 1), unbiased=True))
                 bank, mean_feats, std_feats = build_embedding_bank(model, test_dataloader, device, pool='tokens',
                                                                    bank_dtype=BANK_DTYPES[args.bank_dtype],
-                                                                   standardise_with_first_batch=True)
+                                                                   standardise_with_first_batch=True, standardise_stats=stats)
             print(f'Token bank: {bank.numel() * bank.element_size() / 1e9:.3f} GB, {bank.dtype}')
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             avg, w = determine_target_features(tl)
             scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
-                                                    weights=w, top_t=args.n_top_sims)
+                                                    weights=w, top_t=args.n_top_sims, select=select)
         test_scores, order = scores[0], idx[0].cpu().numpy()
         ds = test_dataloader.dataset
         items = [ds[int(j)] for j in order if j >= 0]

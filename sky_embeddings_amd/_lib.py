@@ -155,6 +155,12 @@ PROTOTYPES = {
                                                c_vp]),
     "skyemb_cosine_token_topk_top": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
                                              c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    # selection of images (a packed bitmask): additive again
+    "skyemb_cosine_token_scores_sel": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp,
+                                               c_vp, c_vp]),
+    "skyemb_cosine_token_topk_sel": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
+                                             c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_pack_select": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
 }
 
 _LIB = None

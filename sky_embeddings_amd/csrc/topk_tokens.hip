@@ -24,6 +24,16 @@
 // max(carry[i], new[15 - i]) is the 16 largest of the union as a bitonic sequence, which a bitonic merge sorts again.  Equal
 // values are interchangeable, so neither result depends on how the network orders ties.  An image with fewer than top_t
 // scores above -inf gives -inf.  No LDS and no global scratch beyond the plain kernel's.
+//
+// Selection (SEL, the `_sel` entry points): a packed bitmask over the images (bit i & 31 of 32-bit word i >> 5 is image i,
+// ceil(N / 32) words, padding bits zero; skyemb_pack_select builds it) restricts the search to the images whose bit is set: the
+// result is that of the compacted bank, image indices mapped back.  The decision is per wave (a counter of images and the mask word of
+// the current 32 images live in scalar registers; the word is loaded by every lane once per 32 images and made scalar with
+// readfirstlane), so nothing diverges.  16 | P: an image whose bit is clear is passed over whole -- none of its
+// P / 16 tiles, neither rows nor norms, is loaded.  P | 16: a tile holds the 16 / P neighbouring images n0 / P ..., whose bits lie
+// in one word (n0 / P is a multiple of 16 / P, which divides 32); the tile is passed over when all are clear, else it is scored
+// as ever and the lead lanes of the deselected images stay out of the candidate ballot.  Whole images are skipped, so `carry` and
+// `tile_in_image` are untouched.  The !LISTS kernel writes -inf for every deselected image.  The mask is only read.
 #include "topk_stream.h"
 
 namespace {
@@ -110,15 +120,16 @@ __device__ __forceinline__ float top_finish(float v, int lane, int tp, int top_t
 // LISTS: part_s / part_i [Q, nlists, k] as cosine_topk_stream_kernel writes them (idx = idx_offset + image).
 // !LISTS: scores [Q, n_img] combined scores.
 // TOPT: the top-t combine with 1 <= top_t <= min(P, 16) (MIN and MEAN only); !TOPT ignores top_t.
-template <typename T, int WAVES, int COMBINE, bool LISTS, bool TOPT>
-__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(TOPT && WAVES == 8 ? 4 : 1)))
+// SEL: only the images whose bit in `sel` is set take part; !SEL ignores sel.
+template <typename T, int WAVES, int COMBINE, bool LISTS, bool TOPT, bool SEL>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu((TOPT || SEL) && WAVES == 8 ? 4 : 1)))
 void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
                                                                   const T *__restrict__ bank, const float *__restrict__ xn,
                                                                   int Q, int64_t R, int P, int D, int k, float eps,
                                                                   int64_t idx_offset, int64_t rows_per_wave,
                                                                   float *__restrict__ part_s, int64_t *__restrict__ part_i,
                                                                   const float *__restrict__ thr0, float *__restrict__ scores,
-                                                                  int64_t n_img, int top_t) {
+                                                                  int64_t n_img, int top_t, const uint32_t *__restrict__ sel) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nchunk = D >> 4;
@@ -153,8 +164,42 @@ void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__
     }
     const float fP = (float)P;
     int tile_in_image = 0;
+    const int lg_tp = __builtin_ctz(tp);                            // SEL, P < 16: lane n of a tile belongs to its image n >> lg_tp
+    // SEL: wave-uniform state in scalar registers -- the first image of the coming tile (counted, one division per wave), the
+    // mask word of images 32 sel_word_at .. and which word that is
+    unsigned sel_img = SEL ? (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)r_begin / (unsigned)P)) : 0u;
+    unsigned sel_word = 0;
+    int sel_word_at = -1;
 
     for (int64_t n0 = r_begin; n0 < r_end; n0 += 16) {
+        bool on_lane = true;                                        // SEL: this lane's image is selected
+        if (SEL && (P < 16 || tile_in_image == 0)) {                // 16 | P: the first tile of an image decides for all of them
+            const unsigned img0 = sel_img;                          // the tile's first image (< n_img: n0 < r_end <= R), a scalar
+            sel_img += P < 16 ? 16u >> lg_tp : 1u;                  // the first image of the next tile (P | 16) / the next image
+            if ((int)(img0 >> 5) != sel_word_at) {                  // one load per 32 images, made scalar
+                sel_word_at = (int)(img0 >> 5);
+                sel_word = (unsigned)__builtin_amdgcn_readfirstlane((int)sel[sel_word_at]);
+            }
+            if (P >= 16) {
+                if (!((sel_word >> (img0 & 31)) & 1u)) {            // the whole wave passes the image over
+                    if (!LISTS && lane < Q) scores[(int64_t)lane * n_img + img0] = -INFINITY;
+                    n0 += P - 16;
+                    continue;
+                }
+            } else {
+                const int ipt = 16 >> lg_tp;                        // images per tile; their bits lie in one word
+                const unsigned bits = (sel_word >> (img0 & 31)) & (0xffffu >> (16 - ipt));   // padding bits are zero: images past n_img
+                if (bits == 0) {                                    // no image of this tile is selected
+                    if (!LISTS)
+                        for (int e = lane; e < ipt * Q; e += 64) {
+                            const int64_t img = (int64_t)img0 + (e & (ipt - 1));
+                            if (img < n_img) scores[(int64_t)(e >> (4 - lg_tp)) * n_img + img] = -INFINITY;
+                        }
+                    continue;
+                }
+                on_lane = (bits >> (n_lane >> lg_tp)) & 1u;
+            }
+        }
         int64_t row = n0 + n_lane;
         const bool row_ok = row < r_end;
         if (!row_ok) row = r_end - 1;                                // clamp: masked below
@@ -184,6 +229,7 @@ void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__
                 }
             }
             if (!LISTS) {
+                if (SEL && !on_lane) c = -INFINITY;
                 if (lead && q_mine < Q) scores[(int64_t)q_mine * n_img + (int64_t)((unsigned)(n0 + n_lane) / (unsigned)P)] = c;
                 continue;
             }
@@ -191,7 +237,7 @@ void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__
             float my_thr = -INFINITY;
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) my_thr = (g == gg) ? thr[4 * gg + r] : my_thr;
-            unsigned long long m = __ballot(lead && q_mine < Q && c > my_thr);
+            unsigned long long m = __ballot(lead && (!SEL || on_lane) && q_mine < Q && c > my_thr);
             while (m) {
                 const int srcl = __builtin_ctzll(m);
                 m &= m - 1;
@@ -245,27 +291,40 @@ int64_t image_unit(int P) { return P < 16 ? 16 : P; }              // lcm(P, 16)
 
 bool combine_ok(int combine) { return combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MEAN || combine == SKYEMB_COMBINE_MAX; }
 
-template <typename T, int WAVES, bool LISTS>
-int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
-                  const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
-                  int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
-                  int top_t) {
+template <typename T, int WAVES, bool LISTS, bool SEL>
+int launch_tokens_sel(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
+                      const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
+                      int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
+                      int top_t, const uint32_t *sel) {
     auto go = [&](auto kern) {
         if (smem > 64 * 1024) {
             const int rc = sky_set_lds_limit((const void *)kern, LDS_BYTES, who);
             if (rc != 0) return rc;
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), smem, st, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
-                           rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t);
+                           rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, sel);
         SKY_LAUNCH_CHECK(who);
         return 0;
     };
     // top_t == 0: all tokens, the plain kernels; max is d[0] for every top_t, the plain max kernel
-    if (top_t != 0 && combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true>);
-    if (top_t != 0 && combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true>);
-    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false>);
-    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false>);
-    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false>);
+    if (top_t != 0 && combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true, SEL>);
+    if (top_t != 0 && combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true, SEL>);
+    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false, SEL>);
+    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false, SEL>);
+    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false, SEL>);
+}
+
+// sel == nullptr: the kernels without the selection switch, the search over every image
+template <typename T, int WAVES, bool LISTS>
+int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
+                  const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
+                  int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
+                  int top_t, const uint32_t *sel) {
+    if (sel)
+        return launch_tokens_sel<T, WAVES, LISTS, true>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
+                                                        rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, sel);
+    return launch_tokens_sel<T, WAVES, LISTS, false>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
+                                                     rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, nullptr);
 }
 
 bool top_t_ok(int top_t, int P) { return top_t >= 0 && top_t <= (P < 16 ? P : 16); }
@@ -302,7 +361,7 @@ extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, i
 template <typename T>
 int token_topk(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D, int k,
                int combine, int top_t, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i,
-               void *stream) {
+               void *stream, const uint32_t *sel = nullptr) {
     SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "%s: bad arguments", who);
     SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
     SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
@@ -311,32 +370,34 @@ int token_topk(const char *who, const float *tw, const float *qn, const T *bank,
     SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
                   who);
     SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
+    SKY_CHECK_ARG(((uintptr_t)sel & 3) == 0, "%s: select must be 4-byte aligned", who);
     const int waves = token_waves(Q, D, k);
     const int64_t R = N * P, unit = image_unit(P);
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, nlists), unit) * unit;
     const size_t smem = image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
     if (waves == 8)
         return launch_tokens<T, 8, true>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                         idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t);
+                                         idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t, sel);
     return launch_tokens<T, 4, true>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                     idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t);
+                                     idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t, sel);
 }
 
 template <typename T>
 int token_scores(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D,
-                 int combine, int top_t, float eps, float *scores, void *stream) {
+                 int combine, int top_t, float eps, float *scores, void *stream, const uint32_t *sel = nullptr) {
     SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "%s: bad arguments", who);
     SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, 1);
     SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
     SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
     SKY_CHECK_ARG(N * P < (1ll << 31), "%s: bank too large (N * P < 2^31 rows per call)", who);
     SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
+    SKY_CHECK_ARG(((uintptr_t)sel & 3) == 0, "%s: select must be 4-byte aligned", who);
     const int64_t R = N * P, unit = image_unit(P);
     int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), 4);
     if (blocks > 2048) blocks = 2048;
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, blocks * 4), unit) * unit;
     return launch_tokens<T, 4, false>(combine, (int)blocks, image_bytes(D), (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, 1,
-                                      eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N, top_t);
+                                      eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N, top_t, sel);
 }
 
 extern "C" int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
@@ -404,4 +465,63 @@ extern "C" int skyemb_cosine_token_scores_top(const float *tw, const float *qn, 
     if (bank_dtype == SKYEMB_BF16)
         return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
     return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
+}
+
+// Selection (include/skyemb.h): the `_top` calls restricted to the images whose bit is set in `select`.  select == NULL IS the
+// `_top` call (one definition of the plain call: its checks, its kernels, its error texts).
+extern "C" int skyemb_cosine_token_topk_sel(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
+                                            int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset,
+                                            int nlists, const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select,
+                                            void *stream) {
+    const char *who = "skyemb_cosine_token_topk_sel";
+    if (!select)
+        return skyemb_cosine_token_topk_top(tw, qn, bank, bank_dtype, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
+                                            part_s, part_i, stream);
+    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_sel: " TOP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_F32)
+        return token_topk(who, tw, qn, (const float *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
+                          part_i, stream, select);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
+                          part_i, stream, select);
+    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s, part_i,
+                      stream, select);
+}
+
+extern "C" int skyemb_cosine_token_scores_sel(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn,
+                                              int Q, int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
+                                              const uint32_t *select, void *stream) {
+    const char *who = "skyemb_cosine_token_scores_sel";
+    if (!select) return skyemb_cosine_token_scores_top(tw, qn, bank, bank_dtype, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
+    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_sel: " TOP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_F32)
+        return token_scores(who, tw, qn, (const float *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+}
+
+namespace {
+
+// one byte per image -> the packed words: a wave's ballot is two words; images past N vote 0, which zeroes the padding bits
+__global__ __launch_bounds__(256) void pack_select_kernel(const uint8_t *__restrict__ flags, int64_t N, uint32_t *__restrict__ words,
+                                                          int64_t nwords) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long m = __ballot(i < N && flags[i] != 0);
+    const int lane = threadIdx.x & 63;
+    const int64_t w = i >> 5;
+    if ((lane & 31) == 0 && w < nwords) words[w] = (uint32_t)(lane ? m >> 32 : m);
+}
+
+}  // namespace
+
+extern "C" int skyemb_pack_select(const uint8_t *flags, int64_t N, uint32_t *words, void *stream) {
+    SKY_CHECK_ARG(flags && words && N > 0, "skyemb_pack_select: bad arguments");
+    SKY_CHECK_ARG(N < (1ll << 31), "skyemb_pack_select: N < 2^31 images");
+    SKY_CHECK_ARG(((uintptr_t)words & 3) == 0, "skyemb_pack_select: words must be 4-byte aligned");
+    const int64_t nwords = ceil_div64(N, 32);
+    hipLaunchKernelGGL(pack_select_kernel, dim3((unsigned)ceil_div64(N, 256)), dim3(256), 0, (hipStream_t)stream, flags, N, words,
+                       nwords);
+    SKY_LAUNCH_CHECK("skyemb_pack_select");
+    return 0;
 }

@@ -453,11 +453,23 @@ def cosine_token_topk_chunks(N, P, Q, D, k):
     return lib().skyemb_cosine_token_topk_chunks(N, P, Q, D, k)
 
 
-def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores, top_t=0):
+def pack_select(flags, words):
+    """flags u8 [N] on the device (non-zero = selected) -> words i32 [ceil(N / 32)]: bit i & 31 of word i >> 5 is image i, padding
+    bits zero (skyemb_pack_select)."""
+    check(lib().skyemb_pack_select(_p(flags), flags.shape[0], _p(words), _stream()), "skyemb_pack_select")
+
+
+def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores, top_t=0, select=None):
     """bank [N, P, D] fp32, fp16 or bf16, xn [N * P], combine: a COMBINE_* code -> scores [Q, N].  top_t: 0 = all tokens (the
-    plain calls), else only the top_t best token scores of an image count (skyemb_cosine_token_scores_top)."""
+    plain calls), else only the top_t best token scores of an image count (skyemb_cosine_token_scores_top).  select: None, or
+    the packed words of a selection of images (pack_select): deselected images score -inf (skyemb_cosine_token_scores_sel)."""
     Q, D = tw.shape
     N, P = bank.shape[0], bank.shape[1]
+    if select is not None:
+        check(lib().skyemb_cosine_token_scores_sel(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_scores"), _p(xn),
+                                                   Q, N, P, D, combine, top_t, eps, _p(scores), _p(select), _stream()),
+              "skyemb_cosine_token_scores_sel")
+        return
     if top_t != 0:
         check(lib().skyemb_cosine_token_scores_top(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_scores"), _p(xn),
                                                    Q, N, P, D, combine, top_t, eps, _p(scores), _stream()),
@@ -471,9 +483,14 @@ def cosine_token_scores(tw, qn, bank, xn, combine, eps, scores, top_t=0):
           "skyemb_cosine_token_scores")
 
 
-def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None, top_t=0):
+def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None, top_t=0, select=None):
     Q, D = tw.shape
     N, P = bank.shape[0], bank.shape[1]
+    if select is not None:
+        check(lib().skyemb_cosine_token_topk_sel(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_topk"), _p(xn), Q,
+                                                 N, P, D, k, combine, top_t, eps, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i),
+                                                 _p(select), _stream()), "skyemb_cosine_token_topk_sel")
+        return
     if top_t != 0:
         check(lib().skyemb_cosine_token_topk_top(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_topk"), _p(xn), Q,
                                                  N, P, D, k, combine, top_t, eps, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i),

@@ -142,7 +142,7 @@ def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps):
 
 
 def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | None = None, eps: float = 1e-6,
-                process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None):
+                process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None, select=None):
     """-> (scores f32 [Q,k], indices i64 [Q,k]).  ``bank`` is a [N,D] tensor or a PreparedBank
     (this rank's shard; ``idx_offset`` = first global row of the shard).  More than 16 queries take the two-stage
     path (fp16 matrix-core prefilter with a proven error bound, exact fp32 re-score of the survivors: same results bit
@@ -151,7 +151,21 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     A 2-D fp16 / bf16 tensor is a half-precision resident bank: it is served as a token bank with one token per row
     (``cosine_topk_tokens`` on ``bank.unsqueeze(1)``, ``stats['path'] == 'tokens'``) under that search's limits -- k <= 512,
     more than 16 queries in groups of 16 -- with the results of the fp32 search on the widened bank, bit for bit.  The
-    many-query prefilter over a 16-bit flat bank is out of scope.  fp32 banks take exactly the paths described above."""
+    many-query prefilter over a 16-bit flat bank is out of scope.  fp32 banks take exactly the paths described above.
+
+    ``select`` (None: nothing above changes; a bool tensor [N] or a ``Selection``): only the rows marked True are eligible, with
+    the result of the search over the compacted bank and indices mapped back (``cosine_topk_tokens``'s ``select``).  A flat
+    [N,D] bank of any dtype is then served as a token bank with one token per row (``stats['path'] == 'tokens'``) under that
+    search's limits: k <= 512, D % 64 == 0, D <= 1024, queries in groups of 16.  A PreparedBank with ``select`` is a ValueError:
+    its many-query prefilter under a selection is out of scope."""
+    if select is not None:
+        if isinstance(bank, PreparedBank):
+            raise ValueError("cosine_topk: select is served by the token search (cosine_topk_tokens with one token per row); pass "
+                             "the flat [N, D] tensor, not a PreparedBank -- the prefiltered many-query route takes no selection")
+        if not (isinstance(bank, torch.Tensor) and bank.dim() == 2):
+            raise ValueError("cosine_topk: select needs a flat [N, D] bank tensor")
+        return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats,
+                                  select=select)
     if isinstance(bank, torch.Tensor) and bank.dim() == 2 and bank.dtype in ops.LP_DTYPES:
         return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats)
     pb = bank if isinstance(bank, PreparedBank) else PreparedBank(bank, weights)
@@ -208,9 +222,11 @@ class TokenBank:
         self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self.norms = torch.empty(bank.shape[0] * bank.shape[1], device=bank.device)
         self._sample = None
+        self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
 
     def set_weights(self, weights):
+        self._version += 1
         self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
         rows = self.bank.view(-1, self.bank.shape[2])
         if self.dtype == torch.float32:
@@ -231,6 +247,70 @@ class TokenBank:
         return self._sample
 
 
+class Selection:
+    """A selection of a bank's images: ``flags`` is a bool tensor [N] (host or device), True = eligible.  Holds the packed words
+    the kernels read (``words`` i32 [ceil(N / 32)] on the device: bit i & 31 of word i >> 5 is image i, padding bits zero), ``N``
+    and the selected ``count``; packed once (one short launch), reusable across searches and banks of N images.  A search with a
+    selection returns what the same search returns over the compacted bank ``bank[flags]``, image indices mapped back."""
+
+    def __init__(self, flags: torch.Tensor, device=None):
+        if not isinstance(flags, torch.Tensor) or flags.dtype != torch.bool or flags.dim() != 1:
+            what = f"{tuple(flags.shape)} {flags.dtype}" if isinstance(flags, torch.Tensor) else type(flags).__name__
+            raise ValueError(f"Selection: flags must be a bool tensor with one dimension [N], got {what}")
+        if not flags.is_cuda:                              # host flags: packed on ``device`` (default: the current GPU)
+            flags = flags.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+        self.flags = flags.contiguous()
+        self.N = int(flags.shape[0])
+        self.words = torch.empty((self.N + 31) // 32, device=flags.device, dtype=torch.int32)
+        if self.N:
+            ops.pack_select(self.flags.view(torch.uint8), self.words)
+        self.count = int(self.flags.sum())
+        self._indices = None
+        self._sample = None                                # bank -> (its weights version, images, the floor's sample)
+
+    def sample(self, tb: "TokenBank", images: int):
+        """A strided sample of ``images`` SELECTED whole images of ``tb`` (tokens + the norms of their rows) for the pruning floor.
+        Kept here, with the selection it belongs to -- not in the bank -- until the bank, its weights or the size change, so
+        that repeated searches under one Selection do not gather it again."""
+        import weakref
+        if self._sample is None:
+            self._sample = weakref.WeakKeyDictionary()     # one entry per bank: a Selection may serve several (fp32 and fp16)
+        got = self._sample.get(tb)
+        if got is None or got[0] != tb._version or got[1] != images:
+            N, P = tb.bank.shape[0], tb.bank.shape[1]
+            idx = self.indices()[torch.arange(images, device=tb.bank.device) * (self.count // images)]
+            got = (tb._version, images, tb.bank.index_select(0, idx), tb.norms.view(N, P).index_select(0, idx).view(-1))
+            self._sample[tb] = got
+        return got[2], got[3]
+
+    def indices(self):
+        """The selected images, ascending (i64 on the device): compacted position -> image."""
+        if self._indices is None:
+            self._indices = torch.nonzero(self.flags).squeeze(1)
+        return self._indices
+
+
+def _selection_arg(select, N, who, device=None):
+    """``select`` (None | bool tensor [N] | Selection) -> None | Selection; ValueError unless it describes N images.  ``device``:
+    the bank's, when it lives on a GPU -- flags are packed there, and a Selection packed on another device is a ValueError (its
+    words would reach the kernel as a pointer into the wrong device's memory)."""
+    if select is None:
+        return None
+    n = select.N if isinstance(select, Selection) else (select.shape[0] if isinstance(select, torch.Tensor) and select.dim() == 1 else None)
+    if n is not None and n != N:
+        raise ValueError(f"{who}: select describes {n} images, the bank has {N}")
+    if device is not None and device.type != "cuda":
+        device = None
+    if not isinstance(select, Selection):
+        if device is not None and isinstance(select, torch.Tensor) and select.is_cuda and select.device != device:
+            raise ValueError(f"{who}: select is on {select.device}, the bank on {device}")
+        return Selection(select, device)
+    if device is not None and select.words.device != device:
+        raise ValueError(f"{who}: the Selection was packed on {select.words.device}, the bank is on {device}: build it with "
+                         f"Selection(flags, device=bank.device)")
+    return select
+
+
 def _combine_code(combine, who):
     if combine not in ops.COMBINE_CODES:
         raise ValueError(f"{who}: combine = {combine!r}, expected one of {sorted(ops.COMBINE_CODES)}")
@@ -246,25 +326,33 @@ def _top_t_arg(top_t, P, who):
     return int(top_t)
 
 
-def _token_scores(tw, qn, tokens, norms, code, eps, top_t=0):
-    """[Q, N] combined scores of Q <= 16 prepared queries."""
+def _token_scores(tw, qn, tokens, norms, code, eps, top_t=0, words=None):
+    """[Q, N] combined scores of Q <= 16 prepared queries (words: a Selection's, deselected images score -inf)."""
     out = torch.empty(tw.shape[0], tokens.shape[0], device=tw.device)
-    ops.cosine_token_scores(tw, qn, tokens, norms, code, eps, out, top_t)
+    ops.cosine_token_scores(tw, qn, tokens, norms, code, eps, out, top_t, words)
     return out
 
 
 def token_pruning_floor(tw, qn, tb: "TokenBank", k: int, combine: str = 'min', eps: float = 1e-6, sample_images: int | None = None,
-                        top_t: int | None = None):
+                        top_t: int | None = None, select=None):
     """Per-query floor for the token search: the k-th best COMBINED score over a sample of whole images, one ulp lower
     (``pruning_floor``'s argument, with images for rows).  None under the same size rule: N < 8 x the sample.  ``top_t``: the
-    search's own, so that the sample is scored as the search scores it and the floor stays a lower bound of its k-th best."""
+    search's own, so that the sample is scored as the search scores it and the floor stays a lower bound of its k-th best.
+    ``select`` (None | bool tensor | Selection): the sample is drawn from the selected images only, strided over them, so the
+    floor is a lower bound of the k-th best SELECTED score; the size rule applies to the selected count.  That sample changes
+    with the selection, so it is not kept in the bank (``TokenBank._sample``): a ``Selection`` keeps its own (``Selection.sample``),
+    a bool tensor is packed and sampled anew on every call."""
     t = _top_t_arg(top_t, tb.bank.shape[1], "token_pruning_floor")
-    N = tb.bank.shape[0]
+    N, P = tb.bank.shape[0], tb.bank.shape[1]
+    sel = _selection_arg(select, N, "token_pruning_floor", tb.bank.device)
     if sample_images is None:
         sample_images = 256 * k
-    if N < 8 * sample_images:
+    if (N if sel is None else sel.count) < 8 * sample_images:
         return None
-    st, sn = tb.sample(sample_images)
+    if sel is None:
+        st, sn = tb.sample(sample_images)
+    else:
+        st, sn = sel.sample(tb, sample_images)
     sc = _token_scores(tw, qn, st, sn, _combine_code(combine, "token_pruning_floor"), eps, t)
     floor = torch.empty(tw.shape[0], device=tw.device)
     ops.kth_largest_floor(sc, k, floor)
@@ -279,7 +367,7 @@ def _check_token_shape(who, Q, P, D, k):
 
 def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min', weights: torch.Tensor | None = None,
                        eps: float = 1e-6, process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None,
-                       top_t: int | None = None):
+                       top_t: int | None = None, select=None):
     """-> (scores f32 [Q,k], image indices i64 [Q,k]): exact top-k images by the combined score of their P patch tokens
     (reference: compute_similarity with max_pool = False, utils/similarity.py:214-268, + update_best_scores), order
     (score desc, image asc).  ``bank`` is a [N,P,D] tensor (fp32, or fp16 / bf16: see TokenBank) or a TokenBank (this rank's
@@ -293,7 +381,15 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     a NaN score ranks as, last -- torch.topk would rank NaN largest): max is d[0] (unchanged), min is d[top_t-1], mean is
     (((0 + d[0]) + d[1]) + ... + d[top_t-1]) / float32(top_t), summed largest first.  ``top_t == P`` with 'min' is the plain min
     bit for bit; with 'mean' it is NOT the plain mean, which sums in token order.  An image with fewer than top_t scores above
-    -inf scores -inf under min and mean and is never returned.  ValueError outside the range, before the first launch."""
+    -inf scores -inf under min and mean and is never returned.  ValueError outside the range, before the first launch.
+
+    ``select`` (None: every image, the search above unchanged; a bool tensor [N] or a ``Selection``): only the images marked
+    True are eligible.  The result is exactly that of the same search over the compacted bank ``bank[select]`` -- scores bit for
+    bit, order (score desc, image asc) -- with every index mapped back to this bank (then offset by ``idx_offset``).  The bank is
+    not copied, deselected images cost no HBM bytes when P is a multiple of 16 (P < 16: a 16-row tile is passed over when all
+    of its 16 / P images are deselected) and a NaN or inf in them changes nothing.  Fewer than k selected images: the tail is
+    (-inf, -1).  One selection serves all queries; with ``world_size > 1`` it describes this rank's shard.  A length other than
+    N is a ValueError before any launch; ``stats`` gains ``selected``."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
     N, P = tokens.shape[0], tokens.shape[1]
@@ -305,6 +401,8 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     if world_size == 1 and k > N:
         raise ValueError(f"cosine_topk_tokens: k = {k} exceeds the {N} images of the bank")
     _check_token_shape("cosine_topk_tokens", Q, P, D, k)     # every refusal above and here: before the first launch
+    sel = _selection_arg(select, N, "cosine_topk_tokens", tokens.device)
+    words = None if sel is None else sel.words
     tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
     q = queries.to(tb.bank.device, torch.float32).contiguous()
     out_s = torch.empty(Q, k, device=q.device)
@@ -316,17 +414,19 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     for lo in range(0, Q, 16):
         tw, qn = tw_all[lo:lo + 16], qn_all[lo:lo + 16]
         Qg = tw.shape[0]
-        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps, top_t=top_t) if prune else None
+        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps, top_t=top_t, select=sel) if prune else None
         pruned = pruned or thr0 is not None
         nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
         ps = torch.empty(Qg, nl, k, device=q.device)
         pi = torch.empty(Qg, nl, k, device=q.device, dtype=torch.int64)
-        ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, tb.idx_offset, nl, ps, pi, thr0, t)
+        ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, tb.idx_offset, nl, ps, pi, thr0, t, words)
         ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + 16], out_i[lo:lo + 16], torch.empty(Qg, device=q.device, dtype=torch.int32))
     if stats is not None:
         stats.update(path="tokens", groups=(Q + 15) // 16, pruned=pruned)
         if top_t is not None:
             stats.update(top_t=t)
+        if sel is not None:
+            stats.update(selected=sel.count)
     if world_size > 1:
         from .distributed import gather_topk
         gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
@@ -335,18 +435,21 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
 
 
 def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weights: torch.Tensor | None = None, eps: float = 1e-6,
-                        top_t: int | None = None):
+                        top_t: int | None = None, select=None):
     """[Q, N] combined score of every image of a [N,P,D] token bank (fp32, fp16 or bf16; or a TokenBank), in groups of at most
     16 queries.
     ``weights`` is ignored when ``bank`` is a TokenBank (it carries its own).  ``top_t``: as for ``cosine_topk_tokens`` (None:
     all tokens; else only the top_t best token scores of an image count, mean summed largest first -- so 'mean' with
-    ``top_t == P`` is not the plain mean)."""
+    ``top_t == P`` is not the plain mean).  ``select``: as for ``cosine_topk_tokens``; every [Q, N] slot is written, a deselected
+    image gets -inf."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
     assert tokens.dim() == 3 and D == tokens.shape[2]
     code = _combine_code(combine, "cosine_token_scores")
     t = _top_t_arg(top_t, tokens.shape[1], "cosine_token_scores")
     _check_token_shape("cosine_token_scores", Q, tokens.shape[1], D, 1)
+    sel = _selection_arg(select, tokens.shape[0], "cosine_token_scores", tokens.device)
+    words = None if sel is None else sel.words
     tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
     q = queries.to(tb.bank.device, torch.float32).contiguous()
     out = torch.empty(Q, tb.bank.shape[0], device=q.device)
@@ -354,5 +457,5 @@ def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weigh
         return out
     tw, qn = prepare_queries(q, tb.weights)
     for lo in range(0, Q, 16):
-        out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps, t)
+        out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps, t, words)
     return out

@@ -83,7 +83,7 @@ def mae_latent(model, dataloader, device, n_batches=None, return_images=False, v
 
 
 def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None, bank_dtype=torch.float32,
-                         standardise_with_first_batch=False):
+                         standardise_with_first_batch=False, standardise_stats=None):
     """Encode a dataset ONCE into a resident [N, D] fp32 bank (cls token, or max / mean pool over
     the patch tokens -- all permutation invariant, so the reference's shuffled token order does not
     matter).  The reference re-encodes every test image per search (utils/similarity.py:81).
@@ -96,13 +96,16 @@ def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None, 
     resident bank without its fp32 image ever existing at full size: mean / unbiased std over (batch, patch) of the FIRST batch
     (as mae_simsearch takes them, utils/similarity.py:98-100), every batch standardised and rounded once to nearest-even
     (``search.standardise_to``), the 16-bit batches concatenated -> ``(bank, mean, std)``.  A 16-bit bank is stored
-    standardised only: rounding raw features first would let ``standardise_`` amplify the rounding error.  The defaults
-    return what they always returned."""
+    standardised only: rounding raw features first would let ``standardise_`` amplify the rounding error.
+    ``standardise_stats=(mean, std)`` replaces the first batch's statistics (those of another set of images, e.g. the first
+    batch of a selection of this dataset).  The defaults return what they always returned."""
     from .. import search
     lp = bank_dtype != torch.float32
     if bank_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"build_embedding_bank: bank_dtype {bank_dtype} is not supported, expected torch.float32, torch.float16 or "
                          "torch.bfloat16")
+    if standardise_stats is not None and not lp:
+        raise ValueError("build_embedding_bank: standardise_stats applies to a 16-bit bank (standardise_with_first_batch=True)")
     if lp != bool(standardise_with_first_batch) or (lp and pool != 'tokens'):
         raise ValueError("build_embedding_bank: a 16-bit bank_dtype and standardise_with_first_batch=True go together, with "
                          "pool='tokens'")
@@ -119,7 +122,7 @@ def build_embedding_bank(model, dataloader, device, pool='max', n_batches=None, 
             feats = reduce[pool](net.forward_features(samples.to(device, non_blocking=True), ra_dec=ra_decs, reshape_out=False)[0])
             if lp:
                 if done == 1:
-                    mean, std = feats.mean(dim=(0, 1)), feats.std(dim=(0, 1), unbiased=True)
+                    mean, std = standardise_stats or (feats.mean(dim=(0, 1)), feats.std(dim=(0, 1), unbiased=True))
                 feats = search.standardise_to(feats, mean, std, bank_dtype)
             rows.append(feats)
             if n_batches is not None and done >= n_batches:

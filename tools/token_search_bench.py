@@ -6,6 +6,8 @@ one-vector streaming top-k over a bank of the same byte size.  HIP-event timing,
 usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim 768] [--k 100] [--iters 10] [--out FILE]
                                          [--bank-dtype f32 | f16 | bf16 | a comma list, e.g. f32,f16,bf16]
                                          [--combine min | mean | max | a comma list] [--top-t T | a comma list, e.g. 4,16]
+                                         [--select-frac F | a comma list, e.g. 1.0,0.5,0.1] [--select-pattern random | runs]
+                                         [--fused-only]
 --bank-dtype: element type(s) of the resident token bank the fused pass runs on (16-bit banks: the fp32 bank rounded to nearest);
 the fused variants of every listed type run interleaved in the same rounds, named fused_tokens[f16] etc.; the comparison variants
 (baseline and one-vector) need the fp32 bank and run when f32 is listed.
@@ -14,6 +16,15 @@ token scores of an image count) and, with f32 listed, the unfused route to the s
 token rows, torch.topk over the P scores of every image, the reduce, torch.topk), in the same interleaved rounds.
 "fused_equals_baseline" compares the fused result with the baseline's torch.topk, whose order among equal scores is unspecified:
 False may come from exact ties alone and is not by itself a mismatch (the tests compare against the CPU restatement).
+--select-frac: for every listed fraction F and every listed bank type, in the same interleaved rounds, the fused pass under a
+selection of about F x images (fused_tokens_sel0.5 etc.: search.cosine_topk_tokens(select=), the Selection packed once outside the
+timed region) and the plain fused pass over a PRE-COMPACTED bank of the same selected images (fused_tokens_compact0.5: what the
+caller would run after bank[sel].contiguous(); the copy is not in that figure and is timed once on its own as "compact_ms", with
+the norms of the copy in "compact_norms_ms"; at F = 1.0 also fused_tokens_sel1_no_floor, against fused_tokens_no_floor the cost
+of the kernel's switch alone).  --select-pattern random: Bernoulli(F) per image, fixed seed; runs: runs of 64
+images, a run selected with probability F.  "bank_bytes" of a _sel leg counts the selected images only (the bytes the kernel has
+to read when P is a multiple of 16); "equals_compact" says whether the two legs returned the same lists (indices mapped back).
+--fused-only leaves out the comparison variants (baseline, one-vector): memory for the compacted banks.
 Bytes counted per pass: images x tokens x dim x element size (the bank; norms and lists are under 0.4 % of it).  Peak: 8.0 TB/s
 (spec)."""
 import argparse
@@ -54,6 +65,33 @@ def combines(text):
     return names
 
 
+def float_list(text):
+    try:
+        vals = [float(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        vals = []
+    if not vals or min(vals) <= 0 or max(vals) > 1:
+        raise argparse.ArgumentTypeError(f"expected a fraction in (0, 1] or a comma list of them, got {text!r}")
+    return vals
+
+
+def selection_flags(N, frac, pattern):
+    g = torch.Generator(device="cuda").manual_seed(int(frac * 1000) + 31)
+    if pattern == "random":
+        return torch.rand(N, device="cuda", generator=g) < frac
+    runs = torch.rand((N + 63) // 64, device="cuda", generator=g) < frac
+    return runs.repeat_interleave(64)[:N].contiguous()
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return out, e0.elapsed_time(e1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=250_000)
@@ -66,6 +104,9 @@ def main():
     ap.add_argument("--top-t", type=int_list, default=[])
     ap.add_argument("--out", default=None)
     ap.add_argument("--bank-dtype", type=bank_dtypes, default=["f32"])
+    ap.add_argument("--select-frac", type=float_list, default=[])
+    ap.add_argument("--select-pattern", choices=("random", "runs"), default="random")
+    ap.add_argument("--fused-only", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("token_search_bench.py needs a GPU")
@@ -88,10 +129,22 @@ def main():
     chunk = (1 << 20) // P * P                              # rows per cosine_scores call (streaming score kernel: <= 2^20 rows)
     if with_f32:
         tb = search.TokenBank(bank, w)
-        pb = search.PreparedBank(rows, w)                   # the same bytes as a one-vector bank of N * P rows
-        chunks = [search.PreparedBank(rows[s:s + chunk], w) for s in range(0, N * P, chunk)]
+        if not a.fused_only:
+            pb = search.PreparedBank(rows, w)               # the same bytes as a one-vector bank of N * P rows
+            chunks = [search.PreparedBank(rows[s:s + chunk], w) for s in range(0, N * P, chunk)]
     else:
         del bank, rows
+    # selections: packed once; the compacted twin of every bank (the copy and its norms timed once, outside the rounds)
+    banks = dict(lp_banks, **({"f32": tb} if with_f32 else {}))
+    sels, compact, extra = {}, {}, {}
+    for frac in a.select_frac:
+        flags = selection_flags(N, frac, a.select_pattern)
+        sels[frac] = search.Selection(flags)
+        for name, b in banks.items():
+            cb, ms_copy = timed(lambda: b.bank[flags].contiguous())
+            ctb, ms_norms = timed(lambda: search.TokenBank(cb, w))
+            compact[frac, name] = ctb
+            extra[frac, name] = dict(selected=sels[frac].count, compact_ms=round(ms_copy, 4), compact_norms_ms=round(ms_norms, 4))
     reducers = {"min": torch.amin, "max": torch.amax, "mean": torch.mean}
     elems = N * P * D
     results = []
@@ -107,25 +160,26 @@ def main():
                 parts.append(reducers[combine](sc, dim=2))
             return torch.topk(torch.cat(parts, dim=1), k, dim=1)
 
-        variants, nbytes, same, combine_of = {}, {}, {}, {}
+        variants, nbytes, same, combine_of, more = {}, {}, {}, {}, {}
         for combine in a.combine:
             tag = "" if len(a.combine) == 1 else f"/{combine}"
             mine = {}
             if with_f32:
-                mine = {
-                    "baseline_scores_amin_topk": lambda c=combine: baseline(c),
-                    "fused_tokens": lambda c=combine: search.cosine_topk_tokens(q, tb, k, c),
-                    "fused_tokens_no_floor": lambda c=combine: search.cosine_topk_tokens(q, tb, k, c, prune=False),
-                }
-                if combine == a.combine[0]:
+                if not a.fused_only:
+                    mine["baseline_scores_amin_topk"] = lambda c=combine: baseline(c)
+                mine["fused_tokens"] = lambda c=combine: search.cosine_topk_tokens(q, tb, k, c)
+                mine["fused_tokens_no_floor"] = lambda c=combine: search.cosine_topk_tokens(q, tb, k, c, prune=False)
+                if combine == a.combine[0] and not a.fused_only:
                     mine["one_vector_stream_same_bytes"] = lambda: search.cosine_topk(q, pb, k)
                     mine["one_vector_stream_no_floor"] = lambda: search.cosine_topk(q, pb, k, prune=False)
                 for t in a.top_t:
-                    mine[f"unfused_top{t}"] = lambda c=combine, t=t: baseline(c, t)
+                    if not a.fused_only:
+                        mine[f"unfused_top{t}"] = lambda c=combine, t=t: baseline(c, t)
                     mine[f"fused_tokens_top{t}"] = lambda c=combine, t=t: search.cosine_topk_tokens(q, tb, k, c, top_t=t)
-                bs, bi = baseline(combine)
-                fs, fi = mine["fused_tokens"]()
-                same[combine] = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
+                if not a.fused_only:
+                    bs, bi = baseline(combine)
+                    fs, fi = mine["fused_tokens"]()
+                    same[combine] = bool(torch.equal(fi, bi)) and bool(torch.equal(fs, bs))
             for name, lpb in lp_banks.items():
                 lp = {f"fused_tokens[{name}]": lambda lpb=lpb, c=combine: search.cosine_topk_tokens(q, lpb, k, c),
                       f"fused_tokens_no_floor[{name}]": lambda lpb=lpb, c=combine: search.cosine_topk_tokens(q, lpb, k, c, prune=False)}
@@ -134,6 +188,19 @@ def main():
                 for v in lp:
                     nbytes[v + tag] = elems * lpb.bank.element_size()
                 mine.update(lp)
+            for (frac, name), ctb in compact.items():
+                sfx = "" if name == "f32" else f"[{name}]"
+                b, sel = banks[name], sels[frac]
+                pair = {f"fused_tokens_sel{frac:g}{sfx}": lambda b=b, sel=sel, c=combine: search.cosine_topk_tokens(q, b, k, c, select=sel),
+                        f"fused_tokens_compact{frac:g}{sfx}": lambda ctb=ctb, c=combine: search.cosine_topk_tokens(q, ctb, k, c)}
+                if frac == 1.0:                              # the switch alone: all ones, no floor, against fused_tokens_no_floor
+                    pair[f"fused_tokens_sel1_no_floor{sfx}"] = lambda b=b, sel=sel, c=combine: search.cosine_topk_tokens(q, b, k, c, prune=False, select=sel)
+                (ss, si), (cs, ci) = (fn() for fn in list(pair.values())[:2])
+                back = torch.where(ci >= 0, sel.indices()[ci.clamp(min=0)], ci)
+                for v in pair:
+                    nbytes[v + tag] = sel.count * P * D * b.bank.element_size()
+                    more[v + tag] = dict(extra[frac, name], equals_compact=bool(torch.equal(ss, cs)) and bool(torch.equal(si, back)))
+                mine.update(pair)
             for v, fn in mine.items():
                 variants[v + tag] = fn
                 combine_of[v + tag] = combine
@@ -154,7 +221,7 @@ def main():
             results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, combine=combine_of[name], variant=name, ms_median=round(med, 4),
                                 ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), bank_bytes=nb,
                                 tb_per_s=round(nb / (med * 1e-3) / 1e12, 3), hbm_peak_fraction=round(nb / (med * 1e-3) / HBM_PEAK, 4),
-                                fused_equals_baseline=same.get(combine_of[name])))
+                                fused_equals_baseline=same.get(combine_of[name]), **more.get(name, {})))
             print(json.dumps(results[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
