@@ -550,6 +550,50 @@ int skyemb_cosine_token_topk_sel(const float *tw, const float *qn, const void *b
                                  const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
 int skyemb_pack_select(const uint8_t *flags, int64_t N, uint32_t *words, void *stream);
 
+/* Weighted MSE / MAE patch-token search (additive to ABI version 111: nothing above changes): utils/similarity.py:174-212 scored
+ * token by token and combined per image (214-268), for Q <= 16 queries t [Q, D] over a bank [N, P, D] of fp32, fp16 or bf16
+ * (bank_dtype: SKYEMB_F32 / SKYEMB_F16 / SKYEMB_BF16).  c [D] = fp32(w / sum(w)), prepared by the caller (w = 1 without weights).
+ *
+ * Arithmetic contract (csrc/distance_tokens.hip and tests/token_distance_reference.py state the same, word for word):
+ *   All arithmetic is fp32, every operation rounds to nearest even on its own, and there is no fused multiply-add anywhere in
+ *   the score.  With x [D] a bank row (a 16-bit row is widened exactly on load):
+ *     term[d] = c[d] * v[d],  v[d] = |x[d] - t[d]| for MAE,  v[d] = (x[d] - t[d]) * (x[d] - t[d]) for MSE;
+ *     16 partial sums: p[j] = 0, then p[j] = p[j] + term[d] over the elements with (d >> 2) & 15 == j, in ascending d;
+ *     four folds: p[j] = p[j] + p[j ^ 8], then p[j] = p[j] + p[j ^ 4], then p[j] = p[j] + p[j ^ 2], then p[j] = p[j] + p[j ^ 1]
+ *     (every fold on all 16 partials at once; addition commutes, so afterwards all 16 are equal);
+ *     dist = p[0] / (float)D, one IEEE division.
+ *   The order does not depend on Q, launch geometry, wave, P, bank dtype, top_t or the selection.  A 16-bit bank gives the fp32
+ *   call's result on the widened bank, bit for bit.
+ *
+ * Ordering and combine.  Smaller is better.  The kernels work on key = -dist, an exact negation, and a NaN token distance ranks
+ * as key -inf, i.e. distance +inf (torch would propagate the NaN).  With a[0] <= a[1] <= ... the top_t smallest token distances
+ * of an image (top_t == 0: all P of them):
+ *   MIN   a[0], for every top_t;
+ *   MAX   the largest of those used: a[top_t - 1], or the plain max for top_t == 0;
+ *   MEAN  (((0 + a[0]) + a[1]) + ...) / (float)top_t, smallest first; top_t == 0: token order p = 0 .. P-1, divided by (float)P.
+ * In key space these ARE the cosine search's MAX, MIN and MEAN (negation commutes with every rounding), so its combine code,
+ * lists, thr0 floors, ties (key descending, image ascending), the (-inf, -1) terminator and skyemb_topk_merge serve unchanged.
+ * A +inf token distance is ignored by MIN and makes MAX and MEAN +inf; under MAX and MEAN an image with fewer than top_t finite
+ * token distances combines to +inf; an image whose combined distance is +inf is never returned.
+ *
+ *   skyemb_distance_token_scores  scores [Q, N]: every slot is written as a DISTANCE; a deselected image gets +inf.
+ *   skyemb_distance_token_topk    part_s f32 / part_i i64 [Q, nlists, k] in KEY space (part_s = -distance, best first, ended by
+ *                                 (-inf, -1)), nlists = skyemb_cosine_token_topk_chunks(N, P, Q, D, k); thr0 [Q] (or NULL):
+ *                                 per-query key floors, only keys strictly above enter.  skyemb_topk_merge merges them as they are;
+ *                                 the caller negates the merged keys.
+ * metric: SKYEMB_METRIC_MSE | SKYEMB_METRIC_MAE; combine: SKYEMB_COMBINE_*; top_t: 0 (all tokens) or 1 .. min(P, 16); select: NULL
+ * or the packed words of skyemb_pack_select (a deselected image costs no HBM bytes when 16 | P).  Shape limits: those of
+ * skyemb_cosine_token_applicable (its LDS rule covers these kernels: t takes 4 Q D <= 64 D bytes, four waves' lists 32 Q k).
+ * Refusals (return 1 before any launch, text in skyemb_last_error): a bad metric, combine, dtype, top_t or shape, N * P >= 2^31,
+ * a wrong nlists, bank / c / t not 16-byte aligned, select not 4-byte aligned. */
+#define SKYEMB_METRIC_MSE 1
+#define SKYEMB_METRIC_MAE 2
+int skyemb_distance_token_scores(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P, int D,
+                                 int metric, int combine, int top_t, float *scores, const uint32_t *select, void *stream);
+int skyemb_distance_token_topk(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P, int D,
+                               int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists, const float *thr0,
+                               float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

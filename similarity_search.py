@@ -11,7 +11,10 @@ test set ONCE into a resident embedding bank and runs the fused cosine top-k ker
 instead of re-scoring streamed batches: one vector per sample with -mp True or -ct True, or, with both False, the
 patch tokens of every sample scored one by one and combined per image (-c min | mean | max) by the fused token kernel;
 ``--bank-dtype f16 | bf16`` keeps that token bank in 16 bits (half the memory and half the bytes per search; the standardised
-features are rounded once when stored).  Cosine metric only.  ``-nts / --n_top_sims T`` (extension) combines only the T best
+features are rounded once when stored).  ``-m MSE | MAE`` with ``--bank`` runs the fused distance kernel over the same resident bank in
+all three modes (search.distance_topk_tokens; the pooled modes as a token bank with one token per sample, under that search's
+limits: -ns <= 512 and a feature width that is a multiple of 64, at most 1024); ``test_scores`` are then distances, best
+(smallest) first, as on the streamed path.  ``-nts / --n_top_sims T`` (extension) combines only the T best
 patch scores of a sample (compute_similarity's n_top_sims): streamed without --bank, and with ``--bank -mp False -ct False``
 inside the fused token kernel (1 <= T <= min(patches, 16)).  ``--bank-select-snr`` (extension, only with ``--bank``) encodes
 EVERY row of the test file once and turns the ``-snr`` window into a selection of the resident bank (search.Selection) instead
@@ -38,6 +41,7 @@ from utils.vit import build_model as build_vit
 
 
 BANK_DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+BANK_METRICS = ("cosine", "MSE", "MAE")
 
 
 def parseArguments():
@@ -74,6 +78,8 @@ def main():
     max_pool, cls_token = str2bool(args.max_pool), str2bool(args.cls_token)
     if (max_pool or cls_token) and args.n_top_sims not in (None, 1):
         raise SystemExit("-mp True / -ct True score one vector per sample: --n_top_sims must be 1 or left out")
+    if args.bank and args.metric not in BANK_METRICS:
+        raise SystemExit(f"--bank: unknown metric -m {args.metric}, expected one of {', '.join(BANK_METRICS)}")
     if args.bank_select_snr and not args.bank:
         raise SystemExit("--bank-select-snr selects images of the resident bank: it needs --bank")
     snr_range = ast.literal_eval(args.snr_range)
@@ -119,8 +125,6 @@ def main():
                                               remove_cls=False)
     if args.bank:
         from sky_embeddings_amd import search
-        if args.metric != 'cosine':
-            raise SystemExit("--bank runs the weighted cosine metric only (-m cosine)")
         if args.bank_dtype != "f32" and (max_pool or cls_token):
             raise SystemExit("--bank-dtype f16 / bf16 applies to the patch-token bank (-mp False -ct False)")
         mod = model.module
@@ -144,7 +148,11 @@ def main():
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             search.standardise_(bank, mean_feats, std_feats)
             avg, w = determine_target_features(tl)
-            scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w, select=select)
+            if args.metric == 'cosine':
+                scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w, select=select)
+            else:                                # one token per sample: every combine is that token's distance
+                scores, idx = search.distance_topk_tokens(avg.reshape(1, -1), bank.unsqueeze(1), min(k, bank.shape[0]),
+                                                          metric=args.metric, combine=args.combine, weights=w, select=select)
         else:                                    # every patch token scored, combined per image (-c min | mean | max)
             tl = tl[:, mod.num_extra_tokens:]
             if args.bank_dtype == "f32":
@@ -164,8 +172,12 @@ def main():
             print(f'Token bank: {bank.numel() * bank.element_size() / 1e9:.3f} GB, {bank.dtype}')
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             avg, w = determine_target_features(tl)
-            scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
-                                                    weights=w, top_t=args.n_top_sims, select=select)
+            if args.metric == 'cosine':
+                scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
+                                                        weights=w, top_t=args.n_top_sims, select=select)
+            else:
+                scores, idx = search.distance_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), metric=args.metric,
+                                                          combine=args.combine, weights=w, top_t=args.n_top_sims, select=select)
         test_scores, order = scores[0], idx[0].cpu().numpy()
         ds = test_dataloader.dataset
         items = [ds[int(j)] for j in order if j >= 0]

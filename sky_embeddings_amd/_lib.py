@@ -23,6 +23,7 @@ ABI_VERSION = 111          # skyemb_version() of the library this binding was wr
 KC, RC = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU = 0, 1, 2
 COMBINE_MIN, COMBINE_MEAN, COMBINE_MAX = 0, 1, 2       # SKYEMB_COMBINE_*: how the token scores of an image are combined
+METRIC_MSE, METRIC_MAE = 1, 2                          # SKYEMB_METRIC_*: the distance metrics of the patch-token search
 
 
 class SkyembLibraryError(RuntimeError):
@@ -161,6 +162,10 @@ PROTOTYPES = {
     "skyemb_cosine_token_topk_sel": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
                                              c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_pack_select": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    # weighted MSE / MAE over a token bank: additive again
+    "skyemb_distance_token_scores": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "skyemb_distance_token_topk": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _LIB = None

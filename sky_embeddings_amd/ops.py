@@ -11,8 +11,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (ACT_DGELU, ACT_GELU, ACT_NONE, BF16, COMBINE_MAX, COMBINE_MEAN, COMBINE_MIN, F16, F32, KC, RC, AdamwDesc,
-                   GemmArgs, GemmGroupInfo, LnBwdSide, check, lib)
+from ._lib import (ACT_DGELU, ACT_GELU, ACT_NONE, BF16, COMBINE_MAX, COMBINE_MEAN, COMBINE_MIN, F16, F32, KC, METRIC_MAE, METRIC_MSE, RC,
+                   AdamwDesc, GemmArgs, GemmGroupInfo, LnBwdSide, check, lib)
 
 TORCH_DTYPE = {BF16: torch.bfloat16, F32: torch.float32, F16: torch.float16}
 LP_DTYPES = (torch.bfloat16, torch.float16)     # the two 16-bit operand formats of the MFMA kernels (SKYEMB_BF16 / SKYEMB_F16)
@@ -503,3 +503,25 @@ def cosine_token_topk(tw, qn, bank, xn, k, combine, eps, idx_offset, nlists, par
         return
     check(lib().skyemb_cosine_token_topk(_p(tw), _p(qn), _p(bank), _p(xn), Q, N, P, D, k, combine, eps, idx_offset, nlists, _p(thr0),
                                          _p(part_s), _p(part_i), _stream()), "skyemb_cosine_token_topk")
+
+
+METRIC_CODES = {"MSE": METRIC_MSE, "MAE": METRIC_MAE}     # the distance metrics of the patch-token search (SKYEMB_METRIC_*)
+
+
+def distance_token_scores(c, t, bank, metric, combine, scores, top_t=0, select=None):
+    """c [D] = fp32(w / sum(w)), t [Q, D] queries, bank [N, P, D] fp32, fp16 or bf16, metric: a METRIC_* code, combine: a COMBINE_*
+    code -> scores [Q, N] combined DISTANCES (+inf for an image the packed ``select`` words leave out).  include/skyemb.h."""
+    Q, D = t.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_distance_token_scores(_p(c), _p(t), _p(bank), bank_dtype_code(bank.dtype, "distance_token_scores"), Q, N, P, D,
+                                             metric, combine, top_t, _p(scores), _p(select), _stream()), "skyemb_distance_token_scores")
+
+
+def distance_token_topk(c, t, bank, metric, combine, k, idx_offset, nlists, part_s, part_i, thr0=None, top_t=0, select=None):
+    """Per-wave lists [Q, nlists, k] in KEY space (part_s = -distance, best first; nlists: cosine_token_topk_chunks), which
+    topk_merge merges as they are.  thr0 [Q]: key floors.  include/skyemb.h."""
+    Q, D = t.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_distance_token_topk(_p(c), _p(t), _p(bank), bank_dtype_code(bank.dtype, "distance_token_topk"), Q, N, P, D, metric,
+                                           combine, top_t, k, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i), _p(select), _stream()),
+          "skyemb_distance_token_topk")

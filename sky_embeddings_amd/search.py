@@ -459,3 +459,152 @@ def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weigh
     for lo in range(0, Q, 16):
         out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps, t, words)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the distance metrics (weighted MSE / MAE, utils/similarity.py:174-212) over the same token banks: smaller is better
+# ------------------------------------------------------------------------------------------------
+def _metric_code(metric, who):
+    if metric not in ops.METRIC_CODES:
+        raise ValueError(f"{who}: metric = {metric!r}, expected one of {sorted(ops.METRIC_CODES)} (the cosine metric is "
+                         f"cosine_topk_tokens / cosine_token_scores)")
+    return ops.METRIC_CODES[metric]
+
+
+def prepare_distance_weights(weights, D, device):
+    """c = fp32(w / sum(w)) [D] on the device, by torch: the feature weights as the distance kernels take them (None: w = 1)."""
+    w = torch.ones(D, device=device) if weights is None else weights.to(device, torch.float32).reshape(D)
+    return (w / w.sum()).contiguous()
+
+
+def _distance_scores(c, t, tokens, mcode, ccode, top_t=0, words=None):
+    out = torch.empty(t.shape[0], tokens.shape[0], device=t.device)
+    ops.distance_token_scores(c, t, tokens, mcode, ccode, out, top_t, words)
+    return out
+
+
+def _distance_sample(bank, sel, images):
+    """The floor's strided sample of ``images`` whole images [S, P, D]: a TokenBank's own (``TokenBank.sample``) or, under a
+    selection, the one that Selection keeps for it; a plain tensor is gathered anew (no norms are computed for it)."""
+    if isinstance(bank, TokenBank):
+        return bank.sample(images)[0] if sel is None else sel.sample(bank, images)[0]
+    n = bank.shape[0] if sel is None else sel.count
+    idx = torch.arange(images, device=bank.device) * (n // images)
+    return bank.index_select(0, idx if sel is None else sel.indices()[idx])
+
+
+def distance_pruning_floor(c, t, bank, k: int, metric: str = 'MAE', combine: str = 'mean', sample_images: int | None = None,
+                           top_t: int | None = None, select=None):
+    """``token_pruning_floor`` for the distance metrics, in KEY space (key = -distance): the same sample of whole images (the
+    selection's own under ``select``) is scored by the distance kernel, negated, and its k-th largest key, one ulp lower, is a
+    floor of the k-th best key of the search.  None under the same size rule (fewer than 8 x the sample's images).  ``c``:
+    ``prepare_distance_weights``; ``t`` [Q <= 16, D]; ``bank``: a [N,P,D] tensor or a TokenBank."""
+    tokens = bank.bank if isinstance(bank, TokenBank) else bank
+    N, P = tokens.shape[0], tokens.shape[1]
+    tt = _top_t_arg(top_t, P, "distance_pruning_floor")
+    mcode, ccode = _metric_code(metric, "distance_pruning_floor"), _combine_code(combine, "distance_pruning_floor")
+    sel = _selection_arg(select, N, "distance_pruning_floor", tokens.device)
+    if sample_images is None:
+        sample_images = 256 * k
+    if (N if sel is None else sel.count) < 8 * sample_images:
+        return None
+    keys = _distance_scores(c, t, _distance_sample(bank, sel, sample_images), mcode, ccode, tt).neg_()
+    floor = torch.empty(t.shape[0], device=t.device)
+    ops.kth_largest_floor(keys, k, floor)
+    return floor
+
+
+def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE', combine: str = 'mean',
+                         weights: torch.Tensor | None = None, prune: bool = True, stats: dict | None = None, top_t: int | None = None,
+                         select=None, process_group=None, world_size: int = 1):
+    """-> (distances f32 [Q,k] ascending, image indices i64 [Q,k]): exact top-k images by the combined weighted MSE / MAE distance
+    of their P patch tokens to each query (reference: compute_similarity with metric 'MSE' | 'MAE', utils/similarity.py:174-268,
+    + update_best_scores), order (distance asc, image asc).  ``bank``: a [N,P,D] tensor (fp32, fp16 or bf16) or a TokenBank (its
+    norms go unused; its weights are the feature weights, ``weights`` is then ignored); one pass per group of at most 16
+    queries.  The arithmetic and its fixed summation order are the contract in include/skyemb.h: a 16-bit bank gives the fp32
+    result on the widened bank bit for bit.
+
+    Combine, with a[0] <= a[1] <= ... the ``top_t`` smallest token distances of an image (``top_t`` None: all P): 'min' is a[0];
+    'max' the largest of those used (a[top_t-1], or the plain max); 'mean' (((0 + a[0]) + a[1]) + ...) / float32(top_t), smallest
+    first (``top_t`` None: token order, divided by P -- so top_t == P is not the plain mean).  A NaN token distance ranks as +inf
+    (torch would propagate the NaN): 'min' ignores it, 'max' and 'mean' become +inf, as they do for an image with fewer than top_t
+    finite token distances; an image whose combined distance is +inf is never returned.  Missing entries are (+inf, -1).
+
+    ``select``, ``prune``, ``stats``, ``world_size``: as for ``cosine_topk_tokens`` (the floor and the merges work on
+    key = -distance).  Every ValueError -- an unknown metric or combine, top_t outside 1 .. min(P, 16), k, a selection of
+    another length, a shape the kernels do not take -- is raised before the first launch."""
+    who = "distance_topk_tokens"
+    tokens = bank.bank if isinstance(bank, TokenBank) else bank
+    Q, D = queries.shape
+    N, P = tokens.shape[0], tokens.shape[1]
+    assert tokens.dim() == 3 and D == tokens.shape[2]
+    mcode, ccode = _metric_code(metric, who), _combine_code(combine, who)
+    tt = _top_t_arg(top_t, P, who)
+    if k < 1:
+        raise ValueError(f"{who}: k = {k}")
+    if world_size == 1 and k > N:
+        raise ValueError(f"{who}: k = {k} exceeds the {N} images of the bank")
+    ops.bank_dtype_code(tokens.dtype, who)
+    _check_token_shape(who, Q, P, D, k)
+    sel = _selection_arg(select, N, who, tokens.device)
+    words = None if sel is None else sel.words
+    dev = tokens.device
+    if isinstance(bank, TokenBank):
+        weights, idx_offset = bank.weights, bank.idx_offset
+    else:
+        idx_offset = 0
+    q = queries.to(dev, torch.float32).contiguous()
+    out_s = torch.empty(Q, k, device=dev)
+    out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
+    if Q == 0:
+        return out_s, out_i
+    c = prepare_distance_weights(weights, D, dev)
+    pruned = False
+    for lo in range(0, Q, 16):
+        t = q[lo:lo + 16]
+        Qg = t.shape[0]
+        thr0 = distance_pruning_floor(c, t, bank, k, metric, combine, top_t=top_t, select=sel) if prune else None
+        pruned = pruned or thr0 is not None
+        nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
+        ps = torch.empty(Qg, nl, k, device=dev)
+        pi = torch.empty(Qg, nl, k, device=dev, dtype=torch.int64)
+        ops.distance_token_topk(c, t, tokens, mcode, ccode, k, idx_offset, nl, ps, pi, thr0, tt, words)
+        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + 16], out_i[lo:lo + 16], torch.empty(Qg, device=dev, dtype=torch.int32))
+    if stats is not None:
+        stats.update(path="tokens", metric=metric, groups=(Q + 15) // 16, pruned=pruned)
+        if top_t is not None:
+            stats.update(top_t=tt)
+        if sel is not None:
+            stats.update(selected=sel.count)
+    if world_size > 1:
+        from .distributed import gather_topk
+        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # keys: [Q, world, k]
+        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    return out_s.neg_(), out_i                                          # keys -> distances: (-inf, -1) becomes (+inf, -1)
+
+
+def distance_token_scores(queries: torch.Tensor, bank, metric: str = 'MAE', combine: str = 'mean', weights: torch.Tensor | None = None,
+                          top_t: int | None = None, select=None):
+    """[Q, N] combined weighted MSE / MAE distance of every image of a [N,P,D] token bank (fp32, fp16 or bf16; or a TokenBank, whose
+    weights then replace ``weights``), in groups of at most 16 queries; ``metric``, ``combine``, ``top_t`` and the NaN rule as for
+    ``distance_topk_tokens``.  ``select``: every [Q, N] slot is written, a deselected image gets +inf."""
+    who = "distance_token_scores"
+    tokens = bank.bank if isinstance(bank, TokenBank) else bank
+    Q, D = queries.shape
+    assert tokens.dim() == 3 and D == tokens.shape[2]
+    mcode, ccode = _metric_code(metric, who), _combine_code(combine, who)
+    tt = _top_t_arg(top_t, tokens.shape[1], who)
+    ops.bank_dtype_code(tokens.dtype, who)
+    _check_token_shape(who, Q, tokens.shape[1], D, 1)
+    sel = _selection_arg(select, tokens.shape[0], who, tokens.device)
+    words = None if sel is None else sel.words
+    if isinstance(bank, TokenBank):
+        weights = bank.weights
+    q = queries.to(tokens.device, torch.float32).contiguous()
+    out = torch.empty(Q, tokens.shape[0], device=tokens.device)
+    if Q == 0:
+        return out
+    c = prepare_distance_weights(weights, D, tokens.device)
+    for lo in range(0, Q, 16):
+        out[lo:lo + 16] = _distance_scores(c, q[lo:lo + 16], tokens, mcode, ccode, tt, words)
+    return out

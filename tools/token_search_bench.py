@@ -7,7 +7,7 @@ usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim
                                          [--bank-dtype f32 | f16 | bf16 | a comma list, e.g. f32,f16,bf16]
                                          [--combine min | mean | max | a comma list] [--top-t T | a comma list, e.g. 4,16]
                                          [--select-frac F | a comma list, e.g. 1.0,0.5,0.1] [--select-pattern random | runs]
-                                         [--fused-only]
+                                         [--fused-only] [--metric MAE | MSE | a comma list]
 --bank-dtype: element type(s) of the resident token bank the fused pass runs on (16-bit banks: the fp32 bank rounded to nearest);
 the fused variants of every listed type run interleaved in the same rounds, named fused_tokens[f16] etc.; the comparison variants
 (baseline and one-vector) need the fp32 bank and run when f32 is listed.
@@ -25,6 +25,12 @@ of the kernel's switch alone).  --select-pattern random: Bernoulli(F) per image,
 images, a run selected with probability F.  "bank_bytes" of a _sel leg counts the selected images only (the bytes the kernel has
 to read when P is a multiple of 16); "equals_compact" says whether the two legs returned the same lists (indices mapped back).
 --fused-only leaves out the comparison variants (baseline, one-vector): memory for the compacted banks.
+--metric: for every listed distance metric and every listed bank type, in the same interleaved rounds, the fused distance pass
+(fused_distance[MAE] etc.: search.distance_topk_tokens, combine as --combine, with its pruning floor; fused_distance_no_floor[MAE]
+without) and, with f32 listed and no --fused-only, the torch formula on the same resident bank (torch_distance[MAE]:
+utils.similarity.weighted_MAE / weighted_MSE per query over slabs of images -- the elementwise temporaries of the whole bank would
+not fit next to it --, the reduce over the P tokens, torch.topk(largest=False)).  "fused_equals_baseline" of these legs compares
+indices exactly and distances to 1e-5 relative (torch's summation order differs from the contract's).
 Bytes counted per pass: images x tokens x dim x element size (the bank; norms and lists are under 0.4 % of it).  Peak: 8.0 TB/s
 (spec)."""
 import argparse
@@ -62,6 +68,13 @@ def combines(text):
     names = [t.strip() for t in text.split(",") if t.strip()]
     if not names or any(n not in ("min", "mean", "max") for n in names):
         raise argparse.ArgumentTypeError(f"expected min, mean, max or a comma list of them, got {text!r}")
+    return names
+
+
+def metrics(text):
+    names = [t.strip() for t in text.split(",") if t.strip()]
+    if not names or any(n not in ("MAE", "MSE") for n in names):
+        raise argparse.ArgumentTypeError(f"expected MAE, MSE or a comma list of them, got {text!r}")
     return names
 
 
@@ -107,6 +120,7 @@ def main():
     ap.add_argument("--select-frac", type=float_list, default=[])
     ap.add_argument("--select-pattern", choices=("random", "runs"), default="random")
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--metric", type=metrics, default=[])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("token_search_bench.py needs a GPU")
@@ -160,6 +174,16 @@ def main():
                 parts.append(reducers[combine](sc, dim=2))
             return torch.topk(torch.cat(parts, dim=1), k, dim=1)
 
+        def torch_distance(metric, combine):
+            from sky_embeddings_amd.utils.similarity import weighted_MAE, weighted_MSE
+            fn = weighted_MAE if metric == "MAE" else weighted_MSE
+            slab = max(1, (1 << 27) // (P * D))             # images per slab: 512 MiB of fp32 temporaries per elementwise step
+            parts = []
+            for s in range(0, N, slab):
+                d = torch.stack([fn(q[j], bank[s:s + slab], w) for j in range(Q)])      # [Q, slab, P]
+                parts.append(reducers[combine](d, dim=2))
+            return torch.topk(torch.cat(parts, dim=1), k, dim=1, largest=False)
+
         variants, nbytes, same, combine_of, more = {}, {}, {}, {}, {}
         for combine in a.combine:
             tag = "" if len(a.combine) == 1 else f"/{combine}"
@@ -201,6 +225,20 @@ def main():
                     nbytes[v + tag] = sel.count * P * D * b.bank.element_size()
                     more[v + tag] = dict(extra[frac, name], equals_compact=bool(torch.equal(ss, cs)) and bool(torch.equal(si, back)))
                 mine.update(pair)
+            for metric in a.metric:
+                for name, b in banks.items():
+                    sfx = f"[{metric}]" if name == "f32" else f"[{metric},{name}]"
+                    pair = {f"fused_distance{sfx}": lambda b=b, m=metric, c=combine: search.distance_topk_tokens(q, b, k, m, c),
+                            f"fused_distance_no_floor{sfx}": lambda b=b, m=metric, c=combine: search.distance_topk_tokens(q, b, k, m, c, prune=False)}
+                    for v in pair:
+                        nbytes[v + tag] = elems * b.bank.element_size()
+                    mine.update(pair)
+                if with_f32 and not a.fused_only:
+                    mine[f"torch_distance[{metric}]"] = lambda m=metric, c=combine: torch_distance(m, c)
+                    (ts_, ti_), (fs_, fi_) = torch_distance(metric, combine), search.distance_topk_tokens(q, tb, k, metric, combine)
+                    agree = bool(torch.equal(fi_, ti_)) and bool(torch.allclose(fs_, ts_, rtol=1e-5, atol=0))
+                    for v in (f"fused_distance[{metric}]", f"fused_distance_no_floor[{metric}]", f"torch_distance[{metric}]"):
+                        more[v + tag] = dict(more.get(v + tag, {}), fused_equals_baseline=agree)
             for v, fn in mine.items():
                 variants[v + tag] = fn
                 combine_of[v + tag] = combine
@@ -221,7 +259,7 @@ def main():
             results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, combine=combine_of[name], variant=name, ms_median=round(med, 4),
                                 ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), bank_bytes=nb,
                                 tb_per_s=round(nb / (med * 1e-3) / 1e12, 3), hbm_peak_fraction=round(nb / (med * 1e-3) / HBM_PEAK, 4),
-                                fused_equals_baseline=same.get(combine_of[name]), **more.get(name, {})))
+                                **dict(dict(fused_equals_baseline=same.get(combine_of[name])), **more.get(name, {}))))
             print(json.dumps(results[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
