@@ -204,7 +204,10 @@ int skyemb_random_mask_from_noise(const float *noise, int B, int L, int keep, in
 /* SimMIM mask generator on the device (replaces utils/dataloaders.py:197-219 MaskGenerator.__call__, which runs per item in
  * the loader workers): per sample ratio = ratio_u[b] * max_ratio, count = ceil(L * ratio); per channel the `count` patches
  * with the smallest noise[b, c, :] are masked (a uniformly random subset, like randperm(L)[:count]); out_mask float 0 / 1
- * [B, C, grid*p, grid*p].  noise [B, C, L] and ratio_u [B] are uniform [0, 1) draws supplied by the caller. */
+ * [B, C, grid*p, grid*p].  noise [B, C, L] and ratio_u [B] are uniform [0, 1) draws supplied by the caller.
+ * Both generators take L <= 4096 (here L == grid * grid, p % 4 == 0, 0 <= max_ratio <= 1): a row of noise is ranked in LDS, 16 L
+ * bytes per workgroup in skyemb_random_mask_from_noise (64 KB at the limit) and 32 L bytes here (128 KB at the limit; above 64 KB
+ * the kernel's dynamic-LDS limit is raised first).  Any other shape returns 1 before any launch, skyemb_last_error set. */
 int skyemb_simmim_mask_from_noise(const float *noise, const float *ratio_u, double max_ratio, int B, int C, int L, int grid, int p,
                                   float *out_mask, void *stream);
 

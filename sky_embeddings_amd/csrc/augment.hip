@@ -17,6 +17,16 @@ struct Taps {
 // torch's separable anti-aliased bilinear weights (aten UpSampleKernel.cpp, _compute_indices_min_size_weights_aa):
 // scale = in / out, support = max(scale, 1), centre = scale * (o + 0.5), taps [centre - support + 0.5, centre + support + 0.5)
 __device__ __forceinline__ Taps taps_of(int o, int in_size, int out_size) {
+    if (in_size == out_size) {
+        // torch skips a pass that does not resize.  The formula below gives the same value (weights 1 and 0) but reads the next
+        // pixel with weight zero, and 0 * NaN would blank a pixel that torch leaves alone.
+        Taps t;
+        t.lo = o;
+        t.n = 1;
+        t.w[0] = 1.0f;
+        t.w[1] = t.w[2] = 0.f;
+        return t;
+    }
     const float scale = (float)in_size / (float)out_size;
     const float support = scale >= 1.0f ? scale : 1.0f, invscale = scale >= 1.0f ? 1.0f / scale : 1.0f;
     const float center = scale * ((float)o + 0.5f);

@@ -314,6 +314,11 @@ extern "C" int skyemb_simmim_mask_from_noise(const float *noise, const float *ra
                                              int p, float *out_mask, void *stream) {
     SKY_CHECK_ARG(noise && ratio_u && out_mask && B > 0 && C > 0 && L == grid * grid && L <= 4096 && p > 0 && p % 4 == 0 &&
                   max_ratio >= 0.0 && max_ratio <= 1.0, "skyemb_simmim_mask_from_noise: bad arguments (L=%d grid=%d p=%d)", L, grid, p);
+    // 8 L floats of LDS: above 64 KB from L = 2049 (grid 46), 128 KB at the L = 4096 the header admits; a launch above 64 KB
+    // needs the kernel's limit raised first (once, to the largest request: the helper remembers the kernel, not the size)
+    if ((size_t)8 * L * sizeof(float) > 65536)
+        if (const int rc = sky_set_lds_limit((const void *)simmim_mask_kernel, 8 * 4096 * (int)sizeof(float), "skyemb_simmim_mask_from_noise"))
+            return rc;
     hipLaunchKernelGGL(simmim_mask_kernel, dim3((B * C + 3) / 4), dim3(256), (size_t)8 * L * sizeof(float), (hipStream_t)stream, noise,
                        ratio_u, max_ratio, B * C, C, L, grid, p, out_mask);
     SKY_LAUNCH_CHECK("skyemb_simmim_mask_from_noise");
