@@ -334,6 +334,19 @@ int skyemb_adamw(float *p, void *g, float *m, float *v, void *p_lp, int dtype, i
                  const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps, float wd,
                  float grad_scale, int zero_grad, int grad_dtype, void *stream);
 int skyemb_cast(const float *src, void *dst, int dtype, int64_t n, void *stream);
+/* Overflow guard of an optimiser step whose gradients carry a DYNAMIC loss scale (the downstream predictor in fp16: its loss is the
+ * caller's code, so no scale can be planned ahead).  Additive to ABI version 111.
+ * skyemb_grad_probe: one read of the `n` gradients at `g` (grad_dtype SKYEMB_F32 / SKYEMB_F16 / SKYEMB_BF16; n % 4 == 0, alignment
+ * as skyemb_adamw: 16 bytes for fp32, 8 for the 16-bit formats).  `state`: two device words the caller zeroes once per step; launches
+ * ACCUMULATE into them: state[0] becomes non-zero if any element is +-inf or NaN (exponent field all ones; +-0 and subnormals are
+ * finite), state[1] is the bit pattern, as fp32, of the largest finite |g| (non-negative floats order like their unsigned bits).
+ * skyemb_adamw_guarded: skyemb_adamw's kernel with `skip` = that state: skip[0] != 0 -> the launch writes NOTHING (p, m, v, p_lp
+ * untouched, g not zeroed); skip[0] == 0 -> bit-identical to skyemb_adamw.  Stream order is the contract: every probe of a step
+ * first, then its guarded launches, all on one stream. */
+int skyemb_grad_probe(const void *g, int grad_dtype, int64_t n, uint32_t *state, void *stream);
+int skyemb_adamw_guarded(float *p, void *g, float *m, float *v, void *p_lp, int dtype, int64_t n, int64_t n_decay,
+                         const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps, float wd,
+                         float grad_scale, int zero_grad, int grad_dtype, const uint32_t *skip, void *stream);
 
 /* ------------------------------------------------------------ input feeder -
  * utils/dataloaders.py:285-328 (H5Dataset.__getitem__): the reference opens the file and reads ONE cutout per python

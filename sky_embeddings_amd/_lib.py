@@ -123,6 +123,10 @@ PROTOTYPES = {
     "skyemb_adamw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32,
                              c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_vp]),
     "skyemb_cast": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_vp]),
+    # overflow guard of a dynamically scaled optimiser step: additive to ABI version 111
+    "skyemb_grad_probe": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp]),
+    "skyemb_adamw_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32,
+                                     c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp]),
     "skyemb_standardise": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "skyemb_weighted_norms": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "skyemb_cosine_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32]),

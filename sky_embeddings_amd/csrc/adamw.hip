@@ -13,7 +13,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float *__restrict__ p, GT *_
                                                     float *__restrict__ v, T *__restrict__ p_lp, int64_t n4,
                                                     int64_t n_decay, const float *__restrict__ hyper, float lr_arg,
                                                     float bc1_arg, float bc2_arg, float beta1, float beta2, float eps,
-                                                    float wd, float grad_scale, int zero_grad) {
+                                                    float wd, float grad_scale, int zero_grad,
+                                                    const uint32_t *__restrict__ skip) {
+    // overflow guard (skyemb_adamw_guarded): a gradient probe earlier on the stream left a non-zero word -> the launch writes
+    // nothing.  One word read by every thread: the branch is uniform.  nullptr (skyemb_adamw): no guard
+    if (skip && *skip) return;
     // hyper (device) wins when given: kernel arguments are frozen inside a captured HIP graph
     const float lr = hyper ? hyper[0] : lr_arg, bc1 = hyper ? hyper[1] : bc1_arg, bc2 = hyper ? hyper[2] : bc2_arg;
     const SkyAdamScalars sc = sky_adam_scalars(lr, bc1, bc2, beta1, beta2, eps, wd, grad_scale);
@@ -70,9 +74,9 @@ extern "C" int skyemb_set_scalars(float *dst, float a, float b, float c, float d
     return 0;
 }
 
-extern "C" int skyemb_adamw(float *p, void *g, float *m, float *v, void *p_lp, int dtype, int64_t n, int64_t n_decay,
-                            const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps,
-                            float wd, float grad_scale, int zero_grad, int grad_dtype, void *stream) {
+static int adamw_launch(const char *who, float *p, void *g, float *m, float *v, void *p_lp, int dtype, int64_t n, int64_t n_decay,
+                        const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps, float wd,
+                        float grad_scale, int zero_grad, int grad_dtype, const uint32_t *skip, void *stream) {
     SKY_CHECK_ARG(n > 0 && n % 4 == 0 && n_decay >= 0 && n_decay <= n, "skyemb_adamw: n must be a positive multiple of 4");
     SKY_CHECK_ARG(aligned16(p) && aligned16(m) && aligned16(v) && (((uintptr_t)g) & 7) == 0, "skyemb_adamw: unaligned buffers");
     SKY_CHECK_ARG(grad_dtype == SKYEMB_F32 || sky_is_lp(grad_dtype), "skyemb_adamw: bad grad_dtype %d", grad_dtype);
@@ -84,7 +88,7 @@ extern "C" int skyemb_adamw(float *p, void *g, float *m, float *v, void *p_lp, i
     dim3 grid((unsigned)blocks), block(256);
 #define ADAMW_LAUNCH(T, LP, GT, lp_ptr)                                                                                        \
     hipLaunchKernelGGL((adamw_kernel<T, LP, GT>), grid, block, 0, st, p, (GT *)g, m, v, lp_ptr, n / 4, n_decay, hyper, lr, bc1, \
-                       bc2, beta1, beta2, eps, wd, grad_scale, zero_grad)
+                       bc2, beta1, beta2, eps, wd, grad_scale, zero_grad, skip)
     const bool g16 = grad_dtype == SKYEMB_BF16, gh = grad_dtype == SKYEMB_F16;
     if (!p_lp) {
         if (g16) ADAMW_LAUNCH(float, false, bf16_t, (float *)nullptr);
@@ -102,6 +106,22 @@ extern "C" int skyemb_adamw(float *p, void *g, float *m, float *v, void *p_lp, i
         else ADAMW_LAUNCH(float, true, float, (float *)p_lp);
     }
 #undef ADAMW_LAUNCH
-    SKY_LAUNCH_CHECK("skyemb_adamw");
+    SKY_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int skyemb_adamw(float *p, void *g, float *m, float *v, void *p_lp, int dtype, int64_t n, int64_t n_decay,
+                            const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps,
+                            float wd, float grad_scale, int zero_grad, int grad_dtype, void *stream) {
+    return adamw_launch("skyemb_adamw", p, g, m, v, p_lp, dtype, n, n_decay, hyper, lr, bc1, bc2, beta1, beta2, eps, wd, grad_scale,
+                        zero_grad, grad_dtype, nullptr, stream);
+}
+
+// skyemb_adamw behind the overflow flag of skyemb_grad_probe (grad_guard.hip): the same kernel, the same bits when the flag is 0
+extern "C" int skyemb_adamw_guarded(float *p, void *g, float *m, float *v, void *p_lp, int dtype, int64_t n, int64_t n_decay,
+                                    const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps,
+                                    float wd, float grad_scale, int zero_grad, int grad_dtype, const uint32_t *skip, void *stream) {
+    SKY_CHECK_ARG(skip != nullptr && (((uintptr_t)skip) & 3) == 0, "skyemb_adamw_guarded: null or unaligned skip word");
+    return adamw_launch("skyemb_adamw_guarded", p, g, m, v, p_lp, dtype, n, n_decay, hyper, lr, bc1, bc2, beta1, beta2, eps, wd,
+                        grad_scale, zero_grad, grad_dtype, skip, stream);
 }

@@ -322,6 +322,23 @@ def adamw(p, g, m, v, p_lp, n, n_decay, hyper, beta1, beta2, eps, wd, grad_scale
                              beta2, eps, wd, grad_scale, int(zero_grad), dtype_code(g.dtype), _stream()), "skyemb_adamw")
 
 
+def grad_probe(g, n, state):
+    """Accumulates into `state` (device int32[2], zeroed by the caller once per step) whether any of the n gradients at g is
+    +-inf / NaN (state[0] != 0) and the largest finite |g| (state[1]: its fp32 bits); see include/skyemb.h."""
+    assert state.dtype == torch.int32 and state.numel() >= 2
+    check(lib().skyemb_grad_probe(_p(g), dtype_code(g.dtype), n, _p(state), _stream()), "skyemb_grad_probe")
+
+
+def adamw_guarded(p, g, m, v, p_lp, n, n_decay, hyper, beta1, beta2, eps, wd, skip, grad_scale=1.0, zero_grad=False, lr=0.0,
+                  bc1=1.0, bc2=1.0):
+    """adamw() that writes nothing when skip[0] != 0 (skip: the state of grad_probe, earlier on the same stream)."""
+    assert skip.dtype == torch.int32
+    code = dtype_code(p_lp.dtype) if p_lp is not None else F32
+    check(lib().skyemb_adamw_guarded(_p(p), _p(g), _p(m), _p(v), _p(p_lp), code, n, n_decay, _p(hyper), lr, bc1, bc2, beta1,
+                                     beta2, eps, wd, grad_scale, int(zero_grad), dtype_code(g.dtype), _p(skip), _stream()),
+          "skyemb_adamw_guarded")
+
+
 def set_scalars(dst, a, b=0.0, c=0.0, d=0.0):
     check(lib().skyemb_set_scalars(_p(dst), a, b, c, d, _stream()), "skyemb_set_scalars")
 

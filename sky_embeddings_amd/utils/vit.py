@@ -28,6 +28,7 @@ import torch
 
 from .. import ops
 from ..engine import MAEEngine
+from ..loss_scale import make_loss_scaler
 from ..model_config import MODEL_TYPES, config_for
 from ..predictor_head import PredictorHead
 from .lr_decay import param_groups_lrd
@@ -58,17 +59,26 @@ class VisionTransformer:
     """utils/vit.py:258-393."""
 
     def __init__(self, cfg, device, compute_dtype, num_classes=0, global_pool='token', label_means=(0.0,), label_stds=(1.0,),
-                 drop_rate=0.0, seed=None):
+                 drop_rate=0.0, seed=None, loss_scale=None):
+        """loss_scale: None, or 'dynamic' | a power of two (fixed) | a loss_scale.LossScaler -- d loss / d predictions enters the
+        backward schedules times the scaler's factor, PredictorOptimizer probes the gradients, skips the step they overflowed in and
+        divides the factor out (any compute dtype; what compute_dtype = torch.float16 needs)."""
         if global_pool not in ('', 'avg', 'token', 'map'):
             raise ValueError(f"global_pool = {global_pool!r}")
         self.cfg = cfg
-        if compute_dtype == torch.float16:
+        self.scaler = make_loss_scaler(loss_scale) if loss_scale is not None else None
+        if compute_dtype == torch.float16 and self.scaler is None:
             # the predictor's loss lives in the caller's torch code: its backward enters the engine unscaled, and fp16 data gradients
-            # need the static loss scale the MIM engines apply in their own loss kernels
-            raise NotImplementedError("the downstream predictor runs in bf16 or f32 (compute_dtype = f16 is a pretraining mode)")
+            # need a loss scale -- which, for an arbitrary loss, only the dynamic scaler can find (loss_scale = 'dynamic')
+            raise NotImplementedError("the downstream predictor runs in bf16 or f32; compute_dtype = f16 needs loss_scale = 'dynamic' "
+                                      "(or a fixed power of two)")
         self.engine = MAEEngine(cfg, device=device, compute_dtype=compute_dtype, seed=seed)
         self.engine.fold_decoder_wgrads = False      # backward_decoder never runs here: its folded weight gradients would read garbage
         dev = self.engine.device
+        self._backward_scale = 1.0                   # the factor the gradient buffers of the last backward carry
+        if self.scaler is not None:
+            self.engine.loss_scale = 1.0             # the scaler owns the factor: the engine plans none of its own
+            self.scaler.to(dev)
         self.patch_embed = _PatchEmbedInfo(cfg)
         self.num_extra_tokens, self.attn_pool, self.simmim = cfg.num_extra_tokens, None, False
         self.in_chans, self.pixel_mean, self.pixel_std, self.ra_dec = cfg.in_chans, cfg.pixel_mean, cfg.pixel_std, cfg.ra_dec
@@ -214,6 +224,11 @@ class VisionTransformer:
         dlat = w["dln"][:Me * D].view(Me, D)                      # the final norm's incoming gradient (compute dtype)
         if self.num_classes <= 0:
             raise NotImplementedError("backward through a model without a classifier")
+        if self.scaler is not None:
+            # every later step of backward is linear in d predictions: the gradient buffers hold scale x the gradients, and the
+            # optimiser divides the (power-of-two) factor out again.  [B, num_classes] elementwise: glue.
+            self._backward_scale = self.scaler.scale
+            dpred = dpred * self._backward_scale
         dfeat = hd.backward(dpred, B, Ne, tokens_lp=w["lat_lp"], dtokens_lp=dlat)
         if self.global_pool == 'avg':
             if self.frozen_encoder:
@@ -238,6 +253,12 @@ class VisionTransformer:
         eng.start_backward_at("norm")
         eng.backward_encoder()
         eng.backward_embed()
+
+    def unscaled_grad(self, name):
+        """d loss / d tensor `name` of the last backward, without the loss scale its storage carries."""
+        hs = self._head_mod.store
+        g = hs.grad(name) if name in hs.offsets else self.engine.store.grad(name)
+        return g.clone() if self._backward_scale == 1.0 else g / self._backward_scale
 
     def forward_head(self, x, pre_logits=False):
         """timm VisionTransformer.forward_head on a token tensor [B, N, D] (inference): pooling, fc_norm, classifier -- the head's
@@ -287,6 +308,7 @@ class PredictorOptimizer:
             g["initial_lr"] = g["lr"]
             self.param_groups.append(g)
         self.step_count = 0
+        self._ranges = None
 
     def zero_grad(self, set_to_none=True):
         """Nothing to do: every backward overwrites the gradient buffers (engine and head) it computes."""
@@ -302,10 +324,39 @@ class PredictorOptimizer:
         n = (int(np.prod(st.shapes[name])) + 7) // 8 * 8
         return tuple(b[o:o + n] for b in (st.p, st.g, st.m, st.v, st.p_lp)), st
 
+    def _probe_ranges(self):
+        """The gradient elements a step consumes as few contiguous slices of the flat gradient buffers as they form: the runs of the
+        stepped tensors, adjacent ones joined.  Frozen tensors and the engine's unused MAE decoder are in no group: their gradient
+        storage is stale and is not looked at."""
+        if self._ranges is None:
+            spans = defaultdict(list)
+            for name in self._names():
+                (_, gr, _, _, _), store = self._buffers(name)
+                lo = gr.storage_offset()
+                spans[id(store)].append((lo, lo + gr.numel(), store))
+            self._ranges = []
+            for runs in spans.values():
+                runs.sort(key=lambda r: r[:2])
+                lo, hi, store = runs[0]
+                for a, b, _ in runs[1:]:
+                    if a == hi:
+                        hi = b
+                    else:
+                        self._ranges.append(store.g[lo:hi])
+                        lo, hi = a, b
+                self._ranges.append(store.g[lo:hi])
+        return self._ranges
+
     def step(self):
-        self.step_count += 1
-        t = self.step_count
+        scaler = getattr(self.model, "scaler", None)
+        t = self.step_count + 1
         eps = self.defaults["eps"]
+        if scaler is not None:
+            # probes first, guarded launches after, on one stream: a step whose gradients overflowed writes nothing
+            scaler.begin_step()
+            for r in self._probe_ranges():
+                scaler.probe(r)
+            unscale = 1.0 / self.model._backward_scale
         for g in self.param_groups:
             lr, wd = g["lr"], g["weight_decay"]
             b1, b2 = g["betas"]
@@ -313,7 +364,14 @@ class PredictorOptimizer:
             for name in g["params"]:
                 (p, gr, m, v, p_lp), _ = self._buffers(name)
                 n = p.numel()
-                ops.adamw(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, lr=lr, bc1=bc1, bc2=bc2)
+                if scaler is None:
+                    ops.adamw(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, lr=lr, bc1=bc1, bc2=bc2)
+                else:
+                    ops.adamw_guarded(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, scaler.state,
+                                      grad_scale=unscale, lr=lr, bc1=bc1, bc2=bc2)
+        # a skipped step does not count: its retry uses the same t (bias corrections) -- the lr schedule moves on regardless
+        if scaler is None or scaler.finish_step():
+            self.step_count = t
 
     def _names(self):
         return [n for g in self.param_groups for n in g["params"]]
@@ -336,7 +394,10 @@ class PredictorOptimizer:
             d["params"] = list(range(k, k + len(g["params"])))
             k += len(g["params"])
             groups.append(d)
-        return {"state": state, "param_groups": groups, "param_names": names}
+        out = {"state": state, "param_groups": groups, "param_names": names}
+        if getattr(self.model, "scaler", None) is not None:
+            out["loss_scaler"] = self.model.scaler.state_dict()
+        return out
 
     def load_state_dict(self, sd):
         """Accepts torch's layout (the reference's checkpoints: ids in group order) and this repo's earlier name-keyed one."""
@@ -354,6 +415,8 @@ class PredictorOptimizer:
             for k in ("lr", "initial_lr", "weight_decay", "betas"):
                 if k in saved:
                     g[k] = tuple(saved[k]) if k == "betas" else saved[k]
+        if "loss_scaler" in sd and getattr(self.model, "scaler", None) is not None:
+            self.model.scaler.load_state_dict(sd["loss_scaler"])
 
 
 def apply_onecycle_side_effects(optimizer, max_lr, div_factor=25.0, max_momentum=0.95, final_div_factor=1e4):
@@ -454,16 +517,23 @@ def build_model(config, mae_config, model_filename, mae_filename, device, build_
             num_labels = num_labels // 2
     else:
         num_labels = 0                           # similarity_search.py routes through forward_features only
-    dt = _compute_dtype(mae_config, default='bf16')
-    if dt == torch.float16:      # (a pretraining ini that names f16: the predictor's loss is the caller's torch code -- no loss scale -- so bf16)
-        dt = torch.bfloat16
+    # opt-in through the predictor's own ini: [TRAINING] loss_scale = dynamic | <power of two> turns the scaler on, and then
+    # compute_dtype (the predictor's [TRAINING] section first, the MAE ini otherwise) is honoured as written, f16 included
+    tr_own = config['TRAINING'] if 'TRAINING' in config else {}
+    loss_scale = tr_own.get('loss_scale')
+    if loss_scale is not None:
+        dt = _compute_dtype(config if 'compute_dtype' in tr_own else mae_config, default='bf16')
+    else:
+        dt = _compute_dtype(mae_config, default='bf16')
+        if dt == torch.float16:      # (a pretraining ini that names f16: without a loss scale of the predictor's own, bf16)
+            dt = torch.bfloat16
     model = VisionTransformer(cfg, device, dt, num_classes=num_labels,
                               global_pool=config['ARCHITECTURE'].get('global_pool', 'token'),
                               # utils/vit.py:38-39 as written: the LENGTHS of the configured lists -- 1 for every shipped ini, so
                               # labels are normalised as (y - 1) / 1 whatever the ini says (label_stds = [0] in all cls_*.ini)
                               label_means=len(ast.literal_eval(data['label_means'])) if 'label_means' in data else 1,
                               label_stds=len(ast.literal_eval(data['label_stds'])) if 'label_stds' in data else 1,
-                              drop_rate=float(ast.literal_eval(config['ARCHITECTURE'].get('dropout', '0.0'))))
+                              drop_rate=float(ast.literal_eval(config['ARCHITECTURE'].get('dropout', '0.0'))), loss_scale=loss_scale)
     model = _DataParallelShim(model)
     if not build_optimizer:
         return load_model(model, model_filename, mae_filename)

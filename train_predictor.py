@@ -70,6 +70,9 @@ def main(args):
     model, losses, cur_iter, optimizer, lr_scheduler = build_model(config, mae_config, best_filename if os.path.exists(best_filename) else model_filename,
                                                                    mae_filename, device, build_optimizer=True)
     tr = config['TRAINING']
+    scaler = model.module.scaler
+    print('GEMM operand format: %s' % str(model.module.engine.dtype).replace('torch.', '') +
+          ('' if scaler is None else ', %s loss scale, now %g' % ('dynamic' if scaler.dynamic else 'fixed', scaler.scale)))
     loss_fn = tr['loss_fn']
     use_label_errs = str2bool(tr.get('use_label_errs', 'False'))
     num_workers = max(1, min(os.cpu_count(), 12) - 1)
@@ -113,6 +116,8 @@ def main(args):
                 for tag, name in (('train', 'Training'), ('val', 'Validation')):
                     print('\t%s Dataset\n\t\tTotal Loss: %0.3e' % (name, losses[tag + '_loss'][-1]))
                     print(('\t\tMAE: %0.3e' if metric == 'mae' else '\t\tAccuracy: %0.3f') % (losses[f'{tag}_{metric}'][-1]))
+                if scaler is not None:
+                    print('\tLoss scale: %g, skipped steps: %i, largest |gradient|: %0.3e' % (scaler.scale, scaler.skipped_steps, scaler.last_absmax))
                 losses_cp = defaultdict(list)
                 if losses['val_loss'][-1] < best_val_loss:
                     best_val_loss = losses['val_loss'][-1]
