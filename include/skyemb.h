@@ -610,6 +610,50 @@ int skyemb_distance_token_topk(const float *c, const float *t, const void *bank,
                                int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists, const float *thr0,
                                float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
 
+/* ------------------------------------------------------- linear-probe fits -
+ * (additive to ABI version 111: nothing above changes.)  utils/pretrain_fns.py:52-159 fits two scikit-learn estimators on the
+ * host every `verbose_iters` iterations: StandardScaler + LogisticRegression(lbfgs, C = 0.01) on `class` and
+ * ElasticNet(alpha = 1e-4, l1_ratio = 0.9) on `zspec`.  These calls are the device side of the same fits
+ * (sky_embeddings_amd/probe.py drives them; csrc/probe.hip).  No atomics: every sum has one order that the shapes alone fix
+ * (SKYEMB_PROBE_CHUNKS row chunks added in chunk order, fixed trees, one thread per output), so results depend neither on
+ * launch geometry nor on the row strides ldx / ldo (elements, >= F).  Bad shapes and null pointers return 1 before any launch.
+ *
+ *   skyemb_probe_colstats   X [n, F] fp32 -> mean, var (population), scale = sqrt(var), exactly 1 where var == 0
+ *                           (StandardScaler's rule), all fp64 [F], two passes (sum, then sum of squared deviations).
+ *                           ws: fp64 [SKYEMB_PROBE_CHUNKS * F].
+ *   skyemb_probe_scale      out[i, f] = fp32((X[i, f] - mean[f]) / scale[f]) in fp64, one rounding; scale == NULL: centre only.
+ *                           Any rows (the held-out split takes the fit split's mean / scale); out may be X.
+ *   skyemb_probe_softmax_loss_grad   multinomial logistic regression, 3 <= K <= 16 classes, F <= SKYEMB_PROBE_MAX_F:
+ *                           loss = (1 / m) sum_i CE_i + 0.5 l2 ||W||^2 (fp64, device), gW [K, F] = R^T X + l2 W, gb [K] = column
+ *                           sums of R, R = (softmax - onehot) / m.  X [m, F], W [K, F], b [K] fp32, y int32 in [0, K).
+ *                           Logits, max-subtracted softmax and R in fp32; row losses, the chunk sums of gW, gb and ||W||^2 are
+ *                           added in fp64; gW, gb are stored as fp32.  ws: skyemb_probe_softmax_ws_bytes(m, F, K) bytes, 8-byte
+ *                           aligned (-1 for a refused shape).
+ *   skyemb_probe_gram       Xc [m, F] fp32 (centred), yc [m] fp32 -> G = Xc^T Xc fp64 [F, F] (symmetric bit for bit), q = Xc^T yc
+ *                           fp64 [F], ynorm2 = ||yc||^2 (one fp64): inputs widened exactly, fp64 fma chains over the rows in
+ *                           ascending order.  F <= SKYEMB_PROBE_MAX_F.
+ *   skyemb_probe_enet_cd    cyclic coordinate descent (scikit-learn's selection = 'cyclic', Gram form) from w = 0 by ONE persistent
+ *                           workgroup, w and H = G w fp64 in LDS: for j = 0 .. F-1 with G[j, j] != 0:
+ *                             t = (q[j] - H[j]) + w[j] G[j, j];  w[j] = sign(t) max(|t| - a1, 0) / (G[j, j] + b2);  H += dw G[:, j].
+ *                           After a sweep with max|dw| / max|w| < tol, or max|w| == 0, or the last one: the duality gap of
+ *                           scikit-learn's enet_coordinate_descent_gram; stop when gap < tol * ynorm2.
+ *                           a1 = alpha l1_ratio m, b2 = alpha (1 - l1_ratio) m.  -> w fp64 [F], status int32[2] = {sweeps run,
+ *                           1 if the gap test passed else 0}, gap (the last one computed; tol + 1 if none). */
+#define SKYEMB_PROBE_CHUNKS 32
+#define SKYEMB_PROBE_MAX_F 4096
+#define SKYEMB_PROBE_MIN_K 3
+#define SKYEMB_PROBE_MAX_K 16
+int skyemb_probe_colstats(const float *X, int64_t ldx, int n, int F, double *mean, double *var, double *scale, double *ws,
+                          void *stream);
+int skyemb_probe_scale(const float *X, int64_t ldx, int n, int F, const double *mean, const double *scale, float *out, int64_t ldo,
+                       void *stream);
+int64_t skyemb_probe_softmax_ws_bytes(int m, int F, int K);
+int skyemb_probe_softmax_loss_grad(const float *X, int64_t ldx, const int32_t *y, int m, int F, int K, const float *W, const float *b,
+                                   double l2, double *loss, float *gW, float *gb, void *ws, int64_t ws_bytes, void *stream);
+int skyemb_probe_gram(const float *Xc, int64_t ldx, const float *yc, int m, int F, double *G, double *q, double *ynorm2, void *stream);
+int skyemb_probe_enet_cd(const double *G, const double *q, const double *ynorm2, int F, double a1, double b2, int max_iter, double tol,
+                         double *w, int32_t *status, double *gap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ Reads ``configs/<model_name>.ini``, builds the model / optimiser / scheduler
 (``utils.mim_vit.build_model``), streams HDF5 cutouts, runs ``run_iter`` per batch, evaluates the
 validation loss every ``verbose_iters``, checkpoints ``models/<model_name>.pth.tar`` every
 ``cp_time`` minutes in the reference's format (batch_iters, losses, optimizer, lr_scheduler, model).
-The linear-probe validation hook (``lp_class_data_file`` / ``lp_regress_data_file`` / ``lp_combine``) runs on rank 0; plots are
+The linear-probe validation hook (``lp_class_data_file`` / ``lp_regress_data_file`` / ``lp_combine``; ``lp_device = True`` fits
+the probes on the GPU instead of with scikit-learn on the host) runs on rank 0; plots are
 out of scope.
 """
 import ast
@@ -128,6 +129,7 @@ def main(args):
     lp_files = {key: os.path.join(data_dir, config['DATA'][key]) if key in config['DATA'] else None
                 for key in ('lp_class_data_file', 'lp_regress_data_file')}
     lp_combine = config['DATA'].get('lp_combine', 'central')
+    lp_device = config['DATA'].get('lp_device', 'False').strip().lower() in ('true', '1', 'yes')   # fit the probes on the GPU
     total_batch_iters = int(float(config['TRAINING']['total_batch_iters']))
     if rank == 0:
         print('Training the network with a batch size of %i per GPU ...' % (common['batch_size']))
@@ -187,10 +189,10 @@ def main(args):
                 probing = rank == 0 and any(lp_files.values())
                 if probing:     # the encoder is replicated: rank 0's probe is every rank's
                     linear_probe(model, losses_cp, device, dataloader_val, lp_files['lp_class_data_file'],
-                                 lp_files['lp_regress_data_file'], combine=lp_combine)
+                                 lp_files['lp_regress_data_file'], combine=lp_combine, on_device=lp_device)
                     model.train(True)       # the probe leaves the model in eval mode (utils/pretrain_fns.py:62)
                 if world > 1 and any(lp_files.values()):
-                    # the other ranks wait for rank 0's host-side scikit-learn fits HERE, on the host, not inside the next
+                    # the other ranks wait for rank 0's probe fits (host-side scikit-learn, or the device fits of lp_device) HERE, on the host, not inside the next
                     # step's gradient all-reduce (whose watchdog would abort the job after ten minutes)
                     sdist.host_barrier()
                 for k in list(losses_cp.keys()):

@@ -24,6 +24,7 @@ KC, RC = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU = 0, 1, 2
 COMBINE_MIN, COMBINE_MEAN, COMBINE_MAX = 0, 1, 2       # SKYEMB_COMBINE_*: how the token scores of an image are combined
 METRIC_MSE, METRIC_MAE = 1, 2                          # SKYEMB_METRIC_*: the distance metrics of the patch-token search
+PROBE_CHUNKS, PROBE_MAX_F, PROBE_MIN_K, PROBE_MAX_K = 32, 4096, 3, 16   # SKYEMB_PROBE_*: limits of the linear-probe fits
 
 
 class SkyembLibraryError(RuntimeError):
@@ -35,6 +36,7 @@ class SkyembError(RuntimeError):
 
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+c_f64 = ctypes.c_double
 
 
 class GemmArgs(ctypes.Structure):
@@ -170,6 +172,14 @@ PROTOTYPES = {
     "skyemb_distance_token_scores": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "skyemb_distance_token_topk": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32,
                                            c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # linear-probe fits on the device (csrc/probe.hip): additive again
+    "skyemb_probe_colstats": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_probe_scale": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "skyemb_probe_softmax_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "skyemb_probe_softmax_loss_grad": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                               c_vp]),
+    "skyemb_probe_gram": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_probe_enet_cd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f64, c_f64, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _LIB = None

@@ -542,3 +542,45 @@ def distance_token_topk(c, t, bank, metric, combine, k, idx_offset, nlists, part
     check(lib().skyemb_distance_token_topk(_p(c), _p(t), _p(bank), bank_dtype_code(bank.dtype, "distance_token_topk"), Q, N, P, D, metric,
                                            combine, top_t, k, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i), _p(select), _stream()),
           "skyemb_distance_token_topk")
+
+
+# ---- linear-probe fits on the device (csrc/probe.hip; driven by sky_embeddings_amd/probe.py)
+def probe_colstats(X, n=None, F=None, ldx=None):
+    """X [n, F] fp32 (row stride ``ldx`` elements) -> (mean, var, scale) fp64 [F]; scale is exactly 1 where var == 0."""
+    n, F = (X.shape[0] if n is None else n), (X.shape[1] if F is None else F)
+    mean, var, scale = (torch.empty(F, device=X.device, dtype=torch.float64) for _ in range(3))
+    ws = torch.empty(_lib.PROBE_CHUNKS * F, device=X.device, dtype=torch.float64)
+    check(lib().skyemb_probe_colstats(_p(X), X.stride(0) if ldx is None else ldx, n, F, _p(mean), _p(var), _p(scale), _p(ws), _stream()),
+          "skyemb_probe_colstats")
+    return mean, var, scale
+
+
+def probe_scale(X, mean, scale, out, n=None, F=None, ldx=None, ldo=None):
+    """out = fp32((X - mean) / scale) (``scale`` None: centre only)."""
+    n, F = (X.shape[0] if n is None else n), (X.shape[1] if F is None else F)
+    check(lib().skyemb_probe_scale(_p(X), X.stride(0) if ldx is None else ldx, n, F, _p(mean), _p(scale), _p(out),
+                                   out.stride(0) if ldo is None else ldo, _stream()), "skyemb_probe_scale")
+    return out
+
+
+def probe_softmax_ws_bytes(m, F, K):
+    return int(lib().skyemb_probe_softmax_ws_bytes(m, F, K))
+
+
+def probe_softmax_loss_grad(X, y, W, b, l2, loss, gW, gb, ws, m=None, F=None, K=None, ldx=None):
+    m, F, K = (X.shape[0] if m is None else m), (X.shape[1] if F is None else F), (W.shape[0] if K is None else K)
+    check(lib().skyemb_probe_softmax_loss_grad(_p(X), X.stride(0) if ldx is None else ldx, _p(y), m, F, K, _p(W), _p(b), float(l2), _p(loss),
+                                               _p(gW), _p(gb), _p(ws), 0 if ws is None else ws.numel() * ws.element_size(), _stream()),
+          "skyemb_probe_softmax_loss_grad")
+
+
+def probe_gram(Xc, yc, G, q, ynorm2, m=None, F=None, ldx=None):
+    m, F = (Xc.shape[0] if m is None else m), (Xc.shape[1] if F is None else F)
+    check(lib().skyemb_probe_gram(_p(Xc), Xc.stride(0) if ldx is None else ldx, _p(yc), m, F, _p(G), _p(q), _p(ynorm2), _stream()),
+          "skyemb_probe_gram")
+
+
+def probe_enet_cd(G, q, ynorm2, a1, b2, max_iter, tol, w, status, gap, F=None):
+    F = q.numel() if F is None else F
+    check(lib().skyemb_probe_enet_cd(_p(G), _p(q), _p(ynorm2), F, float(a1), float(b2), int(max_iter), float(tol), _p(w), _p(status),
+                                     _p(gap), _stream()), "skyemb_probe_enet_cd")
