@@ -610,6 +610,44 @@ int skyemb_distance_token_topk(const float *c, const float *t, const void *bank,
                                int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists, const float *thr0,
                                float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
 
+/* Per-query feature weights (additive to ABI version 111: nothing above changes).  The reference derives the weights from the
+ * target (utils/similarity.py:134-147), so two targets never share them: here every query q of a call has its own row of
+ * w [Q, D] (cosine) or c [Q, D] (distance), and one pass over the bank serves up to 16 targets with 16 weight vectors.
+ *
+ * Cosine (`skyemb_cosine_token_*_pq`): the `_sel` calls with `w` in place of `xn`; every other argument, select == NULL (every
+ * image) included, as there.  tw [Q, D] and qn [Q] are prepared per query with that query's row (skyemb_weighted_norms).  The
+ * bank norm is computed in the pass, per (query, row), and no norm array is read:
+ *     x2[d] = x[d] * x[d], one fp32 rounding;  acc2 = 0, then acc2 = fma(w[q][d], x2[d], acc2) over d = 0, 1, 2, ... -- the
+ *     contract's fma chain of the score with (w_q, x o x) as operands;  xn_q = sqrt(acc2), IEEE;
+ *     score = dot / fma(qn[q], xn_q, eps), NaN -> -inf, as in every other call.
+ *   This is NOT skyemb_weighted_norms' order (fma(w[d] * x[d], x[d], acc)), so the call with one shared weight vector and this
+ *   call with Q identical rows may differ in the last bits of a score.  A 16-bit bank gives the fp32 result on the widened bank,
+ *   bit for bit.  A negative acc2 (negative weights) gives a NaN norm and a NaN score, which ranks as -inf; an all-zero weight row
+ *   gives the score 0 / eps = 0 for every token.  Combine, top_t, selection, lists, thr0, terminator and skyemb_topk_merge are
+ *   those of the `_sel` calls.  Two operand images are resident in LDS, so the shape rule reads 128 D + 32 Q k <= 163840 where
+ *   skyemb_cosine_token_applicable has 64 D: skyemb_cosine_token_pq_applicable(Q, P, D, k) says so without touching the device and
+ *   on 0 leaves the limits and the refused shape as skyemb_last_error.  nlists is skyemb_cosine_token_topk_chunks', unchanged.
+ *   Refusals before any launch: those of the `_sel` calls with this shape rule, and a `w` that is not 16-byte aligned.
+ *
+ * Distance (`skyemb_distance_token_*_pq`): the calls above with c [Q, D], row q = fp32(w_q / sum(w_q)); term[d] of query q is
+ *   c[q][d] * v[d] and the arithmetic contract holds word for word, so query q's result is bit-identical to the single-c call
+ *   with that row.  c sits in LDS beside t (8 Q D <= 128 D bytes together), so the shape rule is
+ *   skyemb_cosine_token_pq_applicable's; the remaining refusals are those of the calls above.
+ *
+ * Per-query token-position masks and per-query selections remain out of scope: one `select` serves all queries of a call. */
+int skyemb_cosine_token_pq_applicable(int Q, int P, int D, int k);
+int skyemb_cosine_token_scores_pq(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *w, int Q,
+                                  int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
+                                  const uint32_t *select, void *stream);
+int skyemb_cosine_token_topk_pq(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *w, int Q,
+                                int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset, int nlists,
+                                const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
+int skyemb_distance_token_scores_pq(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P, int D,
+                                    int metric, int combine, int top_t, float *scores, const uint32_t *select, void *stream);
+int skyemb_distance_token_topk_pq(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P, int D,
+                                  int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists, const float *thr0,
+                                  float *part_s, int64_t *part_i, const uint32_t *select, void *stream);
+
 /* ------------------------------------------------------- linear-probe fits -
  * (additive to ABI version 111: nothing above changes.)  utils/pretrain_fns.py:52-159 fits two scikit-learn estimators on the
  * host every `verbose_iters` iterations: StandardScaler + LogisticRegression(lbfgs, C = 0.01) on `class` and

@@ -22,7 +22,13 @@ of filtering before the encoder: another S/N range is then another search over t
 standardisation statistics are those of the first ``-bs`` SELECTED images (the reference's first batch of the filtered set; for
 a 16-bit bank those images are encoded first to get them), results are looked up in the full test file.  It works in all three
 --bank modes; the pooled ones (-mp True / -ct True) then run as the token search with one token per sample, under its limits:
--ns <= 512 and a feature width that is a multiple of 64, at most 1024.
+-ns <= 512 and a feature width that is a multiple of 64, at most 1024.  ``--per-target`` (extension, only with ``--bank``) makes every
+entry of ``-tgt_i`` its own query instead of pooling all targets into one mean vector and one weight vector: target t gets
+``determine_target_features`` over its own latents alone (with ``-aug True`` its own 64 augmentations), i.e. its own inverse-variance
+weights, and all targets are searched in one pass over the bank (search.* with ``weights`` [T, D]), in all three --bank modes and
+with all three metrics.  The output is ``..._simsearch_results_per_target.npz``: the keys above with a leading target axis
+(``test_scores`` [T, n_save], ...).  A target with fewer than two latent vectors (-aug False with -mp True / -ct True) has no
+variance to weight by: the run exits with a message.
 """
 import argparse
 import ast
@@ -69,7 +75,24 @@ def parseArguments():
                         help="element type of the resident patch-token bank (--bank -mp False -ct False)")
     parser.add_argument("--bank-select-snr", action="store_true",
                         help="with --bank: encode every test row once and apply -snr as a selection of the resident bank")
+    parser.add_argument("--per-target", action="store_true",
+                        help="with --bank: every -tgt_i entry is its own query with its own inverse-variance weights")
     return parser
+
+
+def target_queries(tl, n_targets, per_target):
+    """(queries [Q, D], weights) from the standardised target latents tl [n_targets * copies, tokens, D] (a target's copies are
+    consecutive rows): one mean vector and one weight vector [D] over all of them, or, per target, [T, D] each from that target's
+    own latents."""
+    if not per_target:
+        avg, w = determine_target_features(tl)
+        return avg.reshape(1, -1), w
+    groups = tl.reshape(n_targets, -1, tl.shape[-1])
+    if groups.shape[1] < 2:
+        raise SystemExit(f"--per-target: each target has {groups.shape[1]} latent vector, no variance to weight by (use -aug True, or "
+                         f"-mp False -ct False)")
+    pairs = [determine_target_features(g) for g in groups]
+    return torch.stack([a for a, _ in pairs]), torch.stack([w for _, w in pairs])
 
 
 def main():
@@ -82,6 +105,8 @@ def main():
         raise SystemExit(f"--bank: unknown metric -m {args.metric}, expected one of {', '.join(BANK_METRICS)}")
     if args.bank_select_snr and not args.bank:
         raise SystemExit("--bank-select-snr selects images of the resident bank: it needs --bank")
+    if args.per_target and not args.bank:
+        raise SystemExit("--per-target searches the resident bank once for all targets: it needs --bank")
     snr_range = ast.literal_eval(args.snr_range)
     cur_dir = os.path.dirname(os.path.abspath(__file__))
     config_dir, model_dir = os.path.join(cur_dir, 'configs/'), os.path.join(cur_dir, 'models/')
@@ -129,6 +154,7 @@ def main():
             raise SystemExit("--bank-dtype f16 / bf16 applies to the patch-token bank (-mp False -ct False)")
         mod = model.module
         tl = target_latent.to(device)
+        n_targets = tl.shape[0] // (65 if str2bool(args.augment_targets) else 1)     # a target and its 64 copies are consecutive
         k = args.n_save
         select, first_rows = None, slice(args.batch_size)
         if args.bank_select_snr:
@@ -142,16 +168,17 @@ def main():
             k = min(k, select.count)         # the saved arrays line up: no (-inf, -1) tail
         if max_pool or cls_token:                # one vector per sample
             tl = tl[:, :1] if cls_token else tl[:, mod.num_extra_tokens:].max(dim=1, keepdim=True).values
+            target_queries(tl, n_targets, args.per_target)     # too few latents per target: exit before the bank is encoded
             bank = build_embedding_bank(model, test_dataloader, device, pool='cls' if cls_token else 'max')
             first = bank[first_rows]         # the reference standardises with the first batch (utils/similarity.py:98-100)
             mean_feats, std_feats = first.mean(dim=0), first.std(dim=0, unbiased=True)
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             search.standardise_(bank, mean_feats, std_feats)
-            avg, w = determine_target_features(tl)
+            queries, w = target_queries(tl, n_targets, args.per_target)
             if args.metric == 'cosine':
-                scores, idx = search.cosine_topk(avg.reshape(1, -1), bank, min(k, bank.shape[0]), weights=w, select=select)
+                scores, idx = search.cosine_topk(queries, bank, min(k, bank.shape[0]), weights=w, select=select)
             else:                                # one token per sample: every combine is that token's distance
-                scores, idx = search.distance_topk_tokens(avg.reshape(1, -1), bank.unsqueeze(1), min(k, bank.shape[0]),
+                scores, idx = search.distance_topk_tokens(queries, bank.unsqueeze(1), min(k, bank.shape[0]),
                                                           metric=args.metric, combine=args.combine, weights=w, select=select)
         else:                                    # every patch token scored, combined per image (-c min | mean | max)
             tl = tl[:, mod.num_extra_tokens:]
@@ -171,24 +198,34 @@ def main():
                                                                    standardise_with_first_batch=True, standardise_stats=stats)
             print(f'Token bank: {bank.numel() * bank.element_size() / 1e9:.3f} GB, {bank.dtype}')
             tl = (tl - mean_feats) / (std_feats + 1e-8)
-            avg, w = determine_target_features(tl)
+            queries, w = target_queries(tl, n_targets, args.per_target)
             if args.metric == 'cosine':
-                scores, idx = search.cosine_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), combine=args.combine,
+                scores, idx = search.cosine_topk_tokens(queries, bank, min(k, bank.shape[0]), combine=args.combine,
                                                         weights=w, top_t=args.n_top_sims, select=select)
             else:
-                scores, idx = search.distance_topk_tokens(avg.reshape(1, -1), bank, min(k, bank.shape[0]), metric=args.metric,
+                scores, idx = search.distance_topk_tokens(queries, bank, min(k, bank.shape[0]), metric=args.metric,
                                                           combine=args.combine, weights=w, top_t=args.n_top_sims, select=select)
-        test_scores, order = scores[0], idx[0].cpu().numpy()
         ds = test_dataloader.dataset
-        items = [ds[int(j)] for j in order if j >= 0]
-        test_images = torch.stack([it[0] for it in items])
-        test_ra_decs = torch.stack([it[2] for it in items])
-        test_latent, _, _ = model.module.forward_features(test_images.to(device), reshape_out=False)
+
+        def lookup(order):
+            items = [ds[int(j)] for j in order if j >= 0]
+            images = torch.stack([it[0] for it in items])
+            return images, torch.stack([it[2] for it in items]), model.module.forward_features(images.to(device), reshape_out=False)[0]
+        if args.per_target:                      # every array gains a leading target axis
+            if bool((idx < 0).any()):
+                raise SystemExit("--per-target: fewer than -ns images have a finite score for some target; lower -ns")
+            rows = [lookup(order) for order in idx.cpu().numpy()]
+            test_scores = scores
+            test_images, test_ra_decs, test_latent = (torch.stack([r[j] for r in rows]) for j in range(3))
+        else:
+            test_scores = scores[0]
+            test_images, test_ra_decs, test_latent = lookup(idx[0].cpu().numpy())
     else:
         test_images, test_latent, test_ra_decs, test_scores = mae_simsearch(
             model, target_latent, test_dataloader, device, metric=args.metric, combine=args.combine, use_weights=True,
             max_pool=max_pool, cls_token=cls_token, nested_batches=False, n_save=args.n_save, n_top_sims=args.n_top_sims)
-    out = os.path.join(results_dir, f'{args.model_name}_{args.target_fn[:-3]}_simsearch_results_f.npz')
+    out = os.path.join(results_dir, f'{args.model_name}_{args.target_fn[:-3]}_simsearch_results_'
+                                    f'{"per_target" if args.per_target else "f"}.npz')
     np.savez(out, test_ra_decs=test_ra_decs.cpu().numpy(), test_scores=test_scores.cpu().numpy(),
              target_images=target_images.cpu().numpy(), target_features=target_latent.cpu().numpy(),
              test_images=test_images.cpu().numpy(), test_features=test_latent.cpu().numpy())

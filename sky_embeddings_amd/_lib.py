@@ -172,6 +172,16 @@ PROTOTYPES = {
     "skyemb_distance_token_scores": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "skyemb_distance_token_topk": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32,
                                            c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # per-query feature weights (w / c [Q, D]): additive again
+    "skyemb_cosine_token_pq_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "skyemb_cosine_token_scores_pq": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp,
+                                              c_vp, c_vp]),
+    "skyemb_cosine_token_topk_pq": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
+                                            c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_distance_token_scores_pq": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                                c_vp]),
+    "skyemb_distance_token_topk_pq": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,
+                                              c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     # linear-probe fits on the device (csrc/probe.hip): additive again
     "skyemb_probe_colstats": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_probe_scale": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -26,6 +26,10 @@
 // commutes with every rounding: distance min = key MAX, distance max = key MIN, distance mean = key MEAN; "the top_t smallest
 // distances" are the top_t largest keys.  So token_combine.h, the lists, thr0, ties (key desc, image asc), the (-inf, -1)
 // terminator and skyemb_topk_merge apply unchanged.  The scores call writes -key: distances, +inf for a deselected image.
+//
+// Per-query feature weights (PQC, the `_pq` entry points): c is [Q, D], one row per query, staged in LDS behind t (another 4 Q D
+// bytes); term[d] of query q takes c[q][d].  The contract above is otherwise untouched, so query q's result is bit-identical to
+// the single-c call with that row.  LDS: 8 Q D <= 128 D for t and c, so these calls answer to skyemb_cosine_token_pq_applicable.
 #include "topk_stream.h"
 #include "token_combine.h"
 
@@ -66,8 +70,8 @@ __device__ __forceinline__ float dist_term(float p, float x, float t, float c) {
 }
 
 // KCOMBINE is the combine in KEY space (see the head of this file); the other switches are cosine_token_kernel's.
-// c [D], t [Q, D]; LDS: t, then [DWAVES][Q][k] list scores and [DWAVES][Q][k] list images.
-template <typename T, int METRIC, int KCOMBINE, bool LISTS, bool TOPT, bool SEL>
+// c [D] (PQC: [Q, D]), t [Q, D]; LDS: t, (PQC: c,) then [DWAVES][Q][k] list scores and [DWAVES][Q][k] list images.
+template <typename T, int METRIC, int KCOMBINE, bool LISTS, bool TOPT, bool SEL, bool PQC>
 __global__ __launch_bounds__(DWAVES * 64) void distance_token_kernel(const float *__restrict__ cw, const float *__restrict__ tq,
                                                                       const T *__restrict__ bank, int Q, int64_t R, int P, int D, int k,
                                                                       int64_t idx_offset, int64_t rows_per_wave,
@@ -78,9 +82,12 @@ __global__ __launch_bounds__(DWAVES * 64) void distance_token_kernel(const float
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nm = D >> 6, D4 = D >> 2;                             // float4 steps per lane and row; float4s per row
     float4 *t4 = (float4 *)lds;                                     // [Q][D / 4]
-    float *ls_all = lds + (size_t)Q * D;                            // [DWAVES][Q][k]
+    const float4 *c4 = t4 + (size_t)Q * D4;                         // PQC: [Q][D / 4]
+    float *ls_all = lds + (size_t)Q * D * (PQC ? 2 : 1);            // [DWAVES][Q][k]
     int *li_all = (int *)(ls_all + (size_t)DWAVES * Q * k);         // [DWAVES][Q][k]
     for (int e = tid; e < Q * D4; e += DWAVES * 64) t4[e] = ((const float4 *)tq)[e];
+    if (PQC)
+        for (int e = tid; e < Q * D4; e += DWAVES * 64) t4[Q * D4 + e] = ((const float4 *)cw)[e];
     __syncthreads();
     float *ls = ls_all + (size_t)wave * Q * k;
     int *li = li_all + (size_t)wave * Q * k;
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(DWAVES * 64) void distance_token_kernel(const float
                 int64_t row = n0 + 4 * ls_ + g;
                 if (row >= r_end) row = r_end - 1;                  // clamp: masked below
                 xv[u] = row4<T>(bank + row * D + 64 * lm + 4 * n_lane);
-                cv4[u] = *(const float4 *)(cw + 64 * lm + 4 * n_lane);
+                if (!PQC) cv4[u] = *(const float4 *)(cw + 64 * lm + 4 * n_lane);
                 if (++lm == nm) { lm = 0; ++ls_; }
             }
 #pragma unroll
@@ -165,10 +172,11 @@ __global__ __launch_bounds__(DWAVES * 64) void distance_token_kernel(const float
                 for (int q = 0; q < 16; ++q) {
                     if (q < Q) {                                    // wave-uniform
                         const float4 tv = t4[q * D4 + 16 * m + n_lane];
-                        p[q] = dist_term<METRIC>(p[q], xv[u].x, tv.x, cv4[u].x);
-                        p[q] = dist_term<METRIC>(p[q], xv[u].y, tv.y, cv4[u].y);
-                        p[q] = dist_term<METRIC>(p[q], xv[u].z, tv.z, cv4[u].z);
-                        p[q] = dist_term<METRIC>(p[q], xv[u].w, tv.w, cv4[u].w);
+                        const float4 cv = PQC ? c4[q * D4 + 16 * m + n_lane] : cv4[u];
+                        p[q] = dist_term<METRIC>(p[q], xv[u].x, tv.x, cv.x);
+                        p[q] = dist_term<METRIC>(p[q], xv[u].y, tv.y, cv.y);
+                        p[q] = dist_term<METRIC>(p[q], xv[u].z, tv.z, cv.z);
+                        p[q] = dist_term<METRIC>(p[q], xv[u].w, tv.w, cv.w);
                     }
                 }
                 if (++m == nm) {                                    // rows n0 + 4 s + g are complete: fold, divide, hand over
@@ -284,10 +292,11 @@ struct Launch {
     int64_t n_img;
     int top_t;
     const uint32_t *sel;
+    bool pq;                                                        // c is [Q, D]
 };
 
-template <typename T, int METRIC, bool LISTS, bool SEL>
-int launch_sel(const Launch &a, const T *bank, int combine) {
+template <typename T, int METRIC, bool LISTS, bool SEL, bool PQC>
+int launch_pq(const Launch &a, const T *bank, int combine) {
     auto go = [&](auto kern) {
         if (a.smem > 64 * 1024) {
             const int rc = sky_set_lds_limit((const void *)kern, LDS_BYTES, a.who);
@@ -299,11 +308,16 @@ int launch_sel(const Launch &a, const T *bank, int combine) {
         return 0;
     };
     // distance -> key space: min = key MAX (a[0] for every top_t: the plain kernel), max = key MIN, mean = key MEAN
-    if (combine == SKYEMB_COMBINE_MIN) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MAX, LISTS, false, SEL>);
-    if (a.top_t != 0 && combine == SKYEMB_COMBINE_MAX) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MIN, LISTS, true, SEL>);
-    if (a.top_t != 0) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MEAN, LISTS, true, SEL>);
-    if (combine == SKYEMB_COMBINE_MAX) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MIN, LISTS, false, SEL>);
-    return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MEAN, LISTS, false, SEL>);
+    if (combine == SKYEMB_COMBINE_MIN) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MAX, LISTS, false, SEL, PQC>);
+    if (a.top_t != 0 && combine == SKYEMB_COMBINE_MAX) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MIN, LISTS, true, SEL, PQC>);
+    if (a.top_t != 0) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MEAN, LISTS, true, SEL, PQC>);
+    if (combine == SKYEMB_COMBINE_MAX) return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MIN, LISTS, false, SEL, PQC>);
+    return go(distance_token_kernel<T, METRIC, SKYEMB_COMBINE_MEAN, LISTS, false, SEL, PQC>);
+}
+
+template <typename T, int METRIC, bool LISTS, bool SEL>
+int launch_sel(const Launch &a, const T *bank, int combine) {
+    return a.pq ? launch_pq<T, METRIC, LISTS, SEL, true>(a, bank, combine) : launch_pq<T, METRIC, LISTS, SEL, false>(a, bank, combine);
 }
 
 template <typename T, bool LISTS>
@@ -323,8 +337,9 @@ int launch_any(const Launch &a, const void *bank, int bank_dtype, int metric, in
 }
 
 // the refusals both calls share; every one of them comes before any launch
+// (pq: c is [Q, D] and sits in LDS with t, which the rule with two images covers)
 int check_common(const char *who, const void *c, const void *t, const void *bank, int bank_dtype, int Q, int64_t N, int P, int D, int k,
-                 int metric, int combine, int top_t, const void *out, const uint32_t *select) {
+                 int metric, int combine, int top_t, const void *out, const uint32_t *select, bool pq = false) {
     SKY_CHECK_ARG(c && t && bank && out && N > 0, "%s: bad arguments", who);
     SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype),
                   "%s: bank_dtype must be SKYEMB_BF16 (0), SKYEMB_F32 (1) or SKYEMB_F16 (2), got %d", who, bank_dtype);
@@ -332,7 +347,7 @@ int check_common(const char *who, const void *c, const void *t, const void *bank
                   "%s: metric must be SKYEMB_METRIC_MSE (1) or SKYEMB_METRIC_MAE (2), got %d", who, metric);
     SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MEAN || combine == SKYEMB_COMBINE_MAX,
                   "%s: unknown combine code %d", who, combine);
-    if (!skyemb_cosine_token_applicable(Q, P, D, k)) {               // its text names the limits; prefix the caller
+    if (!(pq ? skyemb_cosine_token_pq_applicable(Q, P, D, k) : skyemb_cosine_token_applicable(Q, P, D, k))) {   // its text names the limits; prefix the caller
         char why[512];
         snprintf(why, sizeof why, "%s", skyemb_last_error());
         skyemb_set_error("%s: %s", who, why);
@@ -346,32 +361,60 @@ int check_common(const char *who, const void *c, const void *t, const void *bank
     return 0;
 }
 
+// the two calls; pq: c is [Q, D] (the `_pq` entry points)
+int distance_topk(const char *who, bool pq, const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P, int D,
+                  int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists, const float *thr0, float *part_s,
+                  int64_t *part_i, const uint32_t *select, void *stream) {
+    if (check_common(who, c, t, bank, bank_dtype, Q, N, P, D, k, metric, combine, top_t, part_s, select, pq)) return 1;
+    SKY_CHECK_ARG(part_i, "%s: bad arguments", who);
+    SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
+                  who);
+    // nlists is a multiple of 4 (blocks x 4 or 8 waves); 4 Q D <= 64 D, so four waves' lists fit under the cosine search's LDS rule
+    // (pq: 8 Q D <= 128 D under the rule with two images)
+    const int64_t R = N * P, unit = P < 16 ? 16 : P;
+    Launch a = {nlists / DWAVES, (size_t)4 * Q * D * (pq ? 2 : 1) + (size_t)2 * 4 * DWAVES * Q * k, (hipStream_t)stream, who, c, t, Q, R, P,
+                D, k, idx_offset, ceil_div64(ceil_div64(R, nlists), unit) * unit, part_s, part_i, thr0, nullptr, N, top_t, select, pq};
+    return launch_any<true>(a, bank, bank_dtype, metric, combine);
+}
+
+int distance_scores(const char *who, bool pq, const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P,
+                    int D, int metric, int combine, int top_t, float *scores, const uint32_t *select, void *stream) {
+    if (check_common(who, c, t, bank, bank_dtype, Q, N, P, D, 1, metric, combine, top_t, scores, select, pq)) return 1;
+    const int64_t R = N * P, unit = P < 16 ? 16 : P;
+    int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), DWAVES);
+    if (blocks > 2048) blocks = 2048;
+    Launch a = {(int)blocks, (size_t)4 * Q * D * (pq ? 2 : 1), (hipStream_t)stream, who, c, t, Q, R, P, D, 1, 0,
+                ceil_div64(ceil_div64(R, blocks * DWAVES), unit) * unit, nullptr, nullptr, nullptr, scores, N, top_t, select, pq};
+    return launch_any<false>(a, bank, bank_dtype, metric, combine);
+}
+
 }  // namespace
 
 extern "C" int skyemb_distance_token_topk(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P,
                                           int D, int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists,
                                           const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select, void *stream) {
-    const char *who = "skyemb_distance_token_topk";
-    if (check_common(who, c, t, bank, bank_dtype, Q, N, P, D, k, metric, combine, top_t, part_s, select)) return 1;
-    SKY_CHECK_ARG(part_i, "%s: bad arguments", who);
-    SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
-                  who);
-    // nlists is a multiple of 4 (blocks x 4 or 8 waves); 4 Q D <= 64 D, so four waves' lists fit under the cosine search's LDS rule
-    const int64_t R = N * P, unit = P < 16 ? 16 : P;
-    Launch a = {nlists / DWAVES, (size_t)4 * Q * D + (size_t)2 * 4 * DWAVES * Q * k, (hipStream_t)stream, who, c, t, Q, R, P, D, k,
-                idx_offset, ceil_div64(ceil_div64(R, nlists), unit) * unit, part_s, part_i, thr0, nullptr, N, top_t, select};
-    return launch_any<true>(a, bank, bank_dtype, metric, combine);
+    return distance_topk("skyemb_distance_token_topk", false, c, t, bank, bank_dtype, Q, N, P, D, metric, combine, top_t, k, idx_offset,
+                         nlists, thr0, part_s, part_i, select, stream);
 }
 
 extern "C" int skyemb_distance_token_scores(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P,
                                             int D, int metric, int combine, int top_t, float *scores, const uint32_t *select,
                                             void *stream) {
-    const char *who = "skyemb_distance_token_scores";
-    if (check_common(who, c, t, bank, bank_dtype, Q, N, P, D, 1, metric, combine, top_t, scores, select)) return 1;
-    const int64_t R = N * P, unit = P < 16 ? 16 : P;
-    int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), DWAVES);
-    if (blocks > 2048) blocks = 2048;
-    Launch a = {(int)blocks, (size_t)4 * Q * D, (hipStream_t)stream, who, c, t, Q, R, P, D, 1, 0,
-                ceil_div64(ceil_div64(R, blocks * DWAVES), unit) * unit, nullptr, nullptr, nullptr, scores, N, top_t, select};
-    return launch_any<false>(a, bank, bank_dtype, metric, combine);
+    return distance_scores("skyemb_distance_token_scores", false, c, t, bank, bank_dtype, Q, N, P, D, metric, combine, top_t, scores, select,
+                           stream);
+}
+
+// Per-query feature weights (include/skyemb.h): the same two calls with c [Q, D], row q for query q.
+extern "C" int skyemb_distance_token_topk_pq(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P,
+                                             int D, int metric, int combine, int top_t, int k, int64_t idx_offset, int nlists,
+                                             const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select, void *stream) {
+    return distance_topk("skyemb_distance_token_topk_pq", true, c, t, bank, bank_dtype, Q, N, P, D, metric, combine, top_t, k, idx_offset,
+                         nlists, thr0, part_s, part_i, select, stream);
+}
+
+extern "C" int skyemb_distance_token_scores_pq(const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P,
+                                               int D, int metric, int combine, int top_t, float *scores, const uint32_t *select,
+                                               void *stream) {
+    return distance_scores("skyemb_distance_token_scores_pq", true, c, t, bank, bank_dtype, Q, N, P, D, metric, combine, top_t, scores,
+                           select, stream);
 }

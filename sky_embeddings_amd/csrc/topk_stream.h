@@ -189,6 +189,107 @@ __device__ __forceinline__ f32x4 stream_dot16(const T *__restrict__ src, const f
     return acc;
 }
 
+// ---- per-query feature weights (PQW, the `_pq` entry points): next to the score chain a second chain over the same fragments,
+// acc2[q][n] = fma(w[q][d], x2[n][d], acc2), x2[d] = x[d] * x[d] rounded once, same k-step order -- the squared weighted norm of
+// bank row n under query q's own weights, in the score's C/D layout (lane (n, g) holds the queries 4 g + r).  imgW: the image of
+// w [Q, D] in build_imgA's layout.
+
+// one k-group of four MFMA steps on both chains; b is a transposed fragment (the score chain's B operand)
+__device__ __forceinline__ void mfma4_pq(f32x4 &acc, f32x4 &acc2, const float4 a, const float4 w, const float4 b) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, __fmul_rn(b.x, b.x), acc2, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, __fmul_rn(b.y, b.y), acc2, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, __fmul_rn(b.z, b.z), acc2, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, __fmul_rn(b.w, b.w), acc2, 0, 0, 0);
+}
+
+// stream_dot16 with the norm chain: the same loads, register sets and k-step order; returns the score chain, acc2 by reference
+__device__ __forceinline__ f32x4 stream_dot16_pq(const float *__restrict__ src, const float4 *__restrict__ imgA,
+                                                 const float4 *__restrict__ imgW, int nchunk, int lane, f32x4 &acc2) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc2 = acc;
+    float4 b0[UNROLL], b1[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) b0[u] = *(const float4 *)(src + 16 * u);
+    for (int c0 = 0; c0 < nchunk; c0 += 2 * UNROLL) {
+        const bool more1 = c0 + UNROLL < nchunk, more2 = c0 + 2 * UNROLL < nchunk;
+        if (more1) {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) b1[u] = *(const float4 *)(src + 16 * (c0 + UNROLL + u));
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            transpose4(b0[u]);
+            mfma4_pq(acc, acc2, imgA[(c0 + u) * 64 + lane], imgW[(c0 + u) * 64 + lane], b0[u]);
+        }
+        if (more2) {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) b0[u] = *(const float4 *)(src + 16 * (c0 + 2 * UNROLL + u));
+        }
+        if (more1) {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                transpose4(b1[u]);
+                mfma4_pq(acc, acc2, imgA[(c0 + UNROLL + u) * 64 + lane], imgW[(c0 + UNROLL + u) * 64 + lane], b1[u]);
+            }
+        }
+    }
+    return acc;
+}
+
+// mfma32_lp with the norm chain: the widened, transposed halves in mfma32_lp's order lo.x hi.x lo.y hi.y | lo.z hi.z lo.w hi.w
+template <typename T>
+__device__ __forceinline__ void mfma32_lp_pq(f32x4 &acc, f32x4 &acc2, const uint4 r, const float4 a0, const float4 a1, const float4 w0,
+                                             const float4 w1) {
+    float4 lo, hi;
+    widen2<T>(r.x, lo.x, lo.y);
+    widen2<T>(r.y, lo.z, lo.w);
+    widen2<T>(r.z, hi.x, hi.y);
+    widen2<T>(r.w, hi.z, hi.w);
+    transpose4(lo);
+    transpose4(hi);
+    mfma4_pq(acc, acc2, a0, w0, make_float4(lo.x, hi.x, lo.y, hi.y));
+    mfma4_pq(acc, acc2, a1, w1, make_float4(lo.z, hi.z, lo.w, hi.w));
+}
+
+template <typename T>
+__device__ __forceinline__ f32x4 stream_dot16_pq(const T *__restrict__ src, const float4 *__restrict__ imgA,
+                                                 const float4 *__restrict__ imgW, int nchunk, int lane, f32x4 &acc2) {
+    static_assert(sizeof(T) == 2, "16-bit bank rows");
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc2 = acc;
+    uint4 b0[LP_LOADS], b1[LP_LOADS];
+#pragma unroll
+    for (int j = 0; j < LP_LOADS; ++j) b0[j] = *(const uint4 *)(src + 32 * j);
+    for (int c0 = 0; c0 < nchunk; c0 += 2 * UNROLL) {
+        const bool more1 = c0 + UNROLL < nchunk, more2 = c0 + 2 * UNROLL < nchunk;
+        if (more1) {
+#pragma unroll
+            for (int j = 0; j < LP_LOADS; ++j) b1[j] = *(const uint4 *)(src + 16 * (c0 + UNROLL) + 32 * j);
+        }
+#pragma unroll
+        for (int j = 0; j < LP_LOADS; ++j) {
+            const int c = (c0 + 2 * j) * 64 + lane;
+            mfma32_lp_pq<T>(acc, acc2, b0[j], imgA[c], imgA[c + 64], imgW[c], imgW[c + 64]);
+        }
+        if (more2) {
+#pragma unroll
+            for (int j = 0; j < LP_LOADS; ++j) b0[j] = *(const uint4 *)(src + 16 * (c0 + 2 * UNROLL) + 32 * j);
+        }
+        if (more1) {
+#pragma unroll
+            for (int j = 0; j < LP_LOADS; ++j) {
+                const int c = (c0 + UNROLL + 2 * j) * 64 + lane;
+                mfma32_lp_pq<T>(acc, acc2, b1[j], imgA[c], imgA[c + 64], imgW[c], imgW[c + 64]);
+            }
+        }
+    }
+    return acc;
+}
+
 // Insert (cv, cidx) into a sorted list (scores descending) of nq <= k entries that ONE wavefront owns in LDS; returns the new
 // size.  Caller guarantees cv > (nq == k ? lsq[k-1] : -inf).  Candidates arrive in ascending index order, so among equal
 // scores the earlier (lower index) entry stays in front: order = (score desc, index asc).

@@ -34,6 +34,14 @@
 // in one word (n0 / P is a multiple of 16 / P, which divides 32); the tile is passed over when all are clear, else it is scored
 // as ever and the lead lanes of the deselected images stay out of the candidate ballot.  Whole images are skipped, so `carry` and
 // `tile_in_image` are untouched.  The !LISTS kernel writes -inf for every deselected image.  The mask is only read.
+//
+// Per-query feature weights (PQW, the `_pq` entry points): every query has its own weight vector w [Q, D] (the reference derives
+// the weights from the target, utils/similarity.py:134-147), so the bank norm depends on the query and no precomputed xn serves.
+// A second operand image of w sits in LDS beside the A image and a second accumulator chain runs over the fragments the wave
+// already holds: acc2 = fma(w_q[d], x2[d], acc2), x2[d] = x[d] * x[d] rounded once, in the score chain's k-step order
+// (stream_dot16_pq, topk_stream.h); xn_q = sqrtf(acc2), correctly rounded (sqrtf, not __fsqrt_rn: inside this kernel the compiler
+// lowers the latter to the bare v_sqrt_f32 approximation).  From finish_score on the code is the shared one.  No norm array is
+// read.  LDS: 128 D + 32 Q k bytes (skyemb_cosine_token_pq_applicable).
 #include "topk_stream.h"
 #include "token_combine.h"
 
@@ -43,10 +51,11 @@ namespace {
 // !LISTS: scores [Q, n_img] combined scores.
 // TOPT: the top-t combine with 1 <= top_t <= min(P, 16) (MIN and MEAN only); !TOPT ignores top_t.
 // SEL: only the images whose bit in `sel` is set take part; !SEL ignores sel.
-template <typename T, int WAVES, int COMBINE, bool LISTS, bool TOPT, bool SEL>
-__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu((TOPT || SEL) && WAVES == 8 ? 4 : 1)))
+// PQW: `xw` is w [Q, D], the per-query feature weights; !PQW: `xw` is xn [R], the bank norms under the call's one weight vector.
+template <typename T, int WAVES, int COMBINE, bool LISTS, bool TOPT, bool SEL, bool PQW>
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu((TOPT || SEL) && WAVES == 8 && !PQW ? 4 : 1)))
 void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
-                                                                  const T *__restrict__ bank, const float *__restrict__ xn,
+                                                                  const T *__restrict__ bank, const float *__restrict__ xw,
                                                                   int Q, int64_t R, int P, int D, int k, float eps,
                                                                   int64_t idx_offset, int64_t rows_per_wave,
                                                                   float *__restrict__ part_s, int64_t *__restrict__ part_i,
@@ -56,9 +65,11 @@ void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nchunk = D >> 4;
     float4 *imgA = (float4 *)lds;                                   // [nchunk][64]: A fragments of every k-step
-    float *ls_all = lds + (size_t)nchunk * 64 * 4;                  // [WAVES][Q][k]
+    float4 *imgW = imgA + (size_t)nchunk * 64;                      // PQW: [nchunk][64], the same fragments of w
+    float *ls_all = lds + (size_t)nchunk * 64 * 4 * (PQW ? 2 : 1);  // [WAVES][Q][k]
     int *li_all = (int *)(ls_all + (size_t)WAVES * Q * k);         // [WAVES][Q][k]
     build_imgA<WAVES>(imgA, tw, Q, D, nchunk, tid);
+    if (PQW) build_imgA<WAVES>(imgW, xw, Q, D, nchunk, tid);        // rows q >= Q are zero
     __syncthreads();
     float *ls = ls_all + (size_t)wave * Q * k;
     int *li = li_all + (size_t)wave * Q * k;
@@ -126,9 +137,11 @@ void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__
         const bool row_ok = row < r_end;
         if (!row_ok) row = r_end - 1;                                // clamp: masked below
         const T *src = bank + row * D + lane_elems<T>() * g;
-        const f32x4 acc = stream_dot16(src, imgA, nchunk, lane);
+        f32x4 acc, acc2 = {0.f, 0.f, 0.f, 0.f};
+        if (PQW) acc = stream_dot16_pq(src, imgA, imgW, nchunk, lane, acc2);
+        else acc = stream_dot16(src, imgA, nchunk, lane);
         // C/D: col = lane&15 -> bank row n0 + n_lane, row = 4g + r -> query
-        const float xnv = xn[row];
+        const float xnv = PQW ? 0.f : xw[row];
         const bool first_tile = tile_in_image == 0;
         const bool last_tile = ++tile_in_image == tiles_per_image;
         if (last_tile) tile_in_image = 0;
@@ -137,7 +150,7 @@ void cosine_token_kernel(const float *__restrict__ tw, const float *__restrict__
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int q_mine = 4 * g + r;
-            const float s = (row_ok && q_mine < Q) ? finish_score(acc[r], qn4[r], xnv, eps) : -INFINITY;
+            const float s = (row_ok && q_mine < Q) ? finish_score(acc[r], qn4[r], PQW ? sqrtf(acc2[r]) : xnv, eps) : -INFINITY;
             float c;
             if (TOPT) {
                 carry[r] = top_tile(s, carry[r], n_lane, tp, first_tile);
@@ -207,13 +220,16 @@ constexpr int LDS_BYTES = 160 * 1024;
 size_t image_bytes(int D) { return (size_t)(D >> 4) * 64 * 16; }   // the A operand image: 64 D bytes
 
 // 8 waves per workgroup when their private lists (Q x k entries of 8 bytes each) fit next to the A image, else 4
-int token_waves(int Q, int D, int k) { return image_bytes(D) + (size_t)8 * 8 * Q * k <= (size_t)LDS_BYTES ? 8 : 4; }
+// (images: 1, or 2 with per-query weights -- the w image is as large as the A image)
+int token_waves(int Q, int D, int k, int images = 1) {
+    return images * image_bytes(D) + (size_t)8 * 8 * Q * k <= (size_t)LDS_BYTES ? 8 : 4;
+}
 
 int64_t image_unit(int P) { return P < 16 ? 16 : P; }              // lcm(P, 16) for the accepted P
 
 bool combine_ok(int combine) { return combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MEAN || combine == SKYEMB_COMBINE_MAX; }
 
-template <typename T, int WAVES, bool LISTS, bool SEL>
+template <typename T, int WAVES, bool LISTS, bool SEL, bool PQW>
 int launch_tokens_sel(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
                       const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
                       int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
@@ -229,23 +245,23 @@ int launch_tokens_sel(int combine, int blocks, size_t smem, hipStream_t st, cons
         return 0;
     };
     // top_t == 0: all tokens, the plain kernels; max is d[0] for every top_t, the plain max kernel
-    if (top_t != 0 && combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true, SEL>);
-    if (top_t != 0 && combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true, SEL>);
-    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false, SEL>);
-    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false, SEL>);
-    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false, SEL>);
+    if (top_t != 0 && combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true, SEL, PQW>);
+    if (top_t != 0 && combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true, SEL, PQW>);
+    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false, SEL, PQW>);
+    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false, SEL, PQW>);
+    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false, SEL, PQW>);
 }
 
 // sel == nullptr: the kernels without the selection switch, the search over every image
-template <typename T, int WAVES, bool LISTS>
+template <typename T, int WAVES, bool LISTS, bool PQW>
 int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
                   const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
                   int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
                   int top_t, const uint32_t *sel) {
     if (sel)
-        return launch_tokens_sel<T, WAVES, LISTS, true>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
+        return launch_tokens_sel<T, WAVES, LISTS, true, PQW>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
                                                         rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, sel);
-    return launch_tokens_sel<T, WAVES, LISTS, false>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
+    return launch_tokens_sel<T, WAVES, LISTS, false, PQW>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
                                                      rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, nullptr);
 }
 
@@ -270,6 +286,19 @@ extern "C" int skyemb_cosine_token_applicable(int Q, int P, int D, int k) {
     return ok ? 1 : 0;
 }
 
+#define TOKEN_PQ_SHAPE_MSG                                                                                                     \
+    "needs Q <= 16, D %% 64 == 0, D <= 1024, 1 <= P <= 4096 with 16 %% P == 0 or P %% 16 == 0, 1 <= k <= 512 and "             \
+    "128 D + 32 Q k <= 163840 bytes of LDS (Q=%d P=%d D=%d k=%d)"
+
+// The same for the calls with per-query weights: two operand images (tw and w) are resident, so 128 D takes the place of 64 D.
+extern "C" int skyemb_cosine_token_pq_applicable(int Q, int P, int D, int k) {
+    const bool ok = Q >= 1 && Q <= 16 && D >= 64 && D % (16 * UNROLL) == 0 && D <= 1024 && P >= 1 && P <= 4096 &&
+                    (16 % P == 0 || P % 16 == 0) && k >= 1 && k <= 512 &&
+                    2 * image_bytes(D) + (size_t)4 * 8 * Q * k <= (size_t)LDS_BYTES;
+    if (!ok) skyemb_set_error("patch-token search with per-query weights " TOKEN_PQ_SHAPE_MSG, Q, P, D, k);
+    return ok ? 1 : 0;
+}
+
 extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, int k) {
     if (N < 1 || !skyemb_cosine_token_applicable(Q, P, D, k)) return 0;
     const int waves = token_waves(Q, D, k);
@@ -280,45 +309,51 @@ extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, i
 }
 
 // Argument checks and launch geometry of the two calls, for every bank element type (`who`: the entry point's name in error texts).
-template <typename T>
+// PQW: `xn` is w [Q, D] (the `_pq` calls): their own shape rule, the doubled image in the wave choice and in the LDS size
+template <typename T, bool PQW = false>
 int token_topk(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D, int k,
                int combine, int top_t, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i,
                void *stream, const uint32_t *sel = nullptr) {
     SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "%s: bad arguments", who);
-    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
+    if (PQW) SKY_CHECK_ARG(skyemb_cosine_token_pq_applicable(Q, P, D, k), "%s: " TOKEN_PQ_SHAPE_MSG, who, Q, P, D, k);
+    else SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
     SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
     SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
     SKY_CHECK_ARG(N * P < (1ll << 31), "%s: shard too large (N * P < 2^31 rows per call)", who);
     SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
                   who);
     SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
+    if (PQW) SKY_CHECK_ARG(aligned16(xn), "%s: w must be 16-byte aligned", who);
     SKY_CHECK_ARG(((uintptr_t)sel & 3) == 0, "%s: select must be 4-byte aligned", who);
-    const int waves = token_waves(Q, D, k);
+    const int images = PQW ? 2 : 1;
+    const int waves = token_waves(Q, D, k, images);                  // nlists is a multiple of 8 or of 4: either choice divides it
     const int64_t R = N * P, unit = image_unit(P);
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, nlists), unit) * unit;
-    const size_t smem = image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
+    const size_t smem = images * image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
     if (waves == 8)
-        return launch_tokens<T, 8, true>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
+        return launch_tokens<T, 8, true, PQW>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
                                          idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t, sel);
-    return launch_tokens<T, 4, true>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
+    return launch_tokens<T, 4, true, PQW>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
                                      idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t, sel);
 }
 
-template <typename T>
+template <typename T, bool PQW = false>
 int token_scores(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D,
                  int combine, int top_t, float eps, float *scores, void *stream, const uint32_t *sel = nullptr) {
     SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "%s: bad arguments", who);
-    SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, 1);
+    if (PQW) SKY_CHECK_ARG(skyemb_cosine_token_pq_applicable(Q, P, D, 1), "%s: " TOKEN_PQ_SHAPE_MSG, who, Q, P, D, 1);
+    else SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, 1);
     SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
     SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
     SKY_CHECK_ARG(N * P < (1ll << 31), "%s: bank too large (N * P < 2^31 rows per call)", who);
     SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
+    if (PQW) SKY_CHECK_ARG(aligned16(xn), "%s: w must be 16-byte aligned", who);
     SKY_CHECK_ARG(((uintptr_t)sel & 3) == 0, "%s: select must be 4-byte aligned", who);
     const int64_t R = N * P, unit = image_unit(P);
     int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), 4);
     if (blocks > 2048) blocks = 2048;
     const int64_t rows_per_wave = ceil_div64(ceil_div64(R, blocks * 4), unit) * unit;
-    return launch_tokens<T, 4, false>(combine, (int)blocks, image_bytes(D), (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, 1,
+    return launch_tokens<T, 4, false, PQW>(combine, (int)blocks, (PQW ? 2 : 1) * image_bytes(D), (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, 1,
                                       eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N, top_t, sel);
 }
 
@@ -421,6 +456,35 @@ extern "C" int skyemb_cosine_token_scores_sel(const float *tw, const float *qn, 
     if (bank_dtype == SKYEMB_BF16)
         return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
     return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+}
+
+// Per-query feature weights (include/skyemb.h): the `_sel` calls with w [Q, D] in place of xn.  select == NULL: every image.
+extern "C" int skyemb_cosine_token_topk_pq(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *w, int Q,
+                                           int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset,
+                                           int nlists, const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select,
+                                           void *stream) {
+    const char *who = "skyemb_cosine_token_topk_pq";
+    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_pq: " TOP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_F32)
+        return token_topk<float, true>(who, tw, qn, (const float *)bank, w, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
+                                       part_s, part_i, stream, select);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_topk<bf16_t, true>(who, tw, qn, (const bf16_t *)bank, w, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
+                                        part_s, part_i, stream, select);
+    return token_topk<f16_t, true>(who, tw, qn, (const f16_t *)bank, w, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
+                                   part_s, part_i, stream, select);
+}
+
+extern "C" int skyemb_cosine_token_scores_pq(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *w, int Q,
+                                             int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
+                                             const uint32_t *select, void *stream) {
+    const char *who = "skyemb_cosine_token_scores_pq";
+    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_pq: " TOP_DTYPE_MSG, bank_dtype);
+    if (bank_dtype == SKYEMB_F32)
+        return token_scores<float, true>(who, tw, qn, (const float *)bank, w, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+    if (bank_dtype == SKYEMB_BF16)
+        return token_scores<bf16_t, true>(who, tw, qn, (const bf16_t *)bank, w, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+    return token_scores<f16_t, true>(who, tw, qn, (const f16_t *)bank, w, Q, N, P, D, combine, top_t, eps, scores, stream, select);
 }
 
 namespace {

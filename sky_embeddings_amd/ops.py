@@ -544,6 +544,48 @@ def distance_token_topk(c, t, bank, metric, combine, k, idx_offset, nlists, part
           "skyemb_distance_token_topk")
 
 
+# ---- per-query feature weights: every query of a call has its own row of w / c [Q, D] (include/skyemb.h)
+def cosine_token_pq_refusal(Q, P, D, k):
+    """cosine_token_refusal for the calls with per-query weights (two operand images in LDS: 128 D + 32 Q k <= 163840)."""
+    L = lib()
+    return None if L.skyemb_cosine_token_pq_applicable(Q, P, D, k) else L.skyemb_last_error().decode()
+
+
+def cosine_token_scores_pq(tw, qn, bank, w, combine, eps, scores, top_t=0, select=None):
+    """cosine_token_scores with w [Q, D] in place of the bank norms: the norm of a row under query q's weights is computed in the
+    pass (skyemb_cosine_token_scores_pq)."""
+    Q, D = tw.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_cosine_token_scores_pq(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_scores_pq"), _p(w), Q, N,
+                                              P, D, combine, top_t, eps, _p(scores), _p(select), _stream()),
+          "skyemb_cosine_token_scores_pq")
+
+
+def cosine_token_topk_pq(tw, qn, bank, w, k, combine, eps, idx_offset, nlists, part_s, part_i, thr0=None, top_t=0, select=None):
+    Q, D = tw.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_cosine_token_topk_pq(_p(tw), _p(qn), _p(bank), bank_dtype_code(bank.dtype, "cosine_token_topk_pq"), _p(w), Q, N, P,
+                                            D, k, combine, top_t, eps, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i), _p(select),
+                                            _stream()), "skyemb_cosine_token_topk_pq")
+
+
+def distance_token_scores_pq(c, t, bank, metric, combine, scores, top_t=0, select=None):
+    """distance_token_scores with c [Q, D]: row q = fp32(w_q / sum(w_q)) serves query q (skyemb_distance_token_scores_pq)."""
+    Q, D = t.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_distance_token_scores_pq(_p(c), _p(t), _p(bank), bank_dtype_code(bank.dtype, "distance_token_scores_pq"), Q, N, P,
+                                                D, metric, combine, top_t, _p(scores), _p(select), _stream()),
+          "skyemb_distance_token_scores_pq")
+
+
+def distance_token_topk_pq(c, t, bank, metric, combine, k, idx_offset, nlists, part_s, part_i, thr0=None, top_t=0, select=None):
+    Q, D = t.shape
+    N, P = bank.shape[0], bank.shape[1]
+    check(lib().skyemb_distance_token_topk_pq(_p(c), _p(t), _p(bank), bank_dtype_code(bank.dtype, "distance_token_topk_pq"), Q, N, P, D,
+                                              metric, combine, top_t, k, idx_offset, nlists, _p(thr0), _p(part_s), _p(part_i), _p(select),
+                                              _stream()), "skyemb_distance_token_topk_pq")
+
+
 # ---- linear-probe fits on the device (csrc/probe.hip; driven by sky_embeddings_amd/probe.py)
 def probe_colstats(X, n=None, F=None, ldx=None):
     """X [n, F] fp32 (row stride ``ldx`` elements) -> (mean, var, scale) fp64 [F]; scale is exactly 1 where var == 0."""

@@ -157,7 +157,17 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     the result of the search over the compacted bank and indices mapped back (``cosine_topk_tokens``'s ``select``).  A flat
     [N,D] bank of any dtype is then served as a token bank with one token per row (``stats['path'] == 'tokens'``) under that
     search's limits: k <= 512, D % 64 == 0, D <= 1024, queries in groups of 16.  A PreparedBank with ``select`` is a ValueError:
-    its many-query prefilter under a selection is out of scope."""
+    its many-query prefilter under a selection is out of scope.
+
+    ``weights`` [Q, D] (one row per query; [D] or None: nothing above changes): a flat [N,D] bank is served the same way, as
+    ``cosine_topk_tokens`` with per-query weights and one token per row (``stats['path'] == 'tokens'``); a PreparedBank is a
+    ValueError."""
+    if isinstance(weights, torch.Tensor) and weights.dim() == 2:      # per-query weights: the token search with one token per row
+        if not (isinstance(bank, torch.Tensor) and bank.dim() == 2):
+            raise ValueError("cosine_topk: per-query weights [Q, D] are served by the token search (cosine_topk_tokens with one "
+                             "token per row); pass the flat [N, D] tensor, not a PreparedBank")
+        return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats,
+                                  select=select)
     if select is not None:
         if isinstance(bank, PreparedBank):
             raise ValueError("cosine_topk: select is served by the token search (cosine_topk_tokens with one token per row); pass "
@@ -326,6 +336,43 @@ def _top_t_arg(top_t, P, who):
     return int(top_t)
 
 
+def _weights_arg(weights, Q, D, who, ignored=False):
+    """``weights`` (None | [D] | [Q, D]) -> None for shared weights (None or [D]: the calls as they ever were) or the [Q, D]
+    tensor of per-query weights; ValueError naming both shapes for any other rank, leading dimension or D.  ``ignored``: the bank
+    is a TokenBank, which carries its own weights -- the argument is then looked at only when it is [Q, D], and anything else is
+    passed over unchecked, as it always was."""
+    if weights is None:
+        return None
+    shape = tuple(weights.shape) if isinstance(weights, torch.Tensor) else None
+    if ignored and shape != (Q, D):
+        return None
+    if shape not in ((D,), (Q, D)):
+        raise ValueError(f"{who}: weights has shape {shape if shape is not None else type(weights).__name__}, expected ({D},) -- one "
+                         f"vector for all queries -- or ({Q}, {D}) -- one row per query -- for queries of shape ({Q}, {D})")
+    return weights if len(shape) == 2 else None
+
+
+def _pq_group(who, P, D, k):
+    """Queries per pass with per-query weights: the largest g <= 16 the library takes (two operand images in LDS:
+    128 D + 32 g k <= 163840); ValueError with the library's text when not even one query fits."""
+    for g in range(16, 0, -1):
+        why = ops.cosine_token_pq_refusal(g, P, D, k)
+        if why is None:
+            return g
+    raise ValueError(f"{who}: {why}")
+
+
+def prepare_queries_pq(queries: torch.Tensor, weights: torch.Tensor):
+    """``prepare_queries`` with one weight row per query: query q is prepared by the same call with its own row, so tw[q] and
+    qn[q] are bit-equal to what the single-query search prepares."""
+    Q, D = queries.shape
+    tw = torch.empty(Q, D, device=queries.device)
+    qn = torch.empty(Q, device=queries.device)
+    for i in range(Q):
+        ops.weighted_norms(queries[i:i + 1], weights[i], qn[i:i + 1], tw[i:i + 1])
+    return tw, qn
+
+
 def _token_scores(tw, qn, tokens, norms, code, eps, top_t=0, words=None):
     """[Q, N] combined scores of Q <= 16 prepared queries (words: a Selection's, deselected images score -inf)."""
     out = torch.empty(tw.shape[0], tokens.shape[0], device=tw.device)
@@ -333,22 +380,35 @@ def _token_scores(tw, qn, tokens, norms, code, eps, top_t=0, words=None):
     return out
 
 
-def token_pruning_floor(tw, qn, tb: "TokenBank", k: int, combine: str = 'min', eps: float = 1e-6, sample_images: int | None = None,
-                        top_t: int | None = None, select=None):
+def token_pruning_floor(tw, qn, tb, k: int, combine: str = 'min', eps: float = 1e-6, sample_images: int | None = None,
+                        top_t: int | None = None, select=None, weights=None):
     """Per-query floor for the token search: the k-th best COMBINED score over a sample of whole images, one ulp lower
     (``pruning_floor``'s argument, with images for rows).  None under the same size rule: N < 8 x the sample.  ``top_t``: the
     search's own, so that the sample is scored as the search scores it and the floor stays a lower bound of its k-th best.
     ``select`` (None | bool tensor | Selection): the sample is drawn from the selected images only, strided over them, so the
     floor is a lower bound of the k-th best SELECTED score; the size rule applies to the selected count.  That sample changes
     with the selection, so it is not kept in the bank (``TokenBank._sample``): a ``Selection`` keeps its own (``Selection.sample``),
-    a bool tensor is packed and sampled anew on every call."""
-    t = _top_t_arg(top_t, tb.bank.shape[1], "token_pruning_floor")
-    N, P = tb.bank.shape[0], tb.bank.shape[1]
-    sel = _selection_arg(select, N, "token_pruning_floor", tb.bank.device)
+    a bool tensor is packed and sampled anew on every call.
+    ``weights`` [Q, D] (per-query weights, rows for the Q <= 16 queries of ``tw``; None: the floor above, ``tb`` a TokenBank): the
+    same sample -- ``tb`` may then be a plain [N,P,D] tensor, no norms are needed -- is scored by the kernel with per-query
+    weights, as the search scores it."""
+    tokens = tb.bank if isinstance(tb, TokenBank) else tb
+    t = _top_t_arg(top_t, tokens.shape[1], "token_pruning_floor")
+    N, P = tokens.shape[0], tokens.shape[1]
+    W = _weights_arg(weights, tw.shape[0], tw.shape[1], "token_pruning_floor")
+    sel = _selection_arg(select, N, "token_pruning_floor", tokens.device)
     if sample_images is None:
         sample_images = 256 * k
     if (N if sel is None else sel.count) < 8 * sample_images:
         return None
+    if W is not None:
+        W = W.to(tw.device, torch.float32).contiguous()
+        st = _distance_sample(tb, sel, sample_images)
+        sc = torch.empty(tw.shape[0], st.shape[0], device=tw.device)
+        ops.cosine_token_scores_pq(tw, qn, st, W, _combine_code(combine, "token_pruning_floor"), eps, sc, t)
+        floor = torch.empty(tw.shape[0], device=tw.device)
+        ops.kth_largest_floor(sc, k, floor)
+        return floor
     if sel is None:
         st, sn = tb.sample(sample_images)
     else:
@@ -389,40 +449,73 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     not copied, deselected images cost no HBM bytes when P is a multiple of 16 (P < 16: a 16-row tile is passed over when all
     of its 16 / P images are deselected) and a NaN or inf in them changes nothing.  Fewer than k selected images: the tail is
     (-inf, -1).  One selection serves all queries; with ``world_size > 1`` it describes this rank's shard.  A length other than
-    N is a ValueError before any launch; ``stats`` gains ``selected``."""
+    N is a ValueError before any launch; ``stats`` gains ``selected``.
+
+    ``weights`` [Q, D] (per-query weights, one row per query -- the reference derives the weights from the target, so two targets
+    never share them; [D] or None: the search above, same kernels, same bits): query q is scored under its own row, also when
+    ``bank`` is a TokenBank, whose own weights and norms are then neither used nor touched.  Query preparation is the
+    single-query one, row by row (tw[q], qn[q] bit-equal to a Q = 1 search with that row); the norm of a bank row under query q's
+    weights is computed inside the pass as the fma chain acc = fma(w_q[d], x[d] * x[d], acc) over d = 0, 1, 2, ... (x * x
+    rounded once), then one IEEE square root -- no norm pass over the bank, no norm array.  That is not ``TokenBank``'s order,
+    so the search with one shared vector and this one with Q identical rows may differ in the last bits of a score; a 16-bit
+    bank still gives the fp32 result on the widened bank bit for bit, and row q of the result is bit for bit the Q = 1 search
+    with query q and its row.  An all-zero row scores every token 0; a negative sum under the root or a NaN weight gives -inf
+    (never returned).  Queries run in groups of the largest g <= 16 with 128 D + 32 g k <= 163840 (two operand images in LDS;
+    D = 768, k = 300: six per pass), weights sliced along; ValueError with the library's text when g = 1 does not fit, and, naming
+    both shapes, for weights of any other rank, leading dimension or D.  ``stats['per_query_weights']`` is True and
+    ``stats['group']`` is g."""
+    who = "cosine_topk_tokens"
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
     N, P = tokens.shape[0], tokens.shape[1]
     assert tokens.dim() == 3 and D == tokens.shape[2]
-    code = _combine_code(combine, "cosine_topk_tokens")
-    t = _top_t_arg(top_t, P, "cosine_topk_tokens")
+    code = _combine_code(combine, who)
+    t = _top_t_arg(top_t, P, who)
     if k < 1:
-        raise ValueError(f"cosine_topk_tokens: k = {k}")
+        raise ValueError(f"{who}: k = {k}")
     if world_size == 1 and k > N:
-        raise ValueError(f"cosine_topk_tokens: k = {k} exceeds the {N} images of the bank")
-    _check_token_shape("cosine_topk_tokens", Q, P, D, k)     # every refusal above and here: before the first launch
-    sel = _selection_arg(select, N, "cosine_topk_tokens", tokens.device)
+        raise ValueError(f"{who}: k = {k} exceeds the {N} images of the bank")
+    W = _weights_arg(weights, Q, D, who, isinstance(bank, TokenBank))
+    if W is None:
+        _check_token_shape(who, Q, P, D, k)                  # every refusal above and here: before the first launch
+        step = 16
+    else:
+        ops.bank_dtype_code(tokens.dtype, who)
+        step = _pq_group(who, P, D, k)
+    sel = _selection_arg(select, N, who, tokens.device)
     words = None if sel is None else sel.words
-    tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
-    q = queries.to(tb.bank.device, torch.float32).contiguous()
+    if W is None:
+        tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
+        idx_offset = tb.idx_offset
+    else:                                           # no TokenBank is built: its norm pass is what these weights make useless
+        tb = bank
+        idx_offset = bank.idx_offset if isinstance(bank, TokenBank) else 0
+        W = W.to(tokens.device, torch.float32).contiguous()
+    q = queries.to(tokens.device, torch.float32).contiguous()
     out_s = torch.empty(Q, k, device=q.device)
     out_i = torch.empty(Q, k, device=q.device, dtype=torch.int64)
     if Q == 0:                                      # nothing to search for: empty result, no launch
         return out_s, out_i
-    tw_all, qn_all = prepare_queries(q, tb.weights)
+    tw_all, qn_all = prepare_queries(q, tb.weights) if W is None else prepare_queries_pq(q, W)
     pruned = False
-    for lo in range(0, Q, 16):
-        tw, qn = tw_all[lo:lo + 16], qn_all[lo:lo + 16]
+    for lo in range(0, Q, step):
+        tw, qn = tw_all[lo:lo + step], qn_all[lo:lo + step]
+        Wg = None if W is None else W[lo:lo + step]
         Qg = tw.shape[0]
-        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps, top_t=top_t, select=sel) if prune else None
+        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps, top_t=top_t, select=sel, weights=Wg) if prune else None
         pruned = pruned or thr0 is not None
         nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
         ps = torch.empty(Qg, nl, k, device=q.device)
         pi = torch.empty(Qg, nl, k, device=q.device, dtype=torch.int64)
-        ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, tb.idx_offset, nl, ps, pi, thr0, t, words)
-        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + 16], out_i[lo:lo + 16], torch.empty(Qg, device=q.device, dtype=torch.int32))
+        if W is None:
+            ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, idx_offset, nl, ps, pi, thr0, t, words)
+        else:
+            ops.cosine_token_topk_pq(tw, qn, tokens, Wg, k, code, eps, idx_offset, nl, ps, pi, thr0, t, words)
+        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + step], out_i[lo:lo + step], torch.empty(Qg, device=q.device, dtype=torch.int32))
     if stats is not None:
-        stats.update(path="tokens", groups=(Q + 15) // 16, pruned=pruned)
+        stats.update(path="tokens", groups=(Q + step - 1) // step, pruned=pruned)
+        if W is not None:
+            stats.update(per_query_weights=True, group=step)
         if top_t is not None:
             stats.update(top_t=t)
         if sel is not None:
@@ -441,12 +534,27 @@ def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weigh
     ``weights`` is ignored when ``bank`` is a TokenBank (it carries its own).  ``top_t``: as for ``cosine_topk_tokens`` (None:
     all tokens; else only the top_t best token scores of an image count, mean summed largest first -- so 'mean' with
     ``top_t == P`` is not the plain mean).  ``select``: as for ``cosine_topk_tokens``; every [Q, N] slot is written, a deselected
-    image gets -inf."""
+    image gets -inf.  ``weights`` [Q, D]: per-query weights, as for ``cosine_topk_tokens`` (groups of g queries at k = 1)."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
     assert tokens.dim() == 3 and D == tokens.shape[2]
     code = _combine_code(combine, "cosine_token_scores")
     t = _top_t_arg(top_t, tokens.shape[1], "cosine_token_scores")
+    W = _weights_arg(weights, Q, D, "cosine_token_scores", isinstance(bank, TokenBank))
+    if W is not None:
+        ops.bank_dtype_code(tokens.dtype, "cosine_token_scores")
+        step = _pq_group("cosine_token_scores", tokens.shape[1], D, 1)
+        sel = _selection_arg(select, tokens.shape[0], "cosine_token_scores", tokens.device)
+        q = queries.to(tokens.device, torch.float32).contiguous()
+        W = W.to(tokens.device, torch.float32).contiguous()
+        out = torch.empty(Q, tokens.shape[0], device=q.device)
+        if Q == 0:
+            return out
+        tw, qn = prepare_queries_pq(q, W)
+        for lo in range(0, Q, step):
+            ops.cosine_token_scores_pq(tw[lo:lo + step], qn[lo:lo + step], tokens, W[lo:lo + step], code, eps, out[lo:lo + step], t,
+                                       None if sel is None else sel.words)
+        return out
     _check_token_shape("cosine_token_scores", Q, tokens.shape[1], D, 1)
     sel = _selection_arg(select, tokens.shape[0], "cosine_token_scores", tokens.device)
     words = None if sel is None else sel.words
@@ -472,14 +580,19 @@ def _metric_code(metric, who):
 
 
 def prepare_distance_weights(weights, D, device):
-    """c = fp32(w / sum(w)) [D] on the device, by torch: the feature weights as the distance kernels take them (None: w = 1)."""
+    """c = fp32(w / sum(w)) [D] on the device, by torch: the feature weights as the distance kernels take them (None: w = 1).
+    ``weights`` [Q, D] (per-query weights): c [Q, D], every row prepared on its own by the [D] rule, so row q is bit-equal to
+    what the single-query search prepares from it."""
+    if weights is not None and weights.dim() == 2:
+        return torch.stack([prepare_distance_weights(row, D, device) for row in weights]).contiguous()
     w = torch.ones(D, device=device) if weights is None else weights.to(device, torch.float32).reshape(D)
     return (w / w.sum()).contiguous()
 
 
 def _distance_scores(c, t, tokens, mcode, ccode, top_t=0, words=None):
+    """[Q, N] combined distances of Q <= 16 queries; c [D], or [Q, D] with one row per query."""
     out = torch.empty(t.shape[0], tokens.shape[0], device=t.device)
-    ops.distance_token_scores(c, t, tokens, mcode, ccode, out, top_t, words)
+    (ops.distance_token_scores if c.dim() == 1 else ops.distance_token_scores_pq)(c, t, tokens, mcode, ccode, out, top_t, words)
     return out
 
 
@@ -498,10 +611,14 @@ def distance_pruning_floor(c, t, bank, k: int, metric: str = 'MAE', combine: str
     """``token_pruning_floor`` for the distance metrics, in KEY space (key = -distance): the same sample of whole images (the
     selection's own under ``select``) is scored by the distance kernel, negated, and its k-th largest key, one ulp lower, is a
     floor of the k-th best key of the search.  None under the same size rule (fewer than 8 x the sample's images).  ``c``:
-    ``prepare_distance_weights``; ``t`` [Q <= 16, D]; ``bank``: a [N,P,D] tensor or a TokenBank."""
+    ``prepare_distance_weights`` ([D], or [Q, D] with one row per query of ``t``); ``t`` [Q <= 16, D]; ``bank``: a [N,P,D] tensor or
+    a TokenBank."""
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     N, P = tokens.shape[0], tokens.shape[1]
     tt = _top_t_arg(top_t, P, "distance_pruning_floor")
+    if tuple(c.shape) not in ((t.shape[1],), tuple(t.shape)):
+        raise ValueError(f"distance_pruning_floor: c has shape {tuple(c.shape)}, expected ({t.shape[1]},) or {tuple(t.shape)} for "
+                         f"queries of shape {tuple(t.shape)}")
     mcode, ccode = _metric_code(metric, "distance_pruning_floor"), _combine_code(combine, "distance_pruning_floor")
     sel = _selection_arg(select, N, "distance_pruning_floor", tokens.device)
     if sample_images is None:
@@ -532,7 +649,13 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
 
     ``select``, ``prune``, ``stats``, ``world_size``: as for ``cosine_topk_tokens`` (the floor and the merges work on
     key = -distance).  Every ValueError -- an unknown metric or combine, top_t outside 1 .. min(P, 16), k, a selection of
-    another length, a shape the kernels do not take -- is raised before the first launch."""
+    another length, a shape the kernels do not take -- is raised before the first launch.
+
+    ``weights`` [Q, D] (per-query weights, one row per query, also over a TokenBank's own; [D] or None: the search above, same
+    kernels, same bits): query q takes c_q = fp32(w_q / sum(w_q)), prepared row by row, and the contract is untouched, so row q of
+    the result is bit for bit the Q = 1 search with query q and ``weights=w_q``.  c [Q, D] sits in LDS beside the queries, so
+    the queries run in groups of the largest g <= 16 with 128 D + 32 g k <= 163840, as for ``cosine_topk_tokens``;
+    ``stats['per_query_weights']`` is True and ``stats['group']`` is g."""
     who = "distance_topk_tokens"
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
@@ -545,33 +668,41 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     if world_size == 1 and k > N:
         raise ValueError(f"{who}: k = {k} exceeds the {N} images of the bank")
     ops.bank_dtype_code(tokens.dtype, who)
-    _check_token_shape(who, Q, P, D, k)
+    W = _weights_arg(weights, Q, D, who, isinstance(bank, TokenBank))
+    if W is None:
+        _check_token_shape(who, Q, P, D, k)
+        step = 16
+    else:
+        step = _pq_group(who, P, D, k)
     sel = _selection_arg(select, N, who, tokens.device)
     words = None if sel is None else sel.words
     dev = tokens.device
-    if isinstance(bank, TokenBank):
-        weights, idx_offset = bank.weights, bank.idx_offset
-    else:
-        idx_offset = 0
+    idx_offset = bank.idx_offset if isinstance(bank, TokenBank) else 0
+    if isinstance(bank, TokenBank) and W is None:
+        weights = bank.weights
     q = queries.to(dev, torch.float32).contiguous()
     out_s = torch.empty(Q, k, device=dev)
     out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
     if Q == 0:
         return out_s, out_i
-    c = prepare_distance_weights(weights, D, dev)
+    c_all = prepare_distance_weights(weights, D, dev)
     pruned = False
-    for lo in range(0, Q, 16):
-        t = q[lo:lo + 16]
+    for lo in range(0, Q, step):
+        t = q[lo:lo + step]
+        c = c_all if W is None else c_all[lo:lo + step]
         Qg = t.shape[0]
         thr0 = distance_pruning_floor(c, t, bank, k, metric, combine, top_t=top_t, select=sel) if prune else None
         pruned = pruned or thr0 is not None
         nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
         ps = torch.empty(Qg, nl, k, device=dev)
         pi = torch.empty(Qg, nl, k, device=dev, dtype=torch.int64)
-        ops.distance_token_topk(c, t, tokens, mcode, ccode, k, idx_offset, nl, ps, pi, thr0, tt, words)
-        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + 16], out_i[lo:lo + 16], torch.empty(Qg, device=dev, dtype=torch.int32))
+        (ops.distance_token_topk if W is None else ops.distance_token_topk_pq)(c, t, tokens, mcode, ccode, k, idx_offset, nl, ps, pi,
+                                                                               thr0, tt, words)
+        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + step], out_i[lo:lo + step], torch.empty(Qg, device=dev, dtype=torch.int32))
     if stats is not None:
-        stats.update(path="tokens", metric=metric, groups=(Q + 15) // 16, pruned=pruned)
+        stats.update(path="tokens", metric=metric, groups=(Q + step - 1) // step, pruned=pruned)
+        if W is not None:
+            stats.update(per_query_weights=True, group=step)
         if top_t is not None:
             stats.update(top_t=tt)
         if sel is not None:
@@ -587,7 +718,8 @@ def distance_token_scores(queries: torch.Tensor, bank, metric: str = 'MAE', comb
                           top_t: int | None = None, select=None):
     """[Q, N] combined weighted MSE / MAE distance of every image of a [N,P,D] token bank (fp32, fp16 or bf16; or a TokenBank, whose
     weights then replace ``weights``), in groups of at most 16 queries; ``metric``, ``combine``, ``top_t`` and the NaN rule as for
-    ``distance_topk_tokens``.  ``select``: every [Q, N] slot is written, a deselected image gets +inf."""
+    ``distance_topk_tokens``.  ``select``: every [Q, N] slot is written, a deselected image gets +inf.  ``weights`` [Q, D]:
+    per-query weights, as for ``distance_topk_tokens`` (groups of g queries at k = 1)."""
     who = "distance_token_scores"
     tokens = bank.bank if isinstance(bank, TokenBank) else bank
     Q, D = queries.shape
@@ -595,16 +727,21 @@ def distance_token_scores(queries: torch.Tensor, bank, metric: str = 'MAE', comb
     mcode, ccode = _metric_code(metric, who), _combine_code(combine, who)
     tt = _top_t_arg(top_t, tokens.shape[1], who)
     ops.bank_dtype_code(tokens.dtype, who)
-    _check_token_shape(who, Q, tokens.shape[1], D, 1)
+    W = _weights_arg(weights, Q, D, who, isinstance(bank, TokenBank))
+    if W is None:
+        _check_token_shape(who, Q, tokens.shape[1], D, 1)
+        step = 16
+    else:
+        step = _pq_group(who, tokens.shape[1], D, 1)
     sel = _selection_arg(select, tokens.shape[0], who, tokens.device)
     words = None if sel is None else sel.words
-    if isinstance(bank, TokenBank):
+    if isinstance(bank, TokenBank) and W is None:
         weights = bank.weights
     q = queries.to(tokens.device, torch.float32).contiguous()
     out = torch.empty(Q, tokens.shape[0], device=tokens.device)
     if Q == 0:
         return out
     c = prepare_distance_weights(weights, D, tokens.device)
-    for lo in range(0, Q, 16):
-        out[lo:lo + 16] = _distance_scores(c, q[lo:lo + 16], tokens, mcode, ccode, tt, words)
+    for lo in range(0, Q, step):
+        out[lo:lo + step] = _distance_scores(c if W is None else c[lo:lo + step], q[lo:lo + step], tokens, mcode, ccode, tt, words)
     return out
