@@ -320,20 +320,13 @@ int launch_sel(const Launch &a, const T *bank, int combine) {
     return a.pq ? launch_pq<T, METRIC, LISTS, SEL, true>(a, bank, combine) : launch_pq<T, METRIC, LISTS, SEL, false>(a, bank, combine);
 }
 
-template <typename T, bool LISTS>
+template <bool LISTS, typename T>
 int launch_typed(const Launch &a, const T *bank, int metric, int combine) {
     if (metric == SKYEMB_METRIC_MSE)
         return a.sel ? launch_sel<T, SKYEMB_METRIC_MSE, LISTS, true>(a, bank, combine)
                      : launch_sel<T, SKYEMB_METRIC_MSE, LISTS, false>(a, bank, combine);
     return a.sel ? launch_sel<T, SKYEMB_METRIC_MAE, LISTS, true>(a, bank, combine)
                  : launch_sel<T, SKYEMB_METRIC_MAE, LISTS, false>(a, bank, combine);
-}
-
-template <bool LISTS>
-int launch_any(const Launch &a, const void *bank, int bank_dtype, int metric, int combine) {
-    if (bank_dtype == SKYEMB_F32) return launch_typed<float, LISTS>(a, (const float *)bank, metric, combine);
-    if (bank_dtype == SKYEMB_BF16) return launch_typed<bf16_t, LISTS>(a, (const bf16_t *)bank, metric, combine);
-    return launch_typed<f16_t, LISTS>(a, (const f16_t *)bank, metric, combine);
 }
 
 // the refusals both calls share; every one of them comes before any launch
@@ -371,21 +364,19 @@ int distance_topk(const char *who, bool pq, const float *c, const float *t, cons
                   who);
     // nlists is a multiple of 4 (blocks x 4 or 8 waves); 4 Q D <= 64 D, so four waves' lists fit under the cosine search's LDS rule
     // (pq: 8 Q D <= 128 D under the rule with two images)
-    const int64_t R = N * P, unit = P < 16 ? 16 : P;
-    Launch a = {nlists / DWAVES, (size_t)4 * Q * D * (pq ? 2 : 1) + (size_t)2 * 4 * DWAVES * Q * k, (hipStream_t)stream, who, c, t, Q, R, P,
-                D, k, idx_offset, ceil_div64(ceil_div64(R, nlists), unit) * unit, part_s, part_i, thr0, nullptr, N, top_t, select, pq};
-    return launch_any<true>(a, bank, bank_dtype, metric, combine);
+    const int64_t R = N * P;
+    const Launch a = {nlists / DWAVES, (size_t)4 * Q * D * (pq ? 2 : 1) + (size_t)2 * 4 * DWAVES * Q * k, (hipStream_t)stream, who, c, t, Q, R,
+                      P, D, k, idx_offset, token_rows_per_wave(R, nlists, P), part_s, part_i, thr0, nullptr, N, top_t, select, pq};
+    return with_bank_type(bank, bank_dtype, [&](auto *b) { return launch_typed<true>(a, b, metric, combine); });
 }
 
 int distance_scores(const char *who, bool pq, const float *c, const float *t, const void *bank, int bank_dtype, int Q, int64_t N, int P,
                     int D, int metric, int combine, int top_t, float *scores, const uint32_t *select, void *stream) {
     if (check_common(who, c, t, bank, bank_dtype, Q, N, P, D, 1, metric, combine, top_t, scores, select, pq)) return 1;
-    const int64_t R = N * P, unit = P < 16 ? 16 : P;
-    int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), DWAVES);
-    if (blocks > 2048) blocks = 2048;
-    Launch a = {(int)blocks, (size_t)4 * Q * D * (pq ? 2 : 1), (hipStream_t)stream, who, c, t, Q, R, P, D, 1, 0,
-                ceil_div64(ceil_div64(R, blocks * DWAVES), unit) * unit, nullptr, nullptr, nullptr, scores, N, top_t, select, pq};
-    return launch_any<false>(a, bank, bank_dtype, metric, combine);
+    const int64_t R = N * P, blocks = token_scores_blocks(R, P);    // workgroups of DWAVES = 4 waves
+    const Launch a = {(int)blocks, (size_t)4 * Q * D * (pq ? 2 : 1), (hipStream_t)stream, who, c, t, Q, R, P, D, 1, 0,
+                      token_rows_per_wave(R, blocks * DWAVES, P), nullptr, nullptr, nullptr, scores, N, top_t, select, pq};
+    return with_bank_type(bank, bank_dtype, [&](auto *b) { return launch_typed<false>(a, b, metric, combine); });
 }
 
 }  // namespace

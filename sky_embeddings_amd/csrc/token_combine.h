@@ -84,3 +84,27 @@ __device__ __forceinline__ float top_finish(float v, int lane, int tp, int top_t
     const float c = __fdiv_rn(acc, (float)top_t);
     return c == c ? c : -INFINITY;
 }
+
+// ---- host side, shared by topk_tokens.hip and distance_tokens.hip: the launch geometry of the two searches, stated once, and the
+// dispatch on a bank's element type
+
+inline int64_t image_unit(int P) { return P < 16 ? 16 : P; }       // lcm(P, 16) for the accepted P
+
+// rows of one wave when R rows are dealt to `lists` waves: whole images and whole 16-row tiles
+inline int64_t token_rows_per_wave(int64_t R, int64_t lists, int P) {
+    return ceil_div64(ceil_div64(R, lists), image_unit(P)) * image_unit(P);
+}
+
+// workgroups (of four waves) of a scores call: at least 64 rows and one whole image per wave, at most 2048
+inline int64_t token_scores_blocks(int64_t R, int P) {
+    const int64_t blocks = ceil_div64(ceil_div64(R, image_unit(P) < 64 ? 64 : image_unit(P)), 4);
+    return blocks > 2048 ? 2048 : blocks;
+}
+
+// f(bank as a pointer to its element type); the caller has refused every other bank_dtype code
+template <typename F>
+int with_bank_type(const void *bank, int bank_dtype, F &&f) {
+    if (bank_dtype == SKYEMB_F32) return f((const float *)bank);
+    if (bank_dtype == SKYEMB_BF16) return f((const bf16_t *)bank);
+    return f((const f16_t *)bank);
+}

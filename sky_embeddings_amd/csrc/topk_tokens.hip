@@ -225,76 +225,94 @@ int token_waves(int Q, int D, int k, int images = 1) {
     return images * image_bytes(D) + (size_t)8 * 8 * Q * k <= (size_t)LDS_BYTES ? 8 : 4;
 }
 
-int64_t image_unit(int P) { return P < 16 ? 16 : P; }              // lcm(P, 16) for the accepted P
+// the shape limits of both predicates: k <= 512 is the list capacity skyemb_topk_merge sorts; four waves' lists sit next to the
+// operand images (1, or 2 with per-query weights): images x 64 D + 32 Q k <= 160 KiB
+bool token_shape_ok(int images, int Q, int P, int D, int k) {
+    return Q >= 1 && Q <= 16 && D >= 64 && D % (16 * UNROLL) == 0 && D <= 1024 && P >= 1 && P <= 4096 && (16 % P == 0 || P % 16 == 0) &&
+           k >= 1 && k <= 512 && images * image_bytes(D) + (size_t)4 * 8 * Q * k <= (size_t)LDS_BYTES;
+}
 
-bool combine_ok(int combine) { return combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MEAN || combine == SKYEMB_COMBINE_MAX; }
+// which bank_dtype codes an entry point takes
+enum Dtypes { F32_ONLY, LP_ONLY, ANY_DTYPE };
 
+// One call.  The entry points fill the first block; token_topk / token_scores add their own; token_call checks it all and
+// works out the geometry.
+struct Launch {
+    const char *who;
+    Dtypes dtypes;
+    bool pq;                                                        // xw is w [Q, D] (the `_pq` calls), else xn [N * P]
+    const float *tw, *qn;
+    const void *bank;
+    int bank_dtype;
+    const float *xw;
+    int Q;
+    int64_t N;
+    int P, D, combine, top_t;
+    float eps;
+    const uint32_t *sel;                                            // nullptr: the kernels without the selection switch
+    hipStream_t st;
+    // the top-k call: lists part_s / part_i [Q, nlists, k]; the scores call: scores [Q, N], at k = 1
+    int k = 1, nlists = 0;
+    int64_t idx_offset = 0, *part_i = nullptr;
+    const float *thr0 = nullptr;
+    float *part_s = nullptr, *scores = nullptr;
+    // geometry
+    int blocks = 0;
+    size_t smem = 0;
+    int64_t R = 0, rows_per_wave = 0;
+};
+
+template <typename T, int WAVES, int COMBINE, bool LISTS, bool TOPT, bool SEL, bool PQW>
+int launch_kernel(const Launch &a, const T *bank) {
+    const auto kern = cosine_token_kernel<T, WAVES, COMBINE, LISTS, TOPT, SEL, PQW>;
+    if (a.smem > 64 * 1024) {
+        const int rc = sky_set_lds_limit((const void *)kern, LDS_BYTES, a.who);
+        if (rc != 0) return rc;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)a.blocks), dim3(WAVES * 64), a.smem, a.st, a.tw, a.qn, bank, a.xw, a.Q, a.R, a.P, a.D, a.k, a.eps,
+                       a.idx_offset, a.rows_per_wave, a.part_s, a.part_i, a.thr0, a.scores, a.N, a.top_t, a.sel);
+    SKY_LAUNCH_CHECK(a.who);
+    return 0;
+}
+
+// the choice of the instantiation: per-query weights, selection, then combine and top-t
 template <typename T, int WAVES, bool LISTS, bool SEL, bool PQW>
-int launch_tokens_sel(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
-                      const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
-                      int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
-                      int top_t, const uint32_t *sel) {
-    auto go = [&](auto kern) {
-        if (smem > 64 * 1024) {
-            const int rc = sky_set_lds_limit((const void *)kern, LDS_BYTES, who);
-            if (rc != 0) return rc;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), smem, st, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
-                           rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, sel);
-        SKY_LAUNCH_CHECK(who);
-        return 0;
-    };
+int launch_combine(const Launch &a, const T *bank) {
     // top_t == 0: all tokens, the plain kernels; max is d[0] for every top_t, the plain max kernel
-    if (top_t != 0 && combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true, SEL, PQW>);
-    if (top_t != 0 && combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true, SEL, PQW>);
-    if (combine == SKYEMB_COMBINE_MIN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false, SEL, PQW>);
-    if (combine == SKYEMB_COMBINE_MEAN) return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false, SEL, PQW>);
-    return go(cosine_token_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false, SEL, PQW>);
+    if (a.top_t != 0 && a.combine == SKYEMB_COMBINE_MIN) return launch_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, true, SEL, PQW>(a, bank);
+    if (a.top_t != 0 && a.combine == SKYEMB_COMBINE_MEAN) return launch_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, true, SEL, PQW>(a, bank);
+    if (a.combine == SKYEMB_COMBINE_MIN) return launch_kernel<T, WAVES, SKYEMB_COMBINE_MIN, LISTS, false, SEL, PQW>(a, bank);
+    if (a.combine == SKYEMB_COMBINE_MEAN) return launch_kernel<T, WAVES, SKYEMB_COMBINE_MEAN, LISTS, false, SEL, PQW>(a, bank);
+    return launch_kernel<T, WAVES, SKYEMB_COMBINE_MAX, LISTS, false, SEL, PQW>(a, bank);
 }
 
-// sel == nullptr: the kernels without the selection switch, the search over every image
 template <typename T, int WAVES, bool LISTS, bool PQW>
-int launch_tokens(int combine, int blocks, size_t smem, hipStream_t st, const char *who, const float *tw, const float *qn,
-                  const T *bank, const float *xn, int Q, int64_t R, int P, int D, int k, float eps, int64_t idx_offset,
-                  int64_t rows_per_wave, float *part_s, int64_t *part_i, const float *thr0, float *scores, int64_t n_img,
-                  int top_t, const uint32_t *sel) {
-    if (sel)
-        return launch_tokens_sel<T, WAVES, LISTS, true, PQW>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
-                                                        rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, sel);
-    return launch_tokens_sel<T, WAVES, LISTS, false, PQW>(combine, blocks, smem, st, who, tw, qn, bank, xn, Q, R, P, D, k, eps, idx_offset,
-                                                     rows_per_wave, part_s, part_i, thr0, scores, n_img, top_t, nullptr);
+int launch_sel(const Launch &a, const T *bank) {
+    return a.sel ? launch_combine<T, WAVES, LISTS, true, PQW>(a, bank) : launch_combine<T, WAVES, LISTS, false, PQW>(a, bank);
 }
 
-bool top_t_ok(int top_t, int P) { return top_t >= 0 && top_t <= (P < 16 ? P : 16); }
-
-#define TOP_T_MSG "top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)"
+template <int WAVES, bool LISTS, typename T>
+int launch_tokens(const Launch &a, const T *bank) {
+    return a.pq ? launch_sel<T, WAVES, LISTS, true>(a, bank) : launch_sel<T, WAVES, LISTS, false>(a, bank);
+}
 
 }  // namespace
 
-#define TOKEN_SHAPE_MSG                                                                                                        \
-    "needs Q <= 16, D %% 64 == 0, D <= 1024, 1 <= P <= 4096 with 16 %% P == 0 or P %% 16 == 0, 1 <= k <= 512 and "             \
-    "64 D + 32 Q k <= 163840 bytes of LDS (Q=%d P=%d D=%d k=%d)"
+#define TOKEN_LIMITS_MSG "needs Q <= 16, D %% 64 == 0, D <= 1024, 1 <= P <= 4096 with 16 %% P == 0 or P %% 16 == 0, 1 <= k <= 512 and "
+#define TOKEN_SHAPE_MSG TOKEN_LIMITS_MSG "64 D + 32 Q k <= 163840 bytes of LDS (Q=%d P=%d D=%d k=%d)"
+#define TOKEN_PQ_SHAPE_MSG TOKEN_LIMITS_MSG "128 D + 32 Q k <= 163840 bytes of LDS (Q=%d P=%d D=%d k=%d)"
 
 // The one statement of the shape limits: a refusal leaves it as the library's error text (skyemb_last_error), which the callers
-// -- the two entry points below and the Python layer -- pass on instead of restating it.
+// -- the entry points below, distance_tokens.hip and the Python layer -- pass on instead of restating it.
 extern "C" int skyemb_cosine_token_applicable(int Q, int P, int D, int k) {
-    // k <= 512: the list capacity skyemb_topk_merge sorts; four waves' lists next to the A image: 64 D + 32 Q k <= 160 KiB
-    const bool ok = Q >= 1 && Q <= 16 && D >= 64 && D % (16 * UNROLL) == 0 && D <= 1024 && P >= 1 && P <= 4096 &&
-                    (16 % P == 0 || P % 16 == 0) && k >= 1 && k <= 512 &&
-                    image_bytes(D) + (size_t)4 * 8 * Q * k <= (size_t)LDS_BYTES;
+    const bool ok = token_shape_ok(1, Q, P, D, k);
     if (!ok) skyemb_set_error("patch-token search " TOKEN_SHAPE_MSG, Q, P, D, k);
     return ok ? 1 : 0;
 }
 
-#define TOKEN_PQ_SHAPE_MSG                                                                                                     \
-    "needs Q <= 16, D %% 64 == 0, D <= 1024, 1 <= P <= 4096 with 16 %% P == 0 or P %% 16 == 0, 1 <= k <= 512 and "             \
-    "128 D + 32 Q k <= 163840 bytes of LDS (Q=%d P=%d D=%d k=%d)"
-
 // The same for the calls with per-query weights: two operand images (tw and w) are resident, so 128 D takes the place of 64 D.
 extern "C" int skyemb_cosine_token_pq_applicable(int Q, int P, int D, int k) {
-    const bool ok = Q >= 1 && Q <= 16 && D >= 64 && D % (16 * UNROLL) == 0 && D <= 1024 && P >= 1 && P <= 4096 &&
-                    (16 % P == 0 || P % 16 == 0) && k >= 1 && k <= 512 &&
-                    2 * image_bytes(D) + (size_t)4 * 8 * Q * k <= (size_t)LDS_BYTES;
+    const bool ok = token_shape_ok(2, Q, P, D, k);
     if (!ok) skyemb_set_error("patch-token search with per-query weights " TOKEN_PQ_SHAPE_MSG, Q, P, D, k);
     return ok ? 1 : 0;
 }
@@ -308,120 +326,106 @@ extern "C" int skyemb_cosine_token_topk_chunks(int64_t N, int P, int Q, int D, i
     return (int)(blocks * waves);
 }
 
-// Argument checks and launch geometry of the two calls, for every bank element type (`who`: the entry point's name in error texts).
-// PQW: `xn` is w [Q, D] (the `_pq` calls): their own shape rule, the doubled image in the wave choice and in the LDS size
-template <typename T, bool PQW = false>
-int token_topk(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D, int k,
-               int combine, int top_t, float eps, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i,
-               void *stream, const uint32_t *sel = nullptr) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && part_s && part_i && N > 0, "%s: bad arguments", who);
-    if (PQW) SKY_CHECK_ARG(skyemb_cosine_token_pq_applicable(Q, P, D, k), "%s: " TOKEN_PQ_SHAPE_MSG, who, Q, P, D, k);
-    else SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
-    SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
-    SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
-    SKY_CHECK_ARG(N * P < (1ll << 31), "%s: shard too large (N * P < 2^31 rows per call)", who);
-    SKY_CHECK_ARG(nlists == skyemb_cosine_token_topk_chunks(N, P, Q, D, k), "%s: nlists must come from skyemb_cosine_token_topk_chunks",
+// the texts an entry point refuses a bank_dtype code with -- before anything else, so a refused code never reaches a launch
+#define LP_DTYPE_MSG "bank_dtype must be SKYEMB_BF16 (0) or SKYEMB_F16 (2), got %d (an fp32 bank takes the call without _lp)"
+#define TOP_DTYPE_MSG "bank_dtype must be SKYEMB_BF16 (0), SKYEMB_F32 (1) or SKYEMB_F16 (2), got %d"
+
+namespace {
+
+// The argument checks of every call, in one order.  lists: the top-k call (part_i and nlists count), else the scores call.
+int check_tokens(const Launch &a, bool lists) {
+    const char *who = a.who;
+    const int Q = a.Q, P = a.P, D = a.D, k = a.k;
+    SKY_CHECK_ARG(a.tw && a.qn && a.bank && a.xw && (lists ? a.part_s && a.part_i : a.scores != nullptr) && a.N > 0, "%s: bad arguments",
                   who);
-    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
-    if (PQW) SKY_CHECK_ARG(aligned16(xn), "%s: w must be 16-byte aligned", who);
-    SKY_CHECK_ARG(((uintptr_t)sel & 3) == 0, "%s: select must be 4-byte aligned", who);
-    const int images = PQW ? 2 : 1;
-    const int waves = token_waves(Q, D, k, images);                  // nlists is a multiple of 8 or of 4: either choice divides it
-    const int64_t R = N * P, unit = image_unit(P);
-    const int64_t rows_per_wave = ceil_div64(ceil_div64(R, nlists), unit) * unit;
-    const size_t smem = images * image_bytes(D) + (size_t)2 * 4 * waves * Q * k;
-    if (waves == 8)
-        return launch_tokens<T, 8, true, PQW>(combine, nlists / 8, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                         idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t, sel);
-    return launch_tokens<T, 4, true, PQW>(combine, nlists / 4, smem, (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, k, eps,
-                                     idx_offset, rows_per_wave, part_s, part_i, thr0, nullptr, N, top_t, sel);
+    if (a.pq) SKY_CHECK_ARG(skyemb_cosine_token_pq_applicable(Q, P, D, k), "%s: " TOKEN_PQ_SHAPE_MSG, who, Q, P, D, k);
+    else SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, k), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, k);
+    SKY_CHECK_ARG(a.combine == SKYEMB_COMBINE_MIN || a.combine == SKYEMB_COMBINE_MEAN || a.combine == SKYEMB_COMBINE_MAX,
+                  "%s: unknown combine code %d", who, a.combine);
+    SKY_CHECK_ARG(a.top_t >= 0 && a.top_t <= (P < 16 ? P : 16), "%s: top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)", who,
+                  a.top_t, P);
+    SKY_CHECK_ARG(a.N * P < (1ll << 31), "%s: %s too large (N * P < 2^31 rows per call)", who, lists ? "shard" : "bank");
+    if (lists)
+        SKY_CHECK_ARG(a.nlists == skyemb_cosine_token_topk_chunks(a.N, P, Q, D, k),
+                      "%s: nlists must come from skyemb_cosine_token_topk_chunks", who);
+    SKY_CHECK_ARG(aligned16(a.bank) && aligned16(a.tw), "%s: bank and tw must be 16-byte aligned", who);
+    if (a.pq) SKY_CHECK_ARG(aligned16(a.xw), "%s: w must be 16-byte aligned", who);
+    SKY_CHECK_ARG(((uintptr_t)a.sel & 3) == 0, "%s: select must be 4-byte aligned", who);
+    return 0;
 }
 
-template <typename T, bool PQW = false>
-int token_scores(const char *who, const float *tw, const float *qn, const T *bank, const float *xn, int Q, int64_t N, int P, int D,
-                 int combine, int top_t, float eps, float *scores, void *stream, const uint32_t *sel = nullptr) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && scores && N > 0, "%s: bad arguments", who);
-    if (PQW) SKY_CHECK_ARG(skyemb_cosine_token_pq_applicable(Q, P, D, 1), "%s: " TOKEN_PQ_SHAPE_MSG, who, Q, P, D, 1);
-    else SKY_CHECK_ARG(skyemb_cosine_token_applicable(Q, P, D, 1), "%s: " TOKEN_SHAPE_MSG, who, Q, P, D, 1);
-    SKY_CHECK_ARG(combine_ok(combine), "%s: unknown combine code %d", who, combine);
-    SKY_CHECK_ARG(top_t_ok(top_t, P), "%s: " TOP_T_MSG, who, top_t, P);
-    SKY_CHECK_ARG(N * P < (1ll << 31), "%s: bank too large (N * P < 2^31 rows per call)", who);
-    SKY_CHECK_ARG(aligned16(bank) && aligned16(tw), "%s: bank and tw must be 16-byte aligned", who);
-    if (PQW) SKY_CHECK_ARG(aligned16(xn), "%s: w must be 16-byte aligned", who);
-    SKY_CHECK_ARG(((uintptr_t)sel & 3) == 0, "%s: select must be 4-byte aligned", who);
-    const int64_t R = N * P, unit = image_unit(P);
-    int64_t blocks = ceil_div64(ceil_div64(R, unit < 64 ? 64 : unit), 4);
-    if (blocks > 2048) blocks = 2048;
-    const int64_t rows_per_wave = ceil_div64(ceil_div64(R, blocks * 4), unit) * unit;
-    return launch_tokens<T, 4, false, PQW>(combine, (int)blocks, (PQW ? 2 : 1) * image_bytes(D), (hipStream_t)stream, who, tw, qn, bank, xn, Q, R, P, D, 1,
-                                      eps, 0, rows_per_wave, nullptr, nullptr, nullptr, scores, N, top_t, sel);
+// Every call: the dtype refusal, the checks, the launch geometry, the launch.  lists: 8 or 4 waves per workgroup (nlists is a
+// multiple of either) and their lists in LDS; else the scores call's 4 waves.
+int token_call(Launch a, bool lists) {
+    if (a.dtypes == LP_ONLY) SKY_CHECK_ARG(sky_is_lp(a.bank_dtype), "%s: " LP_DTYPE_MSG, a.who, a.bank_dtype);
+    if (a.dtypes == ANY_DTYPE)
+        SKY_CHECK_ARG(a.bank_dtype == SKYEMB_F32 || sky_is_lp(a.bank_dtype), "%s: " TOP_DTYPE_MSG, a.who, a.bank_dtype);
+    if (check_tokens(a, lists)) return 1;
+    const int images = a.pq ? 2 : 1;
+    const int waves = lists ? token_waves(a.Q, a.D, a.k, images) : 4;
+    a.R = a.N * a.P;
+    a.blocks = (int)(lists ? a.nlists / waves : token_scores_blocks(a.R, a.P));
+    a.smem = images * image_bytes(a.D) + (lists ? (size_t)2 * 4 * waves * a.Q * a.k : 0);
+    a.rows_per_wave = token_rows_per_wave(a.R, (int64_t)a.blocks * waves, a.P);
+    return with_bank_type(a.bank, a.bank_dtype, [&](auto *b) {
+        if (!lists) return launch_tokens<4, false>(a, b);
+        return waves == 8 ? launch_tokens<8, true>(a, b) : launch_tokens<4, true>(a, b);
+    });
 }
+
+int token_topk(Launch a, int k, int64_t idx_offset, int nlists, const float *thr0, float *part_s, int64_t *part_i) {
+    a.k = k, a.idx_offset = idx_offset, a.nlists = nlists, a.thr0 = thr0, a.part_s = part_s, a.part_i = part_i;
+    return token_call(a, true);
+}
+
+int token_scores(Launch a, float *scores) {
+    a.scores = scores;
+    return token_call(a, false);
+}
+
+}  // namespace
 
 extern "C" int skyemb_cosine_token_topk(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
                                         int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
                                         const float *thr0, float *part_s, int64_t *part_i, void *stream) {
-    return token_topk("skyemb_cosine_token_topk", tw, qn, bank, xn, Q, N, P, D, k, combine, 0, eps, idx_offset, nlists, thr0, part_s,
-                      part_i, stream);
+    return token_topk({"skyemb_cosine_token_topk", F32_ONLY, false, tw, qn, bank, SKYEMB_F32, xn, Q, N, P, D, combine, 0, eps, nullptr,
+                       (hipStream_t)stream}, k, idx_offset, nlists, thr0, part_s, part_i);
 }
 
 extern "C" int skyemb_cosine_token_scores(const float *tw, const float *qn, const float *bank, const float *xn, int Q, int64_t N,
                                           int P, int D, int combine, float eps, float *scores, void *stream) {
-    return token_scores("skyemb_cosine_token_scores", tw, qn, bank, xn, Q, N, P, D, combine, 0, eps, scores, stream);
+    return token_scores({"skyemb_cosine_token_scores", F32_ONLY, false, tw, qn, bank, SKYEMB_F32, xn, Q, N, P, D, combine, 0, eps, nullptr,
+                         (hipStream_t)stream}, scores);
 }
 
-// Half-precision resident banks: the same two calls on a bf16 / fp16 bank (include/skyemb.h).  The dtype is checked first, so a
-// refused code never reaches a launch.
-#define LP_DTYPE_MSG "bank_dtype must be SKYEMB_BF16 (0) or SKYEMB_F16 (2), got %d (an fp32 bank takes the call without _lp)"
-
+// Half-precision resident banks: the same two calls on a bf16 / fp16 bank (include/skyemb.h).
 extern "C" int skyemb_cosine_token_topk_lp(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
                                            int64_t N, int P, int D, int k, int combine, float eps, int64_t idx_offset, int nlists,
                                            const float *thr0, float *part_s, int64_t *part_i, void *stream) {
-    const char *who = "skyemb_cosine_token_topk_lp";
-    SKY_CHECK_ARG(sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_lp: " LP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, 0, eps, idx_offset, nlists, thr0, part_s, part_i,
-                          stream);
-    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, 0, eps, idx_offset, nlists, thr0, part_s, part_i,
-                      stream);
+    return token_topk({"skyemb_cosine_token_topk_lp", LP_ONLY, false, tw, qn, bank, bank_dtype, xn, Q, N, P, D, combine, 0, eps, nullptr,
+                       (hipStream_t)stream}, k, idx_offset, nlists, thr0, part_s, part_i);
 }
 
 extern "C" int skyemb_cosine_token_scores_lp(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn,
                                              int Q, int64_t N, int P, int D, int combine, float eps, float *scores, void *stream) {
-    const char *who = "skyemb_cosine_token_scores_lp";
-    SKY_CHECK_ARG(sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_lp: " LP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_BF16) return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, 0, eps, scores, stream);
-    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, 0, eps, scores, stream);
+    return token_scores({"skyemb_cosine_token_scores_lp", LP_ONLY, false, tw, qn, bank, bank_dtype, xn, Q, N, P, D, combine, 0, eps, nullptr,
+                         (hipStream_t)stream}, scores);
 }
 
 // Top-t combine (include/skyemb.h): one pair of calls for the three bank element types.  top_t == 0 is the plain call of that
 // type: the same checks, the same kernel, the same launch.
-#define TOP_DTYPE_MSG "bank_dtype must be SKYEMB_BF16 (0), SKYEMB_F32 (1) or SKYEMB_F16 (2), got %d"
-
 extern "C" int skyemb_cosine_token_topk_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn, int Q,
                                             int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset,
                                             int nlists, const float *thr0, float *part_s, int64_t *part_i, void *stream) {
-    const char *who = "skyemb_cosine_token_topk_top";
-    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_top: " TOP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_F32)
-        return token_topk(who, tw, qn, (const float *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
-                          part_i, stream);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
-                          part_i, stream);
-    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s, part_i,
-                      stream);
+    return token_topk({"skyemb_cosine_token_topk_top", ANY_DTYPE, false, tw, qn, bank, bank_dtype, xn, Q, N, P, D, combine, top_t, eps,
+                       nullptr, (hipStream_t)stream}, k, idx_offset, nlists, thr0, part_s, part_i);
 }
 
 extern "C" int skyemb_cosine_token_scores_top(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn,
                                               int Q, int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
                                               void *stream) {
-    const char *who = "skyemb_cosine_token_scores_top";
-    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_top: " TOP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_F32)
-        return token_scores(who, tw, qn, (const float *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
-    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
+    return token_scores({"skyemb_cosine_token_scores_top", ANY_DTYPE, false, tw, qn, bank, bank_dtype, xn, Q, N, P, D, combine, top_t, eps,
+                         nullptr, (hipStream_t)stream}, scores);
 }
 
 // Selection (include/skyemb.h): the `_top` calls restricted to the images whose bit is set in `select`.  select == NULL IS the
@@ -430,32 +434,15 @@ extern "C" int skyemb_cosine_token_topk_sel(const float *tw, const float *qn, co
                                             int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset,
                                             int nlists, const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select,
                                             void *stream) {
-    const char *who = "skyemb_cosine_token_topk_sel";
-    if (!select)
-        return skyemb_cosine_token_topk_top(tw, qn, bank, bank_dtype, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
-                                            part_s, part_i, stream);
-    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_sel: " TOP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_F32)
-        return token_topk(who, tw, qn, (const float *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
-                          part_i, stream, select);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_topk(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s,
-                          part_i, stream, select);
-    return token_topk(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0, part_s, part_i,
-                      stream, select);
+    return token_topk({select ? "skyemb_cosine_token_topk_sel" : "skyemb_cosine_token_topk_top", ANY_DTYPE, false, tw, qn, bank, bank_dtype,
+                       xn, Q, N, P, D, combine, top_t, eps, select, (hipStream_t)stream}, k, idx_offset, nlists, thr0, part_s, part_i);
 }
 
 extern "C" int skyemb_cosine_token_scores_sel(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *xn,
                                               int Q, int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
                                               const uint32_t *select, void *stream) {
-    const char *who = "skyemb_cosine_token_scores_sel";
-    if (!select) return skyemb_cosine_token_scores_top(tw, qn, bank, bank_dtype, xn, Q, N, P, D, combine, top_t, eps, scores, stream);
-    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_sel: " TOP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_F32)
-        return token_scores(who, tw, qn, (const float *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_scores(who, tw, qn, (const bf16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
-    return token_scores(who, tw, qn, (const f16_t *)bank, xn, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+    return token_scores({select ? "skyemb_cosine_token_scores_sel" : "skyemb_cosine_token_scores_top", ANY_DTYPE, false, tw, qn, bank,
+                         bank_dtype, xn, Q, N, P, D, combine, top_t, eps, select, (hipStream_t)stream}, scores);
 }
 
 // Per-query feature weights (include/skyemb.h): the `_sel` calls with w [Q, D] in place of xn.  select == NULL: every image.
@@ -463,28 +450,15 @@ extern "C" int skyemb_cosine_token_topk_pq(const float *tw, const float *qn, con
                                            int64_t N, int P, int D, int k, int combine, int top_t, float eps, int64_t idx_offset,
                                            int nlists, const float *thr0, float *part_s, int64_t *part_i, const uint32_t *select,
                                            void *stream) {
-    const char *who = "skyemb_cosine_token_topk_pq";
-    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_topk_pq: " TOP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_F32)
-        return token_topk<float, true>(who, tw, qn, (const float *)bank, w, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
-                                       part_s, part_i, stream, select);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_topk<bf16_t, true>(who, tw, qn, (const bf16_t *)bank, w, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
-                                        part_s, part_i, stream, select);
-    return token_topk<f16_t, true>(who, tw, qn, (const f16_t *)bank, w, Q, N, P, D, k, combine, top_t, eps, idx_offset, nlists, thr0,
-                                   part_s, part_i, stream, select);
+    return token_topk({"skyemb_cosine_token_topk_pq", ANY_DTYPE, true, tw, qn, bank, bank_dtype, w, Q, N, P, D, combine, top_t, eps, select,
+                       (hipStream_t)stream}, k, idx_offset, nlists, thr0, part_s, part_i);
 }
 
 extern "C" int skyemb_cosine_token_scores_pq(const float *tw, const float *qn, const void *bank, int bank_dtype, const float *w, int Q,
                                              int64_t N, int P, int D, int combine, int top_t, float eps, float *scores,
                                              const uint32_t *select, void *stream) {
-    const char *who = "skyemb_cosine_token_scores_pq";
-    SKY_CHECK_ARG(bank_dtype == SKYEMB_F32 || sky_is_lp(bank_dtype), "skyemb_cosine_token_scores_pq: " TOP_DTYPE_MSG, bank_dtype);
-    if (bank_dtype == SKYEMB_F32)
-        return token_scores<float, true>(who, tw, qn, (const float *)bank, w, Q, N, P, D, combine, top_t, eps, scores, stream, select);
-    if (bank_dtype == SKYEMB_BF16)
-        return token_scores<bf16_t, true>(who, tw, qn, (const bf16_t *)bank, w, Q, N, P, D, combine, top_t, eps, scores, stream, select);
-    return token_scores<f16_t, true>(who, tw, qn, (const f16_t *)bank, w, Q, N, P, D, combine, top_t, eps, scores, stream, select);
+    return token_scores({"skyemb_cosine_token_scores_pq", ANY_DTYPE, true, tw, qn, bank, bank_dtype, w, Q, N, P, D, combine, top_t, eps,
+                         select, (hipStream_t)stream}, scores);
 }
 
 namespace {

@@ -10,9 +10,24 @@ order, so the result is identical to the single-GPU one.
 """
 from __future__ import annotations
 
+import dataclasses
+import weakref
+
 import torch
 
 from . import ops
+
+
+def _sample_index(images: int, n: int, device):
+    """The strided sample every pruning floor draws: ``images`` of n rows / images / selected images, n // images apart."""
+    return torch.arange(images, device=device) * (n // images)
+
+
+def _kth_floor(scores: torch.Tensor, k: int):
+    """[Q] the k-th largest of every row of ``scores`` [Q, S], one ulp lower (radix select, one launch): a pruning floor."""
+    floor = torch.empty(scores.shape[0], device=scores.device)
+    ops.kth_largest_floor(scores, k, floor)
+    return floor
 
 
 class PreparedBank:
@@ -44,7 +59,7 @@ class PreparedBank:
         N = self.bank.shape[0]
         rows = min(rows, N)
         if self._sample is None or self._sample[0].shape[0] != rows:
-            idx = torch.arange(rows, device=self.bank.device) * (N // rows)
+            idx = _sample_index(rows, N, self.bank.device)
             self._sample = (self.bank.index_select(0, idx).contiguous(), self.norms.index_select(0, idx).contiguous())
         return self._sample
 
@@ -111,9 +126,7 @@ def pruning_floor(tw, qn, pb: "PreparedBank", k: int, eps: float, sample_rows: i
         return floor
     sc = torch.empty(tw.shape[0], sb.shape[0], device=tw.device)
     ops.cosine_scores(tw, qn, sb, sn, eps, sc)          # [Q, sample] score matrix (small)
-    floor = torch.empty(tw.shape[0], device=tw.device)
-    ops.kth_largest_floor(sc, k, floor)                 # k-th best of the sample, one ulp lower (radix select, one launch)
-    return floor
+    return _kth_floor(sc, k)
 
 
 def _prefilter_enabled():
@@ -162,22 +175,20 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     ``weights`` [Q, D] (one row per query; [D] or None: nothing above changes): a flat [N,D] bank is served the same way, as
     ``cosine_topk_tokens`` with per-query weights and one token per row (``stats['path'] == 'tokens'``); a PreparedBank is a
     ValueError."""
-    if isinstance(weights, torch.Tensor) and weights.dim() == 2:      # per-query weights: the token search with one token per row
-        if not (isinstance(bank, torch.Tensor) and bank.dim() == 2):
-            raise ValueError("cosine_topk: per-query weights [Q, D] are served by the token search (cosine_topk_tokens with one "
-                             "token per row); pass the flat [N, D] tensor, not a PreparedBank")
-        return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats,
-                                  select=select)
-    if select is not None:
+    flat = isinstance(bank, torch.Tensor) and bank.dim() == 2
+    per_query = isinstance(weights, torch.Tensor) and weights.dim() == 2
+    if per_query and not flat:
+        raise ValueError("cosine_topk: per-query weights [Q, D] are served by the token search (cosine_topk_tokens with one "
+                         "token per row); pass the flat [N, D] tensor, not a PreparedBank")
+    if select is not None and not per_query:
         if isinstance(bank, PreparedBank):
             raise ValueError("cosine_topk: select is served by the token search (cosine_topk_tokens with one token per row); pass "
                              "the flat [N, D] tensor, not a PreparedBank -- the prefiltered many-query route takes no selection")
-        if not (isinstance(bank, torch.Tensor) and bank.dim() == 2):
+        if not flat:
             raise ValueError("cosine_topk: select needs a flat [N, D] bank tensor")
+    if per_query or select is not None or (flat and bank.dtype in ops.LP_DTYPES):     # served by the token search, one token per row
         return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats,
                                   select=select)
-    if isinstance(bank, torch.Tensor) and bank.dim() == 2 and bank.dtype in ops.LP_DTYPES:
-        return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats)
     pb = bank if isinstance(bank, PreparedBank) else PreparedBank(bank, weights)
     q = queries.to(pb.bank.device, torch.float32).contiguous()
     Q, D = q.shape
@@ -251,7 +262,7 @@ class TokenBank:
         N, P, _ = self.bank.shape
         images = min(images, N)
         if self._sample is None or self._sample[0].shape[0] != images:
-            idx = torch.arange(images, device=self.bank.device) * (N // images)
+            idx = _sample_index(images, N, self.bank.device)
             self._sample = (self.bank.index_select(0, idx).contiguous(),
                             self.norms.view(N, P).index_select(0, idx).contiguous().view(-1))
         return self._sample
@@ -282,13 +293,12 @@ class Selection:
         """A strided sample of ``images`` SELECTED whole images of ``tb`` (tokens + the norms of their rows) for the pruning floor.
         Kept here, with the selection it belongs to -- not in the bank -- until the bank, its weights or the size change, so
         that repeated searches under one Selection do not gather it again."""
-        import weakref
         if self._sample is None:
             self._sample = weakref.WeakKeyDictionary()     # one entry per bank: a Selection may serve several (fp32 and fp16)
         got = self._sample.get(tb)
         if got is None or got[0] != tb._version or got[1] != images:
             N, P = tb.bank.shape[0], tb.bank.shape[1]
-            idx = self.indices()[torch.arange(images, device=tb.bank.device) * (self.count // images)]
+            idx = self.indices()[_sample_index(images, self.count, tb.bank.device)]
             got = (tb._version, images, tb.bank.index_select(0, idx), tb.norms.view(N, P).index_select(0, idx).view(-1))
             self._sample[tb] = got
         return got[2], got[3]
@@ -373,10 +383,259 @@ def prepare_queries_pq(queries: torch.Tensor, weights: torch.Tensor):
     return tw, qn
 
 
-def _token_scores(tw, qn, tokens, norms, code, eps, top_t=0, words=None):
-    """[Q, N] combined scores of Q <= 16 prepared queries (words: a Selection's, deselected images score -inf)."""
-    out = torch.empty(tw.shape[0], tokens.shape[0], device=tw.device)
-    ops.cosine_token_scores(tw, qn, tokens, norms, code, eps, out, top_t, words)
+def _check_token_shape(who, Q, P, D, k):
+    why = ops.cosine_token_refusal(max(1, min(Q, 16)), P, D, k)       # Q: queries per launch
+    if why is not None:
+        raise ValueError(f"{who}: {why}")
+
+
+def _metric_code(metric, who):
+    if metric not in ops.METRIC_CODES:
+        raise ValueError(f"{who}: metric = {metric!r}, expected one of {sorted(ops.METRIC_CODES)} (the cosine metric is "
+                         f"cosine_topk_tokens / cosine_token_scores)")
+    return ops.METRIC_CODES[metric]
+
+
+def prepare_distance_weights(weights, D, device):
+    """c = fp32(w / sum(w)) [D] on the device, by torch: the feature weights as the distance kernels take them (None: w = 1).
+    ``weights`` [Q, D] (per-query weights): c [Q, D], every row prepared on its own by the [D] rule, so row q is bit-equal to
+    what the single-query search prepares from it."""
+    if weights is not None and weights.dim() == 2:
+        return torch.stack([prepare_distance_weights(row, D, device) for row in weights]).contiguous()
+    w = torch.ones(D, device=device) if weights is None else weights.to(device, torch.float32).reshape(D)
+    return (w / w.sum()).contiguous()
+
+
+_COSINE = object()                      # ``metric`` of the two cosine functions: not a name a caller can pass
+
+
+@dataclasses.dataclass(frozen=True)
+class TokenRequest:
+    """One patch-token request as it stands before the first launch: everything ``_token_request`` decides."""
+    who: str                            # the public function, for error texts
+    Q: int
+    N: int
+    P: int
+    D: int
+    k: int                              # the scores calls: 1
+    combine: int                        # ops.COMBINE_CODES
+    metric: int | None                  # ops.METRIC_CODES (``metric_name``: its key, for stats); None: cosine
+    metric_name: str | None
+    top_t: int                          # the library's argument: 0 = all tokens
+    per_query: bool                     # weights are [Q, D]
+    step: int                           # queries per pass
+    idx_offset: int
+    tokens: torch.Tensor                # [N, P, D], unwrapped
+    bank: "TokenBank | None"            # the TokenBank the caller gave, if any
+    weights: torch.Tensor | None        # the weights that count (see _token_request)
+    select: "Selection | None"
+
+    @property
+    def groups(self):
+        return (self.Q + self.step - 1) // self.step
+
+
+def _token_request(who, queries, bank, k, combine, metric, weights, top_t, select, world_size=1) -> TokenRequest:
+    """Validate a request of one of the four public token functions and decide what is decided before the first launch.  No
+    device work, except that a bool-tensor ``select`` is packed into a Selection (one short launch).  ``k`` None: a scores call
+    (planned at k = 1); ``metric`` _COSINE: no distance metric.  Every ValueError of those functions is raised here, in this
+    order -- cosine: combine, top_t, k, weights shape, shape rule, selection; distance: metric, combine, top_t, k, bank dtype,
+    weights shape, shape rule, selection.
+
+    ``weights``: a TokenBank's own replace a [D] or None argument (which is then not even looked at); a [Q, D] argument
+    overrides them.  ``step``: 16 with shared weights; with per-query weights the largest g <= 16 the library takes
+    (``_pq_group``)."""
+    tb, tokens = _unwrap(bank)
+    (Q, D), (N, P) = queries.shape, tokens.shape[:2]
+    assert tokens.dim() == 3 and D == tokens.shape[2]
+    mcode = None if metric is _COSINE else _metric_code(metric, who)
+    code = _combine_code(combine, who)
+    t = _top_t_arg(top_t, P, who)
+    if k is not None and k < 1:
+        raise ValueError(f"{who}: k = {k}")
+    if k is not None and world_size == 1 and k > N:
+        raise ValueError(f"{who}: k = {k} exceeds the {N} images of the bank")
+    k = 1 if k is None else k
+    if mcode is not None:
+        ops.bank_dtype_code(tokens.dtype, who)
+    W = _weights_arg(weights, Q, D, who, tb is not None)
+    if W is None:
+        _check_token_shape(who, Q, P, D, k)
+        step = 16
+    else:
+        if mcode is None:                    # cosine with shared weights leaves the dtype to the TokenBank it runs on
+            ops.bank_dtype_code(tokens.dtype, who)
+        step = _pq_group(who, P, D, k)
+    sel = _selection_arg(select, N, who, tokens.device)
+    return TokenRequest(who=who, Q=Q, N=N, P=P, D=D, k=k, combine=code, metric=mcode, metric_name=None if mcode is None else metric,
+                        top_t=t, per_query=W is not None, step=step, idx_offset=0 if tb is None else tb.idx_offset, tokens=tokens,
+                        bank=tb, weights=W if W is not None else (weights if tb is None else tb.weights), select=sel)
+
+
+def _unwrap(bank):
+    """``bank`` (TokenBank | [N, P, D] tensor) -> (the TokenBank or None, the token tensor): the one place that tells them apart."""
+    return (bank, bank.bank) if isinstance(bank, TokenBank) else (None, bank)
+
+
+def _floor_sample(tb, tokens, sel, images):
+    """The floor's strided sample of ``images`` whole images: (tokens [S, P, D], norms of their S * P rows or None).  A TokenBank's
+    own (``TokenBank.sample``) or, under a selection, the one that Selection keeps for it; a plain tensor is gathered anew, and no
+    norms are computed for it."""
+    if tb is not None:
+        return tb.sample(images) if sel is None else sel.sample(tb, images)
+    idx = _sample_index(images, tokens.shape[0] if sel is None else sel.count, tokens.device)
+    return tokens.index_select(0, idx if sel is None else sel.indices()[idx]), None
+
+
+class _CosineScorer:
+    """What is cosine about a token search: how a group of queries -- (tw, qn, w): prepared queries and their [g, D] weight rows,
+    w None for shared weights -- is scored against ``tokens`` or the floor's sample of them.  Shared weights (``W`` None) run on the
+    TokenBank ``tb``, whose norms are an operand; per-query weights ``W`` [Q, D] need none (the kernel computes them), and ``tb`` is
+    then only where the sample comes from, or None."""
+    negate = False                                   # keys are the scores
+
+    def __init__(self, tokens, tb, sel, combine, top_t, eps, W=None):
+        self.tokens, self.tb, self.sel, self.combine, self.top_t, self.eps, self.W = tokens, tb, sel, combine, top_t, eps, W
+        self.norms = tb.norms if W is None else None
+
+    @classmethod
+    def of(cls, rq: TokenRequest, eps):
+        """The scorer of a search.  Shared weights over a plain tensor build a TokenBank here, which costs a norm pass; per-query
+        weights never do: that pass is what they make useless."""
+        if rq.per_query:
+            return cls(rq.tokens, rq.bank, rq.select, rq.combine, rq.top_t, eps, rq.weights.to(rq.tokens.device, torch.float32).contiguous())
+        return cls(rq.tokens, rq.bank if rq.bank is not None else TokenBank(rq.tokens, rq.weights), rq.select, rq.combine, rq.top_t, eps)
+
+    def prepare(self, q):
+        self.tw, self.qn = prepare_queries(q, self.tb.weights) if self.W is None else prepare_queries_pq(q, self.W)
+
+    def group(self, lo, hi):
+        return self.tw[lo:hi], self.qn[lo:hi], None if self.W is None else self.W[lo:hi]
+
+    def sample(self, images):
+        if self.W is None:                           # tokens and norms: of a TokenBank, as this call ever needed
+            return self.tb.sample(images) if self.sel is None else self.sel.sample(self.tb, images)
+        return _floor_sample(self.tb, self.tokens, self.sel, images)[0], None
+
+    def scores(self, group, tokens, norms, out, words=None):
+        tw, qn, w = group
+        if w is None:
+            ops.cosine_token_scores(tw, qn, tokens, norms, self.combine, self.eps, out, self.top_t, words)
+        else:
+            ops.cosine_token_scores_pq(tw, qn, tokens, w, self.combine, self.eps, out, self.top_t, words)
+
+    def lists(self, group, k, idx_offset, nl, ps, pi, thr0, words):
+        tw, qn, w = group
+        if w is None:
+            ops.cosine_token_topk(tw, qn, self.tokens, self.norms, k, self.combine, self.eps, idx_offset, nl, ps, pi, thr0, self.top_t,
+                                  words)
+        else:
+            ops.cosine_token_topk_pq(tw, qn, self.tokens, w, k, self.combine, self.eps, idx_offset, nl, ps, pi, thr0, self.top_t, words)
+
+
+class _DistanceScorer:
+    """What is distance about a token search.  A group is (t, c): the raw queries and ``prepare_distance_weights`` of ``weights``
+    ([D] shared, or the group's [g, D] rows).  No TokenBank is ever built (there are no norms; ``tb`` is only where the sample comes
+    from, or None); keys are negated distances."""
+    negate = True
+    norms = None
+
+    def __init__(self, tokens, tb, sel, metric, combine, top_t, weights=None):
+        self.tokens, self.tb, self.sel, self.metric, self.combine, self.top_t, self.weights = tokens, tb, sel, metric, combine, top_t, weights
+
+    @classmethod
+    def of(cls, rq: TokenRequest):
+        return cls(rq.tokens, rq.bank, rq.select, rq.metric, rq.combine, rq.top_t, rq.weights)
+
+    def prepare(self, q):
+        self.q, self.c = q, prepare_distance_weights(self.weights, q.shape[1], self.tokens.device)
+
+    def group(self, lo, hi):
+        return self.q[lo:hi], self.c[lo:hi] if self.c.dim() == 2 else self.c
+
+    def sample(self, images):
+        return _floor_sample(self.tb, self.tokens, self.sel, images)[0], None
+
+    def scores(self, group, tokens, norms, out, words=None):
+        t, c = group
+        op = ops.distance_token_scores if c.dim() == 1 else ops.distance_token_scores_pq
+        op(c, t, tokens, self.metric, self.combine, out, self.top_t, words)
+
+    def lists(self, group, k, idx_offset, nl, ps, pi, thr0, words):
+        t, c = group
+        op = ops.distance_token_topk if c.dim() == 1 else ops.distance_token_topk_pq
+        op(c, t, self.tokens, self.metric, self.combine, k, idx_offset, nl, ps, pi, thr0, self.top_t, words)
+
+
+def _floor_images(N, sel, k, sample_images):
+    """The size rule of the token floors: the sample's images (default 256 k), or None when the bank -- under a selection: the
+    selected images -- holds fewer than 8 x that and the extra pass would not pay."""
+    images = 256 * k if sample_images is None else sample_images
+    return None if (N if sel is None else sel.count) < 8 * images else images
+
+
+def _token_floor(sc, group, k, sample_images=None):
+    """[g] floor of the k-th best key of one group (whose first member is its [g, D] queries), or None (``_floor_images``).  The
+    sample is scored as the search scores it -- without selection words: it holds selected images only -- and the k-th largest
+    key is taken one ulp lower."""
+    images = _floor_images(sc.tokens.shape[0], sc.sel, k, sample_images)
+    if images is None:
+        return None
+    st, sn = sc.sample(images)
+    keys = torch.empty(group[0].shape[0], st.shape[0], device=group[0].device)
+    sc.scores(group, st, sn, keys)
+    return _kth_floor(keys.neg_() if sc.negate else keys, k)
+
+
+def _topk_tokens(rq: TokenRequest, sc, queries, prune, stats, process_group, world_size):
+    """The top-k driver: per group of ``step`` queries one floor, one pass over the bank into per-wave lists, one merge; then the
+    all-gather and merge across ranks.  Everything runs in key space; the scorer says whether keys are negated on the way out."""
+    Q, k, step, dev = rq.Q, rq.k, rq.step, rq.tokens.device
+    words = None if rq.select is None else rq.select.words
+    q = queries.to(dev, torch.float32).contiguous()
+    out_s = torch.empty(Q, k, device=dev)
+    out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
+    if Q == 0:                                      # nothing to search for: empty result, no launch
+        return out_s, out_i
+    sc.prepare(q)
+    pruned = False
+    for lo in range(0, Q, step):
+        group = sc.group(lo, lo + step)
+        Qg = min(step, Q - lo)
+        thr0 = _token_floor(sc, group, k) if prune else None
+        pruned = pruned or thr0 is not None
+        nl = ops.cosine_token_topk_chunks(rq.N, rq.P, Qg, rq.D, k)
+        ps = torch.empty(Qg, nl, k, device=dev)
+        pi = torch.empty(Qg, nl, k, device=dev, dtype=torch.int64)
+        sc.lists(group, k, rq.idx_offset, nl, ps, pi, thr0, words)
+        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + step], out_i[lo:lo + step], torch.empty(Qg, device=dev, dtype=torch.int32))
+    if stats is not None:
+        stats.update(path="tokens", groups=rq.groups, pruned=pruned)
+        if rq.metric is not None:
+            stats.update(metric=rq.metric_name)
+        if rq.per_query:
+            stats.update(per_query_weights=True, group=step)
+        if rq.top_t != 0:
+            stats.update(top_t=rq.top_t)
+        if rq.select is not None:
+            stats.update(selected=rq.select.count)
+    if world_size > 1:
+        from .distributed import gather_topk
+        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather of keys -> [Q, world, k]
+        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    return (out_s.neg_() if sc.negate else out_s), out_i                # distances: (-inf, -1) becomes (+inf, -1)
+
+
+def _score_tokens(rq: TokenRequest, sc, queries):
+    """The scores driver: [Q, N], one pass over the bank per group of ``step`` queries, written straight into its rows."""
+    words = None if rq.select is None else rq.select.words
+    q = queries.to(rq.tokens.device, torch.float32).contiguous()
+    out = torch.empty(rq.Q, rq.N, device=rq.tokens.device)
+    if rq.Q == 0:
+        return out
+    sc.prepare(q)
+    for lo in range(0, rq.Q, rq.step):
+        sc.scores(sc.group(lo, lo + rq.step), rq.tokens, sc.norms, out[lo:lo + rq.step], words)
     return out
 
 
@@ -392,37 +651,18 @@ def token_pruning_floor(tw, qn, tb, k: int, combine: str = 'min', eps: float = 1
     ``weights`` [Q, D] (per-query weights, rows for the Q <= 16 queries of ``tw``; None: the floor above, ``tb`` a TokenBank): the
     same sample -- ``tb`` may then be a plain [N,P,D] tensor, no norms are needed -- is scored by the kernel with per-query
     weights, as the search scores it."""
-    tokens = tb.bank if isinstance(tb, TokenBank) else tb
-    t = _top_t_arg(top_t, tokens.shape[1], "token_pruning_floor")
-    N, P = tokens.shape[0], tokens.shape[1]
-    W = _weights_arg(weights, tw.shape[0], tw.shape[1], "token_pruning_floor")
-    sel = _selection_arg(select, N, "token_pruning_floor", tokens.device)
-    if sample_images is None:
-        sample_images = 256 * k
-    if (N if sel is None else sel.count) < 8 * sample_images:
+    who = "token_pruning_floor"
+    bank, tokens = _unwrap(tb)
+    t = _top_t_arg(top_t, tokens.shape[1], who)
+    W = _weights_arg(weights, tw.shape[0], tw.shape[1], who)
+    sel = _selection_arg(select, tokens.shape[0], who, tokens.device)
+    if _floor_images(tokens.shape[0], sel, k, sample_images) is None:     # before ``combine`` is read, as it ever was
         return None
     if W is not None:
         W = W.to(tw.device, torch.float32).contiguous()
-        st = _distance_sample(tb, sel, sample_images)
-        sc = torch.empty(tw.shape[0], st.shape[0], device=tw.device)
-        ops.cosine_token_scores_pq(tw, qn, st, W, _combine_code(combine, "token_pruning_floor"), eps, sc, t)
-        floor = torch.empty(tw.shape[0], device=tw.device)
-        ops.kth_largest_floor(sc, k, floor)
-        return floor
-    if sel is None:
-        st, sn = tb.sample(sample_images)
-    else:
-        st, sn = sel.sample(tb, sample_images)
-    sc = _token_scores(tw, qn, st, sn, _combine_code(combine, "token_pruning_floor"), eps, t)
-    floor = torch.empty(tw.shape[0], device=tw.device)
-    ops.kth_largest_floor(sc, k, floor)
-    return floor
-
-
-def _check_token_shape(who, Q, P, D, k):
-    why = ops.cosine_token_refusal(max(1, min(Q, 16)), P, D, k)       # Q: queries per launch
-    if why is not None:
-        raise ValueError(f"{who}: {why}")
+    # shared weights take the sample from ``tb`` itself: a TokenBank, and anything else fails there, as it ever did
+    sc = _CosineScorer(tokens, tb if W is None else bank, sel, _combine_code(combine, who), t, eps, W)
+    return _token_floor(sc, (tw, qn, W), k, sample_images)
 
 
 def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min', weights: torch.Tensor | None = None,
@@ -464,67 +704,8 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     D = 768, k = 300: six per pass), weights sliced along; ValueError with the library's text when g = 1 does not fit, and, naming
     both shapes, for weights of any other rank, leading dimension or D.  ``stats['per_query_weights']`` is True and
     ``stats['group']`` is g."""
-    who = "cosine_topk_tokens"
-    tokens = bank.bank if isinstance(bank, TokenBank) else bank
-    Q, D = queries.shape
-    N, P = tokens.shape[0], tokens.shape[1]
-    assert tokens.dim() == 3 and D == tokens.shape[2]
-    code = _combine_code(combine, who)
-    t = _top_t_arg(top_t, P, who)
-    if k < 1:
-        raise ValueError(f"{who}: k = {k}")
-    if world_size == 1 and k > N:
-        raise ValueError(f"{who}: k = {k} exceeds the {N} images of the bank")
-    W = _weights_arg(weights, Q, D, who, isinstance(bank, TokenBank))
-    if W is None:
-        _check_token_shape(who, Q, P, D, k)                  # every refusal above and here: before the first launch
-        step = 16
-    else:
-        ops.bank_dtype_code(tokens.dtype, who)
-        step = _pq_group(who, P, D, k)
-    sel = _selection_arg(select, N, who, tokens.device)
-    words = None if sel is None else sel.words
-    if W is None:
-        tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
-        idx_offset = tb.idx_offset
-    else:                                           # no TokenBank is built: its norm pass is what these weights make useless
-        tb = bank
-        idx_offset = bank.idx_offset if isinstance(bank, TokenBank) else 0
-        W = W.to(tokens.device, torch.float32).contiguous()
-    q = queries.to(tokens.device, torch.float32).contiguous()
-    out_s = torch.empty(Q, k, device=q.device)
-    out_i = torch.empty(Q, k, device=q.device, dtype=torch.int64)
-    if Q == 0:                                      # nothing to search for: empty result, no launch
-        return out_s, out_i
-    tw_all, qn_all = prepare_queries(q, tb.weights) if W is None else prepare_queries_pq(q, W)
-    pruned = False
-    for lo in range(0, Q, step):
-        tw, qn = tw_all[lo:lo + step], qn_all[lo:lo + step]
-        Wg = None if W is None else W[lo:lo + step]
-        Qg = tw.shape[0]
-        thr0 = token_pruning_floor(tw, qn, tb, k, combine, eps, top_t=top_t, select=sel, weights=Wg) if prune else None
-        pruned = pruned or thr0 is not None
-        nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
-        ps = torch.empty(Qg, nl, k, device=q.device)
-        pi = torch.empty(Qg, nl, k, device=q.device, dtype=torch.int64)
-        if W is None:
-            ops.cosine_token_topk(tw, qn, tb.bank, tb.norms, k, code, eps, idx_offset, nl, ps, pi, thr0, t, words)
-        else:
-            ops.cosine_token_topk_pq(tw, qn, tokens, Wg, k, code, eps, idx_offset, nl, ps, pi, thr0, t, words)
-        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + step], out_i[lo:lo + step], torch.empty(Qg, device=q.device, dtype=torch.int32))
-    if stats is not None:
-        stats.update(path="tokens", groups=(Q + step - 1) // step, pruned=pruned)
-        if W is not None:
-            stats.update(per_query_weights=True, group=step)
-        if top_t is not None:
-            stats.update(top_t=t)
-        if sel is not None:
-            stats.update(selected=sel.count)
-    if world_size > 1:
-        from .distributed import gather_topk
-        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
-        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
-    return out_s, out_i
+    rq = _token_request("cosine_topk_tokens", queries, bank, k, combine, _COSINE, weights, top_t, select, world_size)
+    return _topk_tokens(rq, _CosineScorer.of(rq, eps), queries, prune, stats, process_group, world_size)
 
 
 def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weights: torch.Tensor | None = None, eps: float = 1e-6,
@@ -535,77 +716,13 @@ def cosine_token_scores(queries: torch.Tensor, bank, combine: str = 'min', weigh
     all tokens; else only the top_t best token scores of an image count, mean summed largest first -- so 'mean' with
     ``top_t == P`` is not the plain mean).  ``select``: as for ``cosine_topk_tokens``; every [Q, N] slot is written, a deselected
     image gets -inf.  ``weights`` [Q, D]: per-query weights, as for ``cosine_topk_tokens`` (groups of g queries at k = 1)."""
-    tokens = bank.bank if isinstance(bank, TokenBank) else bank
-    Q, D = queries.shape
-    assert tokens.dim() == 3 and D == tokens.shape[2]
-    code = _combine_code(combine, "cosine_token_scores")
-    t = _top_t_arg(top_t, tokens.shape[1], "cosine_token_scores")
-    W = _weights_arg(weights, Q, D, "cosine_token_scores", isinstance(bank, TokenBank))
-    if W is not None:
-        ops.bank_dtype_code(tokens.dtype, "cosine_token_scores")
-        step = _pq_group("cosine_token_scores", tokens.shape[1], D, 1)
-        sel = _selection_arg(select, tokens.shape[0], "cosine_token_scores", tokens.device)
-        q = queries.to(tokens.device, torch.float32).contiguous()
-        W = W.to(tokens.device, torch.float32).contiguous()
-        out = torch.empty(Q, tokens.shape[0], device=q.device)
-        if Q == 0:
-            return out
-        tw, qn = prepare_queries_pq(q, W)
-        for lo in range(0, Q, step):
-            ops.cosine_token_scores_pq(tw[lo:lo + step], qn[lo:lo + step], tokens, W[lo:lo + step], code, eps, out[lo:lo + step], t,
-                                       None if sel is None else sel.words)
-        return out
-    _check_token_shape("cosine_token_scores", Q, tokens.shape[1], D, 1)
-    sel = _selection_arg(select, tokens.shape[0], "cosine_token_scores", tokens.device)
-    words = None if sel is None else sel.words
-    tb = bank if isinstance(bank, TokenBank) else TokenBank(bank, weights)
-    q = queries.to(tb.bank.device, torch.float32).contiguous()
-    out = torch.empty(Q, tb.bank.shape[0], device=q.device)
-    if Q == 0:
-        return out
-    tw, qn = prepare_queries(q, tb.weights)
-    for lo in range(0, Q, 16):
-        out[lo:lo + 16] = _token_scores(tw[lo:lo + 16], qn[lo:lo + 16], tb.bank, tb.norms, code, eps, t, words)
-    return out
+    rq = _token_request("cosine_token_scores", queries, bank, None, combine, _COSINE, weights, top_t, select)
+    return _score_tokens(rq, _CosineScorer.of(rq, eps), queries)
 
 
 # ------------------------------------------------------------------------------------------------
 # the distance metrics (weighted MSE / MAE, utils/similarity.py:174-212) over the same token banks: smaller is better
 # ------------------------------------------------------------------------------------------------
-def _metric_code(metric, who):
-    if metric not in ops.METRIC_CODES:
-        raise ValueError(f"{who}: metric = {metric!r}, expected one of {sorted(ops.METRIC_CODES)} (the cosine metric is "
-                         f"cosine_topk_tokens / cosine_token_scores)")
-    return ops.METRIC_CODES[metric]
-
-
-def prepare_distance_weights(weights, D, device):
-    """c = fp32(w / sum(w)) [D] on the device, by torch: the feature weights as the distance kernels take them (None: w = 1).
-    ``weights`` [Q, D] (per-query weights): c [Q, D], every row prepared on its own by the [D] rule, so row q is bit-equal to
-    what the single-query search prepares from it."""
-    if weights is not None and weights.dim() == 2:
-        return torch.stack([prepare_distance_weights(row, D, device) for row in weights]).contiguous()
-    w = torch.ones(D, device=device) if weights is None else weights.to(device, torch.float32).reshape(D)
-    return (w / w.sum()).contiguous()
-
-
-def _distance_scores(c, t, tokens, mcode, ccode, top_t=0, words=None):
-    """[Q, N] combined distances of Q <= 16 queries; c [D], or [Q, D] with one row per query."""
-    out = torch.empty(t.shape[0], tokens.shape[0], device=t.device)
-    (ops.distance_token_scores if c.dim() == 1 else ops.distance_token_scores_pq)(c, t, tokens, mcode, ccode, out, top_t, words)
-    return out
-
-
-def _distance_sample(bank, sel, images):
-    """The floor's strided sample of ``images`` whole images [S, P, D]: a TokenBank's own (``TokenBank.sample``) or, under a
-    selection, the one that Selection keeps for it; a plain tensor is gathered anew (no norms are computed for it)."""
-    if isinstance(bank, TokenBank):
-        return bank.sample(images)[0] if sel is None else sel.sample(bank, images)[0]
-    n = bank.shape[0] if sel is None else sel.count
-    idx = torch.arange(images, device=bank.device) * (n // images)
-    return bank.index_select(0, idx if sel is None else sel.indices()[idx])
-
-
 def distance_pruning_floor(c, t, bank, k: int, metric: str = 'MAE', combine: str = 'mean', sample_images: int | None = None,
                            top_t: int | None = None, select=None):
     """``token_pruning_floor`` for the distance metrics, in KEY space (key = -distance): the same sample of whole images (the
@@ -613,22 +730,15 @@ def distance_pruning_floor(c, t, bank, k: int, metric: str = 'MAE', combine: str
     floor of the k-th best key of the search.  None under the same size rule (fewer than 8 x the sample's images).  ``c``:
     ``prepare_distance_weights`` ([D], or [Q, D] with one row per query of ``t``); ``t`` [Q <= 16, D]; ``bank``: a [N,P,D] tensor or
     a TokenBank."""
-    tokens = bank.bank if isinstance(bank, TokenBank) else bank
-    N, P = tokens.shape[0], tokens.shape[1]
-    tt = _top_t_arg(top_t, P, "distance_pruning_floor")
+    who = "distance_pruning_floor"
+    tb, tokens = _unwrap(bank)
+    tt = _top_t_arg(top_t, tokens.shape[1], who)
     if tuple(c.shape) not in ((t.shape[1],), tuple(t.shape)):
         raise ValueError(f"distance_pruning_floor: c has shape {tuple(c.shape)}, expected ({t.shape[1]},) or {tuple(t.shape)} for "
                          f"queries of shape {tuple(t.shape)}")
-    mcode, ccode = _metric_code(metric, "distance_pruning_floor"), _combine_code(combine, "distance_pruning_floor")
-    sel = _selection_arg(select, N, "distance_pruning_floor", tokens.device)
-    if sample_images is None:
-        sample_images = 256 * k
-    if (N if sel is None else sel.count) < 8 * sample_images:
-        return None
-    keys = _distance_scores(c, t, _distance_sample(bank, sel, sample_images), mcode, ccode, tt).neg_()
-    floor = torch.empty(t.shape[0], device=t.device)
-    ops.kth_largest_floor(keys, k, floor)
-    return floor
+    mcode, ccode = _metric_code(metric, who), _combine_code(combine, who)
+    sel = _selection_arg(select, tokens.shape[0], who, tokens.device)
+    return _token_floor(_DistanceScorer(tokens, tb, sel, mcode, ccode, tt), (t, c), k, sample_images)
 
 
 def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE', combine: str = 'mean',
@@ -656,62 +766,8 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     the result is bit for bit the Q = 1 search with query q and ``weights=w_q``.  c [Q, D] sits in LDS beside the queries, so
     the queries run in groups of the largest g <= 16 with 128 D + 32 g k <= 163840, as for ``cosine_topk_tokens``;
     ``stats['per_query_weights']`` is True and ``stats['group']`` is g."""
-    who = "distance_topk_tokens"
-    tokens = bank.bank if isinstance(bank, TokenBank) else bank
-    Q, D = queries.shape
-    N, P = tokens.shape[0], tokens.shape[1]
-    assert tokens.dim() == 3 and D == tokens.shape[2]
-    mcode, ccode = _metric_code(metric, who), _combine_code(combine, who)
-    tt = _top_t_arg(top_t, P, who)
-    if k < 1:
-        raise ValueError(f"{who}: k = {k}")
-    if world_size == 1 and k > N:
-        raise ValueError(f"{who}: k = {k} exceeds the {N} images of the bank")
-    ops.bank_dtype_code(tokens.dtype, who)
-    W = _weights_arg(weights, Q, D, who, isinstance(bank, TokenBank))
-    if W is None:
-        _check_token_shape(who, Q, P, D, k)
-        step = 16
-    else:
-        step = _pq_group(who, P, D, k)
-    sel = _selection_arg(select, N, who, tokens.device)
-    words = None if sel is None else sel.words
-    dev = tokens.device
-    idx_offset = bank.idx_offset if isinstance(bank, TokenBank) else 0
-    if isinstance(bank, TokenBank) and W is None:
-        weights = bank.weights
-    q = queries.to(dev, torch.float32).contiguous()
-    out_s = torch.empty(Q, k, device=dev)
-    out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
-    if Q == 0:
-        return out_s, out_i
-    c_all = prepare_distance_weights(weights, D, dev)
-    pruned = False
-    for lo in range(0, Q, step):
-        t = q[lo:lo + step]
-        c = c_all if W is None else c_all[lo:lo + step]
-        Qg = t.shape[0]
-        thr0 = distance_pruning_floor(c, t, bank, k, metric, combine, top_t=top_t, select=sel) if prune else None
-        pruned = pruned or thr0 is not None
-        nl = ops.cosine_token_topk_chunks(N, P, Qg, D, k)
-        ps = torch.empty(Qg, nl, k, device=dev)
-        pi = torch.empty(Qg, nl, k, device=dev, dtype=torch.int64)
-        (ops.distance_token_topk if W is None else ops.distance_token_topk_pq)(c, t, tokens, mcode, ccode, k, idx_offset, nl, ps, pi,
-                                                                               thr0, tt, words)
-        ops.topk_merge(ps, pi, Qg, nl, k, out_s[lo:lo + step], out_i[lo:lo + step], torch.empty(Qg, device=dev, dtype=torch.int32))
-    if stats is not None:
-        stats.update(path="tokens", metric=metric, groups=(Q + step - 1) // step, pruned=pruned)
-        if W is not None:
-            stats.update(per_query_weights=True, group=step)
-        if top_t is not None:
-            stats.update(top_t=tt)
-        if sel is not None:
-            stats.update(selected=sel.count)
-    if world_size > 1:
-        from .distributed import gather_topk
-        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # keys: [Q, world, k]
-        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
-    return out_s.neg_(), out_i                                          # keys -> distances: (-inf, -1) becomes (+inf, -1)
+    rq = _token_request("distance_topk_tokens", queries, bank, k, combine, metric, weights, top_t, select, world_size)
+    return _topk_tokens(rq, _DistanceScorer.of(rq), queries, prune, stats, process_group, world_size)
 
 
 def distance_token_scores(queries: torch.Tensor, bank, metric: str = 'MAE', combine: str = 'mean', weights: torch.Tensor | None = None,
@@ -720,28 +776,5 @@ def distance_token_scores(queries: torch.Tensor, bank, metric: str = 'MAE', comb
     weights then replace ``weights``), in groups of at most 16 queries; ``metric``, ``combine``, ``top_t`` and the NaN rule as for
     ``distance_topk_tokens``.  ``select``: every [Q, N] slot is written, a deselected image gets +inf.  ``weights`` [Q, D]:
     per-query weights, as for ``distance_topk_tokens`` (groups of g queries at k = 1)."""
-    who = "distance_token_scores"
-    tokens = bank.bank if isinstance(bank, TokenBank) else bank
-    Q, D = queries.shape
-    assert tokens.dim() == 3 and D == tokens.shape[2]
-    mcode, ccode = _metric_code(metric, who), _combine_code(combine, who)
-    tt = _top_t_arg(top_t, tokens.shape[1], who)
-    ops.bank_dtype_code(tokens.dtype, who)
-    W = _weights_arg(weights, Q, D, who, isinstance(bank, TokenBank))
-    if W is None:
-        _check_token_shape(who, Q, tokens.shape[1], D, 1)
-        step = 16
-    else:
-        step = _pq_group(who, tokens.shape[1], D, 1)
-    sel = _selection_arg(select, tokens.shape[0], who, tokens.device)
-    words = None if sel is None else sel.words
-    if isinstance(bank, TokenBank) and W is None:
-        weights = bank.weights
-    q = queries.to(tokens.device, torch.float32).contiguous()
-    out = torch.empty(Q, tokens.shape[0], device=tokens.device)
-    if Q == 0:
-        return out
-    c = prepare_distance_weights(weights, D, tokens.device)
-    for lo in range(0, Q, step):
-        out[lo:lo + step] = _distance_scores(c if W is None else c[lo:lo + step], q[lo:lo + step], tokens, mcode, ccode, tt, words)
-    return out
+    rq = _token_request("distance_token_scores", queries, bank, None, combine, metric, weights, top_t, select)
+    return _score_tokens(rq, _DistanceScorer.of(rq), queries)
