@@ -277,6 +277,28 @@ int skyemb_layernorm_bwd(const void *dy, int dy_is_f32, int dtype, const float *
 int skyemb_mha_fwd(const void *qkv, void *out, int dtype, int B, int N, int H, int hd, void *stream);
 int skyemb_mha_bwd(const void *qkv, const void *dout, void *dqkv, int dtype, int B, int N, int H, int hd,
                    void *stream);
+/* Read-only query (additive to ABI version 111: nothing above changes): the launch skyemb_mha_fwd (bwd = 0) / skyemb_mha_bwd
+ * (bwd != 0) makes for this shape.  Validates as they do (same texts, same return code 1) and touches no device.
+ * `switches`: -1 = what the process's environment says (SKYEMB_MHA_MFMA, SKYEMB_MHA_WPB, read once), else SKYEMB_MHA_SW_* bits. */
+#define SKYEMB_MHA_LDS 0         /* whole heads in LDS as fp32: `waves` heads per workgroup, `per_wave_floats` each           */
+#define SKYEMB_MHA_STREAM 1      /* the fp32 streaming kernels: a head that outgrows LDS                                      */
+#define SKYEMB_MHA_MFMA_PACKED 2 /* N <= 16: 32 / N samples per 32-row tile; `waves` = tiles per workgroup (1 or 4) of `nheads` */
+#define SKYEMB_MHA_MFMA_SINGLE 3 /* 16 < N <= 32: one (sample, head) per tile; `waves`, `nheads` as above                      */
+#define SKYEMB_MHA_MFMA_STRIP 4  /* 32 < N <= 128: `waves` = strips of 32 tokens (2, 3, 4)                                    */
+#define SKYEMB_MHA_MFMA_LONG 5   /* N > 128: K / V streamed through LDS                                                       */
+#define SKYEMB_MHA_SW_NO_MFMA 1  /* SKYEMB_MHA_MFMA=0                                                                         */
+#define SKYEMB_MHA_SW_WPB1 2     /* SKYEMB_MHA_WPB=1                                                                          */
+#define SKYEMB_MHA_SW_WPB4 4     /* SKYEMB_MHA_WPB=<any other non-zero number>                                                */
+typedef struct {
+    int32_t family;                  /* SKYEMB_MHA_* above */
+    int32_t hd;                      /* the MFMA kernels' head-dim instance (32 / 64); 0 for lds and stream */
+    int32_t waves;                   /* waves per workgroup: the kernel's template or run-time parameter named per family above */
+    int32_t per_wave_floats, nheads; /* lds / packed and single; 0 elsewhere */
+    int32_t grid_x, grid_y, block;
+    int64_t lds_bytes;               /* dynamic LDS of the launch */
+    int64_t lds_limit;               /* the dynamic-LDS limit the kernel needs raised before it (0: none) */
+} skyemb_mha_plan_t;
+int skyemb_mha_plan(int bwd, int dtype, int B, int N, int H, int hd, int switches, skyemb_mha_plan_t *out);
 
 /* -------------------------------------------------------- decoder glue ----
  * utils/mim_vit.py:446-453: rows of the decoder sequence that hold a mask token:

@@ -24,6 +24,9 @@ KC, RC = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU = 0, 1, 2
 COMBINE_MIN, COMBINE_MEAN, COMBINE_MAX = 0, 1, 2       # SKYEMB_COMBINE_*: how the token scores of an image are combined
 METRIC_MSE, METRIC_MAE = 1, 2                          # SKYEMB_METRIC_*: the distance metrics of the patch-token search
+# SKYEMB_MHA_*: kernel families of skyemb_mha_plan, and its switch bits
+MHA_LDS, MHA_STREAM, MHA_MFMA_PACKED, MHA_MFMA_SINGLE, MHA_MFMA_STRIP, MHA_MFMA_LONG = range(6)
+MHA_SW_NO_MFMA, MHA_SW_WPB1, MHA_SW_WPB4 = 1, 2, 4
 PROBE_CHUNKS, PROBE_MAX_F, PROBE_MIN_K, PROBE_MAX_K = 32, 4096, 3, 16   # SKYEMB_PROBE_*: limits of the linear-probe fits
 
 
@@ -61,6 +64,12 @@ class LnBwdSide(ctypes.Structure):
     """skyemb_ln_bwd_side (include/skyemb.h): a LayerNorm backward riding in a grouped weight-gradient launch."""
     _fields_ = [("dy", c_vp), ("x", c_vp), ("gamma", c_vp), ("mean", c_vp), ("rstd", c_vp), ("g_in", c_vp), ("g_out", c_vp), ("g_lp", c_vp),
                 ("part", c_vp), ("M", c_i32), ("D", c_i32)]
+
+
+class MhaPlan(ctypes.Structure):
+    """skyemb_mha_plan_t (include/skyemb.h): the launch skyemb_mha_fwd / skyemb_mha_bwd makes for a shape."""
+    _fields_ = [("family", c_i32), ("hd", c_i32), ("waves", c_i32), ("per_wave_floats", c_i32), ("nheads", c_i32),
+                ("grid_x", c_i32), ("grid_y", c_i32), ("block", c_i32), ("lds_bytes", c_i64), ("lds_limit", c_i64)]
 
 
 class GemmGroupInfo(ctypes.Structure):
@@ -117,6 +126,8 @@ PROTOTYPES = {
                                      c_i32, c_i32, c_vp]),
     "skyemb_mha_fwd": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "skyemb_mha_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    # read-only query of the attention launch plan: additive to ABI version 111
+    "skyemb_mha_plan": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(MhaPlan)]),
     "skyemb_fill_mask_tokens": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "skyemb_gather_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "skyemb_rowsum_select": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),

@@ -4,7 +4,12 @@
 // recomputes the probabilities.  0.3 % of the model FLOPs: built for latency, not for MFMA.
 //
 // qkv layout is the reference's: [B, N, 3, H, hd]  (timm Attention: qkv(x).reshape(B,N,3,H,hd)).
+//
+// Also the attention core's host side, at the end of the file: one driver behind skyemb_mha_fwd and skyemb_mha_bwd, which launches
+// what sky_mha_plan (attention_plan.h) says -- these kernels, or the MFMA ones of attention_mfma.hip.
+#include "attention_plan.h"
 #include "common.h"
+#include <stdlib.h>
 
 namespace {
 
@@ -142,7 +147,7 @@ __global__ void mha_bwd_kernel(const T *__restrict__ qkv, const T *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Streaming fallback for the shapes whose whole head does not fit the LDS plan below (long sequences in the fp32 parity
+// Streaming fallback for the shapes whose whole head does not fit the LDS plan of attention_plan.h (long sequences in the fp32 parity
 // mode, head dims other than the MFMA kernels' 32 / 64 -- the 512-wide single decoder head of maesimple): fp32 arithmetic
 // for every dtype, any N <= SKYEMB_MHA_MAX_N, any hd % 8 == 0 up to SH_MAXHD.  Built for correctness, not speed.
 //   forward : one wave per query row; keys in chunks of 64 (lane j scores key j), online softmax with the running max and
@@ -153,7 +158,7 @@ __global__ void mha_bwd_kernel(const T *__restrict__ qkv, const T *__restrict__ 
 //             Fixed summation order: deterministic.  LDS: 2 N floats of statistics + two [hd] rows and two [64] chunks
 //             per wave (49 KB at N = 4098, hd = 512).
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int SH_MAXHD = 512, SH_C = SH_MAXHD / 64;
+constexpr int SH_MAXHD = MHA_STREAM_MAX_HD, SH_C = SH_MAXHD / 64;
 
 template <typename T>
 __device__ __forceinline__ float dot_row(const float *lds_row, const T *g_row, int hd) {
@@ -323,127 +328,81 @@ __global__ __launch_bounds__(256) void mha_bwd_stream_kernel(const T *__restrict
     }
 }
 
-size_t stream_bwd_smem(int N) { return sizeof(float) * (8 * SH_MAXHD + 4 * 128 + 2 * (size_t)N); }
+// what sky_mha_plan refuses, in the entry points' words
+int plan_or_refuse(bool bwd, int dtype, int B, int N, int H, int hd, int switches, skyemb_mha_plan_t *p) {
+    const char *who = bwd ? "skyemb_mha_bwd" : "skyemb_mha_fwd";
+    switch (sky_mha_plan(bwd, dtype, B, N, H, hd, switches, p)) {
+    case MHA_OK: return 0;
+    case MHA_BAD_SHAPE: skyemb_set_error("%s: bad shape (head dim must be a multiple of 8)", who); return 1;
+    case MHA_TOO_LONG: skyemb_set_error("%s: N = %d tokens, more than the supported %d", who, N, SKYEMB_MHA_MAX_N); return 1;
+    default: skyemb_set_error("%s: head dim %d with N = %d tokens: at most %d", who, hd, N, SH_MAXHD); return 1;
+    }
+}
 
+// the two diagnostic switches of INTEGRATION.md as SKYEMB_MHA_SW_* bits, read once per process
+int env_switches() {
+    static const int sw = []() {
+        const char *off = getenv("SKYEMB_MHA_MFMA"), *wpb = getenv("SKYEMB_MHA_WPB");
+        const int w = wpb ? atoi(wpb) : 0;
+        return (off && off[0] == '0' ? SKYEMB_MHA_SW_NO_MFMA : 0) | (w == 1 ? SKYEMB_MHA_SW_WPB1 : w ? SKYEMB_MHA_SW_WPB4 : 0);
+    }();
+    return sw;
+}
+
+// the lds and stream families for element type T (`out` is dqkv in backward)
 template <typename T>
-void launch_stream(bool bwd, const void *qkv, const void *dout, void *out, int B, int N, int H, int hd, hipStream_t st) {
-    if (!bwd)
-        hipLaunchKernelGGL(mha_fwd_stream_kernel<T>, dim3(B * H, (N + 3) / 4), dim3(256), 0, st, (const T *)qkv, (T *)out, B, N, H, hd);
-    else
-        hipLaunchKernelGGL(mha_bwd_stream_kernel<T>, dim3(B * H), dim3(256), stream_bwd_smem(N), st, (const T *)qkv, (const T *)dout,
-                           (T *)out, B, N, H, hd);
-}
-void launch_stream_any(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, hipStream_t st) {
-    if (dtype == SKYEMB_BF16) launch_stream<bf16_t>(bwd, qkv, dout, out, B, N, H, hd, st);
-    else if (dtype == SKYEMB_F16) launch_stream<f16_t>(bwd, qkv, dout, out, B, N, H, hd, st);
-    else launch_stream<float>(bwd, qkv, dout, out, B, N, H, hd, st);
-}
-
-struct Plan {
-    int waves, per_wave_floats;
-    size_t smem;
-};
-
-Plan make_plan(int N, int hd, bool bwd) {
-    Plan p;
-    const int pitch = hd + 4, NP = N + 1;
-    p.per_wave_floats = (bwd ? 4 : 3) * N * pitch + (bwd ? 2 : 1) * N * NP;
-    p.per_wave_floats = (p.per_wave_floats + 3) & ~3;
-    const size_t per = (size_t)p.per_wave_floats * 4;
-    int w = (int)(65536 / per);
-    if (w > 4) w = 4;
-    if (w < 1) w = 1;
-    p.waves = w;
-    p.smem = per * w;
-    return p;
-}
-
-template <typename K>
-int set_lds(K kern, size_t smem, const char *name) {
-    if (smem > 160 * 1024) {
-        skyemb_set_error("%s: sequence too long for the small-N kernel (%zu B LDS per wave)", name, smem);
-        return 1;
+int launch_fp32(const skyemb_mha_plan_t &p, bool bwd, const T *qkv, const T *dout, T *out, int B, int N, int H, int hd,
+                hipStream_t st, const char *who) {
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    if (p.family == SKYEMB_MHA_STREAM) {
+        if (!bwd) hipLaunchKernelGGL(mha_fwd_stream_kernel<T>, grid, block, p.lds_bytes, st, qkv, out, B, N, H, hd);
+        else hipLaunchKernelGGL(mha_bwd_stream_kernel<T>, grid, block, p.lds_bytes, st, qkv, dout, out, B, N, H, hd);
+        return 0;
     }
-    if (smem > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            skyemb_set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
-            return 2;
-        }
-    }
+    if (p.lds_limit)
+        if (const int rc = sky_set_lds_limit(bwd ? (const void *)mha_bwd_kernel<T> : (const void *)mha_fwd_kernel<T>, (int)p.lds_limit, who))
+            return rc;
+    if (!bwd) hipLaunchKernelGGL(mha_fwd_kernel<T>, grid, block, p.lds_bytes, st, qkv, out, B, N, H, hd, p.waves, p.per_wave_floats);
+    else hipLaunchKernelGGL(mha_bwd_kernel<T>, grid, block, p.lds_bytes, st, qkv, dout, out, B, N, H, hd, p.waves, p.per_wave_floats);
     return 0;
 }
 
 }  // namespace
 
-// attention_mfma.hip: bf16 / fp16, head dim 32 / 64, any N <= SKYEMB_MHA_MAX_N; -1 = not handled
-int skyemb_mha_mfma_try(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, hipStream_t st);
+// attention_mfma.hip: launches a plan of one of the SKYEMB_MHA_MFMA_* families (dtype bf16 / fp16); 0, or sky_set_lds_limit's 2
+int skyemb_mha_mfma_launch(const skyemb_mha_plan_t &p, bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N,
+                           int H, hipStream_t st, const char *who);
+
+// both directions: validate, plan, raise the LDS limit where the plan asks, launch, check
+static int mha_run(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, void *stream) {
+    const char *who = bwd ? "skyemb_mha_bwd" : "skyemb_mha_fwd";
+    (void)hipGetLastError();           // as SKY_CHECK_ARG: a stale sticky error is not this call's
+    skyemb_mha_plan_t p;
+    if (const int rc = plan_or_refuse(bwd, dtype, B, N, H, hd, env_switches(), &p)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (p.family >= SKYEMB_MHA_MFMA_PACKED) rc = skyemb_mha_mfma_launch(p, bwd, qkv, dout, out, dtype, B, N, H, st, who);
+    else if (dtype == SKYEMB_BF16) rc = launch_fp32(p, bwd, (const bf16_t *)qkv, (const bf16_t *)dout, (bf16_t *)out, B, N, H, hd, st, who);
+    else if (dtype == SKYEMB_F16) rc = launch_fp32(p, bwd, (const f16_t *)qkv, (const f16_t *)dout, (f16_t *)out, B, N, H, hd, st, who);
+    else rc = launch_fp32(p, bwd, (const float *)qkv, (const float *)dout, (float *)out, B, N, H, hd, st, who);
+    if (rc) return rc;
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
 
 extern "C" int skyemb_mha_fwd(const void *qkv, void *out, int dtype, int B, int N, int H, int hd, void *stream) {
-    SKY_CHECK_ARG(B > 0 && N > 0 && H > 0 && hd > 0 && hd % 8 == 0, "skyemb_mha_fwd: bad shape (head dim must be a multiple of 8)");
-    SKY_CHECK_ARG(N <= SKYEMB_MHA_MAX_N, "skyemb_mha_fwd: N = %d tokens, more than the supported %d", N, SKYEMB_MHA_MAX_N);
-    hipStream_t st = (hipStream_t)stream;
-    if (sky_is_lp(dtype) && skyemb_mha_mfma_try(false, qkv, nullptr, out, dtype, B, N, H, hd, st) == 0) {
-        SKY_LAUNCH_CHECK("skyemb_mha_fwd");
-        return 0;
-    }
-    const Plan p = make_plan(N, hd, false);
-    if (p.smem > 160 * 1024) {         // the head does not fit: the streaming kernel (hd <= SH_MAXHD)
-        SKY_CHECK_ARG(hd <= SH_MAXHD, "skyemb_mha_fwd: head dim %d with N = %d tokens: at most %d", hd, N, SH_MAXHD);
-        launch_stream_any(false, qkv, nullptr, out, dtype, B, N, H, hd, st);
-        SKY_LAUNCH_CHECK("skyemb_mha_fwd");
-        return 0;
-    }
-    dim3 grid((B * H + p.waves - 1) / p.waves), block(64 * p.waves);
-    int rc;
-    if (dtype == SKYEMB_BF16) {
-        if ((rc = set_lds(mha_fwd_kernel<bf16_t>, p.smem, "skyemb_mha_fwd"))) return rc;
-        hipLaunchKernelGGL(mha_fwd_kernel<bf16_t>, grid, block, p.smem, st, (const bf16_t *)qkv, (bf16_t *)out, B, N, H, hd,
-                           p.waves, p.per_wave_floats);
-        } else if (dtype == SKYEMB_F16) {
-        if ((rc = set_lds(mha_fwd_kernel<f16_t>, p.smem, "skyemb_mha_fwd"))) return rc;
-        hipLaunchKernelGGL(mha_fwd_kernel<f16_t>, grid, block, p.smem, st, (const f16_t *)qkv, (f16_t *)out, B, N, H, hd,
-                           p.waves, p.per_wave_floats);
-    } else {
-        if ((rc = set_lds(mha_fwd_kernel<float>, p.smem, "skyemb_mha_fwd"))) return rc;
-        hipLaunchKernelGGL(mha_fwd_kernel<float>, grid, block, p.smem, st, (const float *)qkv, (float *)out, B, N, H, hd,
-                           p.waves, p.per_wave_floats);
-    }
-    SKY_LAUNCH_CHECK("skyemb_mha_fwd");
-    return 0;
+    return mha_run(false, qkv, nullptr, out, dtype, B, N, H, hd, stream);
 }
 
 extern "C" int skyemb_mha_bwd(const void *qkv, const void *dout, void *dqkv, int dtype, int B, int N, int H, int hd,
                               void *stream) {
-    SKY_CHECK_ARG(B > 0 && N > 0 && H > 0 && hd > 0 && hd % 8 == 0, "skyemb_mha_bwd: bad shape (head dim must be a multiple of 8)");
-    SKY_CHECK_ARG(N <= SKYEMB_MHA_MAX_N, "skyemb_mha_bwd: N = %d tokens, more than the supported %d", N, SKYEMB_MHA_MAX_N);
-    hipStream_t st = (hipStream_t)stream;
-    if (sky_is_lp(dtype) && skyemb_mha_mfma_try(true, qkv, dout, dqkv, dtype, B, N, H, hd, st) == 0) {
-        SKY_LAUNCH_CHECK("skyemb_mha_bwd");
-        return 0;
+    return mha_run(true, qkv, dout, dqkv, dtype, B, N, H, hd, stream);
+}
+
+extern "C" int skyemb_mha_plan(int bwd, int dtype, int B, int N, int H, int hd, int switches, skyemb_mha_plan_t *out) {
+    if (!out) {
+        skyemb_set_error("skyemb_mha_plan: out is NULL");
+        return 1;
     }
-    const Plan p = make_plan(N, hd, true);
-    if (p.smem > 160 * 1024) {         // the head does not fit: the streaming kernel (hd <= SH_MAXHD)
-        SKY_CHECK_ARG(hd <= SH_MAXHD, "skyemb_mha_bwd: head dim %d with N = %d tokens: at most %d", hd, N, SH_MAXHD);
-        launch_stream_any(true, qkv, dout, dqkv, dtype, B, N, H, hd, st);
-        SKY_LAUNCH_CHECK("skyemb_mha_bwd");
-        return 0;
-    }
-    dim3 grid((B * H + p.waves - 1) / p.waves), block(64 * p.waves);
-    int rc;
-    if (dtype == SKYEMB_BF16) {
-        if ((rc = set_lds(mha_bwd_kernel<bf16_t>, p.smem, "skyemb_mha_bwd"))) return rc;
-        hipLaunchKernelGGL(mha_bwd_kernel<bf16_t>, grid, block, p.smem, st, (const bf16_t *)qkv, (const bf16_t *)dout,
-                           (bf16_t *)dqkv, B, N, H, hd, p.waves, p.per_wave_floats);
-        } else if (dtype == SKYEMB_F16) {
-        if ((rc = set_lds(mha_bwd_kernel<f16_t>, p.smem, "skyemb_mha_bwd"))) return rc;
-        hipLaunchKernelGGL(mha_bwd_kernel<f16_t>, grid, block, p.smem, st, (const f16_t *)qkv, (const f16_t *)dout,
-                           (f16_t *)dqkv, B, N, H, hd, p.waves, p.per_wave_floats);
-    } else {
-        if ((rc = set_lds(mha_bwd_kernel<float>, p.smem, "skyemb_mha_bwd"))) return rc;
-        hipLaunchKernelGGL(mha_bwd_kernel<float>, grid, block, p.smem, st, (const float *)qkv, (const float *)dout,
-                           (float *)dqkv, B, N, H, hd, p.waves, p.per_wave_floats);
-    }
-    SKY_LAUNCH_CHECK("skyemb_mha_bwd");
-    return 0;
+    return plan_or_refuse(bwd != 0, dtype, B, N, H, hd, switches < 0 ? env_switches() : switches, out);
 }

@@ -12,8 +12,8 @@
 //             dQ^T = K^T . dS^T (sum over j),   dK^T = Q^T . dS,   dV^T = dO^T . P  (sum over i)
 // qkv layout is the reference's [B, N, 3, H, hd] (timm Attention: qkv(x).reshape(B,N,3,H,hd)); softmax statistics,
 // probabilities and dS are fp32, rounded to bf16 only as MFMA operands.
+#include "attention_plan.h"
 #include "lp_twin.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(HD == 
 // ds_read_b64_tr_b16 -- the first version gathered those 2 bytes at a time from global memory, ~300 loads per lane in
 // backward (mim_19: 193 us per layer backward, 49 us forward).
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int MAX_NT = 4;
+constexpr int MAX_NT = MHA_MAX_NT;
 
 __device__ __forceinline__ lp8 row_frag_at(const lp_t *base, int64_t row_stride, int row, int g, int s, int N) {
     return row < N ? *(const lp8 *)(base + (int64_t)row * row_stride + 16 * s + 8 * g) : zero8();
@@ -586,15 +586,15 @@ __global__ __launch_bounds__(64 * NT) __attribute__((amdgpu_waves_per_eu(NT <= 3
 }
 
 template <int HD, int NT>
-int launch_strip(bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st) {
-    const dim3 grid(B * H), block(64 * NT);
-    const int smem = (bwd ? 4 : 2) * (((N + 3) & ~3) + 4) * (HD + 8) * 2;
-    if (smem > 65536) {   // (limit: the longest sequence of this instance)
-        if (const int rc = sky_set_lds_limit((const void *)mha_bwd_strip_kernel<HD, NT>, 4 * (32 * NT + 4) * (HD + 8) * 2, "skyemb_mha"))
+int launch_strip(const skyemb_mha_plan_t &p, bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st,
+                 const char *who) {
+    const dim3 grid(p.grid_x), block(p.block);
+    if (p.lds_limit)
+        if (const int rc = sky_set_lds_limit(bwd ? (const void *)mha_bwd_strip_kernel<HD, NT> : (const void *)mha_fwd_strip_kernel<HD, NT>,
+                                             (int)p.lds_limit, who))
             return rc;
-    }
-    if (!bwd) hipLaunchKernelGGL((mha_fwd_strip_kernel<HD, NT>), grid, block, smem, st, x, out, B, N, H);
-    else hipLaunchKernelGGL((mha_bwd_strip_kernel<HD, NT>), grid, block, smem, st, x, dout, out, B, N, H);
+    if (!bwd) hipLaunchKernelGGL((mha_fwd_strip_kernel<HD, NT>), grid, block, p.lds_bytes, st, x, out, B, N, H);
+    else hipLaunchKernelGGL((mha_bwd_strip_kernel<HD, NT>), grid, block, p.lds_bytes, st, x, dout, out, B, N, H);
     return 0;
 }
 
@@ -613,7 +613,7 @@ int launch_strip(bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, in
 // LDS: two [64][HD + 8] staging tiles (18.4 KB at hd 64) + 2 x round_up(N, 64) statistics floats in backward (32.8 KB
 // at N = 4098): under 64 KB, no hipFuncSetAttribute in the launch path.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int LB = 64, LW = 4;
+constexpr int LB = MHA_LB, LW = MHA_LW;
 
 // two [LB][HD] operand blocks starting at token row0 held in registers (rows >= N zero), then written to two LDS tiles
 template <int HD>
@@ -895,63 +895,47 @@ __global__ __launch_bounds__(64 * LW) void mha_bwd_long_kernel(const lp_t *__res
     }
 }
 
+template <int HD, int WPB>
+void launch_tile(const skyemb_mha_plan_t &p, bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st) {
+    const dim3 grid(p.grid_x), block(p.block);
+    if (!bwd) hipLaunchKernelGGL((mha_fwd_mfma_kernel<HD, WPB>), grid, block, 0, st, x, out, B, N, H, p.nheads);
+    else hipLaunchKernelGGL((mha_bwd_mfma_kernel<HD, WPB>), grid, block, 0, st, x, dout, out, B, N, H, p.nheads);
+}
+
+// the plan's family and `waves` as template arguments of the head-dim instance HD
 template <int HD>
-int launch_long(bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st) {
-    if (!bwd) {
-        hipLaunchKernelGGL((mha_fwd_long_kernel<HD>), dim3(B * H, (N + 32 * LW - 1) / (32 * LW)), dim3(64 * LW), 0, st, x, out, B, N, H);
+int launch_plan(const skyemb_mha_plan_t &p, bool bwd, const lp_t *x, const lp_t *dout, lp_t *out, int B, int N, int H, hipStream_t st,
+                const char *who) {
+    if (p.family == SKYEMB_MHA_MFMA_STRIP) {
+        if (p.waves == 2) return launch_strip<HD, 2>(p, bwd, x, dout, out, B, N, H, st, who);
+        if (p.waves == 3) return launch_strip<HD, 3>(p, bwd, x, dout, out, B, N, H, st, who);
+        return launch_strip<HD, 4>(p, bwd, x, dout, out, B, N, H, st, who);
+    }
+    if (p.family == SKYEMB_MHA_MFMA_LONG) {
+        const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+        if (!bwd) hipLaunchKernelGGL((mha_fwd_long_kernel<HD>), grid, block, p.lds_bytes, st, x, out, B, N, H);
+        else hipLaunchKernelGGL((mha_bwd_long_kernel<HD>), grid, block, p.lds_bytes, st, x, dout, out, B, N, H);
+    } else if (p.waves == 1) {
+        launch_tile<HD, 1>(p, bwd, x, dout, out, B, N, H, st);
     } else {
-        const size_t smem = 2 * LB * (HD + 8) * sizeof(lp_t) + 2 * sizeof(float) * ((N + LB - 1) / LB * LB);
-        hipLaunchKernelGGL((mha_bwd_long_kernel<HD>), dim3(B * H), dim3(64 * LW), smem, st, x, dout, out, B, N, H);
+        launch_tile<HD, 4>(p, bwd, x, dout, out, B, N, H, st);
     }
     return 0;
 }
 
 }  // namespace
 
-// returns -1 when the shape is outside this kernel's subset (caller falls back to the LDS kernel of attention.hip)
+// Launches plan `p` (attention_plan.h: one of the SKYEMB_MHA_MFMA_* families) for this twin's format; the bf16 object hands fp16 calls
+// to its twin.  Returns 0, or 2 when the strip kernel's LDS limit could not be raised (the library's error is set).
 #ifndef SKY_F16
-int skyemb_mha_mfma_try_f16(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, hipStream_t st);
+int skyemb_mha_mfma_launch_f16(const skyemb_mha_plan_t &p, bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N,
+                               int H, hipStream_t st, const char *who);
 #endif
-int SKY_TWIN(skyemb_mha_mfma_try)(bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B, int N, int H, int hd, hipStream_t st) {
+int SKY_TWIN(skyemb_mha_mfma_launch)(const skyemb_mha_plan_t &p, bool bwd, const void *qkv, const void *dout, void *out, int dtype, int B,
+                                     int N, int H, hipStream_t st, const char *who) {
 #ifndef SKY_F16
-    if (dtype == SKYEMB_F16) return skyemb_mha_mfma_try_f16(bwd, qkv, dout, out, dtype, B, N, H, hd, st);
+    if (dtype == SKYEMB_F16) return skyemb_mha_mfma_launch_f16(p, bwd, qkv, dout, out, dtype, B, N, H, st, who);
 #endif
-    if (dtype != SKY_LP_DTYPE) return -1;
-    if (hd != 32 && hd != 64) return -1;
-    static const bool off = []() { const char *e = getenv("SKYEMB_MHA_MFMA"); return e && e[0] == '0'; }();
-    if (off) return -1;
-    const lp_t *x = (const lp_t *)qkv;
-    if (N > 32 * MAX_NT) {
-        if (hd == 32) return launch_long<32>(bwd, x, (const lp_t *)dout, (lp_t *)out, B, N, H, st);
-        return launch_long<64>(bwd, x, (const lp_t *)dout, (lp_t *)out, B, N, H, st);
-    }
-    if (N > 32) {
-        const int nt = (N + 31) / 32;
-#define STRIP(HD_, NT_) launch_strip<HD_, NT_>(bwd, x, (const lp_t *)dout, (lp_t *)out, B, N, H, st)
-        int rc;
-        if (hd == 32) rc = nt == 2 ? STRIP(32, 2) : nt == 3 ? STRIP(32, 3) : STRIP(32, 4);
-        else rc = nt == 2 ? STRIP(64, 2) : nt == 3 ? STRIP(64, 3) : STRIP(64, 4);
-#undef STRIP
-        return rc;
-    }
-    const int P = N <= 16 ? 32 / N : 1;                   // samples packed into one wave's 32-row tile
-    const int nheads = ((B + P - 1) / P) * H;
-    // fewer four-wave workgroups than twice the compute units: one tile per workgroup, so that the tiles spread over every CU
-    static const int wpb_env = []() { const char *e = getenv("SKYEMB_MHA_WPB"); return e ? atoi(e) : 0; }();
-    const bool one = wpb_env ? wpb_env == 1 : (nheads + 3) / 4 < 512;
-    const dim3 grid(one ? nheads : (nheads + 3) / 4), block(one ? 64 : 256);
-#define MHA_GO(KERN, HD_, ...)                                                                         \
-    do {                                                                                               \
-        if (one) hipLaunchKernelGGL((KERN<HD_, 1>), grid, block, 0, st, __VA_ARGS__);                  \
-        else hipLaunchKernelGGL((KERN<HD_, 4>), grid, block, 0, st, __VA_ARGS__);                      \
-    } while (0)
-    if (!bwd) {
-        if (hd == 32) MHA_GO(mha_fwd_mfma_kernel, 32, x, (lp_t *)out, B, N, H, nheads);
-        else MHA_GO(mha_fwd_mfma_kernel, 64, x, (lp_t *)out, B, N, H, nheads);
-    } else {
-        if (hd == 32) MHA_GO(mha_bwd_mfma_kernel, 32, x, (const lp_t *)dout, (lp_t *)out, B, N, H, nheads);
-        else MHA_GO(mha_bwd_mfma_kernel, 64, x, (const lp_t *)dout, (lp_t *)out, B, N, H, nheads);
-    }
-#undef MHA_GO
-    return 0;
+    if (p.hd == 32) return launch_plan<32>(p, bwd, (const lp_t *)qkv, (const lp_t *)dout, (lp_t *)out, B, N, H, st, who);
+    return launch_plan<64>(p, bwd, (const lp_t *)qkv, (const lp_t *)dout, (lp_t *)out, B, N, H, st, who);
 }

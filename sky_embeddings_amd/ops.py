@@ -290,6 +290,15 @@ def mha_bwd(qkv, dout, dqkv, B, N, H, hd):
           "skyemb_mha_bwd")
 
 
+def mha_plan(bwd, dtype, B, N, H, hd, switches=-1):
+    """The launch mha_fwd (bwd=False) / mha_bwd makes for this shape, as a `_lib.MhaPlan`; touches no device.  `switches`: -1 = the
+    process's environment, else `_lib.MHA_SW_*` bits.  Raises SkyembError where the entry points would refuse."""
+    from ._lib import MhaPlan
+    p = MhaPlan()
+    check(lib().skyemb_mha_plan(int(bool(bwd)), dtype_code(dtype), B, N, H, hd, switches, p), "skyemb_mha_plan")
+    return p
+
+
 def fill_mask_tokens(x, mask, mask_token, dec_pos, B, L, Dd, n_extra=1):
     check(lib().skyemb_fill_mask_tokens(_p(x), _p(mask), _p(mask_token), _p(dec_pos), B, L, Dd, n_extra, _stream()),
           "skyemb_fill_mask_tokens")

@@ -152,12 +152,15 @@ def emulate(qkv, dout, H, hd, dtype, rounding="rne"):
 
 
 # ----------------------------------------------------------------------------------------------------- dispatch rules
-LDS_LIMIT = 160 * 1024        # attention.hip, set_lds / skyemb_mha_fwd: past it the streaming kernel
-MFMA_MAX_NT = 4               # attention_mfma.hip, MAX_NT: strips up to 128 tokens
+# An independent restatement of csrc/attention_plan.h (sky_mha_plan); tests/test_attention_reference_cpu.py sweeps it against the
+# library's own answer (skyemb_mha_plan), so a threshold changed on one side only fails there.
+LDS_LIMIT = 160 * 1024        # MHA_LDS_LIMIT: a whole-head LDS plan past it goes to the streaming kernel
+MFMA_MAX_NT = 4               # MHA_MAX_NT: strips up to 128 tokens
+STREAM_MAX_HD = 512           # MHA_STREAM_MAX_HD: the streaming kernels' widest head; wider is refused
 
 
 def lds_plan(N, hd, bwd):
-    """attention.hip make_plan: (waves per block, dynamic LDS bytes) of the whole-head LDS kernel."""
+    """sky_mha_plan, lds family: (waves per block, dynamic LDS bytes) of the whole-head LDS kernel."""
     pitch, NP = hd + 4, N + 1
     per_wave = ((4 if bwd else 3) * N * pitch + (2 if bwd else 1) * N * NP + 3) & ~3
     per = per_wave * 4
@@ -166,11 +169,11 @@ def lds_plan(N, hd, bwd):
 
 
 def family(B, N, H, hd, dtype, bwd, mfma=True):
-    """The kernel skyemb_mha_fwd (bwd=False) / skyemb_mha_bwd (bwd=True) launches for this shape.  Mirrors
-    attention.hip skyemb_mha_fwd / skyemb_mha_bwd (MFMA first for 16-bit, then make_plan and the 160 KB switch to
-    mha_*_stream_kernel) and attention_mfma.hip skyemb_mha_mfma_try (hd 32 / 64 only; N > 32 MAX_NT: long kernels; N > 32:
-    strips, nt = ceil(N / 32); else P = 32 / N samples per tile when N <= 16, nheads = ceil(B / P) H, and one tile per
-    workgroup while (nheads + 3) / 4 < 512, else WPB = 4).  mfma=False: SKYEMB_MHA_MFMA=0."""
+    """The kernel skyemb_mha_fwd (bwd=False) / skyemb_mha_bwd (bwd=True) launches for this shape.  Restates the planner,
+    csrc/attention_plan.h sky_mha_plan: 16-bit at hd 32 / 64 runs on MFMA (N > 32 MAX_NT: long kernels; N > 32: strips,
+    nt = ceil(N / 32); else P = 32 / N samples per tile when N <= 16, nheads = ceil(B / P) H, and one tile per workgroup while
+    (nheads + 3) / 4 < 512, else WPB = 4); everything else takes the whole-head LDS plan, or the streaming kernels where
+    that plan passes 160 KB.  mfma=False: SKYEMB_MHA_MFMA=0."""
     if dtype != torch.float32 and hd in (32, 64) and mfma:
         if N > 32 * MFMA_MAX_NT:
             return "mfma_long"

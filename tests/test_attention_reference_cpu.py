@@ -1,6 +1,7 @@
 """CPU checks of tests/attention_reference.py: the fp64 statement against autograd and the oracle, the bar against the emulated
-kernel arithmetic (round to nearest even meets it, truncation fails the signed-bias check), and the GPU case list of
-tests/test_attention_core_gpu.py against the dispatch rules.
+kernel arithmetic (round to nearest even meets it, truncation fails the signed-bias check), the dispatch rules against the
+library's own planner (skyemb_mha_plan: no device needed) and against the launches traced before the planner existed, and the GPU
+case list of tests/test_attention_core_gpu.py against the dispatch rules.
 
 Worst err/bar of the emulation: 16-bit within [0.2, 1] (output rounding and the one rounding of P / dS are the bar's own
 terms).  fp32 sits near 0.01: the bar's fp32 terms are worst-case gamma_n bounds (module docstring of attention_reference.py,
@@ -217,3 +218,123 @@ def test_gpu_cases_cover_every_family():
 
 
 DTYPE_NAME = {BF: "bf16", F16: "f16", F32: "f32"}
+
+
+# ----------------------------------------------------------------------------------------------------- the library's planner
+def plan_name(p):
+    """A skyemb_mha_plan answer in the words of ar.family."""
+    from sky_embeddings_amd import _lib
+    if p.family == _lib.MHA_LDS:
+        return f"lds_w{p.waves}"
+    if p.family == _lib.MHA_MFMA_STRIP:
+        return f"mfma_strip{p.waves}"
+    if p.family in (_lib.MHA_MFMA_PACKED, _lib.MHA_MFMA_SINGLE):
+        return f"mfma_{'packed' if p.family == _lib.MHA_MFMA_PACKED else 'single'}_wpb{p.waves}"
+    return {_lib.MHA_STREAM: "stream", _lib.MHA_MFMA_LONG: "mfma_long"}[p.family]
+
+
+def test_dispatch_rules_agree_with_the_library_planner():
+    """ar.family / ar.lds_plan against skyemb_mha_plan at every point of: three dtypes x fwd / bwd x MFMA on / off, hd in
+    {8, 16, 32, 40, 64, 80, 128}, every N in 1..400 and 4097, 4098, and (B, H) that put nheads at 1 and at 2043..2052 (H = 1, and
+    H = 3 for the multiples of 3) for packed and single tiles -- both sides of (nheads + 3) / 4 < 512.  Integer work only."""
+    import ctypes
+    from sky_embeddings_amd import _lib, ops
+    L, p = _lib.lib(), _lib.MhaPlan()
+    ref, points = ctypes.byref(p), 0
+    for N in list(range(1, 401)) + [4097, 4098]:
+        P = 32 // N if N <= 16 else 1
+        shapes = [(1, 1)] + [((t - 1) * P + 1, 1) for t in range(2043, 2053)] + [((t - 1) * P + 1, 3) for t in range(681, 685)]
+        for hd in (8, 16, 32, 40, 64, 80, 128):
+            for dt in (BF, F16, F32):
+                code = ops.dtype_code(dt)
+                for bwd in (False, True):
+                    w, smem = ar.lds_plan(N, hd, bwd)
+                    for mfma in (True, False):
+                        sw = 0 if mfma else _lib.MHA_SW_NO_MFMA
+                        for B, H in shapes:
+                            assert L.skyemb_mha_plan(int(bwd), code, B, N, H, hd, sw, ref) == 0, L.skyemb_last_error()
+                            fam = ar.family(B, N, H, hd, dt, bwd, mfma)
+                            at = (DTYPE_NAME[dt], bwd, mfma, B, N, H, hd)
+                            assert plan_name(p) == fam, at
+                            assert p.block == 64 * p.waves, at
+                            if fam.startswith("lds_w"):
+                                assert (p.waves, p.lds_bytes, p.grid_x) == (w, smem, -(-B * H // w)), at
+                                assert p.per_wave_floats * 4 * w == smem and p.lds_limit == (ar.LDS_LIMIT if smem > 65536 else 0), at
+                            elif fam.startswith("mfma_packed") or fam.startswith("mfma_single"):
+                                nheads = -(-B // P) * H
+                                assert (p.hd, p.nheads, p.grid_x, p.lds_bytes) == (hd, nheads, -(-nheads // p.waves), 0), at
+                            elif fam != "stream":
+                                assert (p.hd, p.grid_x) == (hd, B * H), at
+                            points += 1
+    assert points == 402 * 15 * 7 * 3 * 2 * 2
+
+
+def test_planner_refuses_what_the_entry_points_refuse():
+    import ctypes
+    from sky_embeddings_amd import _lib
+    L, p = _lib.lib(), _lib.MhaPlan()
+    for bwd, who in ((0, b"skyemb_mha_fwd: "), (1, b"skyemb_mha_bwd: ")):
+        for dt in (0, 1, 2):
+            assert L.skyemb_mha_plan(bwd, dt, 1, 4099, 1, 64, 0, ctypes.byref(p)) == 1
+            assert L.skyemb_last_error() == who + b"N = 4099 tokens, more than the supported 4098"
+            for hd in (4, 12, 36, 0, -8):
+                assert L.skyemb_mha_plan(bwd, dt, 2, 17, 3, hd, 0, ctypes.byref(p)) == 1
+                assert L.skyemb_last_error() == who + b"bad shape (head dim must be a multiple of 8)"
+            # a head wider than the streaming kernels take is refused exactly where the whole-head LDS plan passes 160 KB
+            hd = ar.STREAM_MAX_HD + 8
+            for N in range(1, 40):
+                rc = L.skyemb_mha_plan(bwd, dt, 2, N, 3, hd, 0, ctypes.byref(p))
+                w, smem = ar.lds_plan(N, hd, bool(bwd))
+                if smem > ar.LDS_LIMIT:
+                    assert rc == 1 and L.skyemb_last_error() == who + b"head dim %d with N = %d tokens: at most 512" % (hd, N)
+                else:
+                    assert rc == 0 and plan_name(p) == f"lds_w{w}"
+            assert L.skyemb_mha_plan(bwd, dt, 2, 4098, 3, ar.STREAM_MAX_HD, 0, ctypes.byref(p)) == 0 and plan_name(p) == "stream"
+    # the entry points refuse in the same words before any device work
+    assert L.skyemb_mha_fwd(None, None, 1, 2, 39, 3, 520, None) == 1
+    assert L.skyemb_last_error() == b"skyemb_mha_fwd: head dim 520 with N = 39 tokens: at most 512"
+    assert L.skyemb_mha_bwd(None, None, None, 0, 2, 17, 3, 36, None) == 1
+    assert L.skyemb_last_error() == b"skyemb_mha_bwd: bad shape (head dim must be a multiple of 8)"
+
+
+def test_planner_switches():
+    """Explicit switch bits: MFMA off, tiles per workgroup forced either way; -1 reads the environment (unset here: the defaults)."""
+    import os
+    from sky_embeddings_amd import _lib, ops
+    assert "SKYEMB_MHA_MFMA" not in os.environ and "SKYEMB_MHA_WPB" not in os.environ
+    for B, N, H, hd in ((256, 5, 12, 64), (256, 17, 16, 32), (3, 65, 3, 64), (3, 129, 3, 32), (3, 40, 3, 80)):
+        for bwd in (False, True):
+            auto, env = ops.mha_plan(bwd, BF, B, N, H, hd, 0), ops.mha_plan(bwd, BF, B, N, H, hd)
+            assert all(getattr(auto, f) == getattr(env, f) for f, _ in _lib.MhaPlan._fields_)
+            for sw, wpb in ((_lib.MHA_SW_WPB1, 1), (_lib.MHA_SW_WPB4, 4)):
+                p = ops.mha_plan(bwd, BF, B, N, H, hd, sw)
+                if N <= 32 and hd in (32, 64):
+                    assert (p.waves, p.block, p.grid_x) == (wpb, 64 * wpb, -(-p.nheads // wpb)) and p.nheads == auto.nheads
+                else:
+                    assert all(getattr(auto, f) == getattr(p, f) for f, _ in _lib.MhaPlan._fields_)
+            off = ops.mha_plan(bwd, BF, B, N, H, hd, _lib.MHA_SW_NO_MFMA)
+            assert plan_name(off) == ar.family(B, N, H, hd, BF, bwd, False)
+
+
+def test_planner_reproduces_the_launches_traced_before_it():
+    """tests/golden/mha_launches.json: kernel, grid in threads and workgroup size of every launch of CASES and NOMFMA_CASES, from a
+    kernel trace of the commit before the planner (tests/golden/make_mha_launch_golden.py)."""
+    import json
+    import os
+    from sky_embeddings_amd import _lib, ops
+    from tests.test_attention_core_gpu import CASES, NOMFMA_CASES, cid
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mha_launches.json")) as f:
+        golden = json.load(f)
+    cases = {cid(c): c for c in CASES + NOMFMA_CASES}
+    assert sorted(golden) == sorted(cases) and len(cases) == len(CASES) + len(NOMFMA_CASES)
+    for name, c in cases.items():
+        for bwd in (False, True):
+            p = ops.mha_plan(bwd, c.dtype, c.B, c.N, c.H, c.hd, 0 if c.mfma else _lib.MHA_SW_NO_MFMA)
+            d = "bwd" if bwd else "fwd"
+            kernel = {_lib.MHA_LDS: f"mha_{d}_kernel", _lib.MHA_STREAM: f"mha_{d}_stream_kernel",
+                      _lib.MHA_MFMA_PACKED: f"mha_{d}_mfma_kernel<{p.hd}, {p.waves}>",
+                      _lib.MHA_MFMA_SINGLE: f"mha_{d}_mfma_kernel<{p.hd}, {p.waves}>",
+                      _lib.MHA_MFMA_STRIP: f"mha_{d}_strip_kernel<{p.hd}, {p.waves}>",
+                      _lib.MHA_MFMA_LONG: f"mha_{d}_long_kernel<{p.hd}>"}[p.family]
+            got = {"kernel": kernel, "operand": DTYPE_NAME[c.dtype], "grid": [p.grid_x * p.block, p.grid_y], "workgroup": p.block}
+            assert got == golden[name][d], (name, d)
