@@ -476,7 +476,22 @@ int skyemb_topk_merge(const float *in_s, const int64_t *in_i, int Q, int nlists,
  *   skyemb_cosine_topk_prefiltered   whole pipeline on `stream`; out_s / out_i [Q, k] final lists; redo[q] != 0 marks a query
  *                           whose answer could not be certified (too many near-ties, candidate overflow, fewer than k
  *                           finite rows): the caller runs those through skyemb_cosine_topk.  thr0 as in skyemb_cosine_topk
- *                           (NULL: the first bank slice supplies the floor).  ws: skyemb_topk_prefilter_ws_bytes(Q, D, k). */
+ *                           (NULL: the first bank slice supplies the floor).  ws: skyemb_topk_prefilter_ws_bytes(Q, D, k).
+ * The same search over a RESIDENT fp16 bank (bank16 [N, D] fp16, 16-byte aligned, D % 32 == 0): the bank is the fp32 bank its
+ * elements widen to (xn: skyemb_weighted_norms_lp), both stages read it directly -- no fp32 copy, no second image -- and the
+ * result is bit-identical to skyemb_cosine_topk_prefiltered on the widened bank.  bf16 rows are not representable in the
+ * fp16 matrix operands: no such call exists for them.
+ *   skyemb_bank16_rowp_lp   once per bank / weights: rowp = {xn, ||x||_2 + the row's fp16-subnormal term, 1, 0} for
+ *                           skyemb_bank16_rowp_rows(N) rows.  tail: one tile [256, D] fp16 (16-byte aligned) that receives a
+ *                           zero-padded copy of the last N % 256 rows -- the search reads whole tiles and never reads past the
+ *                           bank's N * D elements; may be NULL when N % 256 == 0.  Extra memory: 16 bytes per row + that tile.
+ *   skyemb_cosine_topk_prefiltered_lp   skyemb_cosine_topk_prefiltered with the resident bank in place of bank + bank16 and
+ *                           the tail tile of skyemb_bank16_rowp_lp; redo[q] != 0: the caller runs the query through
+ *                           skyemb_cosine_token_topk_lp with one token per row.
+ *   skyemb_topk_prefilter_eps_a   host only: the relative error bound eps_a of stage 1 (|dot^ - dot'| <= eps_a ||q'|| ||x'||) for
+ *                           D features, one (lo = 0) or two (lo = 1) fp16 query passes, over the scaled image of an fp32 bank
+ *                           (resident = 0) or a resident fp16 bank (resident = 1; then a row with nsub fp16-subnormal elements
+ *                           adds ||q'|| sqrt(nsub) 2^-14).  Derivation: csrc/topk_prefilter.hip. */
 int skyemb_topk_prefilter_applicable(int Q, int64_t N, int D, int k);
 int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k);
 int64_t skyemb_bank16_bytes(int64_t N, int D);
@@ -485,6 +500,11 @@ int skyemb_bank16_prepare(const float *bank, const float *xn, int64_t N, int D, 
 int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, int Q, const float *bank, const float *xn, const void *bank16,
                                    const float *rowp, int64_t N, int D, int k, float eps, int64_t idx_offset, const float *thr0,
                                    void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream);
+int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream);
+int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *qn, int Q, const void *bank16, const float *xn, const void *tail,
+                                      const float *rowp, int64_t N, int D, int k, float eps, int64_t idx_offset, const float *thr0,
+                                      void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream);
+double skyemb_topk_prefilter_eps_a(int D, int lo, int resident);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

@@ -156,6 +156,11 @@ PROTOTYPES = {
     "skyemb_bank16_prepare": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "skyemb_cosine_topk_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_i64, c_vp,
                                                c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    # the two-stage search over a resident fp16 bank: additive to ABI version 111
+    "skyemb_bank16_rowp_lp": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_prefiltered_lp": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_i64, c_vp,
+                                                  c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_topk_prefilter_eps_a": (c_f64, [c_i32, c_i32, c_i32]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

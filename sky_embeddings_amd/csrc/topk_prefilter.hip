@@ -28,6 +28,24 @@
 // At the end the K' candidates with the largest U are re-scored exactly; the answer is accepted when its k-th best
 // exact score beats the U of every candidate that was NOT re-scored, otherwise the query is flagged and the caller
 // runs it through the exact kernel (never observed on embedding-like data; forced in the tests).
+//
+// Resident fp16 bank (skyemb_bank16_rowp_lp / skyemb_cosine_topk_prefiltered_lp).  The bank IS the fp32 bank its elements
+// widen to, so stage 1 multiplies the stored rows themselves: x^_i = x_i exactly, e_i = 0, no image is written.  Against
+// dot' = chain(tw, x) * 2^-f the bound keeps its shape, |dot^ - dot'| <= eps_a * ||q'||_2 * ||x||_2 + s_i, with
+//   eps_a = 2^-11 + 2^-21 (hi only: the query's own fp16 rounding, relative; no cross term -- the other factor is exact)
+//           or 2^-21 (hi + lo: the residual q' - qh - ql is <= 2^-22 |q'| per element)
+//         + 6.06 * D * 2^-24 (accumulation, as above: no more products, no more roundings)
+//         + sqrt(D) * 2^-27 (fp16 subnormals of the QUERY operand, absolute <= 2^-14 per element against a query maximum
+//           >= 2^13; the row side's share of that term is gone with the scaling it relied on)
+//   s_i   = ||q'||_2 * sqrt(nsub_i) * 2^-14: row i has nsub_i fp16-subnormal elements (0 < |x| < 2^-14, not rescaled any
+//           more).  If the matrix core flushes them the products q'_d x_d of those d are lost: Cauchy-Schwarz over them.
+//           Nothing is assumed about whether it does.
+// s_i rides in the row's norm slot: rowp[i] = {xn_i, nx_i, 1, 0} with nx_i = ||x_i||_2 (1 + D 2^-22) + sqrt(nsub_i) 2^-14 /
+// eps_a, rounded up -- the slot multiplies eps_a ||q'||.  The row constants are built once and serve both variants, so
+// the division uses the SMALLER eps_a (hi + lo): under hi only the term comes out larger than needed, never smaller.
+// Whole tiles of BT rows are read straight from the bank; the last N % BT rows are served from a zero-padded copy of one
+// tile (a launch of its own, so no read ever passes the bank's N * D elements).  Stage 2 widens the selected rows
+// element by element into the same fma chain: the scores are those of the fp32 kernel on the widened bank, bit for bit.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -61,7 +79,9 @@ __device__ __forceinline__ void glds16(const void *src, char *lds_wave_base) {
 
 // lo: the query enters as hi + lo (see the header); without lo its own fp16 rounding (2^-11 relative, + the cross term) joins
 // the row's
-__host__ __device__ inline double eps_a_of(int D, bool lo) {
+// resident: the rows are a resident fp16 bank, exact in stage 1 (file header): their 2^-11 and their half of the subnormal term go
+__host__ __device__ inline double eps_a_of(int D, bool lo, bool resident = false) {
+    if (resident) return (lo ? 0x1p-21 : 0x1p-11 + 0x1p-21) + 6.06 * D * 0x1p-24 + sqrt((double)D) * 0x1p-27;
     return (lo ? 0x1p-11 + 0x1p-21 : 0x1p-10 + 0x1p-21) + 6.06 * D * 0x1p-24 + 2.0 * sqrt((double)D) * 0x1p-27;
 }
 
@@ -120,6 +140,49 @@ __global__ __launch_bounds__(256) void bank16_kernel(const float *__restrict__ b
         const float nx = sqrtf(ss) * (1.0f + (float)D * 0x1p-22f);
         const float xnv = xn[row];
         rowp[row] = make_float4(xnv * s, nx, s, 0.f);
+    }
+}
+
+// the same for a resident fp16 bank (file header): one wave per row, NO image -- rowp[i] = {xn, nx, 1, 0} with
+// nx = ||x||_2 (1 + D 2^-22) + sqrt(nsub) * sub_scale, rounded up (sub_scale = 2^-14 / eps_a, raised, from the host); the same
+// sentinel for rows N .. rows_padded-1.  tail (NULL when N is a whole number of tiles): one tile [BT, D] that receives rows
+// tail_first .. N-1 (tail_first = N rounded down to whole tiles) and zeros behind them.
+__global__ __launch_bounds__(256) void bank16_rowp_lp_kernel(const half_t *__restrict__ bank, const float *__restrict__ xn, int64_t N,
+                                                              int D, float4 *__restrict__ rowp, int64_t rows_padded,
+                                                              half_t *__restrict__ tail, int64_t tail_first, float sub_scale) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows_padded) return;
+    half_t *t = tail && row >= tail_first ? tail + (row - tail_first) * D : nullptr;
+    if (row >= N) {
+        if (t)
+            for (int d = lane * 4; d < D; d += 256) *(uint2 *)(t + d) = make_uint2(0u, 0u);
+        if (lane == 0) rowp[row] = make_float4(0.f, NAN, 0.f, 0.f);
+        return;
+    }
+    const half_t *x = bank + row * D;
+    float ss = 0.f, nsub = 0.f, bad = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const uint2 raw = *(const uint2 *)(x + d);
+        if (t) *(uint2 *)(t + d) = raw;
+        typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+        const half4 h = __builtin_bit_cast(half4, raw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = (float)h[j];                 // exact
+            const float m = fabsf(a);
+            ss = fmaf(a, a, ss);
+            nsub += (m > 0.f && m < 0x1p-14f) ? 1.f : 0.f;
+            bad = !(m < INFINITY) ? 1.f : bad;           // inf or NaN
+        }
+    }
+    ss = wave_sum(ss);
+    nsub = wave_sum(nsub);                               // <= D <= 4096: exact
+    bad = wave_max(bad);
+    if (lane == 0) {
+        // a row with an inf / NaN element cannot be bounded: ||x|| = inf makes every query keep it (bank16_kernel's rule)
+        const float nx = fmaf(sqrtf(nsub), sub_scale, sqrtf(ss) * (1.0f + (float)D * 0x1p-22f)) * (1.0f + 0x1p-21f);
+        rowp[row] = bad != 0.f ? make_float4(0.f, INFINITY, 1.0f, 0.f) : make_float4(xn[row], nx, 1.0f, 0.f);
     }
 }
 
@@ -860,13 +923,22 @@ __device__ __forceinline__ float finish_score(float dot, float qn, float xn, flo
     return s == s ? s : -INFINITY;
 }
 
+// four consecutive elements of a bank row as fp32: the fp32 bank's own, or a resident fp16 bank's widened exactly
+__device__ __forceinline__ float4 row4(const float *x) { return *(const float4 *)x; }
+__device__ __forceinline__ float4 row4(const half_t *x) {
+    typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+    const half4 h = *(const half4 *)x;
+    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+}
+
 // one workgroup (256 threads) per query; thread c owns candidate c: the contract's fma chain over d = 0..D-1
-__global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ tw, const float *__restrict__ qn,
-                                                      const float *__restrict__ bank, const float *__restrict__ xn, int Q, int D,
-                                                      int k, float eps, int64_t idx_offset, const int *__restrict__ sel_i,
-                                                      const int *__restrict__ nsel, const float *__restrict__ bound,
-                                                      const int *__restrict__ overflow, float *__restrict__ out_s,
-                                                      int64_t *__restrict__ out_i, int *__restrict__ redo) {
+template <typename X>
+__device__ __forceinline__ void rescore_body(const float *__restrict__ tw, const float *__restrict__ qn,
+                                             const X *__restrict__ bank, const float *__restrict__ xn, int Q, int D,
+                                             int k, float eps, int64_t idx_offset, const int *__restrict__ sel_i,
+                                             const int *__restrict__ nsel, const float *__restrict__ bound,
+                                             const int *__restrict__ overflow, float *__restrict__ out_s,
+                                             int64_t *__restrict__ out_i, int *__restrict__ redo) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *sq = (float *)smem;                                // [D] weighted query
     float *ss = sq + D;                                       // [RESCORE_MAX] exact scores
@@ -879,10 +951,10 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ 
     int row = 0x7fffffff;
     if (tid < n) {
         row = sel_i[(int64_t)q * RESCORE_MAX + tid];
-        const float *x = bank + (int64_t)row * D;
+        const X *x = bank + (int64_t)row * D;
         float acc = 0.f;
         for (int d = 0; d < D; d += 4) {      // explicit fmaf only: nothing here for the compiler to contract
-            const float4 v = *(const float4 *)(x + d);
+            const float4 v = row4(x + d);
             acc = fmaf(sq[d], v.x, acc);
             acc = fmaf(sq[d + 1], v.y, acc);
             acc = fmaf(sq[d + 2], v.z, acc);
@@ -918,6 +990,20 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ 
         }
     }
 }
+
+#define RESCORE_PARAMS(X)                                                                                                     \
+    const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank, const float *__restrict__ xn, int Q,   \
+        int D, int k, float eps, int64_t idx_offset, const int *__restrict__ sel_i, const int *__restrict__ nsel,                  \
+        const float *__restrict__ bound, const int *__restrict__ overflow, float *__restrict__ out_s, int64_t *__restrict__ out_i, \
+        int *__restrict__ redo
+__global__ __launch_bounds__(256) void rescore_kernel(RESCORE_PARAMS(float)) {
+    rescore_body(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
+}
+// the resident fp16 bank's rows, widened element by element: same chain, same bits as rescore_kernel on the widened bank
+__global__ __launch_bounds__(256) void rescore_lp_kernel(RESCORE_PARAMS(half_t)) {
+    rescore_body(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
+}
+#undef RESCORE_PARAMS
 
 __global__ void init_state_kernel(int Q, int Q_padded, const float *__restrict__ thr0, const float4 *__restrict__ qbase, float eps,
                                   float4 *__restrict__ qpar, float *__restrict__ tau_q, int *__restrict__ cnt,
@@ -1001,17 +1087,35 @@ extern "C" int skyemb_bank16_prepare(const float *bank, const float *xn, int64_t
     return 0;
 }
 
+extern "C" double skyemb_topk_prefilter_eps_a(int D, int lo, int resident) { return eps_a_of(D, lo != 0, resident != 0); }
+
+extern "C" int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
+    SKY_CHECK_ARG(bank16 && xn && rowp && N > 0 && D > 0 && D % BK == 0, "skyemb_bank16_rowp_lp: bad arguments");
+    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_bank16_rowp_lp: N = %lld is no whole number of %d-row tiles: a tail tile [%d, D] is needed",
+                  (long long)N, BT, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_bank16_rowp_lp: the bank and the tail tile must be 16-byte aligned");
+    const int64_t padded = skyemb_bank16_rowp_rows(N);
+    // one set of row constants serves both variants: the smaller eps_a (hi + lo) gives the larger, always valid, term
+    const float sub_scale = (float)(0x1p-14 / eps_a_of(D, true, true) * (1.0 + 1e-6));
+    hipLaunchKernelGGL(bank16_rowp_lp_kernel, dim3((unsigned)ceil_div64(padded, 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t *)bank16, xn, N, D, (float4 *)rowp, padded, N % BT ? (half_t *)tail : nullptr, N / BT * BT, sub_scale);
+    SKY_LAUNCH_CHECK("skyemb_bank16_rowp_lp");
+    return 0;
+}
+
 extern "C" int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k) { return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr); }
 
-extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, int Q, const float *bank, const float *xn,
-                                              const void *bank16, const float *rowp, int64_t N, int D, int k, float eps,
-                                              int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
-                                              int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && bank16 && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered: null argument");
-    SKY_CHECK_ARG(skyemb_topk_prefilter_applicable(Q, N, D, k), "skyemb_cosine_topk_prefiltered: outside the prefiltered subset "
-                  "(Q >= 17, D %% 32 == 0, k <= %d, N >= %d)", RESCORE_MAX - 64, 8 * BT);
+// The pipeline of both entry points.  bank: the fp32 rows stage 2 re-scores, bank16 their fp16 image (skyemb_bank16_prepare) --
+// or bank NULL: bank16 is a resident fp16 bank that both stages read, its last N % BT rows through `tail` (skyemb_bank16_rowp_lp).
+static int topk_prefiltered(const char *who, const float *tw, const float *qn, int Q, const float *bank, const float *xn,
+                            const void *bank16, const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
+                            int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                            int *redo, void *stream) {
+    const bool resident = bank == nullptr;
+    SKY_CHECK_ARG(skyemb_topk_prefilter_applicable(Q, N, D, k), "%s: outside the prefiltered subset "
+                  "(Q >= 17, D %% 32 == 0, k <= %d, N >= %d)", who, RESCORE_MAX - 64, 8 * BT);
     const int cap = skyemb_topk_prefilter_cap(k);
-    SKY_CHECK_ARG(ws_bytes >= skyemb_topk_prefilter_ws_bytes(Q, D, k), "skyemb_cosine_topk_prefiltered: workspace too small");
+    SKY_CHECK_ARG(ws_bytes >= skyemb_topk_prefilter_ws_bytes(Q, D, k), "%s: workspace too small", who);
     hipStream_t st = (hipStream_t)stream;
     Workspace w;
     carve((char *)ws, Q, D, cap, &w);
@@ -1020,10 +1124,13 @@ extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, 
     // (read per call on purpose: a getenv is a sub-microsecond scan next to a multi-millisecond search, and the tests switch it)
     const char *lo_env = getenv("SKYEMB_PREFILTER_LO");
     const bool use_lo = lo_env && lo_env[0] == '1';
-    const float eps_a = (float)(eps_a_of(D, use_lo) * (1.0 + 1e-6));
+    const float eps_a = (float)(eps_a_of(D, use_lo, resident) * (1.0 + 1e-6));
     hipLaunchKernelGGL(query16_kernel, dim3((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4)), dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql,
                        w.qbase, eps_a);
-    const int T = (int)ceil_div64(N, BT);
+    // tiles the phases below walk: all of them -- of a resident bank the whole ones, the last N % BT rows follow from `tail`
+    const int T = resident ? (int)(N / BT) : (int)ceil_div64(N, BT);
+    const bool has_tail = resident && N % BT != 0;
+    bool tail_done = false;
     // phases: [0, first) is taken whole unless a floor came in; then slices ending at 1/128, 1/32, 1/8, 1/2 and all of the tiles
     int first = (int)(cap / 2 / BT);                           // rows of the take-everything slice <= cap / 2
     if (first < 1) first = 1;
@@ -1034,7 +1141,6 @@ extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, 
                        w.qpar, w.tau, w.cnt, w.overflow, (int)first_rows);
     const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
     constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
-    const char *who = "skyemb_cosine_topk_prefiltered";
     int rc = 0;
 #define PF_ATTR(M, L) if (rc == 0) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L>, smem_max, who)
     PF_ATTR(0, false); PF_ATTR(1, false); PF_ATTR(2, false); PF_ATTR(0, true); PF_ATTR(1, true); PF_ATTR(2, true);
@@ -1064,22 +1170,31 @@ extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, 
 #else
 #define PF_DBG
 #endif
-#define PF_ARGS w.qh, w.ql, (const half_t *)bank16, (const float4 *)rowp, w.qpar, Q, N, D, t0, t1, cap, w.cnt, w.cand_i, w.cand_d, \
-                w.wg_list, w.wg_count, w.capw, w.overflow PF_DBG
-#define PF_LAUNCH(M)                                                                                          \
-    do {                                                                                                      \
-        if (use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS); \
-        else hipLaunchKernelGGL((prefilter_kernel<M, false>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS);     \
+#define PF_ARGS(B, T0, T1) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, w.qpar, Q, N, D, T0, T1, cap, w.cnt, w.cand_i, w.cand_d, \
+                           w.wg_list, w.wg_count, w.capw, w.overflow PF_DBG
+#define PF_LAUNCH(M, B, T0, T1)                                                                                            \
+    do {                                                                                                                   \
+        if (use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1)); \
+        else hipLaunchKernelGGL((prefilter_kernel<M, false>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1));     \
     } while (0)
         if (p == 0) {
-            PF_LAUNCH(0);
+            PF_LAUNCH(0, bank16, t0, t1);
         } else if (!thresholded_once) {
-            PF_LAUNCH(1);
+            PF_LAUNCH(1, bank16, t0, t1);
             thresholded_once = true;
         } else {
-            PF_LAUNCH(2);
+            PF_LAUNCH(2, bank16, t0, t1);
             hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count,
                                w.capw, cap, w.cnt, w.cand_i, w.cand_d);
+        }
+        if (has_tail && t1 == T && !tail_done) {
+            tail_done = true;                                  // (a later, empty phase may end at T once more)
+            // The last N % BT rows of a resident bank, before the final selection: tile T, read from the padded copy.  The kernel
+            // addresses tile t at base + t * BT rows, so the base handed over is the one that puts tile T on `tail` (an address
+            // only: tile T is the single tile of this launch).  Direct appends under the last phase's threshold -- at most BT
+            // candidates per query behind whatever the lists hold (after a take-all phase: behind its first_rows slots).
+            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T * BT * D * sizeof(half_t));
+            PF_LAUNCH(1, tail_base, T, T + 1);
         }
 #undef PF_LAUNCH
 #undef PF_ARGS
@@ -1120,8 +1235,33 @@ extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, 
                            w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, final, w.sel_i, w.nsel, w.bound);
         t0 = t1;
     }
-    hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)Q), dim3(256), (size_t)D * 4 + RESCORE_MAX * 8, st, tw, qn, bank, xn, Q, D, k, eps,
-                       idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo);
-    SKY_LAUNCH_CHECK("skyemb_cosine_topk_prefiltered");
+    if (resident)
+        hipLaunchKernelGGL(rescore_lp_kernel, dim3((unsigned)Q), dim3(256), (size_t)D * 4 + RESCORE_MAX * 8, st, tw, qn,
+                           (const half_t *)bank16, xn, Q, D, k, eps, idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo);
+    else
+        hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)Q), dim3(256), (size_t)D * 4 + RESCORE_MAX * 8, st, tw, qn, bank, xn, Q, D, k, eps,
+                           idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo);
+    SKY_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, int Q, const float *bank, const float *xn,
+                                              const void *bank16, const float *rowp, int64_t N, int D, int k, float eps,
+                                              int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                              int64_t *out_i, int *redo, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank && xn && bank16 && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered: null argument");
+    return topk_prefiltered("skyemb_cosine_topk_prefiltered", tw, qn, Q, bank, xn, bank16, nullptr, rowp, N, D, k, eps, idx_offset, thr0, ws,
+                            ws_bytes, out_s, out_i, redo, stream);
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *qn, int Q, const void *bank16, const float *xn,
+                                                 const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
+                                                 int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                 int64_t *out_i, int *redo, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered_lp: null argument");
+    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_lp: N = %lld is no whole number of %d-row tiles: the tail tile of "
+                  "skyemb_bank16_rowp_lp is needed", (long long)N, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_lp: the bank and the tail tile must be 16-byte aligned");
+    return topk_prefiltered("skyemb_cosine_topk_prefiltered_lp", tw, qn, Q, nullptr, xn, bank16, tail, rowp, N, D, k, eps, idx_offset, thr0,
+                            ws, ws_bytes, out_s, out_i, redo, stream);
 }

@@ -448,6 +448,40 @@ def cosine_topk_prefiltered(tw, qn, bank, xn, bank16, rowp, k, eps, idx_offset, 
     return ws
 
 
+def topk_prefilter_eps_a(D, lo=False, resident=False):
+    """The proven relative error bound of the prefilter's fp16 dot products (host arithmetic only; see include/skyemb.h)."""
+    return lib().skyemb_topk_prefilter_eps_a(D, int(lo), int(resident))
+
+
+def bank16_rowp_lp(bank16, xn):
+    """Per-row constants of a RESIDENT fp16 bank [N, D] for the prefiltered many-query top-k: (tail, rowp).  No image of the bank
+    is written: ``rowp`` [rows, 4] float (``skyemb_bank16_rowp_rows``) and ``tail``, one zero-padded tile [256, D] holding the last
+    N % 256 rows (None when there are none), are all the memory it takes.  ValueError when the bank is not 16-byte aligned."""
+    N, D = bank16.shape
+    assert bank16.dtype == torch.float16 and bank16.is_contiguous()
+    if bank16.data_ptr() % 16:
+        raise ValueError("bank16_rowp_lp: the fp16 bank must be 16-byte aligned (the search reads it by 16-byte LDS-DMA); "
+                         "this tensor starts at an odd offset of its storage -- clone() it")
+    rows = lib().skyemb_bank16_rowp_rows(N)
+    rowp = torch.empty(rows, 4, device=bank16.device, dtype=torch.float32)
+    tail = torch.empty(rows - N // 256 * 256, D, device=bank16.device, dtype=torch.float16) if rows != N else None
+    check(lib().skyemb_bank16_rowp_lp(_p(bank16), _p(xn), N, D, _p(rowp), _p(tail), _stream()), "skyemb_bank16_rowp_lp")
+    return tail, rowp
+
+
+def cosine_topk_prefiltered_lp(tw, qn, bank16, xn, tail, rowp, k, eps, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """``cosine_topk_prefiltered`` over a resident fp16 bank and the (tail, rowp) of ``bank16_rowp_lp``."""
+    Q, D = tw.shape
+    N = bank16.shape[0]
+    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_prefiltered_lp(_p(tw), _p(qn), Q, _p(bank16), _p(xn), _p(tail), _p(rowp), N, D, k, eps, idx_offset,
+                                                  _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
+          "skyemb_cosine_topk_prefiltered_lp")
+    return ws
+
+
 def topk_merge(in_s, in_i, Q, nlists, k, out_s, out_i, ws=None):
     """ws: optional int32 [Q] scratch enabling the gather + block-sort path for many short lists."""
     check(lib().skyemb_topk_merge(_p(in_s), _p(in_i), Q, nlists, k, _p(out_s), _p(out_i), _p(ws), _stream()),

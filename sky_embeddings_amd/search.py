@@ -31,27 +31,58 @@ def _kth_floor(scores: torch.Tensor, k: int):
 
 
 class PreparedBank:
-    """Bank rows + their weighted norms (recomputed only when the weights change)."""
+    """Bank rows + their weighted norms (recomputed only when the weights change).
+
+    ``bank`` is fp32, or fp16 for a half-precision resident bank (``dtype``): such a bank IS the fp32 bank its elements widen
+    to -- norms, scores and every search result are those of the widened bank bit for bit -- and nothing here ever holds an
+    fp32 copy or a second image of it.  It must start 16-byte aligned (ValueError; a fresh tensor does).  bf16 is a ValueError:
+    the many-query search multiplies fp16 matrix operands, which cannot hold bf16 values exactly."""
 
     def __init__(self, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
-        assert bank.is_cuda and bank.dtype == torch.float32 and bank.is_contiguous() and bank.dim() == 2
-        self.bank, self.idx_offset = bank, int(idx_offset)
-        self.norms = torch.empty(bank.shape[0], device=bank.device)
+        if isinstance(bank, torch.Tensor) and bank.dtype == torch.bfloat16:
+            raise ValueError("PreparedBank: a bfloat16 bank is not supported: the many-query search multiplies fp16 matrix operands, "
+                             "which cannot hold bf16 values exactly; pass the flat [N, D] tensor itself to cosine_topk, which serves "
+                             "it by the token search with one token per row (cosine_topk_tokens)")
+        assert bank.is_cuda and bank.dtype in (torch.float32, torch.float16) and bank.is_contiguous() and bank.dim() == 2
+        if bank.dtype == torch.float16 and bank.data_ptr() % 16:
+            raise ValueError("PreparedBank: an fp16 bank must start 16-byte aligned (the search reads it by 16-byte LDS-DMA); this "
+                             "tensor starts at an odd offset of its storage -- clone() it")
+        self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self._sample = None
         self._half = None
-        self.set_weights(weights)
+        self.tail_tile = None
+        if self.dtype == torch.float32:
+            self._tokens = None
+            self.norms = torch.empty(bank.shape[0], device=bank.device)
+            self.set_weights(weights)
+        else:
+            # the same rows as a token bank with one token per row: the route of the searches the two-stage path does not take
+            # (and of its uncertified queries).  It computes the norms (ops.weighted_norms_lp); they are shared, not computed twice.
+            self._tokens = TokenBank(bank.unsqueeze(1), weights, idx_offset)
+            self.norms, self.weights = self._tokens.norms, self._tokens.weights
 
     def set_weights(self, weights):
-        self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
-        ops.weighted_norms(self.bank, self.weights, self.norms)
+        if self._tokens is not None:
+            self._tokens.set_weights(weights)
+            self.weights = self._tokens.weights
+        else:
+            self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
+            ops.weighted_norms(self.bank, self.weights, self.norms)
         self._sample = None
         self._half = None
 
     def half_image(self):
-        """(bank16, rowp): the fp16 image + per-row constants the prefiltered many-query search runs on; built on first
-        use (one pass over the bank, +50 % bank memory) and kept until the weights change."""
+        """(bank16, rowp): the fp16 rows + per-row constants the prefiltered many-query search runs on; built on first use and
+        kept until the weights change.  fp32 bank: bank16 is a scaled fp16 image of it (one pass over the bank, +50 % bank
+        memory).  fp16 bank: bank16 is the bank itself; only ``rowp`` (16 bytes per row) and ``tail_tile`` -- a zero-padded copy
+        of the last N % 256 rows, one tile [256, D], or None -- are allocated."""
         if self._half is None:
-            self._half = ops.bank16_prepare(self.bank, self.norms)
+            if self.dtype == torch.float32:
+                self._half = ops.bank16_prepare(self.bank, self.norms)
+                self.tail_tile = None
+            else:
+                self.tail_tile, rowp = ops.bank16_rowp_lp(self.bank, self.norms)
+                self._half = (self.bank, rowp)
         return self._half
 
     def sample(self, rows: int):
@@ -134,18 +165,26 @@ def _prefilter_enabled():
     return os.environ.get("SKYEMB_TOPK_PREFILTER", "1") != "0"
 
 
-def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps):
+def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps, q=None, prune=True):
     """Two-stage exact top-k of this rank's shard (csrc/topk_prefilter.hip); queries the second stage could not certify
-    (redo flags) go through the exact fp32 kernel."""
+    (redo flags) go through the exact fp32 kernel -- over a resident fp16 bank (``q``: the raw queries): through the token
+    search with one token per row, those queries only, on the bank's own norms."""
     Q = tw.shape[0]
     dev = tw.device
     bank16, rowp = pb.half_image()
     out_s = torch.empty(Q, k, device=dev)
     out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
     redo = torch.empty(Q, device=dev, dtype=torch.int32)
-    ops.cosine_topk_prefiltered(tw, qn, pb.bank, pb.norms, bank16, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
+    if pb.dtype == torch.float32:
+        ops.cosine_topk_prefiltered(tw, qn, pb.bank, pb.norms, bank16, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
+    else:
+        ops.cosine_topk_prefiltered_lp(tw, qn, bank16, pb.norms, pb.tail_tile, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
     again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
-    if again.numel():
+    if again.numel() and pb.dtype != torch.float32:
+        s2, i2 = cosine_topk_tokens(q.index_select(0, again), pb._tokens, k, 'min', None, eps, prune=prune)
+        out_s.index_copy_(0, again, s2)
+        out_i.index_copy_(0, again, i2)
+    elif again.numel():
         tw2, qn2 = tw.index_select(0, again).contiguous(), qn.index_select(0, again).contiguous()
         thr0 = pruning_floor(tw2, qn2, pb, k, eps)
         s2, i2 = _local_topk(tw2, qn2, pb.bank, pb.norms, k, eps, pb.idx_offset, thr0)
@@ -164,7 +203,13 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     A 2-D fp16 / bf16 tensor is a half-precision resident bank: it is served as a token bank with one token per row
     (``cosine_topk_tokens`` on ``bank.unsqueeze(1)``, ``stats['path'] == 'tokens'``) under that search's limits -- k <= 512,
     more than 16 queries in groups of 16 -- with the results of the fp32 search on the widened bank, bit for bit.  The
-    many-query prefilter over a 16-bit flat bank is out of scope.  fp32 banks take exactly the paths described above.
+    many-query prefilter over a 16-bit bank is reached through ``PreparedBank(bank_fp16)``: where the two-stage path applies
+    (more than 16 queries, k <= 192, N >= 2048) it reads the resident fp16 rows directly -- no fp32 copy, no second image: 16 bytes
+    of constants per row and one 256-row tile -- with the results of the fp32 search on the widened bank, bit for bit
+    (``stats['path'] == 'prefiltered'``; uncertified queries are re-run by the token search, ``stats['redone']``); everywhere
+    else, and under SKYEMB_TOPK_PREFILTER=0, it is served as the bare tensor is (``stats['path'] == 'tokens'``), within that
+    search's limits in both cases.  bf16 has no such route (``PreparedBank`` refuses it).  fp32 banks take exactly the paths
+    described above.
 
     ``select`` (None: nothing above changes; a bool tensor [N] or a ``Selection``): only the rows marked True are eligible, with
     the result of the search over the compacted bank and indices mapped back (``cosine_topk_tokens``'s ``select``).  A flat
@@ -200,9 +245,14 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
         raise ValueError(f"cosine_topk: k = {k} exceeds the {N} rows of the bank")
     if Q == 0:                                      # nothing to search for (an empty target list): empty result, no launch
         return (torch.empty(0, k, device=q.device), torch.empty(0, k, device=q.device, dtype=torch.int64))
+    two_stage = _prefilter_enabled() and ops.topk_prefilter_applicable(Q, N, D, k)
+    if pb.dtype != torch.float32:                   # a resident fp16 bank: the two-stage path on its rows, or the token search
+        if not two_stage:
+            return cosine_topk_tokens(q, pb._tokens, k, 'min', None, eps, process_group, world_size, prune, stats)
+        _check_token_shape("cosine_topk", Q, 1, D, k)      # the limits of the route its uncertified queries take
     tw, qn = prepare_queries(q, pb.weights)
-    if _prefilter_enabled() and ops.topk_prefilter_applicable(Q, N, D, k):
-        out_s, out_i, n_redo = _local_topk_prefiltered(tw, qn, pb, k, eps)
+    if two_stage:
+        out_s, out_i, n_redo = _local_topk_prefiltered(tw, qn, pb, k, eps, q, prune)
         if stats is not None:
             stats.update(path="prefiltered", redone=n_redo)
     else:
@@ -220,6 +270,8 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
 def cosine_scores(queries: torch.Tensor, bank, weights: torch.Tensor | None = None, eps: float = 1e-6):
     """Plain [Q,N] score matrix (reference-shaped path with several patches per sample)."""
     pb = bank if isinstance(bank, PreparedBank) else PreparedBank(bank, weights)
+    if pb.dtype != torch.float32:
+        raise ValueError("cosine_scores: an fp16 bank is scored by cosine_token_scores (one token per row: bank.unsqueeze(1))")
     q = queries.to(pb.bank.device, torch.float32).contiguous()
     tw, qn = prepare_queries(q, pb.weights)
     out = torch.empty(q.shape[0], pb.bank.shape[0], device=q.device)
