@@ -424,6 +424,22 @@ int skyemb_augment(const float *imgs, float *out, const float *params, const int
                    int S, int A, void *stream);
 
 /* ------------------------------------------------------ similarity search -
+ * Addressing limits of the search calls below ("Addressing limits", has the table per kernel).  Every element and
+ * byte offset into a bank (row * D, rows of 2 or 4 bytes) and every slot of a [Q, N] score matrix is formed in 64 bits: N * D
+ * and Q * N are bounded by memory, not by these calls.  What is 32 bits wide:
+ *   rows of a bank or shard as list entries    N < 2^31 per call of skyemb_cosine_topk and of the two prefiltered calls
+ *                                              (refused); N * P < 2^31 token rows per call of the token / distance calls
+ *                                              (refused), hence fewer than 2^31 images; skyemb_pack_select N < 2^31 (refused).
+ *                                              Returned indices are int64: idx_offset + row, any idx_offset.
+ *   stage 1 of the prefiltered calls           ceil(N / 2048) * ceil(Q / 256) * (D / 32) < 2^31 (work items and k-steps per
+ *                                              launch; Q / 128 under SKYEMB_PREFILTER_LO=1) -- at D = 768 about Q * N < 4.6e13;
+ *                                              refused, search the queries in batches.
+ *   launch grids                               skyemb_weighted_norms[_lp]: N / 256 workgroups, N < 2^40; skyemb_bank16_prepare
+ *                                              and skyemb_bank16_rowp_lp: N / 4, covered by N < 2^31; skyemb_standardise[_lp]
+ *                                              and the score calls run grid-stride loops over 64-bit counters.
+ * Tested on banks of 2 800 192 x 768 (fp16: past element 2^31 and byte 2^32; fp32: past byte 2^33), tests/test_large_bank_gpu.py;
+ * banks past 2^32 elements (an fp32 bank of 17 GB) are correct by the same reading, not measured.
+ *
  * utils/similarity.py:98-102: standardise bank rows in place or to `out`:
  * (x - mu) / (sigma + 1e-8). */
 int skyemb_standardise(const float *x, const float *mu, const float *sigma, float *out, int64_t N, int D,

@@ -336,7 +336,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
     const int T = t1 - t0, Tx = xcd < T ? (T - xcd + 7) / 8 : 0;
     const int nqt = (Q + QT - 1) / QT;
     const int full = nqt / GQ, last = nqt % GQ;
-    const int items = Tx * nqt;                               // < 2^31: a shard has < 2^31 rows
+    const int items = Tx * nqt;                               // items * KT < 2^31: checked on the host (topk_prefiltered)
     const int KT = D / BK;
     // this workgroup's items: local, local + nlocal, ...
     const int my_items = items > local ? (items - local + nlocal - 1) / nlocal : 0;
@@ -1114,16 +1114,20 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
     const bool resident = bank == nullptr;
     SKY_CHECK_ARG(skyemb_topk_prefilter_applicable(Q, N, D, k), "%s: outside the prefiltered subset "
                   "(Q >= 17, D %% 32 == 0, k <= %d, N >= %d)", who, RESCORE_MAX - 64, 8 * BT);
-    const int cap = skyemb_topk_prefilter_cap(k);
-    SKY_CHECK_ARG(ws_bytes >= skyemb_topk_prefilter_ws_bytes(Q, D, k), "%s: workspace too small", who);
-    hipStream_t st = (hipStream_t)stream;
-    Workspace w;
-    carve((char *)ws, Q, D, cap, &w);
     // one fp16 pass (hi only) by default: half the matrix work, 3/4 of the LDS-DMA bytes, intervals ~1.6x wider -- on
     // embedding-like data a few dozen more candidates per query.  SKYEMB_PREFILTER_LO=1 keeps the hi + lo passes.
     // (read per call on purpose: a getenv is a sub-microsecond scan next to a multi-millisecond search, and the tests switch it)
     const char *lo_env = getenv("SKYEMB_PREFILTER_LO");
     const bool use_lo = lo_env && lo_env[0] == '1';
+    // stage 1 counts an XCD's work items (its bank tiles x the query tiles) and a workgroup's k-steps in 32-bit integers
+    SKY_CHECK_ARG(ceil_div64(ceil_div64(N, BT), 8) * ceil_div64(Q, qtile(use_lo)) * (D / BK) < (1ll << 31),
+                  "%s: Q x N too large: ceil(N / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31, the range of stage 1's work-item "
+                  "and k-step counters (Q=%d N=%lld D=%d); search the queries in batches", who, qtile(use_lo), Q, (long long)N, D);
+    const int cap = skyemb_topk_prefilter_cap(k);
+    SKY_CHECK_ARG(ws_bytes >= skyemb_topk_prefilter_ws_bytes(Q, D, k), "%s: workspace too small", who);
+    hipStream_t st = (hipStream_t)stream;
+    Workspace w;
+    carve((char *)ws, Q, D, cap, &w);
     const float eps_a = (float)(eps_a_of(D, use_lo, resident) * (1.0 + 1e-6));
     hipLaunchKernelGGL(query16_kernel, dim3((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4)), dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql,
                        w.qbase, eps_a);

@@ -64,7 +64,8 @@ def test_full_size_bank_1m_x_768_against_oracle():
     (bank-streaming kernel) and a 32-query sample of the Q = 10,000 launch (tiled many-query kernel, whatever stages it
     runs) must equal oracle/topk_oracle.c bit for bit: scores and indices.  ALL 10,000 answers of the two-stage (prefiltered)
     path are then compared with the exact single-stage kernel's on the same bank (0.2 s on the device; itself oracle-checked
-    through the sample and the Q = 16 launch)."""
+    through the sample and the Q = 16 launch).
+    This bank is 7.68e8 elements and 3.07e9 bytes: it crosses neither element 2^31 nor byte 2^32; tests/test_large_bank_gpu.py does."""
     import os
     from sky_embeddings_amd import search
     N, D, k, Q = 1_000_000, 768, 100, 10_000

@@ -278,3 +278,24 @@ def test_refused_shapes_raise_before_any_launch():
     assert s.shape == (0, 5) and i.shape == (0, 5) and i.dtype == torch.int64
     s, i = search.cosine_topk_tokens(q64, bank, 50)                                            # k == N: every image
     assert torch.isfinite(s).all() and sorted(i[0].tolist()) == list(range(50))
+
+
+def test_prefiltered_search_refuses_a_q_times_n_beyond_its_32_bit_counters_before_any_launch():
+    """Stage 1 of the two-stage search counts work items and k-steps in 32 bits: ceil(N / 2048) * ceil(Q / 256) * (D / 32) must stay
+    below 2^31 (include/skyemb.h, "Addressing limits").  Past that the call returns 1 with the limit in its text and launches
+    nothing -- every pointer here is one small buffer and the workspace is declared empty, so a launch could not go unnoticed; a
+    shape inside the limit gets past this check and is stopped by the next one, the workspace size."""
+    from sky_embeddings_amd import _lib
+    L = _lib.lib()
+    buf = torch.zeros(1024, device="cuda")
+    p, N, D, k = buf.data_ptr(), 2 ** 31 - 256, 768, 100
+    args = lambda Q: (p, p, Q, p, p, p, p, N, D, k, 1e-6, 0, None, p, 0, p, p, p, None)
+    for call in (L.skyemb_cosine_topk_prefiltered,
+                 lambda *a: L.skyemb_cosine_topk_prefiltered_lp(*a[:3], a[5], a[4], None, *a[6:])):   # (tw, qn, Q, bank16, xn, tail, rowp, ...)
+        assert call(*args(600_000)) == 1
+        text = L.skyemb_last_error().decode()
+        assert "Q x N too large" in text and "below 2^31" in text and "Q=600000" in text, text
+        assert call(*args(33)) == 1
+        assert "workspace too small" in L.skyemb_last_error().decode()
+    torch.cuda.synchronize()
+    assert float(buf.abs().sum()) == 0.0
