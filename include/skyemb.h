@@ -521,6 +521,32 @@ int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *qn, int Q, c
                                       const float *rowp, int64_t N, int D, int k, float eps, int64_t idx_offset, const float *thr0,
                                       void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream);
 double skyemb_topk_prefilter_eps_a(int D, int lo, int resident);
+/* The two searches above under a SELECTION of the bank's rows (words: skyemb_pack_select over the N rows; one selection for all
+ * queries).  The result is that of the same search over the compacted bank of the selected rows -- scores bit for bit, order
+ * (score desc, row asc) -- with every index mapped back to this bank; a deselected row contributes nothing, whatever it holds.
+ * Fewer than k selected rows: the list ends in (-inf, -1) entries and the query is NOT flagged for that; a selected row that
+ * scores -inf (a NaN in it) is then not returned, as in the token calls.
+ *   skyemb_prefilter_select_prepare   once per selection, bank and version of rowp: rowp_sel [skyemb_bank16_rowp_rows(N), 4] = rowp
+ *                           with the padding sentinel {0, NaN, 0, 0} in every deselected row (it fails the candidate test for every
+ *                           query, also where rowp held the "keep for every query" constant of an unboundable row); tiles
+ *                           (int32 [ceil(N / 256)]) = the LIVE tiles, ascending: the 256-row tiles with a selected row;
+ *                           info (int32 [2], device) = {their number, 1 if the bank's last tile is one of them}.  Two short launches.
+ *   skyemb_cosine_topk_prefiltered_sel / _lp_sel   the pipelines of skyemb_cosine_topk_prefiltered / _lp with rowp_sel, tiles and
+ *                           the two values of info (read back by the caller: n_live >= 1, and at least one live WHOLE tile over a
+ *                           resident bank) -- stage 1 walks the live tiles only, its phase schedule runs over their number, and the
+ *                           tail tile of a resident bank is launched only when it is live.  No thr0.  Shape limits, workspace and
+ *                           redo as for the unselected calls (on the whole bank's N); redo[q] != 0: the caller runs the query
+ *                           through skyemb_cosine_token_topk_sel with one token per row, under the same words. */
+int skyemb_prefilter_select_prepare(const uint32_t *words, int64_t N, const float *rowp, float *rowp_sel, int *tiles, int *info,
+                                    void *stream);
+int skyemb_cosine_topk_prefiltered_sel(const float *tw, const float *qn, int Q, const float *bank, const float *xn, const void *bank16,
+                                       const float *rowp_sel, const int *tiles, int n_live, int last_live, int64_t N, int D, int k,
+                                       float eps, int64_t idx_offset, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                       int *redo, void *stream);
+int skyemb_cosine_topk_prefiltered_lp_sel(const float *tw, const float *qn, int Q, const void *bank16, const float *xn,
+                                          const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
+                                          int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
+                                          float *out_s, int64_t *out_i, int *redo, void *stream);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

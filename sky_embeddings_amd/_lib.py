@@ -161,6 +161,12 @@ PROTOTYPES = {
     "skyemb_cosine_topk_prefiltered_lp": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_i64, c_vp,
                                                   c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_topk_prefilter_eps_a": (c_f64, [c_i32, c_i32, c_i32]),
+    # the two-stage search under a selection of the bank's rows: additive again
+    "skyemb_prefilter_select_prepare": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32,
+                                                   c_f32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_prefiltered_lp_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32,
+                                                      c_f32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

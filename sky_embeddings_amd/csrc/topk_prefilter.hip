@@ -237,6 +237,50 @@ __global__ __launch_bounds__(256) void query16_kernel(const float *__restrict__ 
     }
 }
 
+// ---- a selection of the bank's rows (skyemb_prefilter_select_prepare) ----------------------------------------------------------
+// words: bit i & 31 of word i >> 5 is row i, padding bits zero (skyemb_pack_select).  The masked copy of the row constants: a
+// deselected row -- whatever it held, the {0, inf, 1, 0} "keep for every query" of an unboundable row included -- and every row
+// past N gets the padding sentinel, whose NaN fails the candidate test for every query.
+__global__ __launch_bounds__(256) void select_rowp_kernel(const unsigned int *__restrict__ words, const float4 *__restrict__ rowp,
+                                                           int64_t N, int64_t rows_padded, float4 *__restrict__ rowp_sel) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows_padded) return;
+    const bool on = i < N && ((words[i >> 5] >> (i & 31)) & 1u) != 0u;
+    rowp_sel[i] = on ? rowp[i] : make_float4(0.f, NAN, 0.f, 0.f);
+}
+// the live tiles -- those of the ceil(N / BT) bank tiles with a selected row: a popcount over the BT / 32 words of each -- in
+// ascending order; info = {their number, 1 if the last bank tile is one of them}.  One workgroup, 1024 tiles per round.
+__global__ __launch_bounds__(1024) void select_tiles_kernel(const unsigned int *__restrict__ words, int64_t nwords, int tiles_all,
+                                                             int *__restrict__ tiles, int *__restrict__ info) {
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int r0 = 0; r0 < tiles_all; r0 += 1024) {
+        const int t = r0 + tid;
+        int pc = 0;
+        if (t < tiles_all)
+            for (int j = 0; j < BT / 32; ++j) {
+                const int64_t wi = (int64_t)t * (BT / 32) + j;
+                if (wi < nwords) pc += __popc(words[wi]);
+            }
+        const bool live = pc > 0;
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) wsum[wave] = __builtin_popcountll(m);
+        __syncthreads();
+        int off = base, tot = 0;
+        for (int w = 0; w < 16; ++w) {
+            off += w < wave ? wsum[w] : 0;
+            tot += wsum[w];
+        }
+        off += __builtin_popcountll(m & ((1ull << lane) - 1));
+        if (live) tiles[off] = t;                              // off < the number of live tiles <= tiles_all
+        if (t == tiles_all - 1) info[1] = live ? 1 : 0;
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) info[0] = base;
+}
+
 // ---- stage 1 ------------------------------------------------------------------------------------------------------
 // Operand tile (rows x 32 k, fp16): 64-byte rows; 16-byte chunk c of row r is stored at chunk c ^ swz(r), the XOR applied
 // to the per-lane SOURCE address (the LDS-DMA destination is wave base + lane * 16).  One instruction = 16 rows.
@@ -295,9 +339,14 @@ __device__ __forceinline__ void wait_vmcnt() {
 // MODE 0: first slice, every pair is stored (slot = row)   1: candidates appended to the per-query lists directly (returning
 // global atomics: the short early phases, whose loose thresholds pass several per cent of the pairs)   2: candidates staged
 // in LDS and flushed to the workgroup's own region (the long late phases)
-template <int MODE, bool LO>
+// SEL (a search under a selection, select_tiles_kernel): [t0, t1) are POSITIONS in the ascending list `tiles` of the live bank
+// tiles -- position p stands for bank tile tiles[p], whose rows, row constants (the masked copy: a deselected row fails every test)
+// and row numbers the item uses; only the take-all slots are counted by position.  Without SEL `tiles` is not read (NULL) and a
+// position is its own tile: the instruction stream of the unselected search.
+template <int MODE, bool LO, bool SEL>
 __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict__ qh, const half_t *__restrict__ ql,
                                                        const half_t *__restrict__ bank16, const float4 *__restrict__ rowp,
+                                                       const int *__restrict__ tiles,
                                                        const float4 *__restrict__ qpar, int Q, int64_t N, int D, int t0, int t1,
                                                        int cap, int *__restrict__ cnt, int *__restrict__ cand_i, float *__restrict__ cand_d,
                                                        uint4 *__restrict__ wg_list, int *__restrict__ wg_count, int capw,
@@ -345,7 +394,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
         return;
     }
 
-    auto item_of = [&](int n, int &qt, int &t) {            // n-th item of this workgroup -> (query tile, bank tile)
+    auto item_of = [&](int n, int &qt, int &t, int &p) {    // n-th item of this workgroup -> (query tile, bank tile, its position)
         const int idx = local + n * nlocal;
         const int per_full = GQ * Tx;
         int g, within, tt;
@@ -361,7 +410,13 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
             within = rem - tt * last;
         }
         qt = __builtin_amdgcn_readfirstlane(g * GQ + within);
-        t = __builtin_amdgcn_readfirstlane(t0 + tt * 8 + xcd);
+        p = __builtin_amdgcn_readfirstlane(t0 + tt * 8 + xcd);
+        if (SEL) {
+            // one scalar load per item, written out: a vector load here would be waited for with vmcnt(0), which drains the ring
+            asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "s"(tiles + p) : "memory");
+        } else {
+            t = p;
+        }
     };
     // ---- issue cursor: the stage being requested runs AHEAD k-steps in front of the one being read, across item boundaries.
     // Each wave owns four 1 KiB pieces of a stage: rows [16 wave, +16) of the hi and of the lo query image, rows
@@ -371,8 +426,8 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
     static_assert(BT / 16 / NW == 2 && Q_BYTES / 1024 / NW == 2, "piece ownership below: two query and two bank pieces per wave");
     const unsigned int lane_off = (unsigned int)((lane >> 2) * D * 2 + (((lane & 3) ^ swz(lane >> 2)) << 4));
     int n_iss = 0, kt_iss = 0;
-    int qt_cur, t_cur, qt_nxt = 0, t_nxt = 0;                // the item being multiplied / the one the issue cursor has entered
-    item_of(0, qt_cur, t_cur);
+    int qt_cur, t_cur, p_cur, qt_nxt = 0, t_nxt = 0, p_nxt = 0;   // the item being multiplied / the one the issue cursor has entered
+    item_of(0, qt_cur, t_cur, p_cur);
     const char *ph, *pl, *pb;
     auto rebase = [&](int qt, int t) {
         const int64_t qoff = ((int64_t)qt * QT + wave * (QT / NW)) * D * 2;   // LO: 16 rows of hi and of lo; else 32 rows of hi
@@ -396,7 +451,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
             if (++kt_iss == KT) {
                 kt_iss = 0;
                 if (++n_iss < my_items) {
-                    item_of(n_iss, qt_nxt, t_nxt);
+                    item_of(n_iss, qt_nxt, t_nxt, p_nxt);
                     rebase(qt_nxt, t_nxt);
                 }
             }
@@ -460,7 +515,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
 #endif
         }
     };
-    auto item_epilogue = [&](int qt, int t) {
+    auto item_epilogue = [&](int qt, int t, int p) {
         // ---- epilogue of the item: per 16x16 block a lane holds queries 4*(lane>>4)+r (r = 0..3) x bank row (lane & 15).
         // All 16 MI tests of the lane are branch-free (bit masks mr[r]); only waves that found something enter the append path.
         // (the lane coordinates go through an empty asm: everything addressed from them is then computed HERE, once per item,
@@ -546,8 +601,10 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int64_t row = (int64_t)t * BT + wn * 64 + j * 16 + l16;
-                        if (q < Q && row < N) {
-                            const int64_t o = (int64_t)q * cap + (row - (int64_t)t0 * BT);
+                        // SEL: slot = position in the list x BT + row in tile; every slot of the slice is written (the host counts
+                        // first * BT of them), rows past N too -- their sentinel constants mark them for select_kernel
+                        if (q < Q && (SEL || row < N)) {
+                            const int64_t o = (int64_t)q * cap + (SEL ? (int64_t)(p - t0) * BT + (wn * 64 + j * 16 + l16) : row - (int64_t)t0 * BT);
                             cand_i[o] = (int)row;
                             cand_d[o] = passed(i, r, j) ? acc[i][j][r] : -INFINITY;
                         }
@@ -624,7 +681,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
         multiply(issue, ibuf, half);
         if (++kt_c == KT) {
             STAMP(4);
-            item_epilogue(qt_cur, t_cur);
+            item_epilogue(qt_cur, t_cur, p_cur);
             zero_acc();
             STAMP(7);
             kt_c = 0;
@@ -632,6 +689,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
             t_done = t_cur;
             qt_cur = qt_nxt;          // (the issue cursor entered the next item AHEAD steps ago, and enters the one after it only later: KT > AHEAD)
             t_cur = t_nxt;
+            p_cur = p_nxt;
         }
     };
     auto landed = [&](int s) {
@@ -790,6 +848,10 @@ __device__ unsigned int radix_kth_largest(const unsigned int *keys, int n, int k
 // final == 0: tau <- max(tau, k-th largest L); keep the candidates with U >= tau; write the test parameters of the next phase.
 // final == 1: sel_i[q][0..nsel) <- the (up to) RESCORE_MAX candidates with the largest U; bound[q] = largest U NOT selected
 //             (-inf when every candidate is selected).
+// SEL (a search under a selection): rowp is the masked copy, and a take-all slice stores pairs of deselected rows -- they are told by
+// the sentinel's third component, 0 where every row that counts holds a power of two, so a selected row whose constants hold a NaN
+// keeps the treatment it has without a selection.  Without SEL none of this is compiled: the unselected search's kernel.
+template <bool SEL>
 __global__ __launch_bounds__(256) void select_kernel(int Q, int k, int cap, float eps, const float4 *__restrict__ qbase,
                                                      const float4 *__restrict__ rowp, const float *__restrict__ xn, int *__restrict__ cnt,
                                                      int *__restrict__ cand_i, float *__restrict__ cand_d,
@@ -811,6 +873,14 @@ __global__ __launch_bounds__(256) void select_kernel(int Q, int k, int cap, floa
     const float inv_sf = 1.0f / qb.z;                         // 2^f (exact)
     for (int e = tid; e < n; e += 256) {
         const float4 rp = rowp[ci[e]];                        // {xn', ||x'||, 2^-e, 0}
+        if (SEL && rp.z == 0.f) {
+            // the sentinel of a deselected row (or of a padding row of the last tile): only a take-all slice stores such pairs.
+            // Key 0 is below orderable(-inf) = 0x007fffff, the least key a row that counts can have: never kept, never counted
+            // (and xn is not read: it ends at row N)
+            kL[e] = 0u;
+            kU[e] = 0u;
+            continue;
+        }
         const float den = fmaf(qb.w, xn[ci[e]], eps);
         const float sc = inv_sf * (1.0f / rp.z);              // 2^(e+f), exact
         const float err = qb.y * rp.y;
@@ -827,8 +897,8 @@ __global__ __launch_bounds__(256) void select_kernel(int Q, int k, int cap, floa
     float tau = tau_q[q];
     if (!final) {
         if (n >= k) {
-            const float kth = unorderable(radix_kth_largest(kL, n, k, hist, tid, 256));
-            tau = fmaxf(tau, kth);
+            const unsigned int kth = radix_kth_largest(kL, n, k, hist, tid, 256);
+            if (!SEL || kth != 0u) tau = fmaxf(tau, unorderable(kth));   // (key 0: fewer than k rows that count -- no k-th lower bound yet)
         }
         // compaction: survivors keep their relative order (deterministic lists)
         const unsigned int tk = orderable(tau);
@@ -869,7 +939,19 @@ __global__ __launch_bounds__(256) void select_kernel(int Q, int k, int cap, floa
     // has U < L_k is out.  When those needed fit the re-score quota (the rule on embedding-like data: k plus a few dozen), only
     // they are re-scored and the answer is certified by construction (bound = -inf) -- half the exact stage's HBM traffic.
     int *so = sel_i + (int64_t)q * RESCORE_MAX;
-    if (n >= k && n > 0) {
+    // rows that count (a take-all slice that is also the last one leaves the sentinel rows in the list, see above)
+    int live = n;
+    if (SEL) {
+        if (tid == 0) hist[0] = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int e = tid; e < n; e += 256) mine += kU[e] != 0u ? 1 : 0;
+        if (mine) atomicAdd(&hist[0], mine);
+        __syncthreads();
+        live = hist[0];
+        __syncthreads();
+    }
+    if (live >= k && live > 0) {
         const unsigned int lk = radix_kth_largest(kL, n, k, hist, tid, 256);
         if (unorderable(lk) > -INFINITY) {            // (k finite lower bounds exist; U = +inf / NaN-turned-inf rows always qualify)
             if (tid == 0) hist[0] = 0;
@@ -891,12 +973,19 @@ __global__ __launch_bounds__(256) void select_kernel(int Q, int k, int cap, floa
         }
     }
     // ---- otherwise: the RESCORE_MAX largest U
-    if (n <= RESCORE_MAX) {
-        for (int e = tid; e < n; e += 256) so[e] = ci[e];
-        if (tid == 0) { nsel[q] = n; bound[q] = -INFINITY; }
+    if (live <= RESCORE_MAX) {
+        if (!SEL || live == n) {
+            for (int e = tid; e < n; e += 256) so[e] = ci[e];
+        } else {
+            if (tid == 0) hist[0] = 0;
+            __syncthreads();
+            for (int e = tid; e < n; e += 256)
+                if (kU[e] != 0u) so[atomicAdd(&hist[0], 1)] = ci[e];
+        }
+        if (tid == 0) { nsel[q] = live; bound[q] = -INFINITY; }
         return;
     }
-    const unsigned int uk = radix_kth_largest(kU, n, RESCORE_MAX, hist, tid, 256);   // RESCORE_MAX-th largest U
+    const unsigned int uk = radix_kth_largest(kU, n, RESCORE_MAX, hist, tid, 256);   // RESCORE_MAX-th largest U (live > RESCORE_MAX: uk != 0)
     // strictly larger first, then ties of uk in list order until the quota is full; bound = uk if anything with U <= uk is left
     if (tid == 0) { hist[0] = 0; hist[1] = 0; }
     __syncthreads();
@@ -932,7 +1021,8 @@ __device__ __forceinline__ float4 row4(const half_t *x) {
 }
 
 // one workgroup (256 threads) per query; thread c owns candidate c: the contract's fma chain over d = 0..D-1
-template <typename X>
+// FEW (a search under a selection, which may hold fewer than k rows): fewer than k candidates are an answer, not a reason to re-run
+template <typename X, bool FEW>
 __device__ __forceinline__ void rescore_body(const float *__restrict__ tw, const float *__restrict__ qn,
                                              const X *__restrict__ bank, const float *__restrict__ xn, int Q, int D,
                                              int k, float eps, int64_t idx_offset, const int *__restrict__ sel_i,
@@ -973,7 +1063,7 @@ __device__ __forceinline__ void rescore_body(const float *__restrict__ tw, const
             const int r2 = si[e];
             rank += (s2 > sc || (s2 == sc && r2 < row)) ? 1 : 0;
         }
-        if (rank < k) {
+        if (rank < k && !(FEW && n < k && !(sc > -INFINITY))) {
             out_s[(int64_t)q * k + rank] = sc;
             out_i[(int64_t)q * k + rank] = idx_offset + row;
         }
@@ -983,8 +1073,12 @@ __device__ __forceinline__ void rescore_body(const float *__restrict__ tw, const
         }
     }
     if (n < k) {                                              // fewer candidates than k (tiny shard, NaN rows): the exact kernel decides
-        if (tid == 0) redo[q] = 1;
-        for (int e = n + tid; e < k; e += 256) {
+        // FEW: the answer stands when every candidate was re-scored -- the rows that score above -inf in order, then the (-inf, -1)
+        // tail.  A row that scores -inf (a NaN in it) is not returned, as in the token search that serves the other selections: stage 1
+        // does not keep every such row of an fp32 bank, so returning those it happens to keep would depend on the schedule.
+        const int have = FEW ? __syncthreads_count(tid < n && sc > -INFINITY) : n;
+        if (tid == 0) redo[q] = !FEW || overflow[q] || bound[q] > -INFINITY ? 1 : 0;
+        for (int e = have + tid; e < k; e += 256) {
             out_s[(int64_t)q * k + e] = -INFINITY;
             out_i[(int64_t)q * k + e] = -1;
         }
@@ -996,12 +1090,14 @@ __device__ __forceinline__ void rescore_body(const float *__restrict__ tw, const
         int D, int k, float eps, int64_t idx_offset, const int *__restrict__ sel_i, const int *__restrict__ nsel,                  \
         const float *__restrict__ bound, const int *__restrict__ overflow, float *__restrict__ out_s, int64_t *__restrict__ out_i, \
         int *__restrict__ redo
+template <bool FEW>
 __global__ __launch_bounds__(256) void rescore_kernel(RESCORE_PARAMS(float)) {
-    rescore_body(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
+    rescore_body<float, FEW>(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
 }
 // the resident fp16 bank's rows, widened element by element: same chain, same bits as rescore_kernel on the widened bank
+template <bool FEW>
 __global__ __launch_bounds__(256) void rescore_lp_kernel(RESCORE_PARAMS(half_t)) {
-    rescore_body(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
+    rescore_body<half_t, FEW>(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
 }
 #undef RESCORE_PARAMS
 
@@ -1105,13 +1201,17 @@ extern "C" int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_
 
 extern "C" int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k) { return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr); }
 
-// The pipeline of both entry points.  bank: the fp32 rows stage 2 re-scores, bank16 their fp16 image (skyemb_bank16_prepare) --
+// The pipeline of all entry points.  bank: the fp32 rows stage 2 re-scores, bank16 their fp16 image (skyemb_bank16_prepare) --
 // or bank NULL: bank16 is a resident fp16 bank that both stages read, its last N % BT rows through `tail` (skyemb_bank16_rowp_lp).
+// tiles (NULL: no selection): the search runs under a selection prepared by skyemb_prefilter_select_prepare -- rowp is then the
+// masked copy, tiles the n_live live tiles of all ceil(N / BT), last_live says whether the last of those is one of them.  The phase
+// schedule runs over the live tiles; a resident bank's tail tile is launched only when it is live.
 static int topk_prefiltered(const char *who, const float *tw, const float *qn, int Q, const float *bank, const float *xn,
                             const void *bank16, const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
                             int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
-                            int *redo, void *stream) {
+                            int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0) {
     const bool resident = bank == nullptr;
+    const bool sel = tiles != nullptr;
     SKY_CHECK_ARG(skyemb_topk_prefilter_applicable(Q, N, D, k), "%s: outside the prefiltered subset "
                   "(Q >= 17, D %% 32 == 0, k <= %d, N >= %d)", who, RESCORE_MAX - 64, 8 * BT);
     // one fp16 pass (hi only) by default: half the matrix work, 3/4 of the LDS-DMA bytes, intervals ~1.6x wider -- on
@@ -1132,24 +1232,35 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
     hipLaunchKernelGGL(query16_kernel, dim3((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4)), dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql,
                        w.qbase, eps_a);
     // tiles the phases below walk: all of them -- of a resident bank the whole ones, the last N % BT rows follow from `tail`
-    const int T = resident ? (int)(N / BT) : (int)ceil_div64(N, BT);
-    const bool has_tail = resident && N % BT != 0;
+    const int T_tail = (int)(N / BT);                          // the tile a resident bank's tail stands for
+    const bool has_tail = resident && N % BT != 0 && (!sel || last_live);
+    const int T = sel ? n_live - (resident && N % BT != 0 && last_live ? 1 : 0) : resident ? T_tail : (int)ceil_div64(N, BT);
+    if (sel) {
+        SKY_CHECK_ARG(n_live >= 1 && n_live <= ceil_div64(N, BT) && (last_live == 0 || last_live == 1),
+                      "%s: n_live = %d, last_live = %d: expected 1 .. %lld live tiles and a flag (skyemb_prefilter_select_prepare's info)",
+                      who, n_live, last_live, (long long)ceil_div64(N, BT));
+        SKY_CHECK_ARG(T >= 1, "%s: the selection's only live tile is the resident bank's tail tile; the phases need a whole live tile", who);
+    }
     bool tail_done = false;
     // phases: [0, first) is taken whole unless a floor came in; then slices ending at 1/128, 1/32, 1/8, 1/2 and all of the tiles
     int first = (int)(cap / 2 / BT);                           // rows of the take-everything slice <= cap / 2
     if (first < 1) first = 1;
     if (first > T) first = T;
-    const int64_t first_rows = (int64_t)first * BT < N ? (int64_t)first * BT : N;
+    // (under a selection the slots are positions in the live list x BT: all of them are written, see prefilter_kernel)
+    const int64_t first_rows = sel || (int64_t)first * BT < N ? (int64_t)first * BT : N;
     const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
     hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
                        w.qpar, w.tau, w.cnt, w.overflow, (int)first_rows);
     const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
     constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
     int rc = 0;
-#define PF_ATTR(M, L) if (rc == 0) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L>, smem_max, who)
+#define PF_ATTR(M, L)                                                                                             \
+    if (rc == 0) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false>, smem_max, who);              \
+    if (rc == 0 && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true>, smem_max, who)
     PF_ATTR(0, false); PF_ATTR(1, false); PF_ATTR(2, false); PF_ATTR(0, true); PF_ATTR(1, true); PF_ATTR(2, true);
 #undef PF_ATTR
-    if (rc == 0) rc = sky_set_lds_limit((const void *)select_kernel, 2 * 8192 * 4 + 272 * 4, who);
+    if (rc == 0) rc = sky_set_lds_limit((const void *)select_kernel<false>, 2 * 8192 * 4 + 272 * 4, who);
+    if (rc == 0 && sel) rc = sky_set_lds_limit((const void *)select_kernel<true>, 2 * 8192 * 4 + 272 * 4, who);
     if (rc != 0) return rc;
     // (the slice right after the first one meets a threshold that still passes ~5 % of the pairs -- k of the ~2000 rows seen --
     // so it is kept short, to ~96 k rows or 1/128 of the tiles, and appends directly; from then on the threshold passes ~1 %
@@ -1174,20 +1285,26 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
 #else
 #define PF_DBG
 #endif
-#define PF_ARGS(B, T0, T1) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, w.qpar, Q, N, D, T0, T1, cap, w.cnt, w.cand_i, w.cand_d, \
-                           w.wg_list, w.wg_count, w.capw, w.overflow PF_DBG
-#define PF_LAUNCH(M, B, T0, T1)                                                                                            \
-    do {                                                                                                                   \
-        if (use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1)); \
-        else hipLaunchKernelGGL((prefilter_kernel<M, false>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1));     \
+#define PF_ARGS(B, T0, T1, TL) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, TL, w.qpar, Q, N, D, T0, T1, cap, w.cnt, w.cand_i, \
+                               w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow PF_DBG
+#define PF_LAUNCH_AS(M, L, S, B, T0, T1, TL) \
+    hipLaunchKernelGGL((prefilter_kernel<M, L, S>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL))
+// TL: the live-tile list the positions [T0, T1) index, or NULL: they are the bank tiles themselves
+#define PF_LAUNCH(M, B, T0, T1, TL)                                                              \
+    do {                                                                                         \
+        const int *tl_ = (TL);                                                                   \
+        if (tl_ && use_lo) PF_LAUNCH_AS(M, true, true, B, T0, T1, tl_);                          \
+        else if (tl_) PF_LAUNCH_AS(M, false, true, B, T0, T1, tl_);                              \
+        else if (use_lo) PF_LAUNCH_AS(M, true, false, B, T0, T1, (const int *)nullptr);          \
+        else PF_LAUNCH_AS(M, false, false, B, T0, T1, (const int *)nullptr);                     \
     } while (0)
         if (p == 0) {
-            PF_LAUNCH(0, bank16, t0, t1);
+            PF_LAUNCH(0, bank16, t0, t1, tiles);
         } else if (!thresholded_once) {
-            PF_LAUNCH(1, bank16, t0, t1);
+            PF_LAUNCH(1, bank16, t0, t1, tiles);
             thresholded_once = true;
         } else {
-            PF_LAUNCH(2, bank16, t0, t1);
+            PF_LAUNCH(2, bank16, t0, t1, tiles);
             hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count,
                                w.capw, cap, w.cnt, w.cand_i, w.cand_d);
         }
@@ -1197,10 +1314,12 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
             // addresses tile t at base + t * BT rows, so the base handed over is the one that puts tile T on `tail` (an address
             // only: tile T is the single tile of this launch).  Direct appends under the last phase's threshold -- at most BT
             // candidates per query behind whatever the lists hold (after a take-all phase: behind its first_rows slots).
-            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T * BT * D * sizeof(half_t));
-            PF_LAUNCH(1, tail_base, T, T + 1);
+            // (under a selection too the tail is bank tile N / BT itself, no list: its masked constants are all it needs)
+            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T_tail * BT * D * sizeof(half_t));
+            PF_LAUNCH(1, tail_base, T_tail, T_tail + 1, (const int *)nullptr);
         }
 #undef PF_LAUNCH
+#undef PF_LAUNCH_AS
 #undef PF_ARGS
 #ifdef PF_CLOCK
         {
@@ -1235,16 +1354,20 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
         }
 #endif
         const int final = t1 == T;
-        hipLaunchKernelGGL(select_kernel, dim3((unsigned)Q), dim3(256), smem_sel, st, Q, k, cap, eps, w.qbase, (const float4 *)rowp, xn,
-                           w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, final, w.sel_i, w.nsel, w.bound);
+#define SELECT_ARGS Q, k, cap, eps, w.qbase, (const float4 *)rowp, xn, w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, final, w.sel_i, \
+                    w.nsel, w.bound
+        if (sel) hipLaunchKernelGGL(select_kernel<true>, dim3((unsigned)Q), dim3(256), smem_sel, st, SELECT_ARGS);
+        else hipLaunchKernelGGL(select_kernel<false>, dim3((unsigned)Q), dim3(256), smem_sel, st, SELECT_ARGS);
+#undef SELECT_ARGS
         t0 = t1;
     }
-    if (resident)
-        hipLaunchKernelGGL(rescore_lp_kernel, dim3((unsigned)Q), dim3(256), (size_t)D * 4 + RESCORE_MAX * 8, st, tw, qn,
-                           (const half_t *)bank16, xn, Q, D, k, eps, idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo);
-    else
-        hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)Q), dim3(256), (size_t)D * 4 + RESCORE_MAX * 8, st, tw, qn, bank, xn, Q, D, k, eps,
-                           idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo);
+    const size_t smem_re = (size_t)D * 4 + RESCORE_MAX * 8;
+#define RESCORE_ARGS(B) tw, qn, B, xn, Q, D, k, eps, idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo
+    if (resident && sel) hipLaunchKernelGGL(rescore_lp_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
+    else if (resident) hipLaunchKernelGGL(rescore_lp_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
+    else if (sel) hipLaunchKernelGGL(rescore_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS(bank));
+    else hipLaunchKernelGGL(rescore_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS(bank));
+#undef RESCORE_ARGS
     SKY_LAUNCH_CHECK(who);
     return 0;
 }
@@ -1268,4 +1391,41 @@ extern "C" int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *q
     SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_lp: the bank and the tail tile must be 16-byte aligned");
     return topk_prefiltered("skyemb_cosine_topk_prefiltered_lp", tw, qn, Q, nullptr, xn, bank16, tail, rowp, N, D, k, eps, idx_offset, thr0,
                             ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// ---- the same searches under a selection of the bank's rows ---------------------------------------------------------------------
+extern "C" int skyemb_prefilter_select_prepare(const uint32_t *words, int64_t N, const float *rowp, float *rowp_sel, int *tiles,
+                                               int *info, void *stream) {
+    SKY_CHECK_ARG(words && rowp && rowp_sel && tiles && info, "skyemb_prefilter_select_prepare: null argument");
+    SKY_CHECK_ARG(N > 0 && N < (1ll << 31), "skyemb_prefilter_select_prepare: N = %lld, expected 1 .. 2^31 - 1 rows", (long long)N);
+    const int64_t padded = skyemb_bank16_rowp_rows(N);
+    hipLaunchKernelGGL(select_rowp_kernel, dim3((unsigned)(padded / 256)), dim3(256), 0, (hipStream_t)stream, words, (const float4 *)rowp,
+                       N, padded, (float4 *)rowp_sel);
+    hipLaunchKernelGGL(select_tiles_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, words, ceil_div64(N, 32), (int)(padded / BT), tiles,
+                       info);
+    SKY_LAUNCH_CHECK("skyemb_prefilter_select_prepare");
+    return 0;
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_sel(const float *tw, const float *qn, int Q, const float *bank, const float *xn,
+                                                  const void *bank16, const float *rowp_sel, const int *tiles, int n_live, int last_live,
+                                                  int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
+                                                  float *out_s, int64_t *out_i, int *redo, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank && xn && bank16 && rowp_sel && tiles && ws && out_s && out_i && redo,
+                  "skyemb_cosine_topk_prefiltered_sel: null argument");
+    return topk_prefiltered("skyemb_cosine_topk_prefiltered_sel", tw, qn, Q, bank, xn, bank16, nullptr, rowp_sel, N, D, k, eps, idx_offset,
+                            nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live);
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_lp_sel(const float *tw, const float *qn, int Q, const void *bank16, const float *xn,
+                                                     const void *tail, const float *rowp_sel, const int *tiles, int n_live,
+                                                     int last_live, int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws,
+                                                     int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp_sel && tiles && ws && out_s && out_i && redo,
+                  "skyemb_cosine_topk_prefiltered_lp_sel: null argument");
+    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_lp_sel: N = %lld is no whole number of %d-row tiles: the tail tile "
+                  "of skyemb_bank16_rowp_lp is needed", (long long)N, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_lp_sel: the bank and the tail tile must be 16-byte aligned");
+    return topk_prefiltered("skyemb_cosine_topk_prefiltered_lp_sel", tw, qn, Q, nullptr, xn, bank16, tail, rowp_sel, N, D, k, eps, idx_offset,
+                            nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live);
 }

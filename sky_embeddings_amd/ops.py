@@ -482,6 +482,41 @@ def cosine_topk_prefiltered_lp(tw, qn, bank16, xn, tail, rowp, k, eps, idx_offse
     return ws
 
 
+def prefilter_select_prepare(words, N, rowp):
+    """What the two-stage search needs of a selection (packed ``words`` of ``pack_select``) over a bank of N rows with row constants
+    ``rowp`` (``bank16_prepare`` / ``bank16_rowp_lp``): (rowp_sel, tiles, n_live, last_live) -- the masked copy of the constants (a
+    deselected row holds the padding sentinel), the ascending list of the live 256-row tiles (i32, its first n_live entries), their
+    number and whether the bank's last tile is one of them.  Two short launches and one read-back of eight bytes."""
+    rows = rowp.shape[0]
+    rowp_sel = torch.empty_like(rowp)
+    tiles = torch.empty(rows // 256, device=rowp.device, dtype=torch.int32)
+    info = torch.empty(2, device=rowp.device, dtype=torch.int32)
+    check(lib().skyemb_prefilter_select_prepare(_p(words), N, _p(rowp), _p(rowp_sel), _p(tiles), _p(info), _stream()),
+          "skyemb_prefilter_select_prepare")
+    n_live, last_live = info.tolist()
+    return rowp_sel, tiles, n_live, last_live
+
+
+def cosine_topk_prefiltered_sel(tw, qn, bank, xn, bank16, tail, prepared, k, eps, idx_offset, out_s, out_i, redo, ws=None):
+    """``cosine_topk_prefiltered`` (``bank`` fp32 and its image ``bank16``) or ``cosine_topk_prefiltered_lp`` (``bank`` None: ``bank16``
+    is the resident fp16 bank, ``tail`` its tail tile) under a selection: ``prepared`` is ``prefilter_select_prepare``'s result."""
+    Q, D = tw.shape
+    rowp_sel, tiles, n_live, last_live = prepared
+    N = xn.shape[0]
+    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    if bank is not None:
+        check(lib().skyemb_cosine_topk_prefiltered_sel(_p(tw), _p(qn), Q, _p(bank), _p(xn), _p(bank16), _p(rowp_sel), _p(tiles), n_live,
+                                                       last_live, N, D, k, eps, idx_offset, _p(ws), ws.numel(), _p(out_s), _p(out_i),
+                                                       _p(redo), _stream()), "skyemb_cosine_topk_prefiltered_sel")
+    else:
+        check(lib().skyemb_cosine_topk_prefiltered_lp_sel(_p(tw), _p(qn), Q, _p(bank16), _p(xn), _p(tail), _p(rowp_sel), _p(tiles), n_live,
+                                                          last_live, N, D, k, eps, idx_offset, _p(ws), ws.numel(), _p(out_s), _p(out_i),
+                                                          _p(redo), _stream()), "skyemb_cosine_topk_prefiltered_lp_sel")
+    return ws
+
+
 def topk_merge(in_s, in_i, Q, nlists, k, out_s, out_i, ws=None):
     """ws: optional int32 [Q] scratch enabling the gather + block-sort path for many short lists."""
     check(lib().skyemb_topk_merge(_p(in_s), _p(in_i), Q, nlists, k, _p(out_s), _p(out_i), _p(ws), _stream()),

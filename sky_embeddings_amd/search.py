@@ -51,6 +51,8 @@ class PreparedBank:
         self._sample = None
         self._half = None
         self.tail_tile = None
+        self._version = 0                                  # counts set_weights calls: what depends on norms or row constants checks it
+        self._row_tokens = None
         if self.dtype == torch.float32:
             self._tokens = None
             self.norms = torch.empty(bank.shape[0], device=bank.device)
@@ -68,8 +70,20 @@ class PreparedBank:
         else:
             self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
             ops.weighted_norms(self.bank, self.weights, self.norms)
+        self._version += 1
+        self._row_tokens = None
         self._sample = None
         self._half = None
+
+    def row_tokens(self):
+        """The same rows as a TokenBank with one token per row: the route of a search under a selection that the two-stage path
+        does not take, and of its uncertified queries.  An fp16 bank has it from the start (it shares the norms); an fp32 bank
+        builds it on first use -- one norm pass, 4 bytes per row, no copy of the rows -- and keeps it until the weights change."""
+        if self._tokens is not None:
+            return self._tokens
+        if self._row_tokens is None:
+            self._row_tokens = TokenBank(self.bank.unsqueeze(1), self.weights, self.idx_offset)
+        return self._row_tokens
 
     def half_image(self):
         """(bank16, rowp): the fp16 rows + per-row constants the prefiltered many-query search runs on; built on first use and
@@ -193,6 +207,64 @@ def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps, q=None, prune=Tr
     return out_s, out_i, int(again.numel())
 
 
+SELECT_MIN_LIVE_TILES = 8      # fewer live whole 256-row tiles than this: a PreparedBank search under a selection takes the token route
+
+
+def _cosine_topk_selected(queries, pb: "PreparedBank", k, select, eps, process_group, world_size, prune, stats):
+    """``cosine_topk`` over a PreparedBank under a selection (see there): the two-stage path over the live tiles, its uncertified
+    queries -- and a selection of fewer than SELECT_MIN_LIVE_TILES live tiles -- through the token search with one token per row."""
+    # where the two-stage route does not apply the call is refused as it ever was, before anything else is looked at (16 queries or
+    # fewer never take it, whatever the bank)
+    if queries.shape[0] <= 16 or not (_prefilter_enabled() and ops.topk_prefilter_applicable(queries.shape[0], pb.bank.shape[0],
+                                                                                           queries.shape[1], k)):
+        raise ValueError("cosine_topk: select is served by the token search (cosine_topk_tokens with one token per row); pass "
+                         "the flat [N, D] tensor, not a PreparedBank -- the prefiltered many-query route takes no selection")
+    q = queries.to(pb.bank.device, torch.float32).contiguous()
+    Q, D = q.shape
+    N = pb.bank.shape[0]
+    assert D == pb.bank.shape[1]
+    if world_size == 1 and k > N:
+        raise ValueError(f"cosine_topk: k = {k} exceeds the {N} rows of the bank")
+    _check_token_shape("cosine_topk", Q, 1, D, k)          # the limits of the route the uncertified queries and small selections take
+    sel = _selection_arg(select, N, "cosine_topk", pb.bank.device)
+    dev = q.device
+    tiles_all = (N + 255) // 256
+    if sel.count == 0:                                      # nothing is eligible: no stage-1 launch
+        out_s = torch.full((Q, k), float("-inf"), device=dev)
+        out_i = torch.full((Q, k), -1, device=dev, dtype=torch.int64)
+        if stats is not None:
+            stats.update(path="prefiltered", redone=0, selected=0, tiles=(0, tiles_all))
+    else:
+        prepared = sel.prefilter(pb)
+        n_live, last_live = prepared[2], prepared[3]
+        tail_live = 1 if (pb.dtype != torch.float32 and N % 256 and last_live) else 0
+        if n_live - tail_live < SELECT_MIN_LIVE_TILES:
+            st = {}
+            out = cosine_topk_tokens(q, pb.row_tokens(), k, 'min', None, eps, process_group, world_size, prune, st, select=sel)
+            if stats is not None:
+                stats.update(st, selected=sel.count, tiles=(n_live, tiles_all))
+            return out
+        tw, qn = prepare_queries(q, pb.weights)
+        bank16 = pb.half_image()[0]
+        out_s = torch.empty(Q, k, device=dev)
+        out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
+        redo = torch.empty(Q, device=dev, dtype=torch.int32)
+        ops.cosine_topk_prefiltered_sel(tw, qn, pb.bank if pb.dtype == torch.float32 else None, pb.norms, bank16, pb.tail_tile, prepared,
+                                        k, eps, pb.idx_offset, out_s, out_i, redo)
+        again = torch.nonzero(redo).squeeze(1)             # host sync: a handful of bytes per search
+        if again.numel():                                   # the exact fp32 kernel takes no selection: the token search, both dtypes
+            s2, i2 = cosine_topk_tokens(q.index_select(0, again), pb.row_tokens(), k, 'min', None, eps, prune=prune, select=sel)
+            out_s.index_copy_(0, again, s2)
+            out_i.index_copy_(0, again, i2)
+        if stats is not None:
+            stats.update(path="prefiltered", redone=int(again.numel()), selected=sel.count, tiles=(n_live, tiles_all))
+    if world_size > 1:
+        from .distributed import gather_topk
+        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
+        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    return out_s, out_i
+
+
 def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | None = None, eps: float = 1e-6,
                 process_group=None, world_size: int = 1, prune: bool = True, stats: dict | None = None, select=None):
     """-> (scores f32 [Q,k], indices i64 [Q,k]).  ``bank`` is a [N,D] tensor or a PreparedBank
@@ -214,12 +286,29 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     ``select`` (None: nothing above changes; a bool tensor [N] or a ``Selection``): only the rows marked True are eligible, with
     the result of the search over the compacted bank and indices mapped back (``cosine_topk_tokens``'s ``select``).  A flat
     [N,D] bank of any dtype is then served as a token bank with one token per row (``stats['path'] == 'tokens'``) under that
-    search's limits: k <= 512, D % 64 == 0, D <= 1024, queries in groups of 16.  A PreparedBank with ``select`` is a ValueError:
-    its many-query prefilter under a selection is out of scope.
+    search's limits: k <= 512, D % 64 == 0, D <= 1024, queries in groups of 16.
+
+    A PreparedBank (fp32 or resident fp16) with ``select`` takes the two-stage path under the selection wherever that path
+    applies to the whole bank (more than 16 queries, k <= 192, N >= 2048, SKYEMB_TOPK_PREFILTER not 0): the result is exactly that
+    of ``cosine_topk(queries, PreparedBank(bank[select], weights), k)`` -- scores bit for bit, order (score desc, index asc), ties
+    to the lower bank row -- with every index mapped back to this bank, then offset by ``idx_offset``.  Nothing is gathered: stage 1
+    walks the live 256-row tiles (those with a selected row) and deselected rows fail its test through a masked copy of the row
+    constants (16 bytes per row, built by two short launches and kept with a ``Selection`` per bank until the bank's weights
+    change; a bool tensor is prepared on every call).  So a NaN, inf or all-zero row that is deselected changes nothing, and only
+    selections that empty whole tiles save bank bytes -- the fp16 image is not compacted.  Fewer than k selected rows: a
+    (-inf, -1) tail (k may exceed the selected count, not N), and a selected row that scores -inf (a NaN in it) is then not
+    returned, as in ``cosine_topk_tokens``; none selected: all (-inf, -1), no launch.  Uncertified queries
+    (``stats['redone']``) are re-run under the same selection by the token search with one token per row, for both bank dtypes
+    (the exact fp32 kernel takes no selection), so D must be a multiple of 64 and at most 1024 (ValueError before any launch).  A
+    selection with fewer than 8 live whole tiles (``SELECT_MIN_LIVE_TILES``: the phase schedule's own minimum, N >= 8 tiles, applied
+    to the live-tile count) is served whole by that token search (``stats['path'] == 'tokens'``), never refused.  ``stats`` gains
+    ``selected`` and ``tiles`` = (live bank tiles, all bank tiles).  Where the two-stage path does not apply (Q <= 16, k > 192,
+    N < 2048, the switch off) the call is a ValueError as before: pass the flat tensor.  One selection serves all queries
+    (per-query selections are out of scope); with ``world_size > 1`` it describes this rank's shard.
 
     ``weights`` [Q, D] (one row per query; [D] or None: nothing above changes): a flat [N,D] bank is served the same way, as
     ``cosine_topk_tokens`` with per-query weights and one token per row (``stats['path'] == 'tokens'``); a PreparedBank is a
-    ValueError."""
+    ValueError (per-query weights on the two-stage path are out of scope), with or without ``select``."""
     flat = isinstance(bank, torch.Tensor) and bank.dim() == 2
     per_query = isinstance(weights, torch.Tensor) and weights.dim() == 2
     if per_query and not flat:
@@ -227,8 +316,7 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
                          "token per row); pass the flat [N, D] tensor, not a PreparedBank")
     if select is not None and not per_query:
         if isinstance(bank, PreparedBank):
-            raise ValueError("cosine_topk: select is served by the token search (cosine_topk_tokens with one token per row); pass "
-                             "the flat [N, D] tensor, not a PreparedBank -- the prefiltered many-query route takes no selection")
+            return _cosine_topk_selected(queries, bank, k, select, eps, process_group, world_size, prune, stats)
         if not flat:
             raise ValueError("cosine_topk: select needs a flat [N, D] bank tensor")
     if per_query or select is not None or (flat and bank.dtype in ops.LP_DTYPES):     # served by the token search, one token per row
@@ -340,6 +428,20 @@ class Selection:
         self.count = int(self.flags.sum())
         self._indices = None
         self._sample = None                                # bank -> (its weights version, images, the floor's sample)
+        self._prefilter = None                             # PreparedBank -> (its version, its row constants, what stage 1 needs)
+
+    def prefilter(self, pb: "PreparedBank"):
+        """What the two-stage many-query search needs of this selection over ``pb`` (``ops.prefilter_select_prepare``: the masked row
+        constants, the live tiles, their number, whether the last tile is live).  Kept here per bank, like ``sample``, until the
+        bank's weights -- and with them its row constants -- change: repeated searches under one Selection do not rebuild it."""
+        if self._prefilter is None:
+            self._prefilter = weakref.WeakKeyDictionary()
+        rowp = pb.half_image()[1]
+        got = self._prefilter.get(pb)
+        if got is None or got[0] != pb._version or got[1] is not rowp:
+            got = (pb._version, rowp, ops.prefilter_select_prepare(self.words, self.N, rowp))
+            self._prefilter[pb] = got
+        return got[2]
 
     def sample(self, tb: "TokenBank", images: int):
         """A strided sample of ``images`` SELECTED whole images of ``tb`` (tokens + the norms of their rows) for the pruning floor.
