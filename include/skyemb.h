@@ -496,8 +496,8 @@ int skyemb_topk_merge(const float *in_s, const int64_t *in_i, int Q, int nlists,
  * The same search over a RESIDENT fp16 bank (bank16 [N, D] fp16, 16-byte aligned, D % 32 == 0): the bank is the fp32 bank its
  * elements widen to (xn: skyemb_weighted_norms_lp), both stages read it directly -- no fp32 copy, no second image -- and the
  * result is bit-identical to skyemb_cosine_topk_prefiltered on the widened bank.  bf16 rows are not representable in the
- * fp16 matrix operands: no such call exists for them.
- *   skyemb_bank16_rowp_lp   once per bank / weights: rowp = {xn, ||x||_2 + the row's fp16-subnormal term, 1, 0} for
+ * fp16 matrix operands: a resident bf16 bank takes the _resident calls further down, which multiply bf16 operands.
+ *   skyemb_bank16_rowp_lp  once per bank / weights: rowp = {xn, ||x||_2 + the row's fp16-subnormal term, 1, 0} for
  *                           skyemb_bank16_rowp_rows(N) rows.  tail: one tile [256, D] fp16 (16-byte aligned) that receives a
  *                           zero-padded copy of the last N % 256 rows -- the search reads whole tiles and never reads past the
  *                           bank's N * D elements; may be NULL when N % 256 == 0.  Extra memory: 16 bytes per row + that tile.
@@ -521,6 +521,31 @@ int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *qn, int Q, c
                                       const float *rowp, int64_t N, int D, int k, float eps, int64_t idx_offset, const float *thr0,
                                       void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream);
 double skyemb_topk_prefilter_eps_a(int D, int lo, int resident);
+/* The resident search for either 16-bit format: `dtype` is SKYEMB_F16 or SKYEMB_BF16, as skyemb_weighted_norms_lp takes it (anything
+ * else is refused).  With SKYEMB_F16 each call below IS its _lp counterpart above, same arguments, same bits.  With SKYEMB_BF16 the
+ * bank is a resident bf16 bank [N, D] (16-byte aligned, D % 32 == 0; xn: skyemb_weighted_norms_lp): stage 1 multiplies the stored
+ * rows and a bf16 split of the query on v_mfma_f32_16x16x32_bf16 -- same tiles, lists, phases and workspace --, stage 2 widens the
+ * selected rows into the contract's fp32 chain: the result is bit-identical to skyemb_cosine_topk_prefiltered on the widened bank.
+ *   skyemb_resident_rowp    skyemb_bank16_rowp_lp for the format given.  bf16: rowp = {xn, ||x||_2, 1, 0}; a row with an inf / NaN
+ *                           element, a nonzero element outside [2^-60, 2^120), or a weighted norm xn that is not finite cannot be
+ *                           bounded and takes the "keep for every query" constants {0, inf, 1, 0}: stage 2 decides it.  Same tail
+ *                           tile (bf16 bits), same extra memory.
+ *   skyemb_cosine_topk_prefiltered_resident / _resident_sel   skyemb_cosine_topk_prefiltered_lp / _lp_sel (the latter declared
+ *                           below, with the selection calls) for the format given; redo[q] != 0: the caller runs the query
+ *                           through skyemb_cosine_token_topk_lp / _sel with one token per row.  A bf16 search also flags every
+ *                           query whose largest |tw| lies outside [2^-50, 2^79). Variant: SKYEMB_PREFILTER_LO=1 runs the two-pass
+ *                           (hi + lo) query split, =0 the one-pass (hi only) one; unset, a bf16 bank runs hi only (measured
+ *                           faster), an fp16 bank as ever.  The 2^31 work-item limit above holds with
+ *                           the query tile of the variant in use (256 queries hi only, 128 hi + lo).
+ *   skyemb_topk_prefilter_eps_a_resident   host only: eps_a of stage 1 over a resident bank of the format given; SKYEMB_F16:
+ *                           skyemb_topk_prefilter_eps_a(D, lo, 1); SKYEMB_BF16: (lo ? 2^-18 : 2^-9) + 6.06 D 2^-24 + D 2^-38, no
+ *                           additive row term.  Derivation: csrc/topk_prefilter.hip. */
+int skyemb_resident_rowp(const void *bank16, int dtype, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream);
+int skyemb_cosine_topk_prefiltered_resident(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                            const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
+                                            int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                            int64_t *out_i, int *redo, void *stream);
+double skyemb_topk_prefilter_eps_a_resident(int D, int lo, int dtype);
 /* The two searches above under a SELECTION of the bank's rows (words: skyemb_pack_select over the N rows; one selection for all
  * queries).  The result is that of the same search over the compacted bank of the selected rows -- scores bit for bit, order
  * (score desc, row asc) -- with every index mapped back to this bank; a deselected row contributes nothing, whatever it holds.
@@ -547,6 +572,10 @@ int skyemb_cosine_topk_prefiltered_lp_sel(const float *tw, const float *qn, int 
                                           const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
                                           int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
                                           float *out_s, int64_t *out_i, int *redo, void *stream);
+int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
+                                                int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
+                                                float *out_s, int64_t *out_i, int *redo, void *stream);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

@@ -167,6 +167,13 @@ PROTOTYPES = {
                                                    c_f32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_topk_prefiltered_lp_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32,
                                                       c_f32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    # the two-stage search over a resident 16-bit bank of either format (a dtype code: fp16 or bf16): additive again
+    "skyemb_resident_rowp": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_prefiltered_resident": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_i64,
+                                                        c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_prefiltered_resident_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64,
+                                                            c_i32, c_i32, c_f32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_topk_prefilter_eps_a_resident": (c_f64, [c_i32, c_i32, c_i32]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

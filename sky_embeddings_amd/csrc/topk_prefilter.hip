@@ -46,6 +46,40 @@
 // Whole tiles of BT rows are read straight from the bank; the last N % BT rows are served from a zero-padded copy of one
 // tile (a launch of its own, so no read ever passes the bank's N * D elements).  Stage 2 widens the selected rows
 // element by element into the same fma chain: the scores are those of the fp32 kernel on the widened bank, bit for bit.
+//
+// Resident bf16 bank (skyemb_resident_rowp / skyemb_cosine_topk_prefiltered_resident with SKYEMB_BF16).  The same construction on
+// v_mfma_f32_16x16x32_bf16: x^_i = x_i exactly, e_i = 0, and the query split is qh = bf16(q'), ql = bf16(q' - qh).  The product of
+// two bf16 numbers (8-bit significands) is exact in fp32 whenever it is a normal number.  bf16 has fp32's exponent range, so the
+// query's scale is chosen for the fp32 ACCUMULATOR, not for the operand format: q' = tw_q 2^-f with the largest |q'_d| in
+// [2^-21, 2^-20).  Overflow: |qh_d + ql_d| < 2^-20 (1 + 2^-8) and |x_d| < 2^128, so the 2 D <= 2^13 products and every partial sum of
+// them stay below 2^121.1 -- no finite row overflows the accumulator, and a row the bound gives up on still has a finite dot^ (its
+// test below then passes for every query; a NaN dot^ would drop it).  Against dot' = chain(tw, x) 2^-f:
+//   |dot^ - dot'| <= eps_a ||q'||_2 ||x||_2,     eps_a = 2^-9 (hi only) or 2^-18 (hi + lo) + 6.06 D 2^-24 + D 2^-38
+//   2^-9 / 2^-18   bf16 rounds to nearest even with 8 significant bits: |q'_d - qh_d| <= 2^-9 |q'_d|; r_d = q'_d - qh_d is exact in fp32
+//                  (a multiple of ulp(q'_d) below 2^24 of them) and |r_d - ql_d| <= 2^-9 |r_d| <= 2^-18 |q'_d|.  Cauchy-Schwarz over d.
+//                  (fp16's hi only: 2^-11, hi + lo: 2^-22.  At D = 768: 2.23e-3 and 2.81e-4, against 7.7e-4 for resident fp16 hi only.)
+//   6.06 D 2^-24   the accumulation of the 2 D products in any order at one ulp each, the chain's own D roundings, and the factor
+//                  1 + 2^-8 by which sum |qh_d + ql_d| |x_d| may exceed sum |q'_d| |x_d|: 5.02 D 2^-24 before the second-order terms.
+//   D 2^-38        everything that happens below 2^-126, where nothing is assumed about the matrix core -- it may flush bf16-subnormal
+//                  operands, products and partial sums to zero or round them -- under TWO conditions that the kernels enforce:
+//                    (R) every nonzero element of the row has 2^-60 <= |x_d|, so ||x|| >= 2^-60 (or the row is zero: dot^ = dot' = 0);
+//                    (Q) the query's scale 2^-f is below 2^30 (largest |tw_d| >= 2^-50), and ||q'|| >= 2^-21 by construction.
+//                  (a) a product or a partial sum below 2^-126 lost or rounded: <= 2^-126 each, 4 D of them: D 2^-124 <=
+//                      D 2^-43 ||q'|| ||x||.  (b) a query operand below 2^-126 flushed, or q'_d itself an fp32 subnormal after the
+//                      scaling: <= 2^-126 |x_d| per product, in all <= 2^-125 sqrt(D) ||x|| <= sqrt(D) 2^-104 ||q'|| ||x|| -- the
+//                      counterpart of the fp16 bound's query-subnormal term sqrt(D) 2^-27, 2^77 times smaller because bf16 operands
+//                      underflow at 2^-126, not at 2^-24: it is kept, and it vanishes in the sum.  Row operands are never subnormal: (R).
+//                      (c) the contract's chain rounds a subnormal partial sum by <= 2^-150, D times, and dot' carries that times
+//                      2^-f: <= D 2^-120 <= D 2^-39 ||q'|| ||x||.  (a) + (b) + (c) < D 2^-38.
+// There is NO additive row term: what the fp16 bound carries in the norm slot is kept out by (R) instead.  Row constants
+// (bankbf16_rowp_kernel): rowp[i] = {xn_i, nx_i, 1, 0}, nx_i = ||x_i||_2 (1 + D 2^-22) rounded up, taken of the row scaled by a power
+// of two (the squares leave fp32's range on both sides).  A row is UNBOUNDABLE and takes {0, inf, 1, 0} -- a candidate of every
+// query, decided by stage 2 -- when it has an inf / NaN element (as ever), a nonzero element below 2^-60 (R), an element at or
+// above 2^120 (nx and eps_a ||q'|| nx must stay finite; far below that, from about 2^64 on, the next rule has already caught it), or
+// a weighted norm xn_i that is not finite: then a xn_i of the test is inf or NaN whatever tau is, while the row's exact score is
+// +-0 and can belong to a top-k that reaches down to zero.  A query outside (Q), or whose scale had to be clamped at 2^-100 (largest
+// |tw_d| >= 2^79), is flagged by init_state_kernel and re-run by the caller; its dot^ are never trusted.  Nothing else changes:
+// same bytes, same tiles, ring, swizzle, candidate test, lists, phases, selection handling, tail tile; stage 2 widens bf16 rows.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -84,6 +118,16 @@ __host__ __device__ inline double eps_a_of(int D, bool lo, bool resident = false
     if (resident) return (lo ? 0x1p-21 : 0x1p-11 + 0x1p-21) + 6.06 * D * 0x1p-24 + sqrt((double)D) * 0x1p-27;
     return (lo ? 0x1p-11 + 0x1p-21 : 0x1p-10 + 0x1p-21) + 6.06 * D * 0x1p-24 + 2.0 * sqrt((double)D) * 0x1p-27;
 }
+
+// the same bound for a resident bf16 bank multiplied by v_mfma_f32_16x16x32_bf16 (file header, "Resident bf16 bank")
+__host__ __device__ inline double eps_a_bf16_of(int D, bool lo) {
+    return (lo ? 0x1p-18 : 0x1p-9) + 6.06 * D * 0x1p-24 + D * 0x1p-38;
+}
+// what a bf16 search asks of its operands: every nonzero row element in [2^-BF_ROW_LO, 2^BF_ROW_HI) and a finite weighted norm --
+// any other row takes the {0, inf, 1, 0} constants --, the query's scale 2^-f in (2^-BF_SCALE_LO, 2^BF_SCALE_HI) -- any other
+// query is flagged for the exact route (init_state_kernel)
+constexpr int BF_QMAX_EXP = -20;          // the largest |q'| of a query lies in [2^(BF_QMAX_EXP - 1), 2^BF_QMAX_EXP)
+constexpr int BF_ROW_LO = 60, BF_ROW_HI = 120, BF_SCALE_LO = 100, BF_SCALE_HI = 30;
 
 // ---- preparation --------------------------------------------------------------------------------------------------
 // one wave per row: scale exponent, fp16 image, ||x'||_2 (rounded up), scaled weighted norm.
@@ -186,7 +230,66 @@ __global__ __launch_bounds__(256) void bank16_rowp_lp_kernel(const half_t *__res
     }
 }
 
+// the same for a resident bf16 bank (file header, "Resident bf16 bank"): rowp[i] = {xn, nx, 1, 0} with nx = ||x||_2 (1 + D 2^-22),
+// rounded up -- no additive term: a row that could need one is outside the window and takes {0, inf, 1, 0}.  The squares of
+// bf16 elements leave fp32's range on both sides, so the norm is taken of the row scaled by a power of two (second pass over
+// the row: it is in L2).  Same sentinel, same tail tile.
+__global__ __launch_bounds__(256) void bankbf16_rowp_kernel(const unsigned short *__restrict__ bank, const float *__restrict__ xn, int64_t N,
+                                                             int D, float4 *__restrict__ rowp, int64_t rows_padded,
+                                                             unsigned short *__restrict__ tail, int64_t tail_first) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows_padded) return;
+    unsigned short *t = tail && row >= tail_first ? tail + (row - tail_first) * D : nullptr;
+    if (row >= N) {
+        if (t)
+            for (int d = lane * 4; d < D; d += 256) *(uint2 *)(t + d) = make_uint2(0u, 0u);
+        if (lane == 0) rowp[row] = make_float4(0.f, NAN, 0.f, 0.f);
+        return;
+    }
+    const unsigned short *x = bank + row * D;
+    float mx = 0.f, bad = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const uint2 raw = *(const uint2 *)(x + d);
+        if (t) *(uint2 *)(t + d) = raw;
+        const unsigned int u[4] = {raw.x << 16, raw.x & 0xFFFF0000u, raw.y << 16, raw.y & 0xFFFF0000u};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float m = fabsf(__uint_as_float(u[j]));                  // exact
+            bad = (!(m < ldexpf(1.0f, BF_ROW_HI)) || (m > 0.f && m < ldexpf(1.0f, -BF_ROW_LO))) ? 1.f : bad;   // inf / NaN / outside the window
+            mx = fmaxf(mx, m);
+        }
+    }
+    mx = wave_max(mx);
+    bad = wave_max(bad);
+    const float xnv = xn[row];
+    if (!(xnv < INFINITY)) bad = 1.f;                        // the weighted norm overflowed (or is NaN): a * xn of the test is not a number
+    if (bad != 0.f) {
+        if (lane == 0) rowp[row] = make_float4(0.f, INFINITY, 1.0f, 0.f);
+        return;
+    }
+    int e = 0;
+    if (mx > 0.f) (void)frexpf(mx, &e);                      // mx 2^-e in [0.5, 1); e in (-BF_ROW_LO, BF_ROW_HI]
+    const float s = ldexpf(1.0f, -e);
+    float ss = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const uint2 raw = *(const uint2 *)(x + d);
+        const float a = __uint_as_float(raw.x << 16) * s, b = __uint_as_float(raw.x & 0xFFFF0000u) * s;
+        const float c = __uint_as_float(raw.y << 16) * s, dd = __uint_as_float(raw.y & 0xFFFF0000u) * s;
+        ss = fmaf(a, a, fmaf(b, b, fmaf(c, c, fmaf(dd, dd, ss))));
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) {
+        // (an element 2^-126 of the row maximum or less loses its square: below 2^-250 of ss, inside the factor's slack)
+        const float nx = ldexpf(sqrtf(ss) * (1.0f + (float)D * 0x1p-22f) * (1.0f + 0x1p-21f), e);
+        rowp[row] = make_float4(xnv, nx, 1.0f, 0.f);
+    }
+}
+
 // queries: tw[q] -> qh, ql (fp16, scaled by 2^-f); qbase[q] = {qn * 2^-f, eps_a * ||q'|| (1 + D 2^-22), 2^-f, qn}
+// BF: the bf16 form -- qh = bf16(q'), ql = bf16(q' - qh), the largest |q'| in [2^(BF_QMAX_EXP - 1), 2^BF_QMAX_EXP): bf16 has fp32's
+// exponent range, so the scale is chosen for the fp32 ACCUMULATOR, which must hold 2 D products against any finite row
+template <bool BF>
 __global__ __launch_bounds__(256) void query16_kernel(const float *__restrict__ tw, const float *__restrict__ qn, int Q, int D,
                                                        half_t *__restrict__ qh, half_t *__restrict__ ql, float4 *__restrict__ qbase,
                                                        float eps_a) {
@@ -211,14 +314,28 @@ __global__ __launch_bounds__(256) void query16_kernel(const float *__restrict__ 
     int e = 0;
     if (mx > 0.f && mx < INFINITY) {
         (void)frexpf(mx, &e);
-        e -= 14;
+        e -= BF ? BF_QMAX_EXP : 14;
     }
     if (e < -126) e = -126;             // keep 2^-e finite; such a query (scale == 2^126) is flagged for the exact path by init_state_kernel
+    if (BF && e > BF_SCALE_LO) e = BF_SCALE_LO;   // (keeps 2^e finite too; flagged likewise)
     const float s = ldexpf(1.0f, -e);
     float ss = 0.f;
     for (int d = lane * 4; d < D; d += 256) {
         const float4 v = *(const float4 *)(x + d);
         const float a[4] = {v.x * s, v.y * s, v.z * s, v.w * s};
+        if (BF) {
+            // (the squares of elements below 2^-43 of the maximum underflow: below 2^-86 of ss, inside the slack of nq's factor)
+            bf16x4 h, l;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ss = fmaf(a[j], a[j], ss);
+                h[j] = (bf16_t)a[j];
+                l[j] = (bf16_t)(a[j] - (float)h[j]);  // exact difference in fp32, then one bf16 rounding
+            }
+            *(bf16x4 *)(qh + (int64_t)q * D + d) = h;
+            *(bf16x4 *)(ql + (int64_t)q * D + d) = l;
+            continue;
+        }
         typedef __attribute__((ext_vector_type(4))) _Float16 half4;
         half4 h, l;
 #pragma unroll
@@ -343,7 +460,9 @@ __device__ __forceinline__ void wait_vmcnt() {
 // tiles -- position p stands for bank tile tiles[p], whose rows, row constants (the masked copy: a deselected row fails every test)
 // and row numbers the item uses; only the take-all slots are counted by position.  Without SEL `tiles` is not read (NULL) and a
 // position is its own tile: the instruction stream of the unselected search.
-template <int MODE, bool LO, bool SEL>
+// BF: the operands are bf16 (a resident bf16 bank, query16_kernel<true>'s images): the same bytes through the same ring and fragments,
+// multiplied by v_mfma_f32_16x16x32_bf16 -- the one difference.  Without BF: the instruction stream it has always been.
+template <int MODE, bool LO, bool SEL, bool BF = false>
 __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict__ qh, const half_t *__restrict__ ql,
                                                        const half_t *__restrict__ bank16, const float4 *__restrict__ rowp,
                                                        const int *__restrict__ tiles,
@@ -507,8 +626,13 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
 #ifndef PF_NOMFMA
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], fb[j], acc[i][j], 0, 0, 0);
-                if (LO) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[i], fb[j], acc[i][j], 0, 0, 0);
+                if constexpr (BF) {      // (the fragments are 16 bytes of LDS either way: the bits are handed over as they are)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fh[i]), __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
+                    if (LO) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fl[i]), __builtin_bit_cast(bf16x8, fb[j]), acc[i][j], 0, 0, 0);
+                } else {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fh[i], fb[j], acc[i][j], 0, 0, 0);
+                    if (LO) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fl[i], fb[j], acc[i][j], 0, 0, 0);
+                }
             }
 #else
             acc[i][0][0] += (float)fh[i][0] + (float)fb[i & 3][2];
@@ -1020,6 +1144,12 @@ __device__ __forceinline__ float4 row4(const half_t *x) {
     return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
 }
 
+__device__ __forceinline__ float4 row4(const bf16_t *x) {
+    const uint2 raw = *(const uint2 *)x;
+    return make_float4(__uint_as_float(raw.x << 16), __uint_as_float(raw.x & 0xFFFF0000u), __uint_as_float(raw.y << 16),
+                       __uint_as_float(raw.y & 0xFFFF0000u));
+}
+
 // one workgroup (256 threads) per query; thread c owns candidate c: the contract's fma chain over d = 0..D-1
 // FEW (a search under a selection, which may hold fewer than k rows): fewer than k candidates are an answer, not a reason to re-run
 template <typename X, bool FEW>
@@ -1099,11 +1229,16 @@ template <bool FEW>
 __global__ __launch_bounds__(256) void rescore_lp_kernel(RESCORE_PARAMS(half_t)) {
     rescore_body<half_t, FEW>(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
 }
+// ... and a resident bf16 bank's
+template <bool FEW>
+__global__ __launch_bounds__(256) void rescore_bf_kernel(RESCORE_PARAMS(bf16_t)) {
+    rescore_body<bf16_t, FEW>(tw, qn, bank, xn, Q, D, k, eps, idx_offset, sel_i, nsel, bound, overflow, out_s, out_i, redo);
+}
 #undef RESCORE_PARAMS
 
 __global__ void init_state_kernel(int Q, int Q_padded, const float *__restrict__ thr0, const float4 *__restrict__ qbase, float eps,
                                   float4 *__restrict__ qpar, float *__restrict__ tau_q, int *__restrict__ cnt,
-                                  int *__restrict__ overflow, int first_rows) {
+                                  int *__restrict__ overflow, int first_rows, float scale_lo, float scale_hi) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= Q) {
         if (q < Q_padded) qpar[q] = make_float4(NAN, NAN, NAN, NAN);   // padding of the last query tile: t = NaN, no pair passes
@@ -1115,7 +1250,8 @@ __global__ void init_state_kernel(int Q, int Q_padded, const float *__restrict__
     const float4 qb = qbase[q];
     // a query whose scale hit the clamp (largest |t w| below ~2^-112) has an fp16 image outside the error bound's
     // assumptions: answered by the exact kernel (redo), never silently by this path
-    overflow[q] = qb.z >= 0x1p126f ? 1 : 0;
+    // (scale_lo = 0, scale_hi = 2^126: that rule.  The bf16 search's bound asks more of the scale: file header)
+    overflow[q] = qb.z >= scale_hi || qb.z <= scale_lo ? 1 : 0;
     const float t = tau > -3.0e38f ? tau : -3.0e38f;
     float a = t * qb.x, b = t * eps * qb.z;
     a -= fabsf(a) * 0x1p-19f;
@@ -1185,6 +1321,11 @@ extern "C" int skyemb_bank16_prepare(const float *bank, const float *xn, int64_t
 
 extern "C" double skyemb_topk_prefilter_eps_a(int D, int lo, int resident) { return eps_a_of(D, lo != 0, resident != 0); }
 
+#define RESIDENT_DTYPE_MSG "must be SKYEMB_BF16 (0) or SKYEMB_F16 (2), got %d"
+extern "C" double skyemb_topk_prefilter_eps_a_resident(int D, int lo, int dtype) {
+    return dtype == SKYEMB_BF16 ? eps_a_bf16_of(D, lo != 0) : eps_a_of(D, lo != 0, true);
+}
+
 extern "C" int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
     SKY_CHECK_ARG(bank16 && xn && rowp && N > 0 && D > 0 && D % BK == 0, "skyemb_bank16_rowp_lp: bad arguments");
     SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_bank16_rowp_lp: N = %lld is no whole number of %d-row tiles: a tail tile [%d, D] is needed",
@@ -1199,17 +1340,35 @@ extern "C" int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_
     return 0;
 }
 
+extern "C" int skyemb_resident_rowp(const void *bank16, int dtype, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
+    SKY_CHECK_ARG(sky_is_lp(dtype), "skyemb_resident_rowp: dtype " RESIDENT_DTYPE_MSG, dtype);
+    if (dtype == SKYEMB_F16) return skyemb_bank16_rowp_lp(bank16, xn, N, D, rowp, tail, stream);
+    SKY_CHECK_ARG(bank16 && xn && rowp && N > 0 && D > 0 && D % BK == 0, "skyemb_resident_rowp: bad arguments");
+    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_resident_rowp: N = %lld is no whole number of %d-row tiles: a tail tile [%d, D] is needed",
+                  (long long)N, BT, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_resident_rowp: the bank and the tail tile must be 16-byte aligned");
+    const int64_t padded = skyemb_bank16_rowp_rows(N);
+    hipLaunchKernelGGL(bankbf16_rowp_kernel, dim3((unsigned)ceil_div64(padded, 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned short *)bank16, xn, N, D, (float4 *)rowp, padded, N % BT ? (unsigned short *)tail : nullptr, N / BT * BT);
+    SKY_LAUNCH_CHECK("skyemb_resident_rowp");
+    return 0;
+}
+
 extern "C" int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k) { return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr); }
+
+// which of its two variants a bf16 search runs when SKYEMB_PREFILTER_LO is unset: the one measured faster
+constexpr bool BF16_DEFAULT_LO = false;
 
 // The pipeline of all entry points.  bank: the fp32 rows stage 2 re-scores, bank16 their fp16 image (skyemb_bank16_prepare) --
 // or bank NULL: bank16 is a resident fp16 bank that both stages read, its last N % BT rows through `tail` (skyemb_bank16_rowp_lp).
 // tiles (NULL: no selection): the search runs under a selection prepared by skyemb_prefilter_select_prepare -- rowp is then the
 // masked copy, tiles the n_live live tiles of all ceil(N / BT), last_live says whether the last of those is one of them.  The phase
 // schedule runs over the live tiles; a resident bank's tail tile is launched only when it is live.
+// bf (bank NULL only): the resident bank is bf16 -- bf16 query images, the BF instances of stage 1, the bf16 re-score.
 static int topk_prefiltered(const char *who, const float *tw, const float *qn, int Q, const float *bank, const float *xn,
                             const void *bank16, const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
                             int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
-                            int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0) {
+                            int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0, bool bf = false) {
     const bool resident = bank == nullptr;
     const bool sel = tiles != nullptr;
     SKY_CHECK_ARG(skyemb_topk_prefilter_applicable(Q, N, D, k), "%s: outside the prefiltered subset "
@@ -1218,7 +1377,8 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
     // embedding-like data a few dozen more candidates per query.  SKYEMB_PREFILTER_LO=1 keeps the hi + lo passes.
     // (read per call on purpose: a getenv is a sub-microsecond scan next to a multi-millisecond search, and the tests switch it)
     const char *lo_env = getenv("SKYEMB_PREFILTER_LO");
-    const bool use_lo = lo_env && lo_env[0] == '1';
+    // a bf16 bank: SKYEMB_PREFILTER_LO=0 forces hi only as well; unset, the variant measured faster
+    const bool use_lo = bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
     // stage 1 counts an XCD's work items (its bank tiles x the query tiles) and a workgroup's k-steps in 32-bit integers
     SKY_CHECK_ARG(ceil_div64(ceil_div64(N, BT), 8) * ceil_div64(Q, qtile(use_lo)) * (D / BK) < (1ll << 31),
                   "%s: Q x N too large: ceil(N / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31, the range of stage 1's work-item "
@@ -1228,9 +1388,10 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
     hipStream_t st = (hipStream_t)stream;
     Workspace w;
     carve((char *)ws, Q, D, cap, &w);
-    const float eps_a = (float)(eps_a_of(D, use_lo, resident) * (1.0 + 1e-6));
-    hipLaunchKernelGGL(query16_kernel, dim3((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4)), dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql,
-                       w.qbase, eps_a);
+    const float eps_a = (float)((bf ? eps_a_bf16_of(D, use_lo) : eps_a_of(D, use_lo, resident)) * (1.0 + 1e-6));
+    const dim3 qgrid((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4));
+    if (bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
+    else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
     // tiles the phases below walk: all of them -- of a resident bank the whole ones, the last N % BT rows follow from `tail`
     const int T_tail = (int)(N / BT);                          // the tile a resident bank's tail stands for
     const bool has_tail = resident && N % BT != 0 && (!sel || last_live);
@@ -1250,13 +1411,16 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
     const int64_t first_rows = sel || (int64_t)first * BT < N ? (int64_t)first * BT : N;
     const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
     hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
-                       w.qpar, w.tau, w.cnt, w.overflow, (int)first_rows);
+                       w.qpar, w.tau, w.cnt, w.overflow, (int)first_rows, bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
+                       bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
     const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
     constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
     int rc = 0;
 #define PF_ATTR(M, L)                                                                                             \
-    if (rc == 0) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false>, smem_max, who);              \
-    if (rc == 0 && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true>, smem_max, who)
+    if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false>, smem_max, who);       \
+    if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true>, smem_max, who); \
+    if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true>, smem_max, who);  \
+    if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true>, smem_max, who)
     PF_ATTR(0, false); PF_ATTR(1, false); PF_ATTR(2, false); PF_ATTR(0, true); PF_ATTR(1, true); PF_ATTR(2, true);
 #undef PF_ATTR
     if (rc == 0) rc = sky_set_lds_limit((const void *)select_kernel<false>, 2 * 8192 * 4 + 272 * 4, who);
@@ -1287,8 +1451,11 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
 #endif
 #define PF_ARGS(B, T0, T1, TL) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, TL, w.qpar, Q, N, D, T0, T1, cap, w.cnt, w.cand_i, \
                                w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow PF_DBG
-#define PF_LAUNCH_AS(M, L, S, B, T0, T1, TL) \
-    hipLaunchKernelGGL((prefilter_kernel<M, L, S>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL))
+#define PF_LAUNCH_AS(M, L, S, B, T0, T1, TL)                                                                                   \
+    do {                                                                                                                       \
+        if (bf) hipLaunchKernelGGL((prefilter_kernel<M, L, S, true>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL)); \
+        else hipLaunchKernelGGL((prefilter_kernel<M, L, S>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL));      \
+    } while (0)
 // TL: the live-tile list the positions [T0, T1) index, or NULL: they are the bank tiles themselves
 #define PF_LAUNCH(M, B, T0, T1, TL)                                                              \
     do {                                                                                         \
@@ -1363,7 +1530,9 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
     }
     const size_t smem_re = (size_t)D * 4 + RESCORE_MAX * 8;
 #define RESCORE_ARGS(B) tw, qn, B, xn, Q, D, k, eps, idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo
-    if (resident && sel) hipLaunchKernelGGL(rescore_lp_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
+    if (bf && sel) hipLaunchKernelGGL(rescore_bf_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const bf16_t *)bank16));
+    else if (bf) hipLaunchKernelGGL(rescore_bf_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const bf16_t *)bank16));
+    else if (resident && sel) hipLaunchKernelGGL(rescore_lp_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
     else if (resident) hipLaunchKernelGGL(rescore_lp_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
     else if (sel) hipLaunchKernelGGL(rescore_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS(bank));
     else hipLaunchKernelGGL(rescore_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS(bank));
@@ -1428,4 +1597,40 @@ extern "C" int skyemb_cosine_topk_prefiltered_lp_sel(const float *tw, const floa
     SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_lp_sel: the bank and the tail tile must be 16-byte aligned");
     return topk_prefiltered("skyemb_cosine_topk_prefiltered_lp_sel", tw, qn, Q, nullptr, xn, bank16, tail, rowp_sel, N, D, k, eps, idx_offset,
                             nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live);
+}
+
+// ---- a resident 16-bit bank of either format: dtype SKYEMB_F16 is the _lp entry point itself, SKYEMB_BF16 the bf16 search ------------
+extern "C" int skyemb_cosine_topk_prefiltered_resident(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                       const float *xn, const void *tail, const float *rowp, int64_t N, int D, int k,
+                                                       float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                       float *out_s, int64_t *out_i, int *redo, void *stream) {
+    SKY_CHECK_ARG(sky_is_lp(dtype), "skyemb_cosine_topk_prefiltered_resident: dtype " RESIDENT_DTYPE_MSG, dtype);
+    if (dtype == SKYEMB_F16)
+        return skyemb_cosine_topk_prefiltered_lp(tw, qn, Q, bank16, xn, tail, rowp, N, D, k, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i,
+                                                 redo, stream);
+    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered_resident: null argument");
+    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_resident: N = %lld is no whole number of %d-row tiles: the tail tile "
+                  "of skyemb_resident_rowp is needed", (long long)N, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_resident: the bank and the tail tile must be 16-byte aligned");
+    return topk_prefiltered("skyemb_cosine_topk_prefiltered_resident", tw, qn, Q, nullptr, xn, bank16, tail, rowp, N, D, k, eps, idx_offset,
+                            thr0, ws, ws_bytes, out_s, out_i, redo, stream, nullptr, 0, 0, true);
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                           const float *xn, const void *tail, const float *rowp_sel, const int *tiles,
+                                                           int n_live, int last_live, int64_t N, int D, int k, float eps,
+                                                           int64_t idx_offset, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                           int *redo, void *stream) {
+    SKY_CHECK_ARG(sky_is_lp(dtype), "skyemb_cosine_topk_prefiltered_resident_sel: dtype " RESIDENT_DTYPE_MSG, dtype);
+    if (dtype == SKYEMB_F16)
+        return skyemb_cosine_topk_prefiltered_lp_sel(tw, qn, Q, bank16, xn, tail, rowp_sel, tiles, n_live, last_live, N, D, k, eps, idx_offset,
+                                                     ws, ws_bytes, out_s, out_i, redo, stream);
+    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp_sel && tiles && ws && out_s && out_i && redo,
+                  "skyemb_cosine_topk_prefiltered_resident_sel: null argument");
+    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_resident_sel: N = %lld is no whole number of %d-row tiles: the tail "
+                  "tile of skyemb_resident_rowp is needed", (long long)N, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail),
+                  "skyemb_cosine_topk_prefiltered_resident_sel: the bank and the tail tile must be 16-byte aligned");
+    return topk_prefiltered("skyemb_cosine_topk_prefiltered_resident_sel", tw, qn, Q, nullptr, xn, bank16, tail, rowp_sel, N, D, k, eps,
+                            idx_offset, nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live, true);
 }

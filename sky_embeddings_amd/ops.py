@@ -482,6 +482,49 @@ def cosine_topk_prefiltered_lp(tw, qn, bank16, xn, tail, rowp, k, eps, idx_offse
     return ws
 
 
+def resident_dtype_code(t: torch.dtype, who: str) -> int:
+    """SKYEMB_* code of a resident 16-bit bank's element type; anything but fp16 / bf16 is a ValueError naming the two."""
+    if t not in LP_DTYPES:
+        raise ValueError(f"{who}: bank dtype {t} is not supported, expected torch.float16 or torch.bfloat16")
+    return dtype_code(t)
+
+
+def topk_prefilter_eps_a_resident(D, dtype, lo=False):
+    """``topk_prefilter_eps_a`` over a resident bank of ``dtype`` (torch.float16: the resident value; torch.bfloat16: the bf16
+    search's bound, host arithmetic only; see include/skyemb.h)."""
+    return lib().skyemb_topk_prefilter_eps_a_resident(D, int(lo), resident_dtype_code(dtype, "topk_prefilter_eps_a_resident"))
+
+
+def resident_rowp(bank16, xn):
+    """``bank16_rowp_lp`` for a resident bank of either 16-bit format, fp16 or bf16 (ValueError for any other): (tail, rowp), the
+    tail tile in the bank's dtype.  ValueError when the bank is not 16-byte aligned."""
+    N, D = bank16.shape
+    code = resident_dtype_code(bank16.dtype, "resident_rowp")
+    assert bank16.is_contiguous()
+    if bank16.data_ptr() % 16:
+        raise ValueError("resident_rowp: the 16-bit bank must be 16-byte aligned (the search reads it by 16-byte LDS-DMA); "
+                         "this tensor starts at an odd offset of its storage -- clone() it")
+    rows = lib().skyemb_bank16_rowp_rows(N)
+    rowp = torch.empty(rows, 4, device=bank16.device, dtype=torch.float32)
+    tail = torch.empty(rows - N // 256 * 256, D, device=bank16.device, dtype=bank16.dtype) if rows != N else None
+    check(lib().skyemb_resident_rowp(_p(bank16), code, _p(xn), N, D, _p(rowp), _p(tail), _stream()), "skyemb_resident_rowp")
+    return tail, rowp
+
+
+def cosine_topk_prefiltered_resident(tw, qn, bank16, xn, tail, rowp, k, eps, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """``cosine_topk_prefiltered_lp`` over a resident bank of either 16-bit format and the (tail, rowp) of ``resident_rowp``."""
+    Q, D = tw.shape
+    N = bank16.shape[0]
+    code = resident_dtype_code(bank16.dtype, "cosine_topk_prefiltered_resident")
+    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_prefiltered_resident(_p(tw), _p(qn), Q, _p(bank16), code, _p(xn), _p(tail), _p(rowp), N, D, k, eps,
+                                                        idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
+                                                        _stream()), "skyemb_cosine_topk_prefiltered_resident")
+    return ws
+
+
 def prefilter_select_prepare(words, N, rowp):
     """What the two-stage search needs of a selection (packed ``words`` of ``pack_select``) over a bank of N rows with row constants
     ``rowp`` (``bank16_prepare`` / ``bank16_rowp_lp``): (rowp_sel, tiles, n_live, last_live) -- the masked copy of the constants (a
@@ -498,8 +541,9 @@ def prefilter_select_prepare(words, N, rowp):
 
 
 def cosine_topk_prefiltered_sel(tw, qn, bank, xn, bank16, tail, prepared, k, eps, idx_offset, out_s, out_i, redo, ws=None):
-    """``cosine_topk_prefiltered`` (``bank`` fp32 and its image ``bank16``) or ``cosine_topk_prefiltered_lp`` (``bank`` None: ``bank16``
-    is the resident fp16 bank, ``tail`` its tail tile) under a selection: ``prepared`` is ``prefilter_select_prepare``'s result."""
+    """``cosine_topk_prefiltered`` (``bank`` fp32 and its image ``bank16``) or ``cosine_topk_prefiltered_lp`` / ``_resident`` (``bank``
+    None: ``bank16`` is the resident fp16 / bf16 bank, ``tail`` its tail tile) under a selection: ``prepared`` is
+    ``prefilter_select_prepare``'s result."""
     Q, D = tw.shape
     rowp_sel, tiles, n_live, last_live = prepared
     N = xn.shape[0]
@@ -510,6 +554,11 @@ def cosine_topk_prefiltered_sel(tw, qn, bank, xn, bank16, tail, prepared, k, eps
         check(lib().skyemb_cosine_topk_prefiltered_sel(_p(tw), _p(qn), Q, _p(bank), _p(xn), _p(bank16), _p(rowp_sel), _p(tiles), n_live,
                                                        last_live, N, D, k, eps, idx_offset, _p(ws), ws.numel(), _p(out_s), _p(out_i),
                                                        _p(redo), _stream()), "skyemb_cosine_topk_prefiltered_sel")
+    elif bank16.dtype == torch.bfloat16:
+        check(lib().skyemb_cosine_topk_prefiltered_resident_sel(_p(tw), _p(qn), Q, _p(bank16), dtype_code(bank16.dtype), _p(xn), _p(tail),
+                                                                _p(rowp_sel), _p(tiles), n_live, last_live, N, D, k, eps, idx_offset,
+                                                                _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
+              "skyemb_cosine_topk_prefiltered_resident_sel")
     else:
         check(lib().skyemb_cosine_topk_prefiltered_lp_sel(_p(tw), _p(qn), Q, _p(bank16), _p(xn), _p(tail), _p(rowp_sel), _p(tiles), n_live,
                                                           last_live, N, D, k, eps, idx_offset, _p(ws), ws.numel(), _p(out_s), _p(out_i),

@@ -33,20 +33,42 @@ def _kth_floor(scores: torch.Tensor, k: int):
 class PreparedBank:
     """Bank rows + their weighted norms (recomputed only when the weights change).
 
-    ``bank`` is fp32, or fp16 for a half-precision resident bank (``dtype``): such a bank IS the fp32 bank its elements widen
-    to -- norms, scores and every search result are those of the widened bank bit for bit -- and nothing here ever holds an
-    fp32 copy or a second image of it.  It must start 16-byte aligned (ValueError; a fresh tensor does).  bf16 is a ValueError:
-    the many-query search multiplies fp16 matrix operands, which cannot hold bf16 values exactly."""
+    ``bank`` is fp32, or fp16 / bf16 for a half-precision resident bank (``dtype``): such a bank IS the fp32 bank its elements
+    widen to -- norms, scores and every search result are those of the widened bank bit for bit -- and nothing here ever holds
+    an fp32 copy or a second image of it.  It must start 16-byte aligned (ValueError; a fresh tensor does).  A resident 16-bit
+    bank of either format is made by ``PreparedBank.resident(bank)``; the plain constructor takes fp32 and fp16 and refuses bf16
+    (ValueError naming ``resident``), as it always has.  The many-query search multiplies a bf16 bank's rows as bf16 matrix
+    operands (v_mfma_f32_16x16x32_bf16) -- no conversion, which fp16 operands could not hold exactly."""
 
     def __init__(self, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
         if isinstance(bank, torch.Tensor) and bank.dtype == torch.bfloat16:
-            raise ValueError("PreparedBank: a bfloat16 bank is not supported: the many-query search multiplies fp16 matrix operands, "
-                             "which cannot hold bf16 values exactly; pass the flat [N, D] tensor itself to cosine_topk, which serves "
-                             "it by the token search with one token per row (cosine_topk_tokens)")
-        assert bank.is_cuda and bank.dtype in (torch.float32, torch.float16) and bank.is_contiguous() and bank.dim() == 2
-        if bank.dtype == torch.float16 and bank.data_ptr() % 16:
-            raise ValueError("PreparedBank: an fp16 bank must start 16-byte aligned (the search reads it by 16-byte LDS-DMA); this "
-                             "tensor starts at an odd offset of its storage -- clone() it")
+            raise ValueError("PreparedBank: the plain constructor does not take a bfloat16 bank (fp16 matrix operands cannot hold bf16 "
+                             "values exactly); build it with PreparedBank.resident(bank, weights, idx_offset), whose many-query search "
+                             "multiplies the rows as bf16 matrix operands -- or pass the flat [N, D] tensor itself to cosine_topk, "
+                             "which serves it by the token search with one token per row (cosine_topk_tokens)")
+        self._init(bank, weights, idx_offset)
+
+    @classmethod
+    def resident(cls, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
+        """A PreparedBank over a resident 16-bit bank [N, D], fp16 or bf16 (ValueError for anything else).  fp16: exactly
+        ``PreparedBank(bank, weights, idx_offset)``.  bf16: the same object over ``TokenBank(bank.unsqueeze(1))``, which computes
+        the norms -- ``half_image()`` returns ``(bank, rowp)``, ``tail_tile`` holds the last N % 256 rows; no fp32 copy and no
+        second image exist."""
+        if not isinstance(bank, torch.Tensor) or bank.dtype not in ops.LP_DTYPES:
+            what = bank.dtype if isinstance(bank, torch.Tensor) else type(bank).__name__
+            raise ValueError(f"PreparedBank.resident: a resident bank is torch.float16 or torch.bfloat16, got {what}; an fp32 bank "
+                             f"takes PreparedBank(bank)")
+        if bank.dtype == torch.float16:
+            return cls(bank, weights, idx_offset)
+        self = cls.__new__(cls)
+        self._init(bank, weights, idx_offset)
+        return self
+
+    def _init(self, bank, weights, idx_offset):
+        if bank.dtype in ops.LP_DTYPES and bank.data_ptr() % 16:
+            raise ValueError(f"PreparedBank: an {'fp16' if bank.dtype == torch.float16 else 'bf16'} bank must start 16-byte aligned "
+                             "(the search reads it by 16-byte LDS-DMA); this tensor starts at an odd offset of its storage -- clone() it")
+        assert bank.is_cuda and bank.dtype in ops.BANK_DTYPES and bank.is_contiguous() and bank.dim() == 2
         self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self._sample = None
         self._half = None
@@ -77,7 +99,7 @@ class PreparedBank:
 
     def row_tokens(self):
         """The same rows as a TokenBank with one token per row: the route of a search under a selection that the two-stage path
-        does not take, and of its uncertified queries.  An fp16 bank has it from the start (it shares the norms); an fp32 bank
+        does not take, and of its uncertified queries.  A 16-bit bank has it from the start (it shares the norms); an fp32 bank
         builds it on first use -- one norm pass, 4 bytes per row, no copy of the rows -- and keeps it until the weights change."""
         if self._tokens is not None:
             return self._tokens
@@ -88,14 +110,17 @@ class PreparedBank:
     def half_image(self):
         """(bank16, rowp): the fp16 rows + per-row constants the prefiltered many-query search runs on; built on first use and
         kept until the weights change.  fp32 bank: bank16 is a scaled fp16 image of it (one pass over the bank, +50 % bank
-        memory).  fp16 bank: bank16 is the bank itself; only ``rowp`` (16 bytes per row) and ``tail_tile`` -- a zero-padded copy
+        memory).  fp16 / bf16 bank: bank16 is the bank itself; only ``rowp`` (16 bytes per row) and ``tail_tile`` -- a zero-padded copy
         of the last N % 256 rows, one tile [256, D], or None -- are allocated."""
         if self._half is None:
             if self.dtype == torch.float32:
                 self._half = ops.bank16_prepare(self.bank, self.norms)
                 self.tail_tile = None
-            else:
+            elif self.dtype == torch.float16:
                 self.tail_tile, rowp = ops.bank16_rowp_lp(self.bank, self.norms)
+                self._half = (self.bank, rowp)
+            else:
+                self.tail_tile, rowp = ops.resident_rowp(self.bank, self.norms)
                 self._half = (self.bank, rowp)
         return self._half
 
@@ -181,7 +206,7 @@ def _prefilter_enabled():
 
 def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps, q=None, prune=True):
     """Two-stage exact top-k of this rank's shard (csrc/topk_prefilter.hip); queries the second stage could not certify
-    (redo flags) go through the exact fp32 kernel -- over a resident fp16 bank (``q``: the raw queries): through the token
+    (redo flags) go through the exact fp32 kernel -- over a resident fp16 / bf16 bank (``q``: the raw queries): through the token
     search with one token per row, those queries only, on the bank's own norms."""
     Q = tw.shape[0]
     dev = tw.device
@@ -191,8 +216,10 @@ def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps, q=None, prune=Tr
     redo = torch.empty(Q, device=dev, dtype=torch.int32)
     if pb.dtype == torch.float32:
         ops.cosine_topk_prefiltered(tw, qn, pb.bank, pb.norms, bank16, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
-    else:
+    elif pb.dtype == torch.float16:
         ops.cosine_topk_prefiltered_lp(tw, qn, bank16, pb.norms, pb.tail_tile, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
+    else:
+        ops.cosine_topk_prefiltered_resident(tw, qn, bank16, pb.norms, pb.tail_tile, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
     again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
     if again.numel() and pb.dtype != torch.float32:
         s2, i2 = cosine_topk_tokens(q.index_select(0, again), pb._tokens, k, 'min', None, eps, prune=prune)
@@ -275,20 +302,24 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     A 2-D fp16 / bf16 tensor is a half-precision resident bank: it is served as a token bank with one token per row
     (``cosine_topk_tokens`` on ``bank.unsqueeze(1)``, ``stats['path'] == 'tokens'``) under that search's limits -- k <= 512,
     more than 16 queries in groups of 16 -- with the results of the fp32 search on the widened bank, bit for bit.  The
-    many-query prefilter over a 16-bit bank is reached through ``PreparedBank(bank_fp16)``: where the two-stage path applies
-    (more than 16 queries, k <= 192, N >= 2048) it reads the resident fp16 rows directly -- no fp32 copy, no second image: 16 bytes
+    many-query prefilter over a 16-bit bank is reached through ``PreparedBank.resident(bank)`` (fp16 or bf16; fp16 also through
+    ``PreparedBank(bank_fp16)``): where the two-stage path applies
+    (more than 16 queries, k <= 192, N >= 2048) it reads the resident 16-bit rows directly -- no fp32 copy, no second image: 16 bytes
     of constants per row and one 256-row tile -- with the results of the fp32 search on the widened bank, bit for bit
     (``stats['path'] == 'prefiltered'``; uncertified queries are re-run by the token search, ``stats['redone']``); everywhere
     else, and under SKYEMB_TOPK_PREFILTER=0, it is served as the bare tensor is (``stats['path'] == 'tokens'``), within that
-    search's limits in both cases.  bf16 has no such route (``PreparedBank`` refuses it).  fp32 banks take exactly the paths
-    described above.
+    search's limits in both cases.  A bf16 bank's rows are multiplied as bf16 matrix operands against a bf16 split of the query
+    (one pass by default, SKYEMB_PREFILTER_LO=1: two); a row with an inf / NaN element, a nonzero element outside [2^-60, 2^120) or
+    an overflowed weighted norm cannot be bounded in stage 1 and is a candidate of every query, decided by the exact stage, and a
+    query whose largest weighted component lies outside [2^-50, 2^79) is re-run by the token search.  fp32 banks take exactly the
+    paths described above.
 
     ``select`` (None: nothing above changes; a bool tensor [N] or a ``Selection``): only the rows marked True are eligible, with
     the result of the search over the compacted bank and indices mapped back (``cosine_topk_tokens``'s ``select``).  A flat
     [N,D] bank of any dtype is then served as a token bank with one token per row (``stats['path'] == 'tokens'``) under that
     search's limits: k <= 512, D % 64 == 0, D <= 1024, queries in groups of 16.
 
-    A PreparedBank (fp32 or resident fp16) with ``select`` takes the two-stage path under the selection wherever that path
+    A PreparedBank (fp32 or resident fp16 / bf16) with ``select`` takes the two-stage path under the selection wherever that path
     applies to the whole bank (more than 16 queries, k <= 192, N >= 2048, SKYEMB_TOPK_PREFILTER not 0): the result is exactly that
     of ``cosine_topk(queries, PreparedBank(bank[select], weights), k)`` -- scores bit for bit, order (score desc, index asc), ties
     to the lower bank row -- with every index mapped back to this bank, then offset by ``idx_offset``.  Nothing is gathered: stage 1
@@ -334,7 +365,7 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     if Q == 0:                                      # nothing to search for (an empty target list): empty result, no launch
         return (torch.empty(0, k, device=q.device), torch.empty(0, k, device=q.device, dtype=torch.int64))
     two_stage = _prefilter_enabled() and ops.topk_prefilter_applicable(Q, N, D, k)
-    if pb.dtype != torch.float32:                   # a resident fp16 bank: the two-stage path on its rows, or the token search
+    if pb.dtype != torch.float32:                   # a resident fp16 / bf16 bank: the two-stage path on its rows, or the token search
         if not two_stage:
             return cosine_topk_tokens(q, pb._tokens, k, 'min', None, eps, process_group, world_size, prune, stats)
         _check_token_shape("cosine_topk", Q, 1, D, k)      # the limits of the route its uncertified queries take

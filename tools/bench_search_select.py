@@ -11,7 +11,8 @@ Legs, interleaved round by round after a warm-up of each (host clock around a ca
   compact_r10           alternative 2: PreparedBank(bank[flags]) built from scratch + one search (gather, norms, half image)
 and, once per selection, the preparation the Selection keeps (two short launches + a read-back).
 Writes one JSON file.  usage: python tools/bench_search_select.py [--rounds 10] [--out profiles/search_select_1m.json]
-(--slow-rounds 0 leaves the two alternatives out, --dtypes fp32 runs one bank: a short run for a kernel trace)"""
+(--slow-rounds 0 leaves the two alternatives out, --dtypes fp32 runs one bank: a short run for a kernel trace; --dtypes takes fp32, fp16
+and bf16 -- the 16-bit banks are built through PreparedBank.resident)"""
 import argparse
 import json
 import os
@@ -47,7 +48,7 @@ def summary(t):
 
 def one_dtype(a, dtype, queries, w):
     bank = rows(a.N, a.D, dtype)
-    pb = PreparedBank(bank, w)
+    pb = PreparedBank(bank, w) if dtype == torch.float32 else PreparedBank.resident(bank, w)   # (a bf16 bank has no other way in)
     g = torch.Generator(device="cuda").manual_seed(11)
     u = torch.rand(a.N, device="cuda", generator=g)
     runs = torch.rand((a.N + 4095) // 4096, device="cuda", generator=g) < 0.1
@@ -63,7 +64,8 @@ def one_dtype(a, dtype, queries, w):
         legs[n] = lambda s=s, n=n: cosine_topk(queries, pb, a.k, stats=stats[n], select=s)
     qs = queries[:a.token_queries]
     slow = {"tokens_r10": lambda: cosine_topk(qs, bank, a.k, weights=w, select=sels["r10"]),
-            "compact_r10": lambda: cosine_topk(queries, PreparedBank(bank[flags["r10"]], w), a.k)}
+            "compact_r10": lambda: cosine_topk(queries, (PreparedBank if dtype == torch.float32 else PreparedBank.resident)(
+                bank[flags["r10"]], w), a.k)}
     if a.slow_rounds == 0:                                        # (a profiler run of the feature's own legs)
         slow = {}
     for fn in list(legs.values()) * 2 + list(slow.values()):      # warm-up: code objects, images, the allocator's blocks
@@ -106,7 +108,7 @@ def main():
     w = w / w.sum()
     res = {"tool": "bench_search_select", "Q": a.Q, "N": a.N, "D": a.D, "k": a.k, "rounds": a.rounds}
     for name in a.dtypes.split(","):
-        res[name] = one_dtype(a, {"fp32": torch.float32, "fp16": torch.float16}[name], queries, w)
+        res[name] = one_dtype(a, {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}[name], queries, w)
         torch.cuda.empty_cache()
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
