@@ -576,6 +576,26 @@ int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, const float *qn
                                                 const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
                                                 int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
                                                 float *out_s, int64_t *out_i, int *redo, void *stream);
+/* The two-stage many-query search over a resident 16-bit PATCH-TOKEN bank [N, P, D] (dtype SKYEMB_F16 or SKYEMB_BF16; 16-byte
+ * aligned), per-image combine SKYEMB_COMBINE_MIN or SKYEMB_COMBINE_MAX: scores and image indices are bit for bit those of
+ * skyemb_cosine_token_topk_lp + skyemb_topk_merge over the same bank -- order (score desc, image asc), images scoring -inf never
+ * returned, tail (-inf, -1).  xn: skyemb_weighted_norms_lp of the N P rows; rowp / tail: skyemb_resident_rowp over the flat
+ * [N P, D] rows.  Stage 1 is the row search's matrix-core pass; an image is a candidate when every (min) / some (max) row of it
+ * passes the row test.  After every slice of tiles each candidate image is re-scored exactly (P token scores by the contract's
+ * chain on the widened rows, then the combine) and merged into the query's running top-k, whose k-th best score is the next
+ * slice's threshold: an exact lower bound at all times, so nothing is left to certify.  thr0 [Q] (or NULL): a floor, the k-th best
+ * combined score over any sample of whole images.  redo[q] != 0: a candidate list or staging region was full, or the query is
+ * outside what stage 1 bounds (a zero query; bf16: skyemb_cosine_topk_prefiltered_resident's window) -- the caller runs it through
+ * skyemb_cosine_token_topk_lp.  Variant: SKYEMB_PREFILTER_LO as for the row search.
+ *   skyemb_token_prefilter_applicable   the shape limits: P a divisor of 64, D % 32 == 0, 128 <= D <= 4096, k <= 256, k <= N,
+ *                                       2048 <= N P < 2^31.  A refusal leaves them as the error text (skyemb_last_error).
+ *   skyemb_token_prefilter_ws_bytes     bytes of `ws`. */
+int skyemb_token_prefilter_applicable(int Q, int64_t N, int P, int D, int k);
+int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k);
+int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                          const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
+                                          int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                          int64_t *out_i, int *redo, void *stream);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

@@ -200,7 +200,12 @@ def main():
             tl = (tl - mean_feats) / (std_feats + 1e-8)
             queries, w = target_queries(tl, n_targets, args.per_target)
             if args.metric == 'cosine':
-                scores, idx = search.cosine_topk_tokens(queries, bank, min(k, bank.shape[0]), combine=args.combine,
+                if bank.dtype != torch.float32 and not args.per_target and bank.data_ptr() % 16 == 0:
+                    # many targets over a 16-bit bank: the two-stage route where it applies, identical results by contract
+                    tokens = search.TokenBank.resident(bank, w)
+                else:
+                    tokens = bank
+                scores, idx = search.cosine_topk_tokens(queries, tokens, min(k, bank.shape[0]), combine=args.combine,
                                                         weights=w, top_t=args.n_top_sims, select=select)
             else:
                 scores, idx = search.distance_topk_tokens(queries, bank, min(k, bank.shape[0]), metric=args.metric,

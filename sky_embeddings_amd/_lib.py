@@ -174,6 +174,11 @@ PROTOTYPES = {
     "skyemb_cosine_topk_prefiltered_resident_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64,
                                                             c_i32, c_i32, c_f32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_topk_prefilter_eps_a_resident": (c_f64, [c_i32, c_i32, c_i32]),
+    # the two-stage search over a resident 16-bit patch-token bank (min | max): additive again
+    "skyemb_token_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),
+    "skyemb_token_prefilter_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "skyemb_cosine_topk_tokens_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32,
+                                                      c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

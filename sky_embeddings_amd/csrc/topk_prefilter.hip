@@ -462,14 +462,18 @@ __device__ __forceinline__ void wait_vmcnt() {
 // position is its own tile: the instruction stream of the unselected search.
 // BF: the operands are bf16 (a resident bf16 bank, query16_kernel<true>'s images): the same bytes through the same ring and fragments,
 // multiplied by v_mfma_f32_16x16x32_bf16 -- the one difference.  Without BF: the instruction stream it has always been.
-template <int MODE, bool LO, bool SEL, bool BF = false>
+// TOK (a resident token bank, "Patch-token banks" below; MODE 1 and 2 only): the rows are the N * P token rows of N images, P = 2^lgp
+// a divisor of 64 (tok = lgp | is_max << 8), and the candidates are IMAGES: between the masks and the appends the pass bits of an
+// image's P rows are folded -- AND under 'min', OR under 'max' -- into the image's first row, whose lane appends the image number.
+// Without TOK `tok` is not read: the instruction stream of the row search.
+template <int MODE, bool LO, bool SEL, bool BF = false, bool TOK = false>
 __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict__ qh, const half_t *__restrict__ ql,
                                                        const half_t *__restrict__ bank16, const float4 *__restrict__ rowp,
                                                        const int *__restrict__ tiles,
                                                        const float4 *__restrict__ qpar, int Q, int64_t N, int D, int t0, int t1,
                                                        int cap, int *__restrict__ cnt, int *__restrict__ cand_i, float *__restrict__ cand_d,
                                                        uint4 *__restrict__ wg_list, int *__restrict__ wg_count, int capw,
-                                                       int *__restrict__ overflow
+                                                       int *__restrict__ overflow, int tok
 #if defined(PF_STAMP) || defined(PF_CLOCK)
                                                        , unsigned long long *__restrict__ dbg
 #endif
@@ -707,6 +711,26 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
             mr[r] = 0;
         }
 #endif
+        if constexpr (TOK) {
+            // Rows of a 16-row block lie across the 16 lanes l16; the four blocks of the wave's strip are bit j of each nibble.  An
+            // image is 2^lgp neighbouring rows of the strip.  Up to 16 rows: a tree over the lane bits with DPP row shifts (lane l
+            // takes lane l + o of its 16-lane row; the first lane of an aligned group ends with the fold of the whole group, the
+            // other lanes are cleared).  No LDS traffic.  32 / 64 rows: bit pairs / all four bits of each nibble besides.
+            const int lgp = tok & 255;
+            const bool is_max = (tok >> 8) != 0;                 // wave-uniform, like lgp
+            const int lg16 = lgp < 4 ? lgp : 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                unsigned int m = mr[r], u;
+                if (lg16 >= 1) { u = (unsigned int)__builtin_amdgcn_update_dpp((int)m, (int)m, 0x101, 0xF, 0xF, false); m = is_max ? (m | u) : (m & u); }   // row_shl:1
+                if (lg16 >= 2) { u = (unsigned int)__builtin_amdgcn_update_dpp((int)m, (int)m, 0x102, 0xF, 0xF, false); m = is_max ? (m | u) : (m & u); }   // row_shl:2
+                if (lg16 >= 3) { u = (unsigned int)__builtin_amdgcn_update_dpp((int)m, (int)m, 0x104, 0xF, 0xF, false); m = is_max ? (m | u) : (m & u); }   // row_shl:4
+                if (lg16 >= 4) { u = (unsigned int)__builtin_amdgcn_update_dpp((int)m, (int)m, 0x108, 0xF, 0xF, false); m = is_max ? (m | u) : (m & u); }   // row_shl:8
+                if (lgp >= 5) { u = m >> 1; m = (is_max ? (m | u) : (m & u)) & 0x55555555u; }    // blocks (0, 1) -> bit 0, (2, 3) -> bit 2
+                if (lgp >= 6) { u = m >> 2; m = (is_max ? (m | u) : (m & u)) & 0x11111111u; }    // all four blocks -> bit 0
+                mr[r] = (l16 & ((1 << lg16) - 1)) == 0 ? m : 0u;
+            }
+        }
         auto passed = [&](int i, int r, int j) -> bool { return (mr[r] >> ((MI - 1 - i) * 4 + j)) & 1u; };
         // Appends are rare (a few per wave and item): the walk over the lane's 128 bits is pruned by WAVE-UNIFORM branches (a
         // ballot per block, then per query row of a flagged block); per-lane branches only below those.  (Thirty-two per-lane
@@ -747,7 +771,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
                                 if (passed(i, r, j)) {
                                     const int pos = atomicAdd(cnt + q, 1);
                                     if (pos < cap) {
-                                        cand_i[(int64_t)q * cap + pos] = t * BT + wn * 64 + j * 16 + l16;
+                                        cand_i[(int64_t)q * cap + pos] = (t * BT + wn * 64 + j * 16 + l16) >> (TOK ? (tok & 255) : 0);
                                         cand_d[(int64_t)q * cap + pos] = acc[i][j][r];
                                     }
                                 }
@@ -787,7 +811,7 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
         uint4 *dst = wg_list + (int64_t)blockIdx.x * capw;
         for (int e = tid; e < n; e += NT) {
             const uint2 c = stg[e];
-            const int q = qt * QT + (int)(c.x >> 8), row = t * BT + (int)(c.x & 255u);
+            const int q = qt * QT + (int)(c.x >> 8), row = (t * BT + (int)(c.x & 255u)) >> (TOK ? (tok & 255) : 0);   // TOK: the image
 #ifdef PF_NOFLUSHSTORE
             asm volatile("" ::"v"(q), "v"(row), "v"(c.y));
             continue;
@@ -1450,7 +1474,7 @@ static int topk_prefiltered(const char *who, const float *tw, const float *qn, i
 #define PF_DBG
 #endif
 #define PF_ARGS(B, T0, T1, TL) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, TL, w.qpar, Q, N, D, T0, T1, cap, w.cnt, w.cand_i, \
-                               w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow PF_DBG
+                               w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, 0 PF_DBG
 #define PF_LAUNCH_AS(M, L, S, B, T0, T1, TL)                                                                                   \
     do {                                                                                                                       \
         if (bf) hipLaunchKernelGGL((prefilter_kernel<M, L, S, true>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL)); \
@@ -1633,4 +1657,288 @@ extern "C" int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, cons
                   "skyemb_cosine_topk_prefiltered_resident_sel: the bank and the tail tile must be 16-byte aligned");
     return topk_prefiltered("skyemb_cosine_topk_prefiltered_resident_sel", tw, qn, Q, nullptr, xn, bank16, tail, rowp_sel, N, D, k, eps,
                             idx_offset, nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live, true);
+}
+
+// ---- Patch-token banks: the same two stages over a resident 16-bit token bank [N, P, D], per-image combine min | max -------------------
+// (skyemb_cosine_topk_tokens_prefiltered).  Stage 1 is prefilter_kernel<.., TOK> over the flat [N P, D] rows with the row constants of
+// skyemb_resident_rowp: an image can reach a query's top-k under 'min' only if EVERY one of its P rows passes the row test
+// (min_i e_i >= tau implies U_i >= tau for every i), under 'max' only if SOME row passes -- the fold of the pass bits in the item
+// epilogue.  P divides 64, so an image never leaves one wave's 64-row strip, and the N P rows are whole images: the tail tile's
+// padding rows belong to none.  A row the bound gives up on passes every test, so its image is decided by stage 2 under both
+// combines (under 'min' when its other rows pass too -- and if they do not, the image is out whatever that row scores).
+// tau_q is EXACT at all times: the k-th best exact combined score over the images decided so far (or the caller's floor, itself the
+// k-th best of a sample).  After every slice of tiles token_rescore_kernel re-scores each candidate image of the slice -- P token
+// scores by the contract's chain on the widened rows, finish_score, then fminf / fmaxf over the tokens (-inf for a NaN score, as the
+// grouped search combines them) --, merges them into the query's running list of at most k (score desc, image asc: one 64-bit key,
+// so ties need no second rule) and publishes the new tau_q into qpar.  Every image that passes stage 1 is re-scored, so nothing is
+// left to certify: the only failure is a full candidate list or staging region, which flags the query (redo) for the grouped search.
+// A query whose eps_a ||q'|| is 0 or not finite (a zero query: 0 * inf in the test of an unboundable row) is flagged as well.
+namespace {
+
+constexpr int TOK_KMAX = RESCORE_MAX;      // the running list of a query: at most k <= TOK_KMAX images
+
+__device__ __forceinline__ unsigned long long image_key(float score, int image) {
+    return ((unsigned long long)orderable(score) << 32) | (unsigned int)~(unsigned int)image;   // larger: better score, then lower image
+}
+
+// key of the kth largest (1-based, kth <= n) among the 64-bit keys[0..n) (LDS); 8 radix passes of 8 bits.  All threads return it.
+__device__ unsigned long long radix_kth_largest64(const unsigned long long *keys, int n, int kth, int *hist, int tid, int nthreads) {
+    unsigned long long prefix = 0, mask = 0;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        for (int b = tid; b < 256; b += nthreads) hist[b] = 0;
+        __syncthreads();
+        for (int e = tid; e < n; e += nthreads) {
+            const unsigned long long kx = keys[e];
+            if ((kx & mask) == prefix) atomicAdd(&hist[(int)((kx >> shift) & 255ull)], 1);
+        }
+        __syncthreads();
+        radix_pick_bin(hist, kth, tid);
+        __syncthreads();
+        const int b = hist[256];
+        kth = hist[257];
+        prefix |= (unsigned long long)b << shift;
+        mask |= 255ull << shift;
+        __syncthreads();
+    }
+    return prefix;
+}
+
+// after init_state_kernel: empty running lists, a floor that is not a number counts as none, and the queries stage 1 cannot serve
+__global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, float *__restrict__ tau_q, int *__restrict__ rn,
+                                   int *__restrict__ overflow) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    rn[q] = 0;
+    if (!(tau_q[q] == tau_q[q])) tau_q[q] = -INFINITY;        // (init_state_kernel has opened the test for it already)
+    const float c = qbase[q].y;                                // eps_a ||q'||
+    if (!(c > 0.f && c < INFINITY)) overflow[q] = 1;
+}
+
+// one workgroup (256 threads) per query: the exact combined scores of the slice's candidate images, the merge into the running
+// list, the new threshold; final: the ordered result.  lgp: P = 2^lgp <= 64 tokens, one lane each, 256 / P images per round.
+template <typename X>
+__device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank,
+                                                   const float *__restrict__ xn, int64_t N, int D, int lgp, int is_max, int k, float eps,
+                                                   int64_t idx_offset, int cap, const float4 *__restrict__ qbase, int *__restrict__ cnt,
+                                                   const int *__restrict__ cand_i, unsigned long long *__restrict__ list,
+                                                   int *__restrict__ rn, float4 *__restrict__ qpar, float *__restrict__ tau_q,
+                                                   int *__restrict__ overflow, int final, float *__restrict__ out_s,
+                                                   int64_t *__restrict__ out_i, int *__restrict__ redo) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long *keys = (unsigned long long *)smem;     // [TOK_KMAX + cap] the running list, then the slice's candidates
+    unsigned long long *kept = keys + TOK_KMAX + cap;          // [TOK_KMAX] the new running list
+    float *sq = (float *)(kept + TOK_KMAX);                    // [D] weighted query
+    int *hist = (int *)(sq + D);                               // [260] + two counters
+    const int tid = threadIdx.x, q = blockIdx.x;
+    const int raw = cnt[q];
+    const int n = raw < cap ? raw : cap;
+    const int r0 = rn[q];                                      // <= k <= TOK_KMAX
+    bool bad = raw > cap;                                      // more candidates than the list holds: the grouped search decides
+    for (int d = tid; d < D; d += 256) sq[d] = tw[(int64_t)q * D + d];
+    unsigned long long *mine = list + (int64_t)q * TOK_KMAX;
+    for (int e = tid; e < r0; e += 256) keys[e] = mine[e];
+    if (tid == 0) { hist[260] = 0; hist[261] = 0; }
+    __syncthreads();
+    const int P = 1 << lgp, G = 256 >> lgp;
+    const int g = tid >> lgp, p = tid & (P - 1);
+    const float qnv = qn[q];
+    for (int base = 0; base < n; base += G) {                  // (uniform trip count: every lane takes part in the shuffles)
+        const int c = base + g;
+        int img = c < n ? cand_i[(int64_t)q * cap + c] : 0;
+        if (img < 0 || img >= N) { img = 0; bad = true; }      // never read outside the bank (stage 1 appends images of real rows only)
+        const int64_t row = (int64_t)img * P + p;
+        const X *x = bank + row * D;
+        float acc = 0.f;
+        for (int d = 0; d < D; d += 4) {                       // explicit fmaf only: the contract's chain, d ascending
+            const float4 v = row4(x + d);
+            acc = fmaf(sq[d], v.x, acc);
+            acc = fmaf(sq[d + 1], v.y, acc);
+            acc = fmaf(sq[d + 2], v.z, acc);
+            acc = fmaf(sq[d + 3], v.w, acc);
+        }
+        float s = finish_score(acc, qnv, xn[row], eps);        // a NaN score is -inf: out under min, ignored under max
+        for (int o = 1; o < P; o <<= 1) {
+            const float u = __shfl_xor(s, o, 64);
+            s = is_max ? fmaxf(s, u) : fminf(s, u);
+        }
+        // an image that scores -inf is never returned: key 0, below every key that counts
+        if (p == 0 && c < n) keys[r0 + c] = s > -INFINITY ? image_key(s, img) : 0ull;
+    }
+    if (__syncthreads_or(bad) && tid == 0) overflow[q] = 1;
+    const int m = r0 + n;
+    int live = 0;
+    for (int e = tid; e < m; e += 256) live += keys[e] != 0ull ? 1 : 0;
+    if (live) atomicAdd(&hist[260], live);
+    __syncthreads();
+    live = hist[260];
+    const int kk = live < k ? live : k;                        // the new running list's length
+    unsigned long long kth = ~0ull;
+    if (kk > 0) kth = radix_kth_largest64(keys, m, kk, hist, tid, 256);   // (keys are distinct: exactly kk of them are >= kth)
+    for (int e = tid; e < m; e += 256)
+        if (kk > 0 && keys[e] >= kth) {
+            const int slot = atomicAdd(&hist[261], 1);
+            if (slot < TOK_KMAX) kept[slot] = keys[e];         // (always: distinct keys)
+        }
+    __syncthreads();
+    for (int e = tid; e < kk; e += 256) mine[e] = kept[e];
+    if (tid == 0) {
+        rn[q] = kk;
+        cnt[q] = 0;
+        float tau = tau_q[q];
+        if (kk == k) tau = fmaxf(tau, unorderable((unsigned int)(kth >> 32)));   // k images decided: their k-th best exact score
+        tau_q[q] = tau;
+        const float4 qb = qbase[q];
+        const float t = tau > -3.0e38f ? tau : -3.0e38f;       // (select_kernel's parameters of the next phase)
+        float a = t * qb.x, b = t * eps * qb.z;
+        a -= fabsf(a) * 0x1p-19f;
+        b -= fabsf(b) * 0x1p-19f;
+        if (!(a > -3.0e38f)) a = -3.0e38f;
+        qpar[q] = test_row(a, b, qb.y);
+    }
+    if (!final) return;
+    for (int e = tid; e < k; e += 256) {
+        if (e < kk) {
+            const unsigned long long me = kept[e];
+            int rank = 0;
+            for (int j = 0; j < kk; ++j) rank += kept[j] > me ? 1 : 0;
+            out_s[(int64_t)q * k + rank] = unorderable((unsigned int)(me >> 32));
+            out_i[(int64_t)q * k + rank] = idx_offset + (int64_t)(~(unsigned int)me);
+        } else {
+            out_s[(int64_t)q * k + e] = -INFINITY;
+            out_i[(int64_t)q * k + e] = -1;
+        }
+    }
+    if (tid == 0) redo[q] = overflow[q] ? 1 : 0;               // (this thread's own store above included)
+}
+
+#define TOKEN_RESCORE_PARAMS(X)                                                                                                  \
+    const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank, const float *__restrict__ xn, int64_t N, \
+        int D, int lgp, int is_max, int k, float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase,                 \
+        int *__restrict__ cnt, const int *__restrict__ cand_i, unsigned long long *__restrict__ list, int *__restrict__ rn,          \
+        float4 *__restrict__ qpar, float *__restrict__ tau_q, int *__restrict__ overflow, int final, float *__restrict__ out_s,     \
+        int64_t *__restrict__ out_i, int *__restrict__ redo
+#define TOKEN_RESCORE_PASS tw, qn, bank, xn, N, D, lgp, is_max, k, eps, idx_offset, cap, qbase, cnt, cand_i, list, rn, qpar, tau_q, overflow, \
+                           final, out_s, out_i, redo
+__global__ __launch_bounds__(256) void token_rescore_lp_kernel(TOKEN_RESCORE_PARAMS(half_t)) { token_rescore_body<half_t>(TOKEN_RESCORE_PASS); }
+__global__ __launch_bounds__(256) void token_rescore_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t)) { token_rescore_body<bf16_t>(TOKEN_RESCORE_PASS); }
+#undef TOKEN_RESCORE_PARAMS
+#undef TOKEN_RESCORE_PASS
+
+inline int log2_of(int P) {
+    int l = 0;
+    while ((1 << l) < P) ++l;
+    return l;
+}
+
+}  // namespace
+
+#define TOKEN_PREFILTER_MSG "many-query patch-token search: needs P a divisor of 64, D %% 32 == 0, 128 <= D <= 4096, 1 <= k <= %d, " \
+                            "k <= N, 2048 <= N * P < 2^31 rows and Q >= 1 (Q=%d N=%lld P=%d D=%d k=%d)"
+extern "C" int skyemb_token_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
+    const bool ok = Q >= 1 && N >= 1 && P >= 1 && P <= 64 && 64 % P == 0 && D % BK == 0 && D >= 4 * BK && D <= 4096 && k >= 1 &&
+                    k <= TOK_KMAX && k <= N && N * P >= 8 * BT && N * P < (1ll << 31);
+    if (!ok) skyemb_set_error(TOKEN_PREFILTER_MSG, TOK_KMAX, Q, (long long)N, P, D, k);
+    return ok ? 1 : 0;
+}
+
+extern "C" int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k) {
+    return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr) + align256((int64_t)Q * TOK_KMAX * 8);
+}
+
+extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                     const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                                     float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                     float *out_s, int64_t *out_i, int *redo, void *stream) {
+    const char *who = "skyemb_cosine_topk_tokens_prefiltered";
+    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
+    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "%s: null argument", who);
+    SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: the two-stage token search "
+                  "combines by min or max (mean is served by skyemb_cosine_token_topk_lp)", who, combine);
+    SKY_CHECK_ARG(skyemb_token_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
+    const int64_t R = N * P;                                   // token rows: whole images, P | 64 | BT
+    SKY_CHECK_ARG(R % BT == 0 || tail, "%s: N * P = %lld rows are no whole number of %d-row tiles: the tail tile of skyemb_resident_rowp "
+                  "is needed", who, (long long)R, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "%s: the bank and the tail tile must be 16-byte aligned", who);
+    const bool bf = dtype == SKYEMB_BF16;
+    const char *lo_env = getenv("SKYEMB_PREFILTER_LO");        // the variant rule of topk_prefiltered
+    const bool use_lo = bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
+    SKY_CHECK_ARG(ceil_div64(ceil_div64(R, BT), 8) * ceil_div64(Q, qtile(use_lo)) * (D / BK) < (1ll << 31),
+                  "%s: Q x N P too large: ceil(N P / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31 (Q=%d N=%lld P=%d D=%d); search the "
+                  "queries in batches", who, qtile(use_lo), Q, (long long)N, P, D);
+    const int cap = skyemb_topk_prefilter_cap(k);
+    SKY_CHECK_ARG(ws_bytes >= skyemb_token_prefilter_ws_bytes(Q, D, k), "%s: workspace too small", who);
+    hipStream_t st = (hipStream_t)stream;
+    Workspace w;
+    const int64_t used = carve((char *)ws, Q, D, cap, &w);
+    unsigned long long *list = (unsigned long long *)((char *)ws + used);
+    int *rn = w.nsel;
+    const float eps_a = (float)((bf ? eps_a_bf16_of(D, use_lo) : eps_a_of(D, use_lo, true)) * (1.0 + 1e-6));
+    const dim3 qgrid((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4));
+    if (bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
+    else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
+    const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
+    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
+                       w.qpar, w.tau, w.cnt, w.overflow, 0, bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f, bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
+    hipLaunchKernelGGL(token_state_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, Q, (const float4 *)w.qbase, w.tau, rn, w.overflow);
+    const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
+    constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
+    const int smem_re = (TOK_KMAX + cap + TOK_KMAX) * 8 + D * 4 + 264 * 4;
+    int rc = 0;
+#define TK_ATTR(M, L)                                                                                                     \
+    if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, true>, smem_max, who);   \
+    if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true>, smem_max, who)
+    TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true);
+#undef TK_ATTR
+    if (rc == 0) rc = sky_set_lds_limit(bf ? (const void *)token_rescore_bf_kernel : (const void *)token_rescore_lp_kernel,
+                                        (2 * TOK_KMAX + 8192) * 8 + 4096 * 4 + 264 * 4, who);
+    if (rc != 0) return rc;
+    const int lgp = log2_of(P), is_max = combine == SKYEMB_COMBINE_MAX ? 1 : 0;
+    const int tok = lgp | (is_max << 8);
+    // the slices of topk_prefiltered's schedule, the first counted in images (96 k of them: the floor comes from a sample of a small
+    // multiple of k images and still passes several per cent of them, so that slice appends directly); no take-all slice
+    const int T = (int)(R / BT);                               // whole tiles; the last R % BT rows follow from `tail`
+    const bool has_tail = R % BT != 0;
+    int direct_end = (int)(ceil_div64((int64_t)96 * k * P, BT) < T ? ceil_div64((int64_t)96 * k * P, BT) : T);
+    if (direct_end < T / 128) direct_end = T / 128;
+    if (direct_end < 1) direct_end = 1;
+    const int ends[5] = {direct_end, T / 32, T / 8, T / 2, T};
+#define TK_ARGS(B, T0, T1) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, (const int *)nullptr, w.qpar, Q, R, D, T0, T1, cap, w.cnt, \
+                           w.cand_i, w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, tok
+#define TK_LAUNCH(M, B, T0, T1)                                                                                                              \
+    do {                                                                                                                                     \
+        if (bf && use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true, false, true, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));   \
+        else if (bf) hipLaunchKernelGGL((prefilter_kernel<M, false, false, true, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));      \
+        else if (use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true, false, false, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));  \
+        else hipLaunchKernelGGL((prefilter_kernel<M, false, false, false, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));             \
+    } while (0)
+    int t0 = 0;
+    bool direct_done = false;
+    for (int p = 0; p < 5; ++p) {
+        const int t1 = ends[p];
+        if (t1 <= t0) continue;
+        if (!direct_done) {
+            TK_LAUNCH(1, bank16, t0, t1);
+            direct_done = true;
+        } else {
+            TK_LAUNCH(2, bank16, t0, t1);
+            hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count, w.capw,
+                               cap, w.cnt, w.cand_i, w.cand_d);
+        }
+        const int final = t1 == T;
+        if (final && has_tail) {
+            // the last R % BT rows, tile T from the padded copy (topk_prefiltered's tail launch): direct appends behind the slice's
+            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T * BT * D * sizeof(half_t));
+            TK_LAUNCH(1, tail_base, T, T + 1);
+        }
+#define TK_RESCORE(B) tw, qn, B, xn, N, D, lgp, is_max, k, eps, idx_offset, cap, (const float4 *)w.qbase, w.cnt, (const int *)w.cand_i, list, rn, \
+                      w.qpar, w.tau, w.overflow, final, out_s, out_i, redo
+        if (bf) hipLaunchKernelGGL(token_rescore_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16));
+        else hipLaunchKernelGGL(token_rescore_lp_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const half_t *)bank16));
+#undef TK_RESCORE
+        t0 = t1;
+    }
+#undef TK_LAUNCH
+#undef TK_ARGS
+    SKY_LAUNCH_CHECK(who);
+    return 0;
 }

@@ -525,6 +525,27 @@ def cosine_topk_prefiltered_resident(tw, qn, bank16, xn, tail, rowp, k, eps, idx
     return ws
 
 
+def token_prefilter_refusal(Q, N, P, D, k):
+    """None when the two-stage token search takes the shape, else the library's own statement of its limits."""
+    L = lib()
+    return None if L.skyemb_token_prefilter_applicable(Q, N, P, D, k) else L.skyemb_last_error().decode()
+
+
+def cosine_topk_tokens_prefiltered(tw, qn, tokens, xn, tail, rowp, k, combine, eps, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """The two-stage many-query search over a resident 16-bit token bank ``tokens`` [N, P, D] and the (tail, rowp) of
+    ``resident_rowp`` over its flat rows; ``combine``: COMBINE_CODES['min'] or ['max'] (include/skyemb.h)."""
+    Q, D = tw.shape
+    N, P = tokens.shape[:2]
+    code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered")
+    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_tokens_prefiltered(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp), N, P, D, k, combine,
+                                                      eps, idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
+                                                      _stream()), "skyemb_cosine_topk_tokens_prefiltered")
+    return ws
+
+
 def prefilter_select_prepare(words, N, rowp):
     """What the two-stage search needs of a selection (packed ``words`` of ``pack_select``) over a bank of N rows with row constants
     ``rowp`` (``bank16_prepare`` / ``bank16_rowp_lp``): (rowp_sel, tiles, n_live, last_live) -- the masked copy of the constants (a

@@ -406,7 +406,13 @@ class TokenBank:
 
     ``bank`` is fp32, or fp16 / bf16 for a half-precision resident bank (``dtype``): such a bank IS the fp32 bank its elements
     widen to -- norms (fp32) and scores are those of the widened bank bit for bit, for half the memory and half the bytes per
-    pass.  The only approximation is the rounding when the bank was stored (``standardise_to``)."""
+    pass.  The only approximation is the rounding when the bank was stored (``standardise_to``).
+
+    ``TokenBank.resident(bank)`` (fp16 / bf16 only) is the same object in every respect -- same norms, ``set_weights``, ``sample`` --
+    that also opens the two-stage many-query route of ``cosine_topk_tokens`` (see there): it carries, built on first use and
+    dropped when the weights change, the stage-1 row constants of its N * P rows (``stage1()``: 16 bytes per row and one
+    zero-padded 256-row tail tile).  No fp32 copy and no second image of the bank exist.  The plain constructor never takes that
+    route."""
 
     def __init__(self, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
         ops.bank_dtype_code(bank.dtype, "TokenBank")          # ValueError for anything but fp32 / fp16 / bf16
@@ -414,8 +420,36 @@ class TokenBank:
         self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self.norms = torch.empty(bank.shape[0] * bank.shape[1], device=bank.device)
         self._sample = None
+        self._resident = False                             # True: made by TokenBank.resident
+        self._stage1 = self._boot = None                   # (tail tile, rowp) / the bootstrap sample of the two-stage route
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
+
+    @classmethod
+    def resident(cls, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
+        """A TokenBank over a resident 16-bit token bank: a contiguous, 16-byte aligned [N, P, D] tensor of fp16 or bf16 (ValueError
+        for anything else), whose many-query min / max searches may take the two-stage route (``cosine_topk_tokens``)."""
+        if not isinstance(bank, torch.Tensor) or bank.dtype not in ops.LP_DTYPES:
+            what = bank.dtype if isinstance(bank, torch.Tensor) else type(bank).__name__
+            raise ValueError(f"TokenBank.resident: a resident token bank is torch.float16 or torch.bfloat16, got {what}; an fp32 bank "
+                             f"takes TokenBank(bank)")
+        if bank.dim() != 3 or not bank.is_contiguous():
+            raise ValueError(f"TokenBank.resident: the bank must be a contiguous [N, P, D] tensor, got shape {tuple(bank.shape)}, "
+                             f"strides {tuple(bank.stride())}")
+        if bank.data_ptr() % 16:
+            raise ValueError(f"TokenBank.resident: an {'fp16' if bank.dtype == torch.float16 else 'bf16'} bank must start 16-byte aligned "
+                             "(the search reads it by 16-byte LDS-DMA); this tensor starts at an odd offset of its storage -- clone() it")
+        self = cls(bank, weights, idx_offset)
+        self._resident = True
+        return self
+
+    def stage1(self):
+        """(tail, rowp) of ``ops.resident_rowp`` over the flat [N * P, D] rows: what stage 1 of the two-stage route reads besides the
+        bank itself.  Built on first use, kept until the weights change."""
+        if self._stage1 is None:
+            N, P, D = self.bank.shape
+            self._stage1 = ops.resident_rowp(self.bank.view(N * P, D), self.norms)
+        return self._stage1
 
     def set_weights(self, weights):
         self._version += 1
@@ -426,6 +460,7 @@ class TokenBank:
         else:
             ops.weighted_norms_lp(rows, self.weights, self.norms)
         self._sample = None
+        self._stage1 = self._boot = None
 
     def sample(self, images: int):
         """A strided sample of WHOLE images (tokens [S, P, D] in the bank's dtype + the norms of their S * P rows) used to
@@ -811,6 +846,80 @@ def _topk_tokens(rq: TokenRequest, sc, queries, prune, stats, process_group, wor
     return (out_s.neg_() if sc.negate else out_s), out_i                # distances: (-inf, -1) becomes (+inf, -1)
 
 
+TOKEN_PREFILTER_MIN_Q = 256    # fewest queries sent through the two-stage token route (measured: DESIGN.md section 6, item 17)
+
+
+def _token_prefilter_refusal(rq: TokenRequest):
+    """None when ``cosine_topk_tokens`` serves the request by the two-stage route, else the first reason why the grouped route
+    serves it.  A pure function of the request (and the bank it names): no device work."""
+    tb = rq.bank
+    if tb is None or not getattr(tb, "_resident", False):
+        return "the bank was not made by TokenBank.resident"
+    if rq.metric is not None:
+        return "a distance metric"
+    if rq.combine not in (ops.COMBINE_CODES['min'], ops.COMBINE_CODES['max']):
+        return "combine is neither 'min' nor 'max'"
+    if rq.top_t != 0:
+        return "top_t"
+    if rq.select is not None:
+        return "select"
+    if rq.per_query:
+        return "per-query weights"
+    if rq.P < 1 or 64 % rq.P:
+        return f"P = {rq.P} does not divide 64"
+    if not _prefilter_enabled():
+        return "SKYEMB_TOPK_PREFILTER=0"
+    if rq.Q < TOKEN_PREFILTER_MIN_Q:
+        return f"Q = {rq.Q} < TOKEN_PREFILTER_MIN_Q = {TOKEN_PREFILTER_MIN_Q}"
+    return ops.token_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
+
+
+def _bootstrap_floor(rq: TokenRequest, tw, qn, eps):
+    """[Q] the k-th best combined score of every query over a strided sample of min(N, max(16 k, 256)) whole images, scored by
+    the grouped kernels, one ulp lower: the two-stage route's first threshold, a lower bound of the k-th best over the bank."""
+    tb, k = rq.bank, rq.k
+    S = min(rq.N, max(16 * k, 256))
+    if tb._boot is None or tb._boot[0] != S:
+        idx = _sample_index(S, rq.N, tb.bank.device)
+        tb._boot = (S, tb.bank.index_select(0, idx).contiguous(), tb.norms.view(rq.N, rq.P).index_select(0, idx).contiguous().view(-1))
+    _, st, sn = tb._boot
+    floor = torch.empty(rq.Q, device=tw.device)
+    keys = torch.empty(16, S, device=tw.device)
+    for lo in range(0, rq.Q, 16):
+        g = min(16, rq.Q - lo)
+        ops.cosine_token_scores(tw[lo:lo + g], qn[lo:lo + g], st, sn, rq.combine, eps, keys[:g], 0, None)
+        ops.kth_largest_floor(keys[:g], k, floor[lo:lo + g])
+    return floor
+
+
+def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, process_group, world_size):
+    """The two-stage driver (csrc/topk_prefilter.hip, "Patch-token banks"): one bootstrap floor, one stage-1 pass with exact
+    re-scoring after every slice; flagged queries go through the grouped route, those queries only."""
+    tb, Q, k, dev = rq.bank, rq.Q, rq.k, rq.tokens.device
+    q = queries.to(dev, torch.float32).contiguous()
+    tw, qn = prepare_queries(q, tb.weights)
+    thr0 = _bootstrap_floor(rq, tw, qn, eps)
+    tail, rowp = tb.stage1()
+    out_s = torch.empty(Q, k, device=dev)
+    out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
+    redo = torch.empty(Q, device=dev, dtype=torch.int32)
+    ops.cosine_topk_tokens_prefiltered(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, eps, rq.idx_offset, out_s, out_i, redo, thr0)
+    again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
+    if again.numel():
+        rq2 = dataclasses.replace(rq, Q=int(again.numel()))
+        s2, i2 = _topk_tokens(rq2, _CosineScorer.of(rq2, eps), q.index_select(0, again), prune, None, None, 1)
+        out_s.index_copy_(0, again, s2)
+        out_i.index_copy_(0, again, i2)
+    if stats is not None:
+        stats.update(path="prefiltered", redone=int(again.numel()),
+                     combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+    if world_size > 1:
+        from .distributed import gather_topk
+        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
+        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    return out_s, out_i
+
+
 def _score_tokens(rq: TokenRequest, sc, queries):
     """The scores driver: [Q, N], one pass over the bank per group of ``step`` queries, written straight into its rows."""
     words = None if rq.select is None else rq.select.words
@@ -856,8 +965,21 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     """-> (scores f32 [Q,k], image indices i64 [Q,k]): exact top-k images by the combined score of their P patch tokens
     (reference: compute_similarity with max_pool = False, utils/similarity.py:214-268, + update_best_scores), order
     (score desc, image asc).  ``bank`` is a [N,P,D] tensor (fp32, or fp16 / bf16: see TokenBank) or a TokenBank (this rank's
-    shard of images; ``idx_offset`` = first global image of the shard).  One pass over the bank per group of at most 16 queries (Q > 16 runs ceil(Q / 16) passes: a
-    many-query prefilter for token banks is out of scope).  Images whose combined score is -inf (a NaN token under min / mean)
+    shard of images; ``idx_offset`` = first global image of the shard).  One pass over the bank per group of at most 16 queries
+    (Q > 16 runs ceil(Q / 16) passes) -- the grouped route, ``stats['path'] == 'tokens'``.
+
+    Two-stage route (``stats['path'] == 'prefiltered'``): a ``TokenBank.resident(bank)`` (fp16 / bf16) with ``combine`` 'min' or
+    'max', no ``top_t``, no ``select``, shared weights, P a divisor of 64, at least ``TOKEN_PREFILTER_MIN_Q`` queries, a shape the
+    library takes (D % 32 == 0, 128 <= D <= 4096, 2048 <= N P < 2^31, k <= 256, k <= N) and SKYEMB_TOPK_PREFILTER not 0 is searched
+    in ONE pass for all queries: the bank's rows are multiplied on the 16-bit matrix cores with a proven error bound, an image is
+    a candidate when every ('min') / some ('max') token of it can still reach the query's threshold, and every candidate is
+    re-scored exactly after each slice of the bank, which also makes the threshold exact.  Scores and indices are bit for bit
+    those of the grouped route over the same bank in a plain ``TokenBank``.  ``stats`` gains ``redone`` (queries whose candidate
+    list was full, re-run by the grouped route) and ``combine``.  Everything else is served by the grouped route as ever, never
+    refused.  Out of scope for the two-stage route: 'mean' (it needs per-pair bounds in score units, a division per pair),
+    ``top_t``, ``select``, per-query weights, the distance metrics, fp32 token banks and P not dividing 64.
+
+    Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
     carries its own (``TokenBank.set_weights``), and the argument is then ignored, as ``cosine_topk`` does with a PreparedBank.
 
@@ -890,6 +1012,8 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     both shapes, for weights of any other rank, leading dimension or D.  ``stats['per_query_weights']`` is True and
     ``stats['group']`` is g."""
     rq = _token_request("cosine_topk_tokens", queries, bank, k, combine, _COSINE, weights, top_t, select, world_size)
+    if _token_prefilter_refusal(rq) is None:
+        return _topk_tokens_prefiltered(rq, eps, queries, prune, stats, process_group, world_size)
     return _topk_tokens(rq, _CosineScorer.of(rq, eps), queries, prune, stats, process_group, world_size)
 
 

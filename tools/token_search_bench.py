@@ -7,7 +7,11 @@ usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim
                                          [--bank-dtype f32 | f16 | bf16 | a comma list, e.g. f32,f16,bf16]
                                          [--combine min | mean | max | a comma list] [--top-t T | a comma list, e.g. 4,16]
                                          [--select-frac F | a comma list, e.g. 1.0,0.5,0.1] [--select-pattern random | runs]
-                                         [--fused-only] [--metric MAE | MSE | a comma list]
+                                         [--fused-only] [--metric MAE | MSE | a comma list] [--many-query Q | a comma list]
+--many-query: for every listed Q and every listed 16-bit bank type, interleaved in the same rounds, the grouped route
+(grouped[f16]: search.cosine_topk_tokens over a plain TokenBank, ceil(Q / 16) passes) and the two-stage route (two_stage[f16]: the
+same call over TokenBank.resident with search.TOKEN_PREFILTER_MIN_Q set to 17), combine as --combine; "redone" is the two-stage
+call's count of re-run queries, "equal" whether both returned the same bits.  Nothing else runs in this mode.
 --bank-dtype: element type(s) of the resident token bank the fused pass runs on (16-bit banks: the fp32 bank rounded to nearest);
 the fused variants of every listed type run interleaved in the same rounds, named fused_tokens[f16] etc.; the comparison variants
 (baseline and one-vector) need the fp32 bank and run when f32 is listed.
@@ -105,6 +109,42 @@ def timed(fn):
     return out, e0.elapsed_time(e1)
 
 
+def many_query(a, lp_banks, w):
+    """--many-query: grouped against two-stage over the same resident 16-bit banks."""
+    search.TOKEN_PREFILTER_MIN_Q = 17
+    N, P, D, k = a.images, a.tokens, a.dim, a.k
+    resident = {name: search.TokenBank.resident(tb.bank, w) for name, tb in lp_banks.items()}
+    results = []
+    for Q in a.many_query:
+        q = torch.randn(Q, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2025 + Q))
+        variants, info = {}, {}
+        for combine in a.combine:
+            for name, tb in lp_banks.items():
+                tag = f"[{name}]" + ("" if len(a.combine) == 1 else f"/{combine}")
+                variants["grouped" + tag] = lambda tb=tb, c=combine: search.cosine_topk_tokens(q, tb, k, c)
+                variants["two_stage" + tag] = lambda rb=resident[name], c=combine: search.cosine_topk_tokens(q, rb, k, c)
+                st = {}
+                (gs, gi), (ts_, ti) = variants["grouped" + tag](), search.cosine_topk_tokens(q, resident[name], k, combine, stats=st)
+                info["two_stage" + tag] = dict(path=st.get("path"), redone=st.get("redone"),
+                                               equal=bool(torch.equal(gs, ts_)) and bool(torch.equal(gi, ti)))
+                info["grouped" + tag] = dict(path="tokens")
+        times = {name: [] for name in variants}
+        for it in range(a.warmup + a.iters):
+            for name, fn in variants.items():                # interleaved: every variant once per round
+                _, ms = timed(fn)
+                if it >= a.warmup:
+                    times[name].append(ms)
+        for name, ts in times.items():
+            ts = sorted(ts)
+            results.append(dict(Q=Q, images=N, tokens=P, dim=D, k=k, variant=name, ms_median=round(ts[len(ts) // 2], 4),
+                                ms_min=round(ts[0], 4), ms_max=round(ts[-1], 4), iters=len(ts), **info[name]))
+            print(json.dumps(results[-1]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=250_000)
@@ -121,6 +161,7 @@ def main():
     ap.add_argument("--select-pattern", choices=("random", "runs"), default="random")
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--metric", type=metrics, default=[])
+    ap.add_argument("--many-query", type=int_list, default=[])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("token_search_bench.py needs a GPU")
@@ -140,6 +181,8 @@ def main():
             for s in range(0, N, 5_000):
                 lp[s:s + 5_000] = bank[s:s + 5_000]         # rounds to nearest-even
             lp_banks[name] = search.TokenBank(lp, w)
+    if a.many_query:
+        return many_query(a, lp_banks, w)
     chunk = (1 << 20) // P * P                              # rows per cosine_scores call (streaming score kernel: <= 2^20 rows)
     if with_f32:
         tb = search.TokenBank(bank, w)
