@@ -451,7 +451,10 @@ int skyemb_weighted_norms(const float *x, const float *w, float *norms, float *x
 /* utils/similarity.py:149-172 + 18-35 fused: per-(query tile, bank chunk) exact partial top-k.
  *   tw [Q,D] (= w*t), qn [Q], bank [N,D], xn [N]  ->  part_s f32 / part_i i64 [Q, nchunks, k]
  * (nchunks = skyemb_cosine_topk_chunks(N, Q, D, k): bank chunks of the tiled kernel, or one list per
- * wavefront of the bank-streaming kernel used when Q <= 16).
+ * wavefront of the bank-streaming kernel used when Q <= 16).  The tiled kernel accepts any caller-chosen nchunks > 0: chunks
+ * are ceil(ceil(N / nchunks) / tile) * tile rows long (tile = 256 bank rows; 128 under SKYEMB_TOPK_NW=4 for Q > 16, k <= 128),
+ * so trailing chunks may be ragged or empty, and an empty chunk's list is a lone terminator.  The bank-streaming kernel
+ * (Q <= 16, k <= 128, D % 64 == 0, D <= 1024, unless SKYEMB_TOPK_STREAM=0) does not: any count but the library's is refused.
  * thr0 (optional, [Q]): a pruning floor per query -- only rows scoring STRICTLY above it are kept.  Any value
  * below the true k-th best score is valid (e.g. nextafter(k-th best of a row sample, -inf)) and leaves
  * the result unchanged while removing most list insertions.

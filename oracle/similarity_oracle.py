@@ -178,6 +178,30 @@ def cosine_topk_np(queries, bank, k, weights=None, eps=1e-6, threads=0):
     return s, i
 
 
+def wnorms_np(x, weights=None):
+    """sqrt of the fixed-order chain fma(w[d] * x[d], x[d], acc) per row: the oracle's own bank / query norm."""
+    x = _f32(x)
+    N, D = x.shape
+    w = _f32(weights) if weights is not None else np.ones(D, np.float32)
+    out = np.empty(N, np.float32)
+    L = _lib()
+    L.skyemb_oracle_wnorms.argtypes = [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_int64] * 2 + [ctypes.POINTER(ctypes.c_float)]
+    assert L.skyemb_oracle_wnorms(_p(x), _p(w), N, D, _p(out)) == 0
+    return out
+
+
+def prep_queries_np(queries, weights=None):
+    """The oracle's query side: (tw = w * t rounded once [Q, D], qn [Q])."""
+    q = _f32(queries)
+    Q, D = q.shape
+    w = _f32(weights) if weights is not None else np.ones(D, np.float32)
+    tw, qn = np.empty((Q, D), np.float32), np.empty(Q, np.float32)
+    L = _lib()
+    L.skyemb_oracle_prep_queries.argtypes = [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_int64] * 2 + [ctypes.POINTER(ctypes.c_float)] * 2
+    assert L.skyemb_oracle_prep_queries(_p(q), _p(w), Q, D, _p(tw), _p(qn)) == 0
+    return tw, qn
+
+
 def standardise_np(x, mu, sigma, threads=0):
     """(x - mu) / (sigma + 1e-8), fp32, IEEE divide (utils/similarity.py:101-102)."""
     x = _f32(x)

@@ -208,3 +208,10 @@ int skyemb_oracle_wnorms(const float *X, const float *w, int64_t N, int64_t D, f
     for (int64_t n = 0; n < N; ++n) out[n] = sqrtf(chain_wnorm2(w, X + n * D, D));
     return 0;
 }
+
+/* the query side of the contract on its own: tw = w * t (one rounding) and qn = sqrt(chain fma(tw, t)) -- what
+ * skyemb_weighted_norms writes to xw_out and norms (tests/exact_search_reference.py) */
+int skyemb_oracle_prep_queries(const float *T, const float *w, int64_t Q, int64_t D, float *tw, float *qn) {
+    prep_queries(T, w, Q, D, tw, qn);
+    return 0;
+}
