@@ -599,6 +599,32 @@ int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int 
                                           const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
                                           int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
                                           int64_t *out_i, int *redo, void *stream);
+/* The search above under a SELECTION of the bank's images (words: skyemb_pack_select over the N images; one selection for all
+ * queries).  The result is that of skyemb_cosine_token_topk_sel + skyemb_topk_merge under the same words, bit for bit: the search
+ * over the compacted bank of the selected images, indices mapped back; a deselected image contributes nothing, whatever it holds.
+ *   skyemb_token_prefilter_select_prepare   once per selection, bank and version of rowp (skyemb_resident_rowp over the flat N P
+ *                           rows; P a divisor of 64): rowp_sel [skyemb_bank16_rowp_rows(N P), 4] = rowp with the padding sentinel
+ *                           {0, NaN, 0, 0} in every row of a deselected image -- also where rowp held the "keep for every query"
+ *                           constant of an unboundable row, which under max would make its image a candidate of every query --;
+ *                           tiles (int32 [ceil(N P / 256)]) = the LIVE tiles, ascending: the 256-row tiles with a selected image;
+ *                           cum (int32, same length) = for each live tile the number of selected images up to and including it;
+ *                           info (int32 [2], device) = {the number of live tiles, 1 if the bank's last tile is one of them}.  Two
+ *                           short launches.
+ *   skyemb_cosine_topk_tokens_prefiltered_sel   the pipeline of skyemb_cosine_topk_tokens_prefiltered with rowp_sel, tiles and the
+ *                           two values of info (read back by the caller: 1 <= n_live <= ceil(N P / 256), at least one live WHOLE
+ *                           tile).  Stage 1 walks positions of the live list, the slice schedule runs over their number, the tail
+ *                           tile is launched as the list's last position only when it is live.  direct_end (1 .. n_live): the
+ *                           position at which the first, direct-append slice ends -- the caller takes it from cum (the first position
+ *                           whose count reaches 96 k, at least n_live / 128).  thr0: a floor over a sample of SELECTED whole images.
+ *                           Shape limits and workspace as for the unselected call (on the whole bank's N); redo[q] != 0: the caller
+ *                           runs the query through skyemb_cosine_token_topk_sel under the same words. */
+int skyemb_token_prefilter_select_prepare(const uint32_t *words, int64_t N, int P, const float *rowp, float *rowp_sel, int *tiles,
+                                          int *cum, int *info, void *stream);
+int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                              const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
+                                              int direct_end, int64_t N, int P, int D, int k, int combine, float eps,
+                                              int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                              int64_t *out_i, int *redo, void *stream);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

@@ -17,7 +17,8 @@ limits: -ns <= 512 and a feature width that is a multiple of 64, at most 1024); 
 (smallest) first, as on the streamed path.  ``-nts / --n_top_sims T`` (extension) combines only the T best
 patch scores of a sample (compute_similarity's n_top_sims): streamed without --bank, and with ``--bank -mp False -ct False``
 inside the fused token kernel (1 <= T <= min(patches, 16)).  ``--bank-select-snr`` (extension, only with ``--bank``) encodes
-EVERY row of the test file once and turns the ``-snr`` window into a selection of the resident bank (search.Selection) instead
+EVERY row of the test file once and turns the ``-snr`` window into a selection of the resident bank (search.Selection; a 16-bit
+cosine patch-token bank searches it on the two-stage many-query route when the window keeps at least 2048 token rows) instead
 of filtering before the encoder: another S/N range is then another search over the same bank, not another encoding.  The
 standardisation statistics are those of the first ``-bs`` SELECTED images (the reference's first batch of the filtered set; for
 a 16-bit bank those images are encoded first to get them), results are looked up in the full test file.  It works in all three

@@ -179,6 +179,11 @@ PROTOTYPES = {
     "skyemb_token_prefilter_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "skyemb_cosine_topk_tokens_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32,
                                                       c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    # ... and under a selection of the bank's images: additive again
+    "skyemb_token_prefilter_select_prepare": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_tokens_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                                          c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
+                                                          c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

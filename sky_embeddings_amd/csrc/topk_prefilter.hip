@@ -1824,6 +1824,73 @@ __global__ __launch_bounds__(256) void token_rescore_bf_kernel(TOKEN_RESCORE_PAR
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
 
+// ---- a selection of the bank's IMAGES (skyemb_token_prefilter_select_prepare) -------------------------------------------------------
+// words: bit i & 31 of word i >> 5 is IMAGE i, padding bits zero (skyemb_pack_select); the row constants and the tiles are per
+// token row.  The masked copy: row i keeps its constants iff image i >> lgp is selected; every other row -- the {0, inf, 1, 0} of
+// an unboundable row included: under 'max' it would make its deselected image a candidate of every query -- and every row past
+// R = N P gets the padding sentinel (select_rowp_kernel's rule, image by image).
+__global__ __launch_bounds__(256) void token_select_rowp_kernel(const unsigned int *__restrict__ words, const float4 *__restrict__ rowp,
+                                                                 int64_t R, int lgp, int64_t rows_padded, float4 *__restrict__ rowp_sel) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows_padded) return;
+    const int64_t img = i >> lgp;
+    const bool on = i < R && ((words[img >> 5] >> (img & 31)) & 1u) != 0u;
+    rowp_sel[i] = on ? rowp[i] : make_float4(0.f, NAN, 0.f, 0.f);
+}
+// the live tiles, ascending (select_tiles_kernel's list), and for each the number of selected images up to and including it.  A
+// tile holds BT >> lgp images: whole words down to 32 images (P <= 8), else an aligned field of 16, 8 or 4 bits of one word.
+// info = {the number of live tiles, 1 if the last bank tile is one of them}.  One workgroup, 1024 tiles per round.
+__global__ __launch_bounds__(1024) void token_select_tiles_kernel(const unsigned int *__restrict__ words, int64_t nwords, int lgp,
+                                                                   int tiles_all, int *__restrict__ tiles, int *__restrict__ cum,
+                                                                   int *__restrict__ info) {
+    __shared__ int wlive[16], wcnt[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ipt = BT >> lgp;                                 // images per tile
+    int base = 0, cbase = 0;
+    for (int r0 = 0; r0 < tiles_all; r0 += 1024) {
+        const int t = r0 + tid;
+        int pc = 0;
+        if (t < tiles_all) {
+            const int64_t first = (int64_t)t * ipt;            // a multiple of ipt: the field never leaves its word
+            if (ipt >= 32) {
+                for (int j = 0; j < ipt / 32; ++j) {
+                    const int64_t wi = (first >> 5) + j;
+                    if (wi < nwords) pc += __popc(words[wi]);
+                }
+            } else if ((first >> 5) < nwords) {
+                pc = __popc((words[first >> 5] >> (int)(first & 31)) & ((1u << ipt) - 1u));
+            }
+        }
+        const bool live = pc > 0;
+        int inc = pc;                                          // inclusive scan of the counts over the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += u;
+        }
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) wlive[wave] = __builtin_popcountll(m);
+        if (lane == 63) wcnt[wave] = inc;
+        __syncthreads();
+        int off = base, tot = 0, coff = cbase, ctot = 0;
+        for (int w = 0; w < 16; ++w) {
+            off += w < wave ? wlive[w] : 0;
+            tot += wlive[w];
+            coff += w < wave ? wcnt[w] : 0;
+            ctot += wcnt[w];
+        }
+        off += __builtin_popcountll(m & ((1ull << lane) - 1));
+        if (live) {                                            // off < the number of live tiles <= tiles_all
+            tiles[off] = t;
+            cum[off] = coff + inc;
+        }
+        if (t == tiles_all - 1) info[1] = live ? 1 : 0;
+        base += tot;
+        cbase += ctot;
+        __syncthreads();
+    }
+    if (tid == 0) info[0] = base;
+}
+
 inline int log2_of(int P) {
     int l = 0;
     while ((1 << l) < P) ++l;
@@ -1845,11 +1912,16 @@ extern "C" int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k) {
     return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr) + align256((int64_t)Q * TOK_KMAX * 8);
 }
 
-extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
-                                                     const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
-                                                     float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
-                                                     float *out_s, int64_t *out_i, int *redo, void *stream) {
-    const char *who = "skyemb_cosine_topk_tokens_prefiltered";
+// The pipeline of both entry points.  tiles (NULL: no selection): the search runs under a selection of images prepared by
+// skyemb_token_prefilter_select_prepare -- rowp is then the masked copy, [0, n_live) the positions of the live-tile list the slices
+// walk (the SEL instances of stage 1), last_live says whether the bank's last tile is one of them, and the first (direct-append)
+// slice ends at position direct_sel, which the caller takes from the cumulative counts of selected images.
+static int topk_tokens_prefiltered(const char *who, const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                   const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
+                                   int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                   int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0,
+                                   int direct_sel = 0) {
+    const bool sel = tiles != nullptr;
     SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
     SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "%s: null argument", who);
     SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: the two-stage token search "
@@ -1859,6 +1931,17 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const floa
     SKY_CHECK_ARG(R % BT == 0 || tail, "%s: N * P = %lld rows are no whole number of %d-row tiles: the tail tile of skyemb_resident_rowp "
                   "is needed", who, (long long)R, BT);
     SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "%s: the bank and the tail tile must be 16-byte aligned", who);
+    const int T_tail = (int)(R / BT);                          // whole tiles; the last R % BT rows follow from `tail` as tile T_tail
+    const bool tail_live = R % BT != 0 && (!sel || last_live != 0);
+    const int T = sel ? n_live - (tail_live ? 1 : 0) : T_tail; // positions the slices walk
+    if (sel) {
+        SKY_CHECK_ARG(n_live >= 1 && n_live <= ceil_div64(R, BT) && (last_live == 0 || last_live == 1),
+                      "%s: n_live = %d, last_live = %d: expected 1 .. %lld live tiles and a flag (skyemb_token_prefilter_select_prepare's "
+                      "info)", who, n_live, last_live, (long long)ceil_div64(R, BT));
+        SKY_CHECK_ARG(T >= 1, "%s: the selection's only live tile is the bank's tail tile; the slices need a whole live tile", who);
+        SKY_CHECK_ARG(direct_sel >= 1 && direct_sel <= n_live, "%s: the first slice ends at position %d, expected 1 .. n_live = %d", who,
+                      direct_sel, n_live);
+    }
     const bool bf = dtype == SKYEMB_BF16;
     const char *lo_env = getenv("SKYEMB_PREFILTER_LO");        // the variant rule of topk_prefiltered
     const bool use_lo = bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
@@ -1884,9 +1967,11 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const floa
     constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
     const int smem_re = (TOK_KMAX + cap + TOK_KMAX) * 8 + D * 4 + 264 * 4;
     int rc = 0;
-#define TK_ATTR(M, L)                                                                                                     \
-    if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, true>, smem_max, who);   \
-    if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true>, smem_max, who)
+#define TK_ATTR(M, L)                                                                                                             \
+    if (rc == 0 && !bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, true>, smem_max, who);   \
+    if (rc == 0 && bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true>, smem_max, who);     \
+    if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, false, true>, smem_max, who);     \
+    if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true, true>, smem_max, who)
     TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true);
 #undef TK_ATTR
     if (rc == 0) rc = sky_set_lds_limit(bf ? (const void *)token_rescore_bf_kernel : (const void *)token_rescore_lp_kernel,
@@ -1895,21 +1980,34 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const floa
     const int lgp = log2_of(P), is_max = combine == SKYEMB_COMBINE_MAX ? 1 : 0;
     const int tok = lgp | (is_max << 8);
     // the slices of topk_prefiltered's schedule, the first counted in images (96 k of them: the floor comes from a sample of a small
-    // multiple of k images and still passes several per cent of them, so that slice appends directly); no take-all slice
-    const int T = (int)(R / BT);                               // whole tiles; the last R % BT rows follow from `tail`
-    const bool has_tail = R % BT != 0;
-    int direct_end = (int)(ceil_div64((int64_t)96 * k * P, BT) < T ? ceil_div64((int64_t)96 * k * P, BT) : T);
-    if (direct_end < T / 128) direct_end = T / 128;
-    if (direct_end < 1) direct_end = 1;
+    // multiple of k images and still passes several per cent of them, so that slice appends directly); no take-all slice.  Under a
+    // selection the fractions are taken of the live tiles and the caller has counted the 96 k SELECTED images.
+    int direct_end;
+    if (sel) {
+        direct_end = direct_sel < T ? direct_sel : T;
+    } else {
+        direct_end = (int)(ceil_div64((int64_t)96 * k * P, BT) < T ? ceil_div64((int64_t)96 * k * P, BT) : T);
+        if (direct_end < T / 128) direct_end = T / 128;
+        if (direct_end < 1) direct_end = 1;
+    }
     const int ends[5] = {direct_end, T / 32, T / 8, T / 2, T};
-#define TK_ARGS(B, T0, T1) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, (const int *)nullptr, w.qpar, Q, R, D, T0, T1, cap, w.cnt, \
+#define TK_ARGS(B, T0, T1) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, tiles, w.qpar, Q, R, D, T0, T1, cap, w.cnt, \
                            w.cand_i, w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, tok
-#define TK_LAUNCH(M, B, T0, T1)                                                                                                              \
-    do {                                                                                                                                     \
-        if (bf && use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true, false, true, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));   \
-        else if (bf) hipLaunchKernelGGL((prefilter_kernel<M, false, false, true, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));      \
-        else if (use_lo) hipLaunchKernelGGL((prefilter_kernel<M, true, false, false, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));  \
-        else hipLaunchKernelGGL((prefilter_kernel<M, false, false, false, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1));             \
+#define TK_LAUNCH_AS(M, L, S, F, B, T0, T1) \
+    hipLaunchKernelGGL((prefilter_kernel<M, L, S, F, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
+#define TK_LAUNCH(M, B, T0, T1)                                                     \
+    do {                                                                            \
+        if (sel) {                                                                  \
+            if (bf && use_lo) TK_LAUNCH_AS(M, true, true, true, B, T0, T1);         \
+            else if (bf) TK_LAUNCH_AS(M, false, true, true, B, T0, T1);             \
+            else if (use_lo) TK_LAUNCH_AS(M, true, true, false, B, T0, T1);         \
+            else TK_LAUNCH_AS(M, false, true, false, B, T0, T1);                    \
+        } else {                                                                    \
+            if (bf && use_lo) TK_LAUNCH_AS(M, true, false, true, B, T0, T1);        \
+            else if (bf) TK_LAUNCH_AS(M, false, false, true, B, T0, T1);            \
+            else if (use_lo) TK_LAUNCH_AS(M, true, false, false, B, T0, T1);        \
+            else TK_LAUNCH_AS(M, false, false, false, B, T0, T1);                   \
+        }                                                                           \
     } while (0)
     int t0 = 0;
     bool direct_done = false;
@@ -1925,10 +2023,11 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const floa
                                cap, w.cnt, w.cand_i, w.cand_d);
         }
         const int final = t1 == T;
-        if (final && has_tail) {
-            // the last R % BT rows, tile T from the padded copy (topk_prefiltered's tail launch): direct appends behind the slice's
-            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T * BT * D * sizeof(half_t));
-            TK_LAUNCH(1, tail_base, T, T + 1);
+        if (final && tail_live) {
+            // the last R % BT rows, tile T_tail from the padded copy (topk_prefiltered's tail launch): direct appends behind the
+            // slice's.  Under a selection it is the list's own last position, n_live - 1 = T, which holds T_tail.
+            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T_tail * BT * D * sizeof(half_t));
+            TK_LAUNCH(1, tail_base, sel ? T : T_tail, (sel ? T : T_tail) + 1);
         }
 #define TK_RESCORE(B) tw, qn, B, xn, N, D, lgp, is_max, k, eps, idx_offset, cap, (const float4 *)w.qbase, w.cnt, (const int *)w.cand_i, list, rn, \
                       w.qpar, w.tau, w.overflow, final, out_s, out_i, redo
@@ -1938,7 +2037,44 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const floa
         t0 = t1;
     }
 #undef TK_LAUNCH
+#undef TK_LAUNCH_AS
 #undef TK_ARGS
     SKY_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                     const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                                     float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                     float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered", tw, qn, Q, bank16, dtype, xn, tail, rowp, N, P, D, k, combine, eps,
+                                   idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// ---- the same search under a selection of the bank's images ---------------------------------------------------------------------------
+extern "C" int skyemb_token_prefilter_select_prepare(const uint32_t *words, int64_t N, int P, const float *rowp, float *rowp_sel,
+                                                     int *tiles, int *cum, int *info, void *stream) {
+    const char *who = "skyemb_token_prefilter_select_prepare";
+    SKY_CHECK_ARG(words && rowp && rowp_sel && tiles && cum && info, "%s: null argument", who);
+    SKY_CHECK_ARG(N > 0 && P >= 1 && P <= 64 && 64 % P == 0 && N * P < (1ll << 31),
+                  "%s: N = %lld, P = %d: expected P a divisor of 64 and 1 .. 2^31 - 1 token rows", who, (long long)N, P);
+    const int64_t R = N * P, padded = skyemb_bank16_rowp_rows(R);
+    const int lgp = log2_of(P);
+    hipLaunchKernelGGL(token_select_rowp_kernel, dim3((unsigned)(padded / 256)), dim3(256), 0, (hipStream_t)stream, words,
+                       (const float4 *)rowp, R, lgp, padded, (float4 *)rowp_sel);
+    hipLaunchKernelGGL(token_select_tiles_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, words, ceil_div64(N, 32), lgp,
+                       (int)(padded / BT), tiles, cum, info);
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+extern "C" int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                         const float *xn, const void *tail, const float *rowp_sel, const int *tiles,
+                                                         int n_live, int last_live, int direct_end, int64_t N, int P, int D, int k,
+                                                         int combine, float eps, int64_t idx_offset, const float *thr0, void *ws,
+                                                         int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    SKY_CHECK_ARG(tiles, "skyemb_cosine_topk_tokens_prefiltered_sel: null argument");
+    return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered_sel", tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, N, P, D, k,
+                                   combine, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live,
+                                   direct_end);
 }

@@ -546,6 +546,42 @@ def cosine_topk_tokens_prefiltered(tw, qn, tokens, xn, tail, rowp, k, combine, e
     return ws
 
 
+def token_prefilter_select_prepare(words, N, P, rowp):
+    """What the two-stage token search needs of a selection of IMAGES (packed ``words`` of ``pack_select`` over the N images) over
+    a resident token bank of N x P rows with row constants ``rowp`` (``resident_rowp`` over the flat rows): (rowp_sel, tiles, n_live,
+    last_live, cum) -- the masked copy of the constants (every row of a deselected image holds the padding sentinel), the ascending
+    list of the live 256-row tiles (i32, its first n_live entries), their number, whether the bank's last tile is one of them, and
+    as a host list the number of selected images up to and including each live tile.  Two short launches and one read-back."""
+    rows = rowp.shape[0]
+    rowp_sel = torch.empty_like(rowp)
+    tiles = torch.empty(rows // 256, device=rowp.device, dtype=torch.int32)
+    cum = torch.empty(rows // 256 + 2, device=rowp.device, dtype=torch.int32)       # the counts, then info: one read-back
+    info = cum[rows // 256:]
+    check(lib().skyemb_token_prefilter_select_prepare(_p(words), N, P, _p(rowp), _p(rowp_sel), _p(tiles), _p(cum), _p(info), _stream()),
+          "skyemb_token_prefilter_select_prepare")
+    host = cum.cpu().numpy()
+    n_live, last_live = int(host[-2]), int(host[-1])
+    return rowp_sel, tiles, n_live, last_live, host[:n_live].tolist()
+
+
+def cosine_topk_tokens_prefiltered_sel(tw, qn, tokens, xn, tail, prepared, direct_end, k, combine, eps, idx_offset, out_s, out_i, redo,
+                                       thr0=None, ws=None):
+    """``cosine_topk_tokens_prefiltered`` under a selection of images: ``prepared`` is ``token_prefilter_select_prepare``'s result,
+    ``direct_end`` the position of the live-tile list at which the first slice ends (include/skyemb.h)."""
+    Q, D = tw.shape
+    N, P = tokens.shape[:2]
+    rowp_sel, tiles, n_live, last_live = prepared[:4]
+    code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered_sel")
+    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_tokens_prefiltered_sel(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp_sel), _p(tiles),
+                                                          n_live, last_live, direct_end, N, P, D, k, combine, eps, idx_offset, _p(thr0),
+                                                          _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
+          "skyemb_cosine_topk_tokens_prefiltered_sel")
+    return ws
+
+
 def prefilter_select_prepare(words, N, rowp):
     """What the two-stage search needs of a selection (packed ``words`` of ``pack_select``) over a bank of N rows with row constants
     ``rowp`` (``bank16_prepare`` / ``bank16_rowp_lp``): (rowp_sel, tiles, n_live, last_live) -- the masked copy of the constants (a

@@ -10,6 +10,7 @@ order, so the result is identical to the single-GPU one.
 """
 from __future__ import annotations
 
+import bisect
 import dataclasses
 import weakref
 
@@ -495,6 +496,7 @@ class Selection:
         self._indices = None
         self._sample = None                                # bank -> (its weights version, images, the floor's sample)
         self._prefilter = None                             # PreparedBank -> (its version, its row constants, what stage 1 needs)
+        self._token_prefilter = None                       # resident TokenBank -> the same
 
     def prefilter(self, pb: "PreparedBank"):
         """What the two-stage many-query search needs of this selection over ``pb`` (``ops.prefilter_select_prepare``: the masked row
@@ -507,6 +509,20 @@ class Selection:
         if got is None or got[0] != pb._version or got[1] is not rowp:
             got = (pb._version, rowp, ops.prefilter_select_prepare(self.words, self.N, rowp))
             self._prefilter[pb] = got
+        return got[2]
+
+    def token_prefilter(self, tb: "TokenBank"):
+        """What the two-stage token search needs of this selection over the resident ``tb`` (``ops.token_prefilter_select_prepare``: the
+        masked row constants, the live tiles, their number, whether the last tile is live, and -- a host list, read back once here,
+        never per search -- the selected images up to and including each live tile).  Kept per bank like ``prefilter``, rebuilt when
+        the bank's weights version or its stage-1 constants change."""
+        if self._token_prefilter is None:
+            self._token_prefilter = weakref.WeakKeyDictionary()
+        rowp = tb.stage1()[1]
+        got = self._token_prefilter.get(tb)
+        if got is None or got[0] != tb._version or got[1] is not rowp:
+            got = (tb._version, rowp, ops.token_prefilter_select_prepare(self.words, tb.bank.shape[0], tb.bank.shape[1], rowp))
+            self._token_prefilter[tb] = got
         return got[2]
 
     def sample(self, tb: "TokenBank", images: int):
@@ -861,8 +877,8 @@ def _token_prefilter_refusal(rq: TokenRequest):
         return "combine is neither 'min' nor 'max'"
     if rq.top_t != 0:
         return "top_t"
-    if rq.select is not None:
-        return "select"
+    if rq.select is not None and not isinstance(rq.select, Selection):
+        return "select is not a Selection"
     if rq.per_query:
         return "per-query weights"
     if rq.P < 1 or 64 % rq.P:
@@ -871,18 +887,30 @@ def _token_prefilter_refusal(rq: TokenRequest):
         return "SKYEMB_TOPK_PREFILTER=0"
     if rq.Q < TOKEN_PREFILTER_MIN_Q:
         return f"Q = {rq.Q} < TOKEN_PREFILTER_MIN_Q = {TOKEN_PREFILTER_MIN_Q}"
-    return ops.token_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
+    why = ops.token_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
+    if why is None and rq.select is not None:
+        # the selection must itself be a bank the route takes (k <= selected images, selected images x P >= 2048 rows): then the
+        # bootstrap sample exists, and the grouped route is cheap in exactly the cases refused here
+        why = ops.token_prefilter_refusal(rq.Q, rq.select.count, rq.P, rq.D, rq.k)
+        why = why if why is None else "the selected images alone: " + why
+    return why
 
 
 def _bootstrap_floor(rq: TokenRequest, tw, qn, eps):
     """[Q] the k-th best combined score of every query over a strided sample of min(N, max(16 k, 256)) whole images, scored by
-    the grouped kernels, one ulp lower: the two-stage route's first threshold, a lower bound of the k-th best over the bank."""
+    the grouped kernels, one ulp lower: the two-stage route's first threshold, a lower bound of the k-th best over the bank.  Under
+    a selection the sample is min(count, max(16 k, 256)) SELECTED images (``Selection.sample``, kept there per bank and weights
+    version): a lower bound of the k-th best selected score."""
     tb, k = rq.bank, rq.k
-    S = min(rq.N, max(16 * k, 256))
-    if tb._boot is None or tb._boot[0] != S:
-        idx = _sample_index(S, rq.N, tb.bank.device)
-        tb._boot = (S, tb.bank.index_select(0, idx).contiguous(), tb.norms.view(rq.N, rq.P).index_select(0, idx).contiguous().view(-1))
-    _, st, sn = tb._boot
+    if rq.select is not None:
+        S = min(rq.select.count, max(16 * k, 256))
+        st, sn = rq.select.sample(tb, S)
+    else:
+        S = min(rq.N, max(16 * k, 256))
+        if tb._boot is None or tb._boot[0] != S:
+            idx = _sample_index(S, rq.N, tb.bank.device)
+            tb._boot = (S, tb.bank.index_select(0, idx).contiguous(), tb.norms.view(rq.N, rq.P).index_select(0, idx).contiguous().view(-1))
+        _, st, sn = tb._boot
     floor = torch.empty(rq.Q, device=tw.device)
     keys = torch.empty(16, S, device=tw.device)
     for lo in range(0, rq.Q, 16):
@@ -894,8 +922,10 @@ def _bootstrap_floor(rq: TokenRequest, tw, qn, eps):
 
 def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, process_group, world_size):
     """The two-stage driver (csrc/topk_prefilter.hip, "Patch-token banks"): one bootstrap floor, one stage-1 pass with exact
-    re-scoring after every slice; flagged queries go through the grouped route, those queries only."""
-    tb, Q, k, dev = rq.bank, rq.Q, rq.k, rq.tokens.device
+    re-scoring after every slice; flagged queries go through the grouped route, those queries only.  Under a selection stage 1
+    walks the live tiles of ``Selection.token_prefilter``; its first slice ends at the first live-tile position whose count of
+    selected images reaches 96 k (never less than n_live / 128 positions, never less than 1), and the re-run keeps the selection."""
+    tb, Q, k, dev, sel = rq.bank, rq.Q, rq.k, rq.tokens.device, rq.select
     q = queries.to(dev, torch.float32).contiguous()
     tw, qn = prepare_queries(q, tb.weights)
     thr0 = _bootstrap_floor(rq, tw, qn, eps)
@@ -903,7 +933,14 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
     out_s = torch.empty(Q, k, device=dev)
     out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
     redo = torch.empty(Q, device=dev, dtype=torch.int32)
-    ops.cosine_topk_tokens_prefiltered(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, eps, rq.idx_offset, out_s, out_i, redo, thr0)
+    if sel is None:
+        ops.cosine_topk_tokens_prefiltered(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, eps, rq.idx_offset, out_s, out_i, redo, thr0)
+    else:
+        prepared = sel.token_prefilter(tb)
+        n_live, cum = prepared[2], prepared[4]
+        direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)
+        ops.cosine_topk_tokens_prefiltered_sel(tw, qn, tb.bank, tb.norms, tail, prepared, direct_end, k, rq.combine, eps, rq.idx_offset,
+                                               out_s, out_i, redo, thr0)
     again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
     if again.numel():
         rq2 = dataclasses.replace(rq, Q=int(again.numel()))
@@ -913,6 +950,8 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
     if stats is not None:
         stats.update(path="prefiltered", redone=int(again.numel()),
                      combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+        if sel is not None:
+            stats.update(selected=sel.count, tiles=(n_live, (rq.N * rq.P + 255) // 256))
     if world_size > 1:
         from .distributed import gather_topk
         gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
@@ -969,15 +1008,20 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     (Q > 16 runs ceil(Q / 16) passes) -- the grouped route, ``stats['path'] == 'tokens'``.
 
     Two-stage route (``stats['path'] == 'prefiltered'``): a ``TokenBank.resident(bank)`` (fp16 / bf16) with ``combine`` 'min' or
-    'max', no ``top_t``, no ``select``, shared weights, P a divisor of 64, at least ``TOKEN_PREFILTER_MIN_Q`` queries, a shape the
+    'max', no ``top_t``, shared weights, P a divisor of 64, at least ``TOKEN_PREFILTER_MIN_Q`` queries, a shape the
     library takes (D % 32 == 0, 128 <= D <= 4096, 2048 <= N P < 2^31, k <= 256, k <= N) and SKYEMB_TOPK_PREFILTER not 0 is searched
     in ONE pass for all queries: the bank's rows are multiplied on the 16-bit matrix cores with a proven error bound, an image is
     a candidate when every ('min') / some ('max') token of it can still reach the query's threshold, and every candidate is
     re-scored exactly after each slice of the bank, which also makes the threshold exact.  Scores and indices are bit for bit
     those of the grouped route over the same bank in a plain ``TokenBank``.  ``stats`` gains ``redone`` (queries whose candidate
-    list was full, re-run by the grouped route) and ``combine``.  Everything else is served by the grouped route as ever, never
-    refused.  Out of scope for the two-stage route: 'mean' (it needs per-pair bounds in score units, a division per pair),
-    ``top_t``, ``select``, per-query weights, the distance metrics, fp32 token banks and P not dividing 64.
+    list was full, re-run by the grouped route) and ``combine``.  With ``select`` the route is taken when the selected images are
+    themselves a bank it takes (k <= selected images, selected images x P >= 2048 rows): stage 1 then reads only the 256-row tiles
+    that hold a selected image, every row of a deselected image fails its test whatever it holds, the first threshold comes from
+    a sample of selected images, and a re-run keeps the selection; ``stats`` gains ``selected`` and ``tiles`` = (live tiles, all
+    tiles).  What the selection needs is kept in the ``Selection`` per bank (``Selection.token_prefilter``): pass the same object to
+    repeated searches.  Everything else is served by the grouped route as ever, never refused.  Out of scope for the two-stage
+    route: 'mean' (it needs per-pair bounds in score units, a division per pair), ``top_t``, per-query weights, the distance
+    metrics, fp32 token banks and P not dividing 64.
 
     Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank

@@ -7,11 +7,15 @@ usage: python tools/token_search_bench.py [--images 250000] [--tokens 16] [--dim
                                          [--bank-dtype f32 | f16 | bf16 | a comma list, e.g. f32,f16,bf16]
                                          [--combine min | mean | max | a comma list] [--top-t T | a comma list, e.g. 4,16]
                                          [--select-frac F | a comma list, e.g. 1.0,0.5,0.1] [--select-pattern random | runs]
-                                         [--fused-only] [--metric MAE | MSE | a comma list] [--many-query Q | a comma list]
+                                         [--fused-only] [--metric MAE | MSE | a comma list] [--many-query Q | a comma list] [--select]
 --many-query: for every listed Q and every listed 16-bit bank type, interleaved in the same rounds, the grouped route
 (grouped[f16]: search.cosine_topk_tokens over a plain TokenBank, ceil(Q / 16) passes) and the two-stage route (two_stage[f16]: the
 same call over TokenBank.resident with search.TOKEN_PREFILTER_MIN_Q set to 17), combine as --combine; "redone" is the two-stage
 call's count of re-run queries, "equal" whether both returned the same bits.  Nothing else runs in this mode.
+--select (with --many-query): besides the unselected pair, both routes under four selections of images, all interleaved in the same
+rounds -- all True (sel_all: the cost of the mask), 50 % and 10 % Bernoulli per image (sel_0.5, sel_0.1) and 10 % in runs of whole
+256-row tiles (sel_0.1_runs: a tile's 256 / tokens images selected together with probability 0.1).  Each Selection is packed and
+its per-bank state built once, outside the timed region; a leg reports "selected" and "tiles" = (live tiles, all tiles).
 --bank-dtype: element type(s) of the resident token bank the fused pass runs on (16-bit banks: the fp32 bank rounded to nearest);
 the fused variants of every listed type run interleaved in the same rounds, named fused_tokens[f16] etc.; the comparison variants
 (baseline and one-vector) need the fp32 bank and run when f32 is listed.
@@ -109,25 +113,41 @@ def timed(fn):
     return out, e0.elapsed_time(e1)
 
 
+def many_query_selections(N, P):
+    """--select: name -> Selection (None: the unselected pair)."""
+    g = torch.Generator(device="cuda").manual_seed(97)
+    per_tile = max(1, 256 // P)
+    runs = torch.rand((N + per_tile - 1) // per_tile, device="cuda", generator=g) < 0.1
+    flags = {"sel_all": torch.ones(N, device="cuda", dtype=torch.bool),
+             "sel_0.5": torch.rand(N, device="cuda", generator=g) < 0.5,
+             "sel_0.1": torch.rand(N, device="cuda", generator=g) < 0.1,
+             "sel_0.1_runs": runs.repeat_interleave(per_tile)[:N].contiguous()}
+    return dict({"": None}, **{name: search.Selection(f) for name, f in flags.items()})
+
+
 def many_query(a, lp_banks, w):
-    """--many-query: grouped against two-stage over the same resident 16-bit banks."""
+    """--many-query: grouped against two-stage over the same resident 16-bit banks; --select: under selections too."""
     search.TOKEN_PREFILTER_MIN_Q = 17
     N, P, D, k = a.images, a.tokens, a.dim, a.k
     resident = {name: search.TokenBank.resident(tb.bank, w) for name, tb in lp_banks.items()}
+    sels = many_query_selections(N, P) if a.select else {"": None}
     results = []
     for Q in a.many_query:
         q = torch.randn(Q, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2025 + Q))
         variants, info = {}, {}
         for combine in a.combine:
-            for name, tb in lp_banks.items():
-                tag = f"[{name}]" + ("" if len(a.combine) == 1 else f"/{combine}")
-                variants["grouped" + tag] = lambda tb=tb, c=combine: search.cosine_topk_tokens(q, tb, k, c)
-                variants["two_stage" + tag] = lambda rb=resident[name], c=combine: search.cosine_topk_tokens(q, rb, k, c)
+            for (name, tb), (sname, sel) in ((b, s) for b in lp_banks.items() for s in sels.items()):
+                tag = f"[{name}]" + ("" if len(a.combine) == 1 else f"/{combine}") + (f"/{sname}" if sname else "")
+                variants["grouped" + tag] = lambda tb=tb, c=combine, sel=sel: search.cosine_topk_tokens(q, tb, k, c, select=sel)
+                variants["two_stage" + tag] = lambda rb=resident[name], c=combine, sel=sel: search.cosine_topk_tokens(q, rb, k, c, select=sel)
                 st = {}
-                (gs, gi), (ts_, ti) = variants["grouped" + tag](), search.cosine_topk_tokens(q, resident[name], k, combine, stats=st)
+                (gs, gi), (ts_, ti) = variants["grouped" + tag](), search.cosine_topk_tokens(q, resident[name], k, combine, stats=st, select=sel)
                 info["two_stage" + tag] = dict(path=st.get("path"), redone=st.get("redone"),
                                                equal=bool(torch.equal(gs, ts_)) and bool(torch.equal(gi, ti)))
                 info["grouped" + tag] = dict(path="tokens")
+                if sel is not None:
+                    for v in ("grouped", "two_stage"):
+                        info[v + tag].update(selected=sel.count, tiles=st.get("tiles"))
         times = {name: [] for name in variants}
         for it in range(a.warmup + a.iters):
             for name, fn in variants.items():                # interleaved: every variant once per round
@@ -162,6 +182,7 @@ def main():
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--metric", type=metrics, default=[])
     ap.add_argument("--many-query", type=int_list, default=[])
+    ap.add_argument("--select", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("token_search_bench.py needs a GPU")
