@@ -490,7 +490,7 @@ int skyemb_topk_merge(const float *in_s, const int64_t *in_i, int Q, int nlists,
  * re-scored with the contract's fp32 fma chain.  Results are bit-identical to skyemb_cosine_topk + skyemb_topk_merge.
  * Replaces the same reference code as skyemb_cosine_topk (utils/similarity.py:18-35,149-172).
  *   skyemb_bank16_prepare   once per bank / weights: bank16 = fp16 rows scaled by 2^-e_i, rowp = 4 floats per row
- *                           {xn 2^-e, ||x'||_2, 2^-e, xn}; BOTH hold skyemb_bank16_rowp_rows(N) rows (N rounded up to whole
+ *                           {xn 2^-e, ||x'||_2, 2^-e, 0}; BOTH hold skyemb_bank16_rowp_rows(N) rows (N rounded up to whole
  *                           tiles: the search kernel reads whole tiles), i.e. skyemb_bank16_bytes(N, D) bytes of bank16
  *   skyemb_cosine_topk_prefiltered   whole pipeline on `stream`; out_s / out_i [Q, k] final lists; redo[q] != 0 marks a query
  *                           whose answer could not be certified (too many near-ties, candidate overflow, fewer than k
@@ -513,6 +513,22 @@ int skyemb_topk_merge(const float *in_s, const int64_t *in_i, int Q, int nlists,
  *                           adds ||q'|| sqrt(nsub) 2^-14).  Derivation: csrc/topk_prefilter.hip. */
 int skyemb_topk_prefilter_applicable(int Q, int64_t N, int D, int k);
 int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k);
+/* Test and diagnostic hook (host only, nothing is launched): where the arrays of that workspace lie.  out[0 .. 13] are the byte offsets
+ * of qh, ql, qbase, qpar, tau, bound, cnt, overflow, nsel, sel_i, cand_i, cand_d, wg_list, wg_count, out[14] = cap (slots of one
+ * query's candidate list), out[15] = capw (entries of one workgroup's region of wg_list); n must be 16, anything else is refused.
+ * With Qp = Q rounded up to 256, what the row search (every skyemb_cosine_topk_prefiltered* call above and below, not the token
+ * search) leaves there when it returns:
+ *   qh, ql [Qp, D] 16-bit   the scaled query images (the bank's operand format), rows Q .. Qp-1 zero
+ *   qbase [Q] float4        {qn 2^-f, eps_a ||q'|| (1 + D 2^-22), 2^-f, qn}
+ *   qpar [Qp] float4        the candidate test's parameters of the LAST threshold, rows Q .. Qp-1 NaN
+ *   tau [Q] float           the last threshold published between phases (thr0, or -inf, when there was none)
+ *   cnt [Q] int             entries appended to the query's list (may exceed cap: the excess was dropped and the query flagged)
+ *   cand_i, cand_d [Q, cap] the list: row numbers and raw dot^ of stage 1, NOT compacted by the final selection
+ *   overflow [Q] int        1: the query's scale left the bound's window, its list or a workgroup's region overflowed, or the staging
+ *                           list of one of its work items did (then for every query of the item) -- redo[q] = 1
+ *   sel_i [Q, 256], nsel [Q], bound [Q]   the rows re-scored exactly, their number, the largest upper bound left out
+ *   wg_list, wg_count       staging of the last staged launch only: scratch. */
+int skyemb_topk_prefilter_ws_layout(int Q, int D, int k, int64_t *out, int n);
 int64_t skyemb_bank16_bytes(int64_t N, int D);
 int64_t skyemb_bank16_rowp_rows(int64_t N);
 int skyemb_bank16_prepare(const float *bank, const float *xn, int64_t N, int D, void *bank16, float *rowp, void *stream);

@@ -807,6 +807,11 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
     auto flush_item = [&](int qt, int t) {
         const int tid = wave * 64 + lane_now();
         int n = *stg_n;      // (a plain LDS read: a volatile one became a FLAT load, whose vmcnt(0) drained the LDS-DMA ring once per item)
+        // More candidates than the staging list holds: WHICH pairs found no slot depends on the order the waves appended in, so
+        // flagging only their queries made the set of re-run queries a matter of timing (a query whose pairs all came first kept
+        // a complete list).  The item hands back ALL its queries: the flags depend on the data alone.  (Workgroup-uniform, once
+        // per item; the answers were exact either way.)
+        if (__builtin_amdgcn_readfirstlane(n) > SCAP && tid < QT && qt * QT + tid < Q) overflow[qt * QT + tid] = 1;
         n = __builtin_amdgcn_readfirstlane(n < SCAP ? n : SCAP);
         uint4 *dst = wg_list + (int64_t)blockIdx.x * capw;
         for (int e = tid; e < n; e += NT) {
@@ -1379,6 +1384,28 @@ extern "C" int skyemb_resident_rowp(const void *bank16, int dtype, const float *
 }
 
 extern "C" int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k) { return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr); }
+
+// Test and diagnostic hook (host arithmetic only, nothing is launched): where carve puts each array of the workspace.  carve
+// itself is run over a base that is only ever subtracted again -- never read or written -- so the two cannot drift.
+// out[0 .. 13]: byte offsets of qh, ql, qbase, qpar, tau, bound, cnt, overflow, nsel, sel_i, cand_i, cand_d, wg_list, wg_count
+// (carve's order); out[14] = cap (slots of a query's candidate list), out[15] = capw (entries of a workgroup's region).
+extern "C" int skyemb_topk_prefilter_ws_layout(int Q, int D, int k, int64_t *out, int n) {
+    constexpr int FIELDS = 14;
+    SKY_CHECK_ARG(out && n == FIELDS + 2, "skyemb_topk_prefilter_ws_layout: out must hold %d values (14 offsets, cap, capw), got n = %d",
+                  FIELDS + 2, n);
+    SKY_CHECK_ARG(Q >= 1 && D >= 1 && k >= 1, "skyemb_topk_prefilter_ws_layout: bad shape (Q=%d D=%d k=%d)", Q, D, k);
+    const int cap = skyemb_topk_prefilter_cap(k);
+    alignas(256) static char anchor[256];                      // an address to count from: carve adds offsets to it, nothing more
+    Workspace w;
+    carve(anchor, Q, D, cap, &w);
+    const char *at[FIELDS] = {(const char *)w.qh,    (const char *)w.ql,       (const char *)w.qbase, (const char *)w.qpar,   (const char *)w.tau,
+                              (const char *)w.bound, (const char *)w.cnt,      (const char *)w.overflow, (const char *)w.nsel, (const char *)w.sel_i,
+                              (const char *)w.cand_i, (const char *)w.cand_d,  (const char *)w.wg_list, (const char *)w.wg_count};
+    for (int i = 0; i < FIELDS; ++i) out[i] = (int64_t)((uintptr_t)at[i] - (uintptr_t)anchor);
+    out[FIELDS] = cap;
+    out[FIELDS + 1] = w.capw;
+    return 0;
+}
 
 // which of its two variants a bf16 search runs when SKYEMB_PREFILTER_LO is unset: the one measured faster
 constexpr bool BF16_DEFAULT_LO = false;

@@ -424,6 +424,17 @@ def topk_prefilter_applicable(Q, N, D, k):
     return bool(lib().skyemb_topk_prefilter_applicable(Q, N, D, k))
 
 
+WS_FIELDS = ("qh", "ql", "qbase", "qpar", "tau", "bound", "cnt", "overflow", "nsel", "sel_i", "cand_i", "cand_d", "wg_list", "wg_count")
+
+
+def topk_prefilter_ws_layout(Q, D, k):
+    """Test and diagnostic hook (host arithmetic only): {field: byte offset} of the two-stage search's workspace in the library's
+    own order, plus 'cap' and 'capw' (include/skyemb.h, skyemb_topk_prefilter_ws_layout)."""
+    out = (ctypes.c_int64 * (len(WS_FIELDS) + 2))()
+    check(lib().skyemb_topk_prefilter_ws_layout(Q, D, k, ctypes.addressof(out), len(out)), "skyemb_topk_prefilter_ws_layout")
+    return dict(zip(WS_FIELDS + ("cap", "capw"), (int(v) for v in out)))
+
+
 def bank16_prepare(bank, xn):
     """fp16 image of the bank for the prefiltered many-query top-k: (bank16 [rows, D] half, rowp [rows, 4] float), both
     padded to whole tiles of rows (``skyemb_bank16_rowp_rows``; ``skyemb_bank16_bytes`` is the image's size)."""
