@@ -1,0 +1,159 @@
+"""What the per-pair (tests/test_prefilter_stage1_gpu.py) and per-candidate (tests/test_prefilter_stage2_gpu.py) GPU tests of the
+two-stage many-query search share: guarded device buffers, the preparation call, and one search call through the C ABI whose
+workspace is read back through skyemb_topk_prefilter_ws_layout.  No test lives here."""
+import numpy as np
+import torch
+
+from tests.prefilter_stage1_reference import EPS
+
+DEV = "cuda"
+PAD, FILL, GUARD = 256, 0xA5, 0xEE
+FILL32 = np.frombuffer(bytes([FILL] * 4), dtype=np.int32)[0]
+TORCH16 = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+class Guarded:
+    """nbytes of device memory pre-filled with FILL between two guard zones; .t(dtype, *shape) views it."""
+    def __init__(self, nbytes):
+        self.n = int(nbytes)
+        self.buf = torch.full((self.n + 2 * PAD,), FILL, dtype=torch.uint8, device=DEV)
+        self.buf[:PAD] = GUARD
+        self.buf[PAD + self.n:] = GUARD
+        self.mem = self.buf[PAD:PAD + self.n]
+
+    def ptr(self):
+        return self.mem.data_ptr()
+
+    def t(self, dtype, *shape):
+        return self.mem.view(dtype).view(*shape)
+
+    def np(self, dtype, *shape):
+        return self.mem.cpu().numpy().view(dtype).reshape(*shape)
+
+    def intact(self):
+        return bool((self.buf[:PAD] == GUARD).all()) and bool((self.buf[PAD + self.n:] == GUARD).all())
+
+    def untouched(self):
+        return self.intact() and bool((self.mem == FILL).all())
+
+
+def dev(a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def bank_tensor(x, fmt):
+    """The device bank of `fmt` holding the float32 values x (each one a number of the format)."""
+    t = dev(np.asarray(x, dtype=np.float32))
+    return t if fmt == "fp32" else t.to(TORCH16[fmt])
+
+
+def patterns16(t):
+    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
+
+
+def prepare(ops, fmt, x, xn):
+    """Run the preparation kernel of `fmt` into guarded buffers: -> (bank tensor, rowp Guarded, image or tail Guarded or None)."""
+    N, D = x.shape
+    L = ops.lib()
+    rows = L.skyemb_bank16_rowp_rows(N)
+    bank = bank_tensor(x, fmt)
+    xn_d = dev(xn)
+    rowp = Guarded(rows * 16)
+    if fmt == "fp32":
+        assert L.skyemb_bank16_bytes(N, D) == rows * D * 2
+        side = Guarded(rows * D * 2)
+        rc = L.skyemb_bank16_prepare(ptr(bank), ptr(xn_d), N, D, side.ptr(), rowp.ptr(), stream())
+    else:
+        side = Guarded(256 * D * 2) if N % 256 else None
+        rc = L.skyemb_resident_rowp(ptr(bank), ops.dtype_code(TORCH16[fmt]), ptr(xn_d), N, D, rowp.ptr(), side.ptr() if side else None, stream())
+    torch.cuda.synchronize()
+    assert rc == 0, L.skyemb_last_error()
+    assert rowp.intact() and (side is None or side.intact())
+    return bank, xn_d, rowp, side
+
+
+def ws_arrays(raw, lay, Q, D):
+    """The workspace's arrays (numpy views of the bytes `raw`) at the offsets of skyemb_topk_prefilter_ws_layout."""
+    Qp, cap = -(-Q // 256) * 256, lay["cap"]
+    shapes = dict(qh=(np.uint16, Qp, D), ql=(np.uint16, Qp, D), qbase=(np.float32, Q, 4), qpar=(np.float32, Qp, 4), tau=(np.float32, Q),
+                  bound=(np.float32, Q), cnt=(np.int32, Q), overflow=(np.int32, Q), nsel=(np.int32, Q), sel_i=(np.int32, Q, 256),
+                  cand_i=(np.int32, Q, cap), cand_d=(np.float32, Q, cap))
+    out = {}
+    for f, (dt, *shape) in shapes.items():
+        n = int(np.prod(shape)) * np.dtype(dt).itemsize
+        out[f] = raw[lay[f]:lay[f] + n].view(dt).reshape(*shape)
+    return out
+
+
+class Search:
+    """One call of the two-stage search of `fmt` through the C ABI with guarded outputs and workspace; .ws holds the workspace's
+    arrays (numpy) as the call left them.  flags (a boolean per row): the search runs under that selection."""
+    def __init__(self, ops, fmt, tw, qn, x, xn, k, thr0=None, flags=None, idx_offset=0):
+        L = ops.lib()
+        Q, D = tw.shape
+        N = x.shape[0]
+        self.Q, self.N, self.D, self.k = Q, N, D, k
+        bank, xn_d, rowp, side = prepare(ops, fmt, x, xn)
+        self.rowp = rowp.np(np.float32, -1, 4)
+        lay = ops.topk_prefilter_ws_layout(Q, D, k)
+        nbytes = L.skyemb_topk_prefilter_ws_bytes(Q, D, k)
+        ws = Guarded(nbytes)
+        out_s, out_i, redo = Guarded(Q * k * 4), Guarded(Q * k * 8), Guarded(Q * 4)
+        tw_d, qn_d, thr_d = dev(tw), dev(qn), dev(thr0)
+        tail = ptr(side.mem) if side is not None and fmt != "fp32" else None
+        self.tiles = None
+        if flags is not None:
+            assert thr0 is None
+            bits = np.zeros(-(-N // 32) * 32, dtype=np.uint8)
+            bits[:N] = flags
+            words = dev(np.packbits(bits, bitorder="little").view(np.uint32).view(np.int32))
+            rowp_sel, tiles, n_live, last_live = ops.prefilter_select_prepare(words, N, rowp.t(torch.float32, -1, 4))
+            self.tiles = tiles.cpu().numpy()[:n_live]
+            self.rowp = rowp_sel.cpu().numpy()
+            if fmt == "fp32":
+                rc = L.skyemb_cosine_topk_prefiltered_sel(ptr(tw_d), ptr(qn_d), Q, ptr(bank), ptr(xn_d), side.ptr(), ptr(rowp_sel), ptr(tiles), n_live,
+                                                          last_live, N, D, k, EPS, idx_offset, ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(),
+                                                          stream())
+            elif fmt == "fp16":
+                rc = L.skyemb_cosine_topk_prefiltered_lp_sel(ptr(tw_d), ptr(qn_d), Q, ptr(bank), ptr(xn_d), tail, ptr(rowp_sel), ptr(tiles), n_live,
+                                                             last_live, N, D, k, EPS, idx_offset, ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(),
+                                                             stream())
+            else:
+                rc = L.skyemb_cosine_topk_prefiltered_resident_sel(ptr(tw_d), ptr(qn_d), Q, ptr(bank), ops.dtype_code(TORCH16[fmt]), ptr(xn_d), tail,
+                                                                   ptr(rowp_sel), ptr(tiles), n_live, last_live, N, D, k, EPS, idx_offset, ws.ptr(),
+                                                                   nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(), stream())
+        elif fmt == "fp32":
+            rc = L.skyemb_cosine_topk_prefiltered(ptr(tw_d), ptr(qn_d), Q, ptr(bank), ptr(xn_d), side.ptr(), rowp.ptr(), N, D, k, EPS, idx_offset,
+                                                  ptr(thr_d), ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(), stream())
+        else:
+            rc = L.skyemb_cosine_topk_prefiltered_resident(ptr(tw_d), ptr(qn_d), Q, ptr(bank), ops.dtype_code(TORCH16[fmt]), ptr(xn_d), tail,
+                                                           rowp.ptr(), N, D, k, EPS, idx_offset, ptr(thr_d), ws.ptr(), nbytes, out_s.ptr(),
+                                                           out_i.ptr(), redo.ptr(), stream())
+        torch.cuda.synchronize()
+        assert rc == 0, L.skyemb_last_error()
+        self.guards_ok = all(g.intact() for g in (ws, out_s, out_i, redo, rowp) + ((side,) if side is not None else ()))
+        self.cap = lay["cap"]
+        self.ws = ws_arrays(ws.mem.cpu().numpy(), lay, Q, D)
+        self.out_s, self.out_i, self.redo = out_s.np(np.float32, Q, k), out_i.np(np.int64, Q, k), redo.np(np.int32, Q)
+
+    def lists(self):
+        """Per query the rows of its list (cnt clipped to cap)."""
+        return [self.ws["cand_i"][q, :min(int(self.ws["cnt"][q]), self.cap)] for q in range(self.Q)]
+
+    def dense_dots(self, n):
+        """dot^ [Q, N] of lists that hold every row once in their first n slots (NaN where a row is missing)."""
+        d = np.full((self.Q, self.N), np.nan, dtype=np.float32)
+        np.put_along_axis(d, self.ws["cand_i"][:, :n].astype(np.int64), self.ws["cand_d"][:, :n], axis=1)
+        return d
+
+
+def set_lo(monkeypatch, lo):
+    monkeypatch.setenv("SKYEMB_PREFILTER_LO", "1" if lo else "0")
