@@ -608,7 +608,9 @@ int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, const float *qn
  * skyemb_cosine_token_topk_lp.  Variant: SKYEMB_PREFILTER_LO as for the row search.
  *   skyemb_token_prefilter_applicable   the shape limits: P a divisor of 64, D % 32 == 0, 128 <= D <= 4096, k <= 256, k <= N,
  *                                       2048 <= N P < 2^31.  A refusal leaves them as the error text (skyemb_last_error).
- *   skyemb_token_prefilter_ws_bytes     bytes of `ws`. */
+ *   skyemb_token_prefilter_ws_bytes     bytes of `ws`: the row search's workspace (skyemb_topk_prefilter_ws_bytes(Q, D, k) bytes, the
+ *                                       fields of skyemb_topk_prefilter_ws_layout; `nsel` [Q] holds the lengths of the running lists),
+ *                                       then the running lists, uint64 [Q, 256] keys (score desc, image asc), padded to 256 bytes. */
 int skyemb_token_prefilter_applicable(int Q, int64_t N, int P, int D, int k);
 int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k);
 int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,

@@ -542,6 +542,15 @@ def token_prefilter_refusal(Q, N, P, D, k):
     return None if L.skyemb_token_prefilter_applicable(Q, N, P, D, k) else L.skyemb_last_error().decode()
 
 
+def token_prefilter_ws_layout(Q, D, k):
+    """``topk_prefilter_ws_layout`` for the token search (host arithmetic only): the same fields -- the running lists' lengths live
+    in 'nsel' -- plus 'list', the byte offset of the running lists u64 [Q, 256], which follow the row search's workspace
+    (include/skyemb.h, skyemb_token_prefilter_ws_bytes)."""
+    out = topk_prefilter_ws_layout(Q, D, k)
+    out["list"] = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
+    return out
+
+
 def cosine_topk_tokens_prefiltered(tw, qn, tokens, xn, tail, rowp, k, combine, eps, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
     """The two-stage many-query search over a resident 16-bit token bank ``tokens`` [N, P, D] and the (tail, rowp) of
     ``resident_rowp`` over its flat rows; ``combine``: COMBINE_CODES['min'] or ['max'] (include/skyemb.h)."""

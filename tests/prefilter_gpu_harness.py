@@ -1,6 +1,7 @@
 """What the per-pair (tests/test_prefilter_stage1_gpu.py) and per-candidate (tests/test_prefilter_stage2_gpu.py) GPU tests of the
 two-stage many-query search share: guarded device buffers, the preparation call, and one search call through the C ABI whose
-workspace is read back through skyemb_topk_prefilter_ws_layout.  No test lives here."""
+workspace is read back through skyemb_topk_prefilter_ws_layout; TokenSearch is the same for the patch-token route
+(tests/test_token_prefilter_stage_gpu.py).  No test lives here."""
 import numpy as np
 import torch
 
@@ -157,3 +158,65 @@ class Search:
 
 def set_lo(monkeypatch, lo):
     monkeypatch.setenv("SKYEMB_PREFILTER_LO", "1" if lo else "0")
+
+
+TOK_KMAX = 256
+
+
+class TokenSearch:
+    """One call of the two-stage TOKEN search (skyemb_cosine_topk_tokens_prefiltered, or _sel under `flags`, a boolean per image)
+    through the C ABI over the bank xw [N, P, D] (float32 values of `fmt`), with guarded outputs and a guarded workspace pre-filled
+    with FILL.  .ws: the workspace's arrays at ops.token_prefilter_ws_layout's offsets as the call left them; .rn the lengths of the
+    running lists (the `nsel` field), .list [Q, TOK_KMAX] their 64-bit keys.
+    token_rescore_body zeroes cnt after every slice, so the candidates are read from cand_i itself: the workspace was filled with
+    FILL32, a negative number no image equals, and every later slice wrote its candidates from slot 0 on.  An entry that is not
+    FILL32 is a candidate some slice appended; those whose image lies in the LAST slice's range are that slice's complete set,
+    the others are what is left of an earlier slice's."""
+    def __init__(self, ops, fmt, tw, qn, xw, xn, k, combine, thr0=None, flags=None, idx_offset=0):
+        import bisect
+        L = ops.lib()
+        Q, D = tw.shape
+        N, P = xw.shape[:2]
+        self.Q, self.N, self.P, self.D, self.k = Q, N, P, D, k
+        bank, xn_d, rowp, side = prepare(ops, fmt, xw.reshape(N * P, D), xn)
+        lay = ops.token_prefilter_ws_layout(Q, D, k)
+        nbytes = L.skyemb_token_prefilter_ws_bytes(Q, D, k)
+        assert lay["list"] == L.skyemb_topk_prefilter_ws_bytes(Q, D, k)
+        assert nbytes == lay["list"] + -(-Q * TOK_KMAX * 8 // 256) * 256
+        ws = Guarded(nbytes)
+        out_s, out_i, redo = Guarded(Q * k * 4), Guarded(Q * k * 8), Guarded(Q * 4)
+        tw_d, qn_d, thr_d = dev(tw), dev(qn), dev(thr0)
+        code, comb, tail = ops.dtype_code(TORCH16[fmt]), ops.COMBINE_CODES[combine], side.ptr() if side is not None else None
+        self.tiles = self.cum = None
+        if flags is None:
+            rc = L.skyemb_cosine_topk_tokens_prefiltered(ptr(tw_d), ptr(qn_d), Q, ptr(bank), code, ptr(xn_d), tail, rowp.ptr(), N, P, D, k, comb,
+                                                         EPS, idx_offset, ptr(thr_d), ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(),
+                                                         stream())
+        else:
+            bits = np.zeros(-(-N // 32) * 32, dtype=np.uint8)
+            bits[:N] = flags
+            words = dev(np.packbits(bits, bitorder="little").view(np.uint32).view(np.int32))
+            rowp_sel, tiles, n_live, last_live, cum = ops.token_prefilter_select_prepare(words, N, P, rowp.t(torch.float32, -1, 4))
+            self.tiles, self.cum, self.last_live = tiles.cpu().numpy()[:n_live], cum, last_live
+            self.direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)     # search.py's rule
+            rc = L.skyemb_cosine_topk_tokens_prefiltered_sel(ptr(tw_d), ptr(qn_d), Q, ptr(bank), code, ptr(xn_d), tail, ptr(rowp_sel),
+                                                             ptr(tiles), n_live, last_live, self.direct_end, N, P, D, k, comb, EPS, idx_offset,
+                                                             ptr(thr_d), ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(), stream())
+        torch.cuda.synchronize()
+        assert rc == 0, L.skyemb_last_error()
+        self.guards_ok = all(g.intact() for g in (ws, out_s, out_i, redo, rowp) + ((side,) if side is not None else ()))
+        self.cap = lay["cap"]
+        raw = ws.mem.cpu().numpy()
+        self.ws = ws_arrays(raw, lay, Q, D)
+        self.rn = self.ws["nsel"]
+        self.list = raw[lay["list"]:lay["list"] + Q * TOK_KMAX * 8].view(np.uint64).reshape(Q, TOK_KMAX)
+        self.out_s, self.out_i, self.redo = out_s.np(np.float32, Q, k), out_i.np(np.int64, Q, k), redo.np(np.int32, Q)
+
+    def candidates(self, q, images=None):
+        """The images left in query q's candidate row (all of them, or those inside the boolean mask `images`), duplicates kept."""
+        row = self.ws["cand_i"][q]
+        row = row[row != FILL32].astype(np.int64)
+        if images is None:
+            return row
+        inside = (row >= 0) & (row < self.N)
+        return row[inside][images[row[inside]]]

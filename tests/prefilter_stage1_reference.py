@@ -1,7 +1,8 @@
 """Plain statements (numpy, float64 and integers) of what STAGE 1 of the two-stage many-query search must compute, quantity by
 quantity -- the row constants and the fp16 image, the query images and constants, every matrix-core dot product, the candidate
 lists at a known threshold, the thresholds -- for the per-pair tests of tests/test_prefilter_stage1_{cpu,gpu}.py.  The file under
-test is csrc/topk_prefilter.hip; its header derives the bound these statements serve.  The token route is not covered.
+test is csrc/topk_prefilter.hip; its header derives the bound these statements serve.  The token route is covered image by image in
+tests/token_prefilter_stage_reference.py, which builds on this file.
 
 Formats (``fmt``): 'fp32' an fp32 bank searched through its scaled fp16 image (bank16_kernel), 'fp16' a resident fp16 bank
 (bank16_rowp_lp_kernel), 'bf16' a resident bf16 bank (bankbf16_rowp_kernel).  A 16-bit value is carried as the float32 it widens
