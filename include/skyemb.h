@@ -643,6 +643,42 @@ int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const float *qn, 
                                               int direct_end, int64_t N, int P, int D, int k, int combine, float eps,
                                               int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
                                               int64_t *out_i, int *redo, void *stream);
+/* The same search with per-image combine SKYEMB_COMBINE_MEAN: scores and image indices are bit for bit those of
+ * skyemb_cosine_token_topk_lp + skyemb_topk_merge under mean -- token scores by the contract's chain, (((0 + s_0) + s_1) + ...) /
+ * float32(P) in token order, an image with a NaN token scores -inf and is never returned.  The mean of an image's token cosines is,
+ * up to eps and rounding, one dot product with the image's pooled unit tokens m = (1/P) sum_p x_p / xn_p, so stage 1 is the ROW
+ * search's matrix-core pass over a derived 16-bit image [N, D] of m (P times fewer rows than the bank) under a proven bound U >= mean
+ * (csrc/topk_prefilter.hip, "combine 'mean'"); stage 2 re-scores every candidate image's P tokens from the bank after each slice, as
+ * above.  No selection, no weights assumption: the bound uses only |tw . x| <= ||tw|| ||x||, so negative weights are served too.
+ *   skyemb_token_mean_pool   one launch per bank and weights version (xn): pooled16 [N, D] in the bank's dtype = the 16-bit rounding
+ *                           of m 2^-e (largest element in [2^13, 2^14); bf16: elements below 2^-40 stored as zero), formed in fp32 as
+ *                           fl(fl(sum_p fl(x_p / xn_p)) / P), p ascending; rowp [skyemb_bank16_rowp_rows(N), 4] = {2^-e, ||m 2^-e||_2 +
+ *                           (kappa / eps_m) c1 2^-e, c2 2^-e, 0} with c1 = mean_p ||x_p / xn_p||_2, c2 = mean_p ||x_p / xn_p||_2 / xn_p,
+ *                           kappa = (1.02 D + 2.03 P + 4) 2^-24, all rounded up; rows past N: the padding sentinel {0, NaN, 0, 0}; tail
+ *                           (NULL when N % 256 == 0): a zero-padded [256, D] copy of the last N % 256 pooled rows.  An image with an
+ *                           inf / NaN element (bf16: a nonzero element outside [2^-60, 2^120)), a token norm outside [2^-40, 2^40] (zero
+ *                           included), ||x_p / xn_p|| outside [2^-20, 2^20], 0 < max |m| < 2^-40 or a constant >= 2^60 cannot be bounded:
+ *                           zeros and {0, inf, 1, 0}, a candidate of every query, decided by stage 2.  Extra memory: 2 D + 16 bytes per
+ *                           image and the tail tile.
+ *   skyemb_token_mean_prefilter_applicable   the shape limits, rows = images: P a divisor of 64, D % 32 == 0, 128 <= D <= 4096,
+ *                           k <= 256, k <= N, N >= 2048, N P < 2^31.  A refusal leaves them as the error text (skyemb_last_error).
+ *   skyemb_token_mean_prefilter_ws_bytes     bytes of `ws` (= skyemb_token_prefilter_ws_bytes: same layout).
+ *   skyemb_token_mean_prefilter_eps_m        host only: eps_m of stage 1 over the pooled image; SKYEMB_F16: skyemb_topk_prefilter_eps_a(D,
+ *                           lo, 0); SKYEMB_BF16: (lo ? 2^-9 : 2^-8) + 2^-17 + 6.06 D 2^-24 + D 2^-37.
+ *   skyemb_cosine_topk_tokens_mean_prefiltered   the arguments of skyemb_cosine_topk_tokens_prefiltered in their order, with tail and
+ *                           rowp those of skyemb_token_mean_pool, and pooled16 before the stream; combine must be SKYEMB_COMBINE_MEAN.
+ *                           redo[q] != 0: a full list or staging region, or a query outside the bound's windows (a zero query, qn
+ *                           outside [2^-20, 2^20], scale outside [2^-34, 2^34], eps negative or not finite) -- the caller runs it
+ *                           through skyemb_cosine_token_topk_lp.  Variant: hi + lo unless SKYEMB_PREFILTER_LO=0. */
+int skyemb_token_mean_pool(const void *bank16, int dtype, const float *xn, int64_t N, int P, int D, void *pooled16, float *rowp,
+                           void *tail, void *stream);
+int skyemb_token_mean_prefilter_applicable(int Q, int64_t N, int P, int D, int k);
+int64_t skyemb_token_mean_prefilter_ws_bytes(int Q, int D, int k);
+double skyemb_token_mean_prefilter_eps_m(int D, int lo, int dtype);
+int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                               const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                               float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                               float *out_s, int64_t *out_i, int *redo, const void *pooled16, void *stream);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

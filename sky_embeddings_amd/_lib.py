@@ -185,6 +185,13 @@ PROTOTYPES = {
     "skyemb_cosine_topk_tokens_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                                           c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
                                                           c_vp, c_vp]),
+    # ... and with combine mean, over the pooled image of the bank: additive again
+    "skyemb_token_mean_pool": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_token_mean_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),
+    "skyemb_token_mean_prefilter_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "skyemb_token_mean_prefilter_eps_m": (c_f64, [c_i32, c_i32, c_i32]),
+    "skyemb_cosine_topk_tokens_mean_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
+                                                           c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -1700,9 +1700,168 @@ extern "C" int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, cons
 // so ties need no second rule) and publishes the new tau_q into qpar.  Every image that passes stage 1 is re-scored, so nothing is
 // left to certify: the only failure is a full candidate list or staging region, which flags the query (redo) for the grouped search.
 // A query whose eps_a ||q'|| is 0 or not finite (a zero query: 0 * inf in the test of an unboundable row) is flagged as well.
+//
+// ---- combine 'mean' (skyemb_token_mean_pool / skyemb_cosine_topk_tokens_mean_prefiltered) ---------------------------------------------
+// The mean of an image's P token cosines is, up to eps and fp32 rounding, ONE dot product with the image's pooled unit tokens, so
+// stage 1 is the ROW search's pass (prefilter_kernel without TOK: a row is an image) over a derived 16-bit image [N, D], P times
+// fewer rows than the bank; stage 2 is token_rescore_kernel with the mean fold, and the threshold and list discipline is that of
+// min / max above.  Notation, per image i and query q (reals unless fl() is written): x_p the widened token rows, n_p = xn[i P + p],
+// u_p = x_p / n_p, m = (1/P) sum_p u_p, r_p = tw . x_p, N_q = ||q'||_2 with q' = tw 2^-f, qn' = qn 2^-f, and the per-image constants
+//   c1 = mean_p ||u_p||_2        c2 = mean_p ||u_p||_2 / n_p         (c1 = 1 under unit weights)
+// Only the plain Cauchy-Schwarz |r_p| <= ||tw||_2 ||x_p||_2 is used, never |r_p| <= qn n_p: nothing is assumed of the weights (they
+// may be negative or zero) beyond what makes n_p a positive finite number -- point (e) of the design is met by not needing it.
+//  (d) contract score of a token  s_p = fl(chain_p / fl(qn n_p + eps)), eps >= 0:  |chain_p - r_p| <= 1.01 D 2^-24 ||tw|| ||x_p||, the fma
+//      and the division round once each, so  |s_p - r_p / (qn n_p + eps)| <= (1.02 D + 2.02) 2^-24 rho_p,  rho_p = ||tw|| ||u_p|| / qn.
+//      The eps term: r_p / (qn n_p + eps) = r_p / (qn n_p) (1 - eps / (qn n_p + eps)) <= r_p / (qn n_p) + rho_p eps / (qn n_p).
+//      The combine's P - 1 adds (the first, 0 + s_0, is exact) err by <= 1.01 (P - 1) 2^-24 sum |s_p|, |s_p| <= rho_p (1 + 2^-20); the
+//      division by float(P), a power of two, is exact.  Together
+//        qn' mean <= q' . m + N_q c1 (1.02 D + 1.02 P + 2) 2^-24 + N_q c2 eps / qn.
+//  (c) the kernel forms m_fl = fl(fl(sum_p fl(x_p / n_p)) / P): P divisions, P - 1 adds in token order, one exact scale per element:
+//      ||m_fl - m|| <= 1.01 P 2^-24 c1 (triangle inequality over the tokens).
+//  (b) + (a) m' = m_fl 2^-e with the largest element in [2^13, 2^14) is rounded to 16 bits and multiplied by the matrix cores: this is
+//      the situation of the fp32 bank's fp16 image, |dot^ - q' . m'| <= eps_m N_q ||m'||,
+//        fp16: eps_m = eps_a_of(D, lo, resident = false)  (row rounding 2^-11 and both operands' subnormals included)
+//        bf16: eps_m = (lo ? 2^-9 + 2^-17 : 2^-8 + 2^-17) + 6.06 D 2^-24 + D 2^-37 -- the resident bf16 bound with the row's own rounding
+//              2^-9 and its cross terms added; elements of m' below 2^-40 are stored as zero (<= sqrt(D) 2^-53 ||m'||, in the last term,
+//              which has doubled), so every nonzero element is >= 2^-40: condition (R).
+// Hence, with kappa = (1.02 D + 2.03 P + 4) 2^-24 (the +2 on top: subnormal roundings of chain, score and mean, <= 2^-100 of the rest
+// under the windows below),
+//     qn' 2^-e mean  <=  dot^ + eps_m N_q [ ||m'|| + (kappa / eps_m) c1 2^-e ] + (N_q eps / qn) c2 2^-e      =: qn' 2^-e U
+// and the image is a candidate iff  t = dot^ - a R0 + c R1 + g R2 >= 0  -- the test instruction of prefilter_kernel as it stands, with
+//     rowp[i] = {R0, R1, R2, 0} = {2^-e, ||m'|| + (kappa / eps_m) c1 2^-e, c2 2^-e, 0}  (norms and constants rounded up)
+//     qpar[q] = {-a, c, g, 0},  a = tau qn' (lowered),  c = eps_m N_q (raised),  g = N_q eps / qn (raised)
+// (kappa / eps_m uses the SMALLER eps_m, hi + lo, so one set of row constants serves both variants.)  U - mean is eps_m c1-ish in
+// cosine units under unit weights: of the order of eps_a, as for the row search.
+// An image is UNBOUNDABLE -- zeros in the pooled row and the constants {0, inf, 1, 0}: a candidate of every query, decided by stage
+// 2 -- when a token has an inf / NaN element (bf16: a nonzero element outside [2^-60, 2^120)), a norm n_p outside [2^-40, 2^40] (zero,
+// inf and NaN included), ||u_p|| outside [2^-20, 2^20]; when 0 < max |m_fl| < 2^-40; or when R1 or R2 reach 2^60.  Inside these windows
+// no intermediate of the kernel overflows or underflows, and c R1, g R2 stay finite, so t is never NaN for a boundable image.
+// A query is flagged (redo: the grouped search answers it) by the rules of min / max and also when qn is outside [2^-20, 2^20], its
+// scale 2^-f outside [2^-34, 2^34], eps is negative or not finite, c or g reach 2^60, or a = tau qn' is not finite.
 namespace {
 
 constexpr int TOK_KMAX = RESCORE_MAX;      // the running list of a query: at most k <= TOK_KMAX images
+constexpr int TOK_MIN = 0, TOK_MAX = 1, TOK_MEAN = 2;      // the fold of token_rescore_kernel
+
+__host__ __device__ inline double eps_m_of(int D, bool lo, bool bf) {
+    if (bf) return (lo ? 0x1p-9 + 0x1p-17 : 0x1p-8 + 0x1p-17) + 6.06 * D * 0x1p-24 + D * 0x1p-37;
+    return eps_a_of(D, lo, false);
+}
+inline double kappa_of(int D, int P) { return (1.02 * D + 2.03 * P + 4.0) * 0x1p-24; }
+
+// the query's row of the test's A operand under 'mean' (see above); *bad: the query leaves the bound's windows
+__device__ __forceinline__ float4 mean_test_row(float tau, float4 qb, float gfac, bool *bad) {
+    const float t = tau > -3.0e38f ? tau : -3.0e38f;
+    float a = t * qb.x;
+    a -= fabsf(a) * 0x1p-19f;
+    if (!(a > -3.0e38f)) a = -3.0e38f;
+    const float g = __fdiv_rn(qb.y * gfac, qb.w) * (1.0f + 0x1p-19f);      // N_q eps / qn: gfac = eps / eps_m, raised on the host
+    *bad = !(a < INFINITY) || !(g >= 0.f && g < 0x1p60f) || !(qb.y < 0x1p60f);
+    return test_row(a, -g, qb.y);
+}
+
+// One wave per image: the pooled row and its constants (the derivation above).  tail / tail_first / the padding sentinel: as in
+// bank16_rowp_lp_kernel, with images for rows.  kfac = kappa / eps_m (hi + lo), raised.
+template <bool BF>
+__global__ __launch_bounds__(128) void token_mean_pool_kernel(const unsigned short *__restrict__ bank, const float *__restrict__ xn, int64_t N,
+                                                               int P, int D, unsigned short *__restrict__ pooled, float4 *__restrict__ rowp,
+                                                               int64_t rows_padded, unsigned short *__restrict__ tail, int64_t tail_first,
+                                                               float kfac) {
+    __shared__ float sm[2][4096];                             // the image's sums, D <= 4096; a lane only ever touches its own elements
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t img = (int64_t)blockIdx.x * 2 + w;
+    if (img >= rows_padded) return;
+    unsigned short *t = tail && img >= tail_first ? tail + (img - tail_first) * D : nullptr;
+    if (img >= N) {
+        if (t)
+            for (int d = lane * 4; d < D; d += 256) *(uint2 *)(t + d) = make_uint2(0u, 0u);
+        if (lane == 0) rowp[img] = make_float4(0.f, NAN, 0.f, 0.f);
+        return;
+    }
+    float *m = sm[w];
+    for (int d = lane * 4; d < D; d += 256) *(float4 *)(m + d) = make_float4(0.f, 0.f, 0.f, 0.f);
+    float bad = 0.f, c1 = 0.f, c2 = 0.f;
+    for (int p = 0; p < P; ++p) {
+        const int64_t row = img * P + p;
+        const float n = xn[row];
+        const bool nok = n >= 0x1p-40f && n <= 0x1p40f;        // (false for 0, inf and NaN)
+        const float nn = nok ? n : 1.0f;
+        const unsigned short *x = bank + row * D;
+        float ss = 0.f;
+        for (int d = lane * 4; d < D; d += 256) {
+            const float4 v = BF ? row4((const bf16_t *)(x + d)) : row4((const half_t *)(x + d));
+            const float a[4] = {v.x, v.y, v.z, v.w};
+            float4 s4 = *(float4 *)(m + d);
+            float *s = (float *)&s4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float mag = fabsf(a[j]);
+                if (BF) bad = (!(mag < ldexpf(1.0f, BF_ROW_HI)) || (mag > 0.f && mag < ldexpf(1.0f, -BF_ROW_LO))) ? 1.f : bad;
+                else bad = !(mag < INFINITY) ? 1.f : bad;
+                const float u = __fdiv_rn(a[j], nn);
+                ss = fmaf(u, u, ss);
+                s[j] = s[j] + u;                               // token order: p ascending
+            }
+            *(float4 *)(m + d) = s4;
+        }
+        ss = wave_sum(ss);
+        const float nu = sqrtf(ss);
+        if (!nok || !(nu >= 0x1p-20f && nu <= 0x1p20f)) bad = 1.f;
+        c1 += nu;
+        c2 += __fdiv_rn(nu, nn);
+    }
+    const float inv_p = 1.0f / (float)P;                      // a power of two
+    float mx = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const float4 v = *(const float4 *)(m + d);
+        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    }
+    mx = wave_max(mx) * inv_p;
+    bad = wave_max(bad);
+    if (!(mx < INFINITY) || (mx > 0.f && mx < 0x1p-40f)) bad = 1.f;
+    int e = 0;
+    if (bad == 0.f && mx > 0.f) {
+        (void)frexpf(mx, &e);
+        e -= 14;                                               // mx 2^-e in [2^13, 2^14); -54 <= e <= 7
+    }
+    const float s = ldexpf(1.0f, -e);
+    // norms rounded up: the fp32 sums of squares and of P terms, the divisions, the square roots
+    const float up = (1.0f + (float)(D + 64) * 0x1p-22f) * (1.0f + 0x1p-20f);
+    float ss = 0.f;
+    if (bad == 0.f)
+        for (int d = lane * 4; d < D; d += 256) {
+            const float4 v = *(const float4 *)(m + d);
+            const float a[4] = {v.x * inv_p * s, v.y * inv_p * s, v.z * inv_p * s, v.w * inv_p * s};
+            for (int j = 0; j < 4; ++j) ss = fmaf(a[j], a[j], ss);
+        }
+    ss = wave_sum(ss);
+    const float r1 = fmaf(kfac * s, c1 * inv_p * up, sqrtf(ss) * up) * (1.0f + 0x1p-21f);
+    const float r2 = c2 * inv_p * s * up;
+    if (!(r1 < 0x1p60f) || !(r2 < 0x1p60f)) bad = 1.f;
+    unsigned short *o = pooled + img * D;
+    for (int d = lane * 4; d < D; d += 256) {
+        const float4 v = *(const float4 *)(m + d);
+        const float a[4] = {v.x * inv_p * s, v.y * inv_p * s, v.z * inv_p * s, v.w * inv_p * s};
+        uint2 raw;
+        if (bad != 0.f) {
+            raw = make_uint2(0u, 0u);
+        } else if (BF) {
+            bf16x4 h;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = (bf16_t)(fabsf(a[j]) < 0x1p-40f ? 0.f : a[j]);
+            raw = __builtin_bit_cast(uint2, h);
+        } else {
+            typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+            half4 h;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = (half_t)a[j];
+            raw = __builtin_bit_cast(uint2, h);
+        }
+        *(uint2 *)(o + d) = raw;
+        if (t) *(uint2 *)(t + d) = raw;
+    }
+    if (lane == 0) rowp[img] = bad != 0.f ? make_float4(0.f, INFINITY, 1.0f, 0.f) : make_float4(s, r1, r2, 0.f);
+}
 
 __device__ __forceinline__ unsigned long long image_key(float score, int image) {
     return ((unsigned long long)orderable(score) << 32) | (unsigned int)~(unsigned int)image;   // larger: better score, then lower image
@@ -1731,22 +1890,30 @@ __device__ unsigned long long radix_kth_largest64(const unsigned long long *keys
 }
 
 // after init_state_kernel: empty running lists, a floor that is not a number counts as none, and the queries stage 1 cannot serve
+// gfac >= 0: the search combines by mean -- the test parameters become those of the mean bound (mean_test_row; gfac = eps / eps_m,
+// NaN when eps is negative or not finite) and the query windows of that bound apply.  gfac < 0: min / max, as ever.
 __global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, float *__restrict__ tau_q, int *__restrict__ rn,
-                                   int *__restrict__ overflow) {
+                                   int *__restrict__ overflow, float gfac, float4 *__restrict__ qpar) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= Q) return;
     rn[q] = 0;
     if (!(tau_q[q] == tau_q[q])) tau_q[q] = -INFINITY;        // (init_state_kernel has opened the test for it already)
-    const float c = qbase[q].y;                                // eps_a ||q'||
+    const float4 qb = qbase[q];
+    const float c = qb.y;                                      // eps_a ||q'||
     if (!(c > 0.f && c < INFINITY)) overflow[q] = 1;
+    if (!(gfac < 0.f)) {
+        bool bad;
+        qpar[q] = mean_test_row(tau_q[q], qb, gfac, &bad);
+        if (bad || !(qb.w >= 0x1p-20f && qb.w <= 0x1p20f) || !(qb.z >= 0x1p-34f && qb.z <= 0x1p34f)) overflow[q] = 1;
+    }
 }
 
 // one workgroup (256 threads) per query: the exact combined scores of the slice's candidate images, the merge into the running
 // list, the new threshold; final: the ordered result.  lgp: P = 2^lgp <= 64 tokens, one lane each, 256 / P images per round.
 template <typename X>
 __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank,
-                                                   const float *__restrict__ xn, int64_t N, int D, int lgp, int is_max, int k, float eps,
-                                                   int64_t idx_offset, int cap, const float4 *__restrict__ qbase, int *__restrict__ cnt,
+                                                   const float *__restrict__ xn, int64_t N, int D, int lgp, int fold, float gfac, int k,
+                                                   float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase, int *__restrict__ cnt,
                                                    const int *__restrict__ cand_i, unsigned long long *__restrict__ list,
                                                    int *__restrict__ rn, float4 *__restrict__ qpar, float *__restrict__ tau_q,
                                                    int *__restrict__ overflow, int final, float *__restrict__ out_s,
@@ -1783,10 +1950,20 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
             acc = fmaf(sq[d + 2], v.z, acc);
             acc = fmaf(sq[d + 3], v.w, acc);
         }
-        float s = finish_score(acc, qnv, xn[row], eps);        // a NaN score is -inf: out under min, ignored under max
-        for (int o = 1; o < P; o <<= 1) {
-            const float u = __shfl_xor(s, o, 64);
-            s = is_max ? fmaxf(s, u) : fminf(s, u);
+        float s = finish_score(acc, qnv, xn[row], eps);        // a NaN score is -inf: out under min and mean, ignored under max
+        if (fold == TOK_MEAN) {
+            // the grouped kernels' fold (combine_tile<SKYEMB_COMBINE_MEAN>, token_combine.h): (((0 + s_0) + s_1) + ...) in token
+            // order, one division by float(P), a sum that is not a number scores -inf
+            const int first = (tid & 63) & ~(P - 1);
+            float sum = 0.f;
+            for (int j = 0; j < P; ++j) sum = sum + __shfl(s, first + j, 64);
+            s = __fdiv_rn(sum, (float)P);
+            s = s == s ? s : -INFINITY;
+        } else {
+            for (int o = 1; o < P; o <<= 1) {
+                const float u = __shfl_xor(s, o, 64);
+                s = fold == TOK_MAX ? fmaxf(s, u) : fminf(s, u);
+            }
         }
         // an image that scores -inf is never returned: key 0, below every key that counts
         if (p == 0 && c < n) keys[r0 + c] = s > -INFINITY ? image_key(s, img) : 0ull;
@@ -1815,12 +1992,18 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
         if (kk == k) tau = fmaxf(tau, unorderable((unsigned int)(kth >> 32)));   // k images decided: their k-th best exact score
         tau_q[q] = tau;
         const float4 qb = qbase[q];
-        const float t = tau > -3.0e38f ? tau : -3.0e38f;       // (select_kernel's parameters of the next phase)
-        float a = t * qb.x, b = t * eps * qb.z;
-        a -= fabsf(a) * 0x1p-19f;
-        b -= fabsf(b) * 0x1p-19f;
-        if (!(a > -3.0e38f)) a = -3.0e38f;
-        qpar[q] = test_row(a, b, qb.y);
+        if (fold == TOK_MEAN) {
+            bool out;
+            qpar[q] = mean_test_row(tau, qb, gfac, &out);
+            if (out) overflow[q] = 1;                          // tau qn' left fp32's range: the grouped search decides
+        } else {
+            const float t = tau > -3.0e38f ? tau : -3.0e38f;   // (select_kernel's parameters of the next phase)
+            float a = t * qb.x, b = t * eps * qb.z;
+            a -= fabsf(a) * 0x1p-19f;
+            b -= fabsf(b) * 0x1p-19f;
+            if (!(a > -3.0e38f)) a = -3.0e38f;
+            qpar[q] = test_row(a, b, qb.y);
+        }
     }
     if (!final) return;
     for (int e = tid; e < k; e += 256) {
@@ -1840,11 +2023,11 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
 
 #define TOKEN_RESCORE_PARAMS(X)                                                                                                  \
     const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank, const float *__restrict__ xn, int64_t N, \
-        int D, int lgp, int is_max, int k, float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase,                 \
+        int D, int lgp, int fold, float gfac, int k, float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase,       \
         int *__restrict__ cnt, const int *__restrict__ cand_i, unsigned long long *__restrict__ list, int *__restrict__ rn,          \
         float4 *__restrict__ qpar, float *__restrict__ tau_q, int *__restrict__ overflow, int final, float *__restrict__ out_s,     \
         int64_t *__restrict__ out_i, int *__restrict__ redo
-#define TOKEN_RESCORE_PASS tw, qn, bank, xn, N, D, lgp, is_max, k, eps, idx_offset, cap, qbase, cnt, cand_i, list, rn, qpar, tau_q, overflow, \
+#define TOKEN_RESCORE_PASS tw, qn, bank, xn, N, D, lgp, fold, gfac, k, eps, idx_offset, cap, qbase, cnt, cand_i, list, rn, qpar, tau_q, overflow, \
                            final, out_s, out_i, redo
 __global__ __launch_bounds__(256) void token_rescore_lp_kernel(TOKEN_RESCORE_PARAMS(half_t)) { token_rescore_body<half_t>(TOKEN_RESCORE_PASS); }
 __global__ __launch_bounds__(256) void token_rescore_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t)) { token_rescore_body<bf16_t>(TOKEN_RESCORE_PASS); }
@@ -1939,25 +2122,78 @@ extern "C" int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k) {
     return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr) + align256((int64_t)Q * TOK_KMAX * 8);
 }
 
+// ---- combine 'mean': the limits of the token route with rows = images (stage 1 walks the pooled image's N rows)
+#define TOKEN_MEAN_PREFILTER_MSG "many-query patch-token search, combine mean: needs P a divisor of 64, D %% 32 == 0, 128 <= D <= 4096, " \
+                                 "1 <= k <= %d, k <= N, N >= 2048 images, N * P < 2^31 rows and Q >= 1 (Q=%d N=%lld P=%d D=%d k=%d)"
+extern "C" int skyemb_token_mean_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
+    const bool ok = Q >= 1 && P >= 1 && P <= 64 && 64 % P == 0 && D % BK == 0 && D >= 4 * BK && D <= 4096 && k >= 1 && k <= TOK_KMAX &&
+                    k <= N && N >= 8 * BT && N * P < (1ll << 31);
+    if (!ok) skyemb_set_error(TOKEN_MEAN_PREFILTER_MSG, TOK_KMAX, Q, (long long)N, P, D, k);
+    return ok ? 1 : 0;
+}
+
+extern "C" int64_t skyemb_token_mean_prefilter_ws_bytes(int Q, int D, int k) { return skyemb_token_prefilter_ws_bytes(Q, D, k); }
+
+extern "C" double skyemb_token_mean_prefilter_eps_m(int D, int lo, int dtype) { return eps_m_of(D, lo != 0, dtype == SKYEMB_BF16); }
+
+extern "C" int skyemb_token_mean_pool(const void *bank16, int dtype, const float *xn, int64_t N, int P, int D, void *pooled16, float *rowp,
+                                      void *tail, void *stream) {
+    const char *who = "skyemb_token_mean_pool";
+    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
+    SKY_CHECK_ARG(bank16 && xn && pooled16 && rowp, "%s: null argument", who);
+    SKY_CHECK_ARG(N > 0 && P >= 1 && P <= 64 && 64 % P == 0 && D % BK == 0 && D >= BK && D <= 4096 && N * P < (1ll << 31),
+                  "%s: expected P a divisor of 64, D %% 32 == 0, D <= 4096 and fewer than 2^31 token rows (N=%lld P=%d D=%d)", who,
+                  (long long)N, P, D);
+    SKY_CHECK_ARG(N % BT == 0 || tail, "%s: N = %lld is no whole number of %d-image tiles: a tail tile [%d, D] is needed", who, (long long)N,
+                  BT, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(pooled16) && aligned16(tail), "%s: the bank, the pooled image and the tail tile must be "
+                  "16-byte aligned", who);
+    const int64_t padded = skyemb_bank16_rowp_rows(N);
+    const bool bf = dtype == SKYEMB_BF16;
+    const float kfac = (float)(kappa_of(D, P) / eps_m_of(D, true, bf) * (1.0 + 1e-6));
+    const dim3 grid((unsigned)(padded / 2));
+#define POOL_ARGS (const unsigned short *)bank16, xn, N, P, D, (unsigned short *)pooled16, (float4 *)rowp, padded, \
+                  N % BT ? (unsigned short *)tail : nullptr, N / BT * BT, kfac
+    if (bf) hipLaunchKernelGGL(token_mean_pool_kernel<true>, grid, dim3(128), 0, (hipStream_t)stream, POOL_ARGS);
+    else hipLaunchKernelGGL(token_mean_pool_kernel<false>, grid, dim3(128), 0, (hipStream_t)stream, POOL_ARGS);
+#undef POOL_ARGS
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
 // The pipeline of both entry points.  tiles (NULL: no selection): the search runs under a selection of images prepared by
 // skyemb_token_prefilter_select_prepare -- rowp is then the masked copy, [0, n_live) the positions of the live-tile list the slices
 // walk (the SEL instances of stage 1), last_live says whether the bank's last tile is one of them, and the first (direct-append)
 // slice ends at position direct_sel, which the caller takes from the cumulative counts of selected images.
+// mo (NULL: min / max): combine 'mean' -- stage 1 runs as the ROW search over the pooled image of skyemb_token_mean_pool (a row is an
+// image: no TOK fold), under the mean bound's constants; stage 2 re-scores the candidate images' tokens from the bank as ever.
+struct MeanOperands { const void *pooled, *tail; const float *rowp; };
 static int topk_tokens_prefiltered(const char *who, const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
                                    const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
                                    int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
                                    int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0,
-                                   int direct_sel = 0) {
-    const bool sel = tiles != nullptr;
+                                   int direct_sel = 0, const MeanOperands *mo = nullptr) {
+    const bool sel = tiles != nullptr, mean = mo != nullptr;
     SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
     SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "%s: null argument", who);
-    SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: the two-stage token search "
-                  "combines by min or max (mean is served by skyemb_cosine_token_topk_lp)", who, combine);
-    SKY_CHECK_ARG(skyemb_token_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
-    const int64_t R = N * P;                                   // token rows: whole images, P | 64 | BT
-    SKY_CHECK_ARG(R % BT == 0 || tail, "%s: N * P = %lld rows are no whole number of %d-row tiles: the tail tile of skyemb_resident_rowp "
-                  "is needed", who, (long long)R, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "%s: the bank and the tail tile must be 16-byte aligned", who);
+    if (mean) {
+        SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MEAN, "%s: combine code %d: this entry combines by mean (min and max are served by "
+                      "skyemb_cosine_topk_tokens_prefiltered)", who, combine);
+        SKY_CHECK_ARG(skyemb_token_mean_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_MEAN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
+    } else {
+        SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: this entry combines by min or "
+                      "max (mean is served by skyemb_cosine_topk_tokens_mean_prefiltered)", who, combine);
+        SKY_CHECK_ARG(skyemb_token_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
+    }
+    const int64_t R = mean ? N : N * P;                        // stage 1's rows -- token rows: whole images, P | 64 | BT; mean: images
+    if (mean) {                                                // from here on stage 1's operands are the pooled image's
+        rowp = mo->rowp;
+        tail = mo->tail;
+    }
+    const void *s1_bank = mean ? mo->pooled : bank16;
+    SKY_CHECK_ARG(R % BT == 0 || tail, "%s: %lld rows are no whole number of %d-row tiles: the tail tile of %s is needed", who, (long long)R, BT,
+                  mean ? "skyemb_token_mean_pool" : "skyemb_resident_rowp");
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail) && aligned16(s1_bank), "%s: the bank and the tail tile must be 16-byte aligned", who);
     const int T_tail = (int)(R / BT);                          // whole tiles; the last R % BT rows follow from `tail` as tile T_tail
     const bool tail_live = R % BT != 0 && (!sel || last_live != 0);
     const int T = sel ? n_live - (tail_live ? 1 : 0) : T_tail; // positions the slices walk
@@ -1971,7 +2207,10 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
     }
     const bool bf = dtype == SKYEMB_BF16;
     const char *lo_env = getenv("SKYEMB_PREFILTER_LO");        // the variant rule of topk_prefiltered
-    const bool use_lo = bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
+    // mean: hi + lo unless SKYEMB_PREFILTER_LO=0 -- stage 1 is P times smaller than the token route's and stage 2, P rows per
+    // candidate, is what the search costs: the tighter bound pays
+    const bool use_lo = mean ? !(lo_env && lo_env[0] == '0')
+                             : bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
     SKY_CHECK_ARG(ceil_div64(ceil_div64(R, BT), 8) * ceil_div64(Q, qtile(use_lo)) * (D / BK) < (1ll << 31),
                   "%s: Q x N P too large: ceil(N P / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31 (Q=%d N=%lld P=%d D=%d); search the "
                   "queries in batches", who, qtile(use_lo), Q, (long long)N, P, D);
@@ -1982,14 +2221,18 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
     const int64_t used = carve((char *)ws, Q, D, cap, &w);
     unsigned long long *list = (unsigned long long *)((char *)ws + used);
     int *rn = w.nsel;
-    const float eps_a = (float)((bf ? eps_a_bf16_of(D, use_lo) : eps_a_of(D, use_lo, true)) * (1.0 + 1e-6));
+    const double eps_a_d = (mean ? eps_m_of(D, use_lo, bf) : bf ? eps_a_bf16_of(D, use_lo) : eps_a_of(D, use_lo, true)) * (1.0 + 1e-6);
+    const float eps_a = (float)eps_a_d;
+    // mean: eps / eps_m, raised (the query's third test parameter is N_q eps / qn = (eps_m N_q) gfac / qn); NaN flags every query
+    const float gfac = !mean ? -1.0f : eps >= 0.f && eps < INFINITY ? (float)((double)eps / eps_a_d * (1.0 + 1e-6)) : NAN;
     const dim3 qgrid((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4));
     if (bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
     else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
     const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
     hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
                        w.qpar, w.tau, w.cnt, w.overflow, 0, bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f, bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
-    hipLaunchKernelGGL(token_state_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, Q, (const float4 *)w.qbase, w.tau, rn, w.overflow);
+    hipLaunchKernelGGL(token_state_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, Q, (const float4 *)w.qbase, w.tau, rn, w.overflow,
+                       gfac, w.qpar);
     const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
     constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
     const int smem_re = (TOK_KMAX + cap + TOK_KMAX) * 8 + D * 4 + 264 * 4;
@@ -1999,13 +2242,19 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
     if (rc == 0 && bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true>, smem_max, who);     \
     if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, false, true>, smem_max, who);     \
     if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true, true>, smem_max, who)
-    TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true);
+    if (!mean) { TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true); }
 #undef TK_ATTR
+#define TM_ATTR(M, L)                                                                                                 \
+    if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, false>, smem_max, who); \
+    if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, false>, smem_max, who)
+    if (mean) { TM_ATTR(1, false); TM_ATTR(2, false); TM_ATTR(1, true); TM_ATTR(2, true); }
+#undef TM_ATTR
     if (rc == 0) rc = sky_set_lds_limit(bf ? (const void *)token_rescore_bf_kernel : (const void *)token_rescore_lp_kernel,
                                         (2 * TOK_KMAX + 8192) * 8 + 4096 * 4 + 264 * 4, who);
     if (rc != 0) return rc;
-    const int lgp = log2_of(P), is_max = combine == SKYEMB_COMBINE_MAX ? 1 : 0;
-    const int tok = lgp | (is_max << 8);
+    const int lgp = log2_of(P), fold = mean ? TOK_MEAN : combine == SKYEMB_COMBINE_MAX ? TOK_MAX : TOK_MIN;
+    const int tok = lgp | ((fold == TOK_MAX ? 1 : 0) << 8);
+    const int rpi = mean ? 1 : P;                              // stage 1's rows per image
     // the slices of topk_prefiltered's schedule, the first counted in images (96 k of them: the floor comes from a sample of a small
     // multiple of k images and still passes several per cent of them, so that slice appends directly); no take-all slice.  Under a
     // selection the fractions are taken of the live tiles and the caller has counted the 96 k SELECTED images.
@@ -2013,7 +2262,7 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
     if (sel) {
         direct_end = direct_sel < T ? direct_sel : T;
     } else {
-        direct_end = (int)(ceil_div64((int64_t)96 * k * P, BT) < T ? ceil_div64((int64_t)96 * k * P, BT) : T);
+        direct_end = (int)(ceil_div64((int64_t)96 * k * rpi, BT) < T ? ceil_div64((int64_t)96 * k * rpi, BT) : T);
         if (direct_end < T / 128) direct_end = T / 128;
         if (direct_end < 1) direct_end = 1;
     }
@@ -2022,9 +2271,16 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
                            w.cand_i, w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, tok
 #define TK_LAUNCH_AS(M, L, S, F, B, T0, T1) \
     hipLaunchKernelGGL((prefilter_kernel<M, L, S, F, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
+#define TM_LAUNCH_AS(M, L, F, B, T0, T1) \
+    hipLaunchKernelGGL((prefilter_kernel<M, L, false, F, false>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
 #define TK_LAUNCH(M, B, T0, T1)                                                     \
     do {                                                                            \
-        if (sel) {                                                                  \
+        if (mean) {                                                                 \
+            if (bf && use_lo) TM_LAUNCH_AS(M, true, true, B, T0, T1);               \
+            else if (bf) TM_LAUNCH_AS(M, false, true, B, T0, T1);                   \
+            else if (use_lo) TM_LAUNCH_AS(M, true, false, B, T0, T1);               \
+            else TM_LAUNCH_AS(M, false, false, B, T0, T1);                          \
+        } else if (sel) {                                                                  \
             if (bf && use_lo) TK_LAUNCH_AS(M, true, true, true, B, T0, T1);         \
             else if (bf) TK_LAUNCH_AS(M, false, true, true, B, T0, T1);             \
             else if (use_lo) TK_LAUNCH_AS(M, true, true, false, B, T0, T1);         \
@@ -2042,10 +2298,10 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
         const int t1 = ends[p];
         if (t1 <= t0) continue;
         if (!direct_done) {
-            TK_LAUNCH(1, bank16, t0, t1);
+            TK_LAUNCH(1, s1_bank, t0, t1);
             direct_done = true;
         } else {
-            TK_LAUNCH(2, bank16, t0, t1);
+            TK_LAUNCH(2, s1_bank, t0, t1);
             hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count, w.capw,
                                cap, w.cnt, w.cand_i, w.cand_d);
         }
@@ -2056,7 +2312,7 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
             const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T_tail * BT * D * sizeof(half_t));
             TK_LAUNCH(1, tail_base, sel ? T : T_tail, (sel ? T : T_tail) + 1);
         }
-#define TK_RESCORE(B) tw, qn, B, xn, N, D, lgp, is_max, k, eps, idx_offset, cap, (const float4 *)w.qbase, w.cnt, (const int *)w.cand_i, list, rn, \
+#define TK_RESCORE(B) tw, qn, B, xn, N, D, lgp, fold, gfac, k, eps, idx_offset, cap, (const float4 *)w.qbase, w.cnt, (const int *)w.cand_i, list, rn, \
                       w.qpar, w.tau, w.overflow, final, out_s, out_i, redo
         if (bf) hipLaunchKernelGGL(token_rescore_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16));
         else hipLaunchKernelGGL(token_rescore_lp_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const half_t *)bank16));
@@ -2065,6 +2321,7 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
     }
 #undef TK_LAUNCH
 #undef TK_LAUNCH_AS
+#undef TM_LAUNCH_AS
 #undef TK_ARGS
     SKY_LAUNCH_CHECK(who);
     return 0;
@@ -2104,4 +2361,16 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const 
     return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered_sel", tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, N, P, D, k,
                                    combine, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live,
                                    direct_end);
+}
+
+// ---- combine 'mean': the same pipeline over the pooled image of skyemb_token_mean_pool --------------------------------------------------
+extern "C" int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                          const float *xn, const void *tail, const float *rowp, int64_t N, int P, int D,
+                                                          int k, int combine, float eps, int64_t idx_offset, const float *thr0, void *ws,
+                                                          int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, const void *pooled16,
+                                                          void *stream) {
+    SKY_CHECK_ARG(pooled16, "skyemb_cosine_topk_tokens_mean_prefiltered: null argument");
+    const MeanOperands mo = {pooled16, tail, rowp};
+    return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_mean_prefiltered", tw, qn, Q, bank16, dtype, xn, tail, rowp, N, P, D, k, combine,
+                                   eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream, nullptr, 0, 0, 0, &mo);
 }

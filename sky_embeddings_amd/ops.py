@@ -566,6 +566,49 @@ def cosine_topk_tokens_prefiltered(tw, qn, tokens, xn, tail, rowp, k, combine, e
     return ws
 
 
+def token_mean_prefilter_refusal(Q, N, P, D, k):
+    """None when the two-stage token search with combine mean takes the shape, else the library's own statement of its limits."""
+    L = lib()
+    return None if L.skyemb_token_mean_prefilter_applicable(Q, N, P, D, k) else L.skyemb_last_error().decode()
+
+
+def token_mean_prefilter_eps_m(D, dtype, lo=True):
+    """eps_m of stage 1 over the pooled image of a ``dtype`` token bank (host arithmetic only; include/skyemb.h)."""
+    return lib().skyemb_token_mean_prefilter_eps_m(D, int(lo), resident_dtype_code(dtype, "token_mean_prefilter_eps_m"))
+
+
+def token_mean_pool(tokens, xn):
+    """(pooled, tail, rowp) of ``skyemb_token_mean_pool`` over a resident 16-bit token bank ``tokens`` [N, P, D] and the norms of
+    its N * P rows: the pooled image [N, D] in the bank's dtype, its zero-padded tail tile (None when N % 256 == 0) and the row
+    constants f32 [ceil(N / 256) * 256, 4] of the mean bound."""
+    N, P, D = tokens.shape
+    code = resident_dtype_code(tokens.dtype, "token_mean_pool")
+    assert tokens.is_contiguous()
+    rows = lib().skyemb_bank16_rowp_rows(N)
+    pooled = torch.empty(N, D, device=tokens.device, dtype=tokens.dtype)
+    rowp = torch.empty(rows, 4, device=tokens.device, dtype=torch.float32)
+    tail = torch.empty(256, D, device=tokens.device, dtype=tokens.dtype) if rows != N else None
+    check(lib().skyemb_token_mean_pool(_p(tokens), code, _p(xn), N, P, D, _p(pooled), _p(rowp), _p(tail), _stream()),
+          "skyemb_token_mean_pool")
+    return pooled, tail, rowp
+
+
+def cosine_topk_tokens_mean_prefiltered(tw, qn, tokens, xn, pooled, tail, rowp, k, eps, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """The two-stage many-query search with combine mean over a resident 16-bit token bank ``tokens`` [N, P, D] and the
+    (pooled, tail, rowp) of ``token_mean_pool`` (include/skyemb.h)."""
+    Q, D = tw.shape
+    N, P = tokens.shape[:2]
+    code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_mean_prefiltered")
+    need = lib().skyemb_token_mean_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_tokens_mean_prefiltered(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp), N, P, D, k,
+                                                           COMBINE_CODES['mean'], eps, idx_offset, _p(thr0), _p(ws), ws.numel(),
+                                                           _p(out_s), _p(out_i), _p(redo), _p(pooled), _stream()),
+          "skyemb_cosine_topk_tokens_mean_prefiltered")
+    return ws
+
+
 def token_prefilter_select_prepare(words, N, P, rowp):
     """What the two-stage token search needs of a selection of IMAGES (packed ``words`` of ``pack_select`` over the N images) over
     a resident token bank of N x P rows with row constants ``rowp`` (``resident_rowp`` over the flat rows): (rowp_sel, tiles, n_live,

@@ -423,13 +423,14 @@ class TokenBank:
         self._sample = None
         self._resident = False                             # True: made by TokenBank.resident
         self._stage1 = self._boot = None                   # (tail tile, rowp) / the bootstrap sample of the two-stage route
+        self._stage1_mean = None                           # (pooled image, its tail tile, rowp) of the route under combine 'mean'
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
 
     @classmethod
     def resident(cls, bank: torch.Tensor, weights: torch.Tensor | None = None, idx_offset: int = 0):
         """A TokenBank over a resident 16-bit token bank: a contiguous, 16-byte aligned [N, P, D] tensor of fp16 or bf16 (ValueError
-        for anything else), whose many-query min / max searches may take the two-stage route (``cosine_topk_tokens``)."""
+        for anything else), whose many-query min / max / mean searches may take the two-stage route (``cosine_topk_tokens``)."""
         if not isinstance(bank, torch.Tensor) or bank.dtype not in ops.LP_DTYPES:
             what = bank.dtype if isinstance(bank, torch.Tensor) else type(bank).__name__
             raise ValueError(f"TokenBank.resident: a resident token bank is torch.float16 or torch.bfloat16, got {what}; an fp32 bank "
@@ -452,6 +453,14 @@ class TokenBank:
             self._stage1 = ops.resident_rowp(self.bank.view(N * P, D), self.norms)
         return self._stage1
 
+    def stage1_mean(self):
+        """(pooled, tail, rowp) of ``ops.token_mean_pool``: what stage 1 of the two-stage route reads under combine 'mean' -- the
+        16-bit image [N, D] of the images' pooled unit tokens, its 256-row tail tile and the row constants of the mean bound
+        (2 D + 16 bytes per image and one tail tile).  Built on first use, kept until the weights change."""
+        if self._stage1_mean is None:
+            self._stage1_mean = ops.token_mean_pool(self.bank, self.norms)
+        return self._stage1_mean
+
     def set_weights(self, weights):
         self._version += 1
         self.weights = None if weights is None else weights.to(self.bank.device, torch.float32).contiguous()
@@ -461,7 +470,7 @@ class TokenBank:
         else:
             ops.weighted_norms_lp(rows, self.weights, self.norms)
         self._sample = None
-        self._stage1 = self._boot = None
+        self._stage1 = self._boot = self._stage1_mean = None
 
     def sample(self, images: int):
         """A strided sample of WHOLE images (tokens [S, P, D] in the bank's dtype + the norms of their S * P rows) used to
@@ -863,20 +872,24 @@ def _topk_tokens(rq: TokenRequest, sc, queries, prune, stats, process_group, wor
 
 
 TOKEN_PREFILTER_MIN_Q = 256    # fewest queries sent through the two-stage token route (measured: DESIGN.md section 6, item 17)
+TOKEN_MEAN_PREFILTER_MIN_Q = 256   # ... under combine 'mean': the smallest measured Q that beats the grouped route
 
 
 def _token_prefilter_refusal(rq: TokenRequest):
     """None when ``cosine_topk_tokens`` serves the request by the two-stage route, else the first reason why the grouped route
     serves it.  A pure function of the request (and the bank it names): no device work."""
     tb = rq.bank
+    if tb is not None and getattr(tb, "dtype", None) == torch.float32:
+        return "an fp32 token bank"
     if tb is None or not getattr(tb, "_resident", False):
         return "the bank was not made by TokenBank.resident"
     if rq.metric is not None:
         return "a distance metric"
-    if rq.combine not in (ops.COMBINE_CODES['min'], ops.COMBINE_CODES['max']):
-        return "combine is neither 'min' nor 'max'"
+    mean = rq.combine == ops.COMBINE_CODES['mean']
     if rq.top_t != 0:
         return "top_t"
+    if mean and rq.select is not None:
+        return "select under combine 'mean'"
     if rq.select is not None and not isinstance(rq.select, Selection):
         return "select is not a Selection"
     if rq.per_query:
@@ -885,6 +898,10 @@ def _token_prefilter_refusal(rq: TokenRequest):
         return f"P = {rq.P} does not divide 64"
     if not _prefilter_enabled():
         return "SKYEMB_TOPK_PREFILTER=0"
+    if mean:                                               # its own size and shape rule: stage 1 walks images, not token rows
+        if rq.Q < TOKEN_MEAN_PREFILTER_MIN_Q:
+            return f"Q = {rq.Q} < TOKEN_MEAN_PREFILTER_MIN_Q = {TOKEN_MEAN_PREFILTER_MIN_Q}"
+        return ops.token_mean_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
     if rq.Q < TOKEN_PREFILTER_MIN_Q:
         return f"Q = {rq.Q} < TOKEN_PREFILTER_MIN_Q = {TOKEN_PREFILTER_MIN_Q}"
     why = ops.token_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
@@ -929,13 +946,17 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
     q = queries.to(dev, torch.float32).contiguous()
     tw, qn = prepare_queries(q, tb.weights)
     thr0 = _bootstrap_floor(rq, tw, qn, eps)
-    tail, rowp = tb.stage1()
     out_s = torch.empty(Q, k, device=dev)
     out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
     redo = torch.empty(Q, device=dev, dtype=torch.int32)
-    if sel is None:
+    if rq.combine == ops.COMBINE_CODES['mean']:            # stage 1 over the pooled image (never under a selection)
+        pooled, tail, rowp = tb.stage1_mean()
+        ops.cosine_topk_tokens_mean_prefiltered(tw, qn, tb.bank, tb.norms, pooled, tail, rowp, k, eps, rq.idx_offset, out_s, out_i, redo, thr0)
+    elif sel is None:
+        tail, rowp = tb.stage1()
         ops.cosine_topk_tokens_prefiltered(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, eps, rq.idx_offset, out_s, out_i, redo, thr0)
     else:
+        tail, rowp = tb.stage1()
         prepared = sel.token_prefilter(tb)
         n_live, cum = prepared[2], prepared[4]
         direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)
@@ -1019,9 +1040,14 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     that hold a selected image, every row of a deselected image fails its test whatever it holds, the first threshold comes from
     a sample of selected images, and a re-run keeps the selection; ``stats`` gains ``selected`` and ``tiles`` = (live tiles, all
     tiles).  What the selection needs is kept in the ``Selection`` per bank (``Selection.token_prefilter``): pass the same object to
-    repeated searches.  Everything else is served by the grouped route as ever, never refused.  Out of scope for the two-stage
-    route: 'mean' (it needs per-pair bounds in score units, a division per pair), ``top_t``, per-query weights, the distance
-    metrics, fp32 token banks and P not dividing 64.
+    repeated searches.  ``combine`` 'mean' takes the route by a stage 1 of its own: the mean of an image's token cosines is, up to
+    ``eps`` and rounding, one dot product with the image's pooled unit tokens, so the matrix cores multiply a derived 16-bit image
+    [N, D] of them (``TokenBank.stage1_mean``, one launch per bank and weights version) under a proven bound U >= mean, and every
+    candidate image's P tokens are re-scored exactly, folded in token order with the one division -- bit for bit the grouped
+    route.  Its rule: no ``select``, no ``top_t``, shared weights, P a divisor of 64, at least ``TOKEN_MEAN_PREFILTER_MIN_Q``
+    queries, D % 32 == 0, 128 <= D <= 4096, N >= 2048 images, N P < 2^31, k <= 256, k <= N.  Everything else is served by the grouped
+    route as ever, never refused.  Out of scope for the two-stage route: ``top_t``, per-query weights, the distance metrics, fp32
+    token banks, P not dividing 64, and ``select`` under 'mean'.
 
     Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
