@@ -643,6 +643,35 @@ int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const float *qn, 
                                               int direct_end, int64_t N, int P, int D, int k, int combine, float eps,
                                               int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
                                               int64_t *out_i, int *redo, void *stream);
+/* Both searches above under the top-t combine (top_t, the reference's n_top_sims; skyemb_cosine_token_topk_top's rule): with
+ * d[0] >= d[1] >= ... an image's token scores in descending order, -inf (a NaN score) last, SKYEMB_COMBINE_MIN scores d[top_t-1] and
+ * SKYEMB_COMBINE_MAX d[0].  Scores and image indices are bit for bit those of skyemb_cosine_token_topk_top (_sel) +
+ * skyemb_topk_merge over the same bank; an image with fewer than top_t scores above -inf scores -inf and is never returned.  The
+ * arguments are those of the plain calls with top_t after combine.
+ *   top_t == 0               IS the plain call: same checks, same kernels.
+ *   max, any top_t           IS the plain max call (d[0] does not depend on top_t).
+ *   min, top_t == P          IS the plain min call (d[P-1] is the min).
+ *   min, 1 <= top_t < P      d[top_t-1] >= tau needs at least top_t rows of the image to pass the row test, so stage 1 makes an image
+ *                            a candidate iff the COUNT of its passing rows is >= top_t (top_t == 1: some row passes, the fold of max),
+ *                            and stage 2 sorts the image's P exact token scores by skyemb_cosine_token_topk_top's own network and
+ *                            takes d[top_t-1].  top_t == 1 is not promised to equal the plain max call to the bit (a NaN score is
+ *                            -inf in both, but the orders of fmaxf differ).
+ *   mean, top_t != 0         refused with a text: the mean of the top_t best scores is not bounded by a count of passing rows; the
+ *                            caller runs skyemb_cosine_token_topk_top.
+ *   skyemb_token_topt_prefilter_applicable   skyemb_token_prefilter_applicable's shape limits, combine min or max, and
+ *                            1 <= top_t <= min(P, 16).  A refusal leaves its reason as the error text (skyemb_last_error).
+ * Workspace, thr0 (a floor of the k-th best score UNDER THE SAME top_t), redo and the variant switch as for the plain calls; a
+ * flagged query is re-run through skyemb_cosine_token_topk_top (_sel) with the same top_t. */
+int skyemb_token_topt_prefilter_applicable(int Q, int64_t N, int P, int D, int k, int combine, int top_t);
+int skyemb_cosine_topk_tokens_prefiltered_top(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                              const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                              int top_t, float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                              float *out_s, int64_t *out_i, int *redo, void *stream);
+int skyemb_cosine_topk_tokens_prefiltered_top_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                  const float *xn, const void *tail, const float *rowp_sel, const int *tiles, int n_live,
+                                                  int last_live, int direct_end, int64_t N, int P, int D, int k, int combine, int top_t,
+                                                  float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                  float *out_s, int64_t *out_i, int *redo, void *stream);
 /* The same search with per-image combine SKYEMB_COMBINE_MEAN: scores and image indices are bit for bit those of
  * skyemb_cosine_token_topk_lp + skyemb_topk_merge under mean -- token scores by the contract's chain, (((0 + s_0) + s_1) + ...) /
  * float32(P) in token order, an image with a NaN token scores -inf and is never returned.  The mean of an image's token cosines is,

@@ -185,6 +185,13 @@ PROTOTYPES = {
     "skyemb_cosine_topk_tokens_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                                           c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
                                                           c_vp, c_vp]),
+    # ... and under top_t (min: the count of passing rows; max: the plain call): additive again
+    "skyemb_token_topt_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "skyemb_cosine_topk_tokens_prefiltered_top": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
+                                                          c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_tokens_prefiltered_top_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                                              c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64,
+                                                              c_vp, c_vp, c_vp, c_vp]),
     # ... and with combine mean, over the pooled image of the bank: additive again
     "skyemb_token_mean_pool": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_token_mean_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),

@@ -81,6 +81,7 @@
 // |tw_d| >= 2^79), is flagged by init_state_kernel and re-run by the caller; its dot^ are never trusted.  Nothing else changes:
 // same bytes, same tiles, ring, swizzle, candidate test, lists, phases, selection handling, tail tile; stage 2 widens bf16 rows.
 #include "common.h"
+#include "token_combine.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -432,6 +433,58 @@ __device__ __forceinline__ int frag_lane(int lane) { return (lane & 15) * 64 + (
 __device__ __forceinline__ half8 frag(const char *sbase, int rbase, int lane_c) {
     return *(const half8 *)(sbase + rbase * 64 + lane_c);
 }
+// ---- the counting fold of a token search under top_t (prefilter_kernel<.., TOK, CNT>) ------------------------------------------------
+// The pass bits of a lane are 32 independent columns (one per query block and row fragment).  The count of passed rows of an image
+// is kept BIT-SLICED: plane c[b] holds bit b of the count of every column, so one half / full adder over whole words adds 32 counts
+// at once.  Same tree as the AND / OR fold: four DPP row shifts (lane l takes lane l + o; the first lane of an aligned group ends
+// with the group's count -- a lane whose source lies outside its row adds its own value and is cleared at the end), then, for
+// P = 32 / 64, the neighbouring bits of each nibble.  Counts reach 2, 4, 8, 16, 32, 64: at most 7 planes.  No LDS, no per-lane
+// branch; lgp and t are wave-uniform.
+template <int NPL>
+__device__ __forceinline__ void planes_add(unsigned int (&c)[7], const unsigned int (&y)[7]) {   // c[0 .. NPL] = c[0 .. NPL) + y[0 .. NPL)
+    unsigned int carry = 0u;
+#pragma unroll
+    for (int b = 0; b < NPL; ++b) {
+        const unsigned int x = c[b] ^ y[b], g = c[b] & y[b];
+        c[b] = x ^ carry;
+        carry = g | (carry & x);
+    }
+    c[NPL] = carry;
+}
+template <int NPL, int CTRL>
+__device__ __forceinline__ void planes_add_dpp(unsigned int (&c)[7]) {
+    unsigned int y[7];
+#pragma unroll
+    for (int b = 0; b < NPL; ++b) y[b] = (unsigned int)__builtin_amdgcn_update_dpp((int)c[b], (int)c[b], CTRL, 0xF, 0xF, false);
+    planes_add<NPL>(c, y);
+}
+template <int NPL>
+__device__ __forceinline__ void planes_add_shr(unsigned int (&c)[7], int sh) {
+    unsigned int y[7];
+#pragma unroll
+    for (int b = 0; b < NPL; ++b) y[b] = c[b] >> sh;
+    planes_add<NPL>(c, y);
+}
+// m: the lane's pass bits -> the bit of an image's first row (first lane of its aligned group of 2^min(lgp, 4) lanes; P = 32 / 64:
+// bit 0 / 2 resp. bit 0 of each nibble) is set iff at least t of its 2^lgp rows passed; every other lane and bit is cleared
+__device__ __forceinline__ unsigned int count_fold(unsigned int m, int lgp, int t, int l16) {
+    const int lg16 = lgp < 4 ? lgp : 4;
+    unsigned int c[7] = {m, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (lg16 >= 1) planes_add_dpp<1, 0x101>(c);              // row_shl:1
+    if (lg16 >= 2) planes_add_dpp<2, 0x102>(c);              // row_shl:2
+    if (lg16 >= 3) planes_add_dpp<3, 0x104>(c);              // row_shl:4
+    if (lg16 >= 4) planes_add_dpp<4, 0x108>(c);              // row_shl:8
+    if (lgp >= 5) planes_add_shr<5>(c, 1);                   // blocks (0, 1) -> bit 0, (2, 3) -> bit 2
+    if (lgp >= 6) planes_add_shr<6>(c, 2);                   // all four blocks -> bit 0
+    // count >= t, from the lowest plane up: a higher plane overrules what the lower ones said, equal bits keep it (count == t: yes)
+    unsigned int ge = ~0u;
+#pragma unroll
+    for (int b = 0; b < 7; ++b) ge = ((t >> b) & 1) ? (c[b] & ge) : (c[b] | ge);
+    if (lgp >= 5) ge &= 0x55555555u;
+    if (lgp >= 6) ge &= 0x11111111u;
+    return (l16 & ((1 << lg16) - 1)) == 0 ? ge : 0u;
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -466,7 +519,9 @@ __device__ __forceinline__ void wait_vmcnt() {
 // a divisor of 64 (tok = lgp | is_max << 8), and the candidates are IMAGES: between the masks and the appends the pass bits of an
 // image's P rows are folded -- AND under 'min', OR under 'max' -- into the image's first row, whose lane appends the image number.
 // Without TOK `tok` is not read: the instruction stream of the row search.
-template <int MODE, bool LO, bool SEL, bool BF = false, bool TOK = false>
+// CNT (with TOK; 'min' under top_t = t, 1 < t < P: tok = lgp | t << 16): the fold COUNTS -- an image is a candidate iff at least t of its
+// P rows passed (count_fold below).  AND is the case t = P and OR the case t = 1: those keep the fold above and its instances.
+template <int MODE, bool LO, bool SEL, bool BF = false, bool TOK = false, bool CNT = false>
 __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict__ qh, const half_t *__restrict__ ql,
                                                        const half_t *__restrict__ bank16, const float4 *__restrict__ rowp,
                                                        const int *__restrict__ tiles,
@@ -711,7 +766,10 @@ __global__ __launch_bounds__(NT) void prefilter_kernel(const half_t *__restrict_
             mr[r] = 0;
         }
 #endif
-        if constexpr (TOK) {
+        if constexpr (TOK && CNT) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mr[r] = count_fold(mr[r], tok & 255, tok >> 16, l16);
+        } else if constexpr (TOK) {
             // Rows of a 16-row block lie across the 16 lanes l16; the four blocks of the wave's strip are bit j of each nibble.  An
             // image is 2^lgp neighbouring rows of the strip.  Up to 16 rows: a tree over the lane bits with DPP row shifts (lane l
             // takes lane l + o of its 16-lane row; the first lane of an aligned group ends with the fold of the whole group, the
@@ -1910,14 +1968,20 @@ __global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, floa
 
 // one workgroup (256 threads) per query: the exact combined scores of the slice's candidate images, the merge into the running
 // list, the new threshold; final: the ordered result.  lgp: P = 2^lgp <= 64 tokens, one lane each, 256 / P images per round.
-template <typename X>
+// TOPT ('min' under top_t, the `_top` entries; fold is TOK_MIN): the image scores d[top_t - 1], the top_t-th best of its token scores,
+// by the grouped kernels' own network (token_combine.h) in their operand order -- so bit for bit their value, ties by fmaxf / fminf.
+// There an image of 32 / 64 tokens meets the network as two / four 16-token tiles, one after the other, with the 16 best so far
+// carried; here the tiles sit side by side on 32 / 64 lanes: each is sorted in its own 16 lanes, then tiles 1, 2, 3 are merged, in
+// that order, into the lanes of tile 0 (top_tile's step with the carry in tile 0's lanes and the new tile fetched across).
+// Without TOPT top_t is not read: the instruction stream of the kernels without it.
+template <typename X, bool TOPT = false>
 __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank,
                                                    const float *__restrict__ xn, int64_t N, int D, int lgp, int fold, float gfac, int k,
                                                    float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase, int *__restrict__ cnt,
                                                    const int *__restrict__ cand_i, unsigned long long *__restrict__ list,
                                                    int *__restrict__ rn, float4 *__restrict__ qpar, float *__restrict__ tau_q,
                                                    int *__restrict__ overflow, int final, float *__restrict__ out_s,
-                                                   int64_t *__restrict__ out_i, int *__restrict__ redo) {
+                                                   int64_t *__restrict__ out_i, int *__restrict__ redo, int top_t = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *keys = (unsigned long long *)smem;     // [TOK_KMAX + cap] the running list, then the slice's candidates
     unsigned long long *kept = keys + TOK_KMAX + cap;          // [TOK_KMAX] the new running list
@@ -1951,7 +2015,19 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
             acc = fmaf(sq[d + 3], v.w, acc);
         }
         float s = finish_score(acc, qnv, xn[row], eps);        // a NaN score is -inf: out under min and mean, ignored under max
-        if (fold == TOK_MEAN) {
+        if constexpr (TOPT) {
+            const int ln = tid & 63, tp = P < 16 ? P : 16, n16 = ln & 15;
+            float v = sort_desc(s, ln & (tp - 1), tp);         // every tile of 16 (or image of P < 16) tokens, descending over its lanes
+            if (P > 16) {                                      // wave-uniform
+                const float mir = lane_xor(v, 15);             // the tile's sorted scores, mirrored: top_tile's second operand
+                const int first = ln & ~(P - 1);
+                for (int j = 1; j < (P >> 4); ++j) {
+                    const float u = __shfl(mir, first + 16 * j + n16, 64);
+                    v = merge_desc16(fmaxf(v, u), n16);        // (what lanes past the image's first 16 hold from here on is not read)
+                }
+            }
+            s = top_finish<SKYEMB_COMBINE_MIN>(v, ln, P, top_t);   // lane first + top_t - 1: d[top_t - 1]; -inf with fewer than top_t scores
+        } else if (fold == TOK_MEAN) {
             // the grouped kernels' fold (combine_tile<SKYEMB_COMBINE_MEAN>, token_combine.h): (((0 + s_0) + s_1) + ...) in token
             // order, one division by float(P), a sum that is not a number scores -inf
             const int first = (tid & 63) & ~(P - 1);
@@ -2031,6 +2107,12 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
                            final, out_s, out_i, redo
 __global__ __launch_bounds__(256) void token_rescore_lp_kernel(TOKEN_RESCORE_PARAMS(half_t)) { token_rescore_body<half_t>(TOKEN_RESCORE_PASS); }
 __global__ __launch_bounds__(256) void token_rescore_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t)) { token_rescore_body<bf16_t>(TOKEN_RESCORE_PASS); }
+__global__ __launch_bounds__(256) void token_rescore_top_lp_kernel(TOKEN_RESCORE_PARAMS(half_t), int top_t) {
+    token_rescore_body<half_t, true>(TOKEN_RESCORE_PASS, top_t);
+}
+__global__ __launch_bounds__(256) void token_rescore_top_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), int top_t) {
+    token_rescore_body<bf16_t, true>(TOKEN_RESCORE_PASS, top_t);
+}
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
 
@@ -2118,6 +2200,25 @@ extern "C" int skyemb_token_prefilter_applicable(int Q, int64_t N, int P, int D,
     return ok ? 1 : 0;
 }
 
+// ---- 'min' / 'max' under top_t: the shape rule above plus 1 <= top_t <= min(P, 16); 'mean' under top_t is not served (the mean of the
+// top_t best is not bounded by a count of pass bits)
+#define TOKEN_TOPT_MEAN_MSG "many-query patch-token search: top_t under combine mean is not served by the two-stage route (the mean of " \
+                            "the top_t best token scores is not bounded by a count of passing rows); the grouped search serves it"
+#define TOKEN_TOPT_RANGE_MSG "many-query patch-token search: top_t must be 1 .. min(P, 16) (top_t=%d P=%d)"
+extern "C" int skyemb_token_topt_prefilter_applicable(int Q, int64_t N, int P, int D, int k, int combine, int top_t) {
+    if (combine != SKYEMB_COMBINE_MIN && combine != SKYEMB_COMBINE_MAX) {
+        if (combine == SKYEMB_COMBINE_MEAN) skyemb_set_error(TOKEN_TOPT_MEAN_MSG);
+        else skyemb_set_error("many-query patch-token search: unknown combine code %d", combine);
+        return 0;
+    }
+    if (!skyemb_token_prefilter_applicable(Q, N, P, D, k)) return 0;     // (its own text)
+    if (top_t < 1 || top_t > (P < 16 ? P : 16)) {
+        skyemb_set_error(TOKEN_TOPT_RANGE_MSG, top_t, P);
+        return 0;
+    }
+    return 1;
+}
+
 extern "C" int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k) {
     return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr) + align256((int64_t)Q * TOK_KMAX * 8);
 }
@@ -2167,12 +2268,16 @@ extern "C" int skyemb_token_mean_pool(const void *bank16, int dtype, const float
 // slice ends at position direct_sel, which the caller takes from the cumulative counts of selected images.
 // mo (NULL: min / max): combine 'mean' -- stage 1 runs as the ROW search over the pooled image of skyemb_token_mean_pool (a row is an
 // image: no TOK fold), under the mean bound's constants; stage 2 re-scores the candidate images' tokens from the bank as ever.
+// top_t (0: all tokens, the search as ever; the `_top` entries): only the top_t best token scores of an image count.  'max' is d[0]
+// whatever top_t is and 'min' with top_t == P is the plain min: both ARE the plain search, same kernels.  'min' with 1 <= top_t < P:
+// an image is a candidate iff at least top_t of its rows pass the row test -- top_t == 1 is the OR fold of 'max', else the CNT
+// instances of stage 1 count -- and stage 2 scores d[top_t - 1] (the TOPT re-score kernels).
 struct MeanOperands { const void *pooled, *tail; const float *rowp; };
 static int topk_tokens_prefiltered(const char *who, const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
                                    const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
                                    int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
                                    int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0,
-                                   int direct_sel = 0, const MeanOperands *mo = nullptr) {
+                                   int direct_sel = 0, const MeanOperands *mo = nullptr, int top_t = 0) {
     const bool sel = tiles != nullptr, mean = mo != nullptr;
     SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
     SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "%s: null argument", who);
@@ -2181,10 +2286,15 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
                       "skyemb_cosine_topk_tokens_prefiltered)", who, combine);
         SKY_CHECK_ARG(skyemb_token_mean_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_MEAN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
     } else {
+        SKY_CHECK_ARG(top_t == 0 || combine != SKYEMB_COMBINE_MEAN, "%s: " TOKEN_TOPT_MEAN_MSG, who);
         SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: this entry combines by min or "
                       "max (mean is served by skyemb_cosine_topk_tokens_mean_prefiltered)", who, combine);
         SKY_CHECK_ARG(skyemb_token_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
+        SKY_CHECK_ARG(top_t >= 0 && top_t <= (P < 16 ? P : 16), "%s: top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)", who,
+                      top_t, P);
     }
+    if (combine == SKYEMB_COMBINE_MAX || top_t == P) top_t = 0;   // d[0] is the max and d[P - 1] the min: the plain search
+    const bool topt = top_t != 0, cnt = top_t > 1;             // stage 2 selects d[top_t - 1]; stage 1 counts (top_t == 1: the OR fold)
     const int64_t R = mean ? N : N * P;                        // stage 1's rows -- token rows: whole images, P | 64 | BT; mean: images
     if (mean) {                                                // from here on stage 1's operands are the pooled image's
         rowp = mo->rowp;
@@ -2242,18 +2352,27 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
     if (rc == 0 && bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true>, smem_max, who);     \
     if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, false, true>, smem_max, who);     \
     if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true, true>, smem_max, who)
-    if (!mean) { TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true); }
+    if (!mean && !cnt) { TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true); }
 #undef TK_ATTR
+#define TC_ATTR(M, L)                                                                                                                 \
+    if (rc == 0 && !bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, true, true>, smem_max, who);  \
+    if (rc == 0 && bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true, true>, smem_max, who);    \
+    if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, false, true, true>, smem_max, who);    \
+    if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true, true, true>, smem_max, who)
+    if (cnt) { TC_ATTR(1, false); TC_ATTR(2, false); TC_ATTR(1, true); TC_ATTR(2, true); }
+#undef TC_ATTR
 #define TM_ATTR(M, L)                                                                                                 \
     if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, false>, smem_max, who); \
     if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, false>, smem_max, who)
     if (mean) { TM_ATTR(1, false); TM_ATTR(2, false); TM_ATTR(1, true); TM_ATTR(2, true); }
 #undef TM_ATTR
-    if (rc == 0) rc = sky_set_lds_limit(bf ? (const void *)token_rescore_bf_kernel : (const void *)token_rescore_lp_kernel,
-                                        (2 * TOK_KMAX + 8192) * 8 + 4096 * 4 + 264 * 4, who);
+    const void *rescore = topt ? (bf ? (const void *)token_rescore_top_bf_kernel : (const void *)token_rescore_top_lp_kernel)
+                               : (bf ? (const void *)token_rescore_bf_kernel : (const void *)token_rescore_lp_kernel);
+    if (rc == 0) rc = sky_set_lds_limit(rescore, (2 * TOK_KMAX + 8192) * 8 + 4096 * 4 + 264 * 4, who);
     if (rc != 0) return rc;
     const int lgp = log2_of(P), fold = mean ? TOK_MEAN : combine == SKYEMB_COMBINE_MAX ? TOK_MAX : TOK_MIN;
-    const int tok = lgp | ((fold == TOK_MAX ? 1 : 0) << 8);
+    // (the instances without CNT read every bit above bit 7 as "is max": top_t travels only to those that count)
+    const int tok = lgp | ((fold == TOK_MAX || top_t == 1 ? 1 : 0) << 8) | (cnt ? top_t << 16 : 0);
     const int rpi = mean ? 1 : P;                              // stage 1's rows per image
     // the slices of topk_prefiltered's schedule, the first counted in images (96 k of them: the floor comes from a sample of a small
     // multiple of k images and still passes several per cent of them, so that slice appends directly); no take-all slice.  Under a
@@ -2271,6 +2390,8 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
                            w.cand_i, w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, tok
 #define TK_LAUNCH_AS(M, L, S, F, B, T0, T1) \
     hipLaunchKernelGGL((prefilter_kernel<M, L, S, F, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
+#define TC_LAUNCH_AS(M, L, S, F, B, T0, T1) \
+    hipLaunchKernelGGL((prefilter_kernel<M, L, S, F, true, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
 #define TM_LAUNCH_AS(M, L, F, B, T0, T1) \
     hipLaunchKernelGGL((prefilter_kernel<M, L, false, F, false>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
 #define TK_LAUNCH(M, B, T0, T1)                                                     \
@@ -2280,6 +2401,16 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
             else if (bf) TM_LAUNCH_AS(M, false, true, B, T0, T1);                   \
             else if (use_lo) TM_LAUNCH_AS(M, true, false, B, T0, T1);               \
             else TM_LAUNCH_AS(M, false, false, B, T0, T1);                          \
+        } else if (cnt && sel) {                                                    \
+            if (bf && use_lo) TC_LAUNCH_AS(M, true, true, true, B, T0, T1);         \
+            else if (bf) TC_LAUNCH_AS(M, false, true, true, B, T0, T1);             \
+            else if (use_lo) TC_LAUNCH_AS(M, true, true, false, B, T0, T1);         \
+            else TC_LAUNCH_AS(M, false, true, false, B, T0, T1);                    \
+        } else if (cnt) {                                                           \
+            if (bf && use_lo) TC_LAUNCH_AS(M, true, false, true, B, T0, T1);        \
+            else if (bf) TC_LAUNCH_AS(M, false, false, true, B, T0, T1);            \
+            else if (use_lo) TC_LAUNCH_AS(M, true, false, false, B, T0, T1);        \
+            else TC_LAUNCH_AS(M, false, false, false, B, T0, T1);                   \
         } else if (sel) {                                                                  \
             if (bf && use_lo) TK_LAUNCH_AS(M, true, true, true, B, T0, T1);         \
             else if (bf) TK_LAUNCH_AS(M, false, true, true, B, T0, T1);             \
@@ -2314,13 +2445,16 @@ static int topk_tokens_prefiltered(const char *who, const float *tw, const float
         }
 #define TK_RESCORE(B) tw, qn, B, xn, N, D, lgp, fold, gfac, k, eps, idx_offset, cap, (const float4 *)w.qbase, w.cnt, (const int *)w.cand_i, list, rn, \
                       w.qpar, w.tau, w.overflow, final, out_s, out_i, redo
-        if (bf) hipLaunchKernelGGL(token_rescore_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16));
+        if (topt && bf) hipLaunchKernelGGL(token_rescore_top_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16), top_t);
+        else if (topt) hipLaunchKernelGGL(token_rescore_top_lp_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const half_t *)bank16), top_t);
+        else if (bf) hipLaunchKernelGGL(token_rescore_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16));
         else hipLaunchKernelGGL(token_rescore_lp_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const half_t *)bank16));
 #undef TK_RESCORE
         t0 = t1;
     }
 #undef TK_LAUNCH
 #undef TK_LAUNCH_AS
+#undef TC_LAUNCH_AS
 #undef TM_LAUNCH_AS
 #undef TK_ARGS
     SKY_LAUNCH_CHECK(who);
@@ -2333,6 +2467,16 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const floa
                                                      float *out_s, int64_t *out_i, int *redo, void *stream) {
     return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered", tw, qn, Q, bank16, dtype, xn, tail, rowp, N, P, D, k, combine, eps,
                                    idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// ... under top_t (0: the call above)
+extern "C" int skyemb_cosine_topk_tokens_prefiltered_top(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                         const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                                         int top_t, float eps, int64_t idx_offset, const float *thr0, void *ws,
+                                                         int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return topk_tokens_prefiltered(top_t ? "skyemb_cosine_topk_tokens_prefiltered_top" : "skyemb_cosine_topk_tokens_prefiltered", tw, qn, Q, bank16,
+                                   dtype, xn, tail, rowp, N, P, D, k, combine, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
+                                   nullptr, 0, 0, 0, nullptr, top_t);
 }
 
 // ---- the same search under a selection of the bank's images ---------------------------------------------------------------------------
@@ -2361,6 +2505,19 @@ extern "C" int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const 
     return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered_sel", tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, N, P, D, k,
                                    combine, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live,
                                    direct_end);
+}
+
+// ... under top_t (0: the call above)
+extern "C" int skyemb_cosine_topk_tokens_prefiltered_top_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                             const float *xn, const void *tail, const float *rowp_sel, const int *tiles,
+                                                             int n_live, int last_live, int direct_end, int64_t N, int P, int D, int k,
+                                                             int combine, int top_t, float eps, int64_t idx_offset, const float *thr0,
+                                                             void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
+                                                             void *stream) {
+    const char *who = top_t ? "skyemb_cosine_topk_tokens_prefiltered_top_sel" : "skyemb_cosine_topk_tokens_prefiltered_sel";
+    SKY_CHECK_ARG(tiles, "%s: null argument", who);
+    return topk_tokens_prefiltered(who, tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, N, P, D, k, combine, eps, idx_offset, thr0, ws, ws_bytes,
+                                   out_s, out_i, redo, stream, tiles, n_live, last_live, direct_end, nullptr, top_t);
 }
 
 // ---- combine 'mean': the same pipeline over the pooled image of skyemb_token_mean_pool --------------------------------------------------

@@ -645,6 +645,58 @@ def cosine_topk_tokens_prefiltered_sel(tw, qn, tokens, xn, tail, prepared, direc
     return ws
 
 
+def token_topt_prefilter_refusal(Q, N, P, D, k, combine, top_t):
+    """None when the two-stage token search takes the shape under ``top_t`` (``combine``: a COMBINE_CODES value), else the library's
+    own reason: the plain search's limits, 1 <= top_t <= min(P, 16), and no mean."""
+    L = lib()
+    return None if L.skyemb_token_topt_prefilter_applicable(Q, N, P, D, k, combine, top_t) else L.skyemb_last_error().decode()
+
+
+def token_topt_folds(P, combine, top_t):
+    """(stage 1 fold, stage 2 fold) the library runs for a two-stage token search under ``top_t`` -- host arithmetic, the rule of
+    include/skyemb.h restated: stage 1 'and' | 'or' | 'count', stage 2 'min' | 'max' | 'top'.  'max' and top_t in (0, P) map onto the
+    plain search; 'min' with top_t == 1 takes the OR fold and the top-t re-score."""
+    if combine == COMBINE_CODES['max']:
+        return 'or', 'max'
+    assert combine == COMBINE_CODES['min'] and 0 <= top_t <= min(P, 16)
+    if top_t in (0, P):
+        return 'and', 'min'
+    return ('or' if top_t == 1 else 'count'), 'top'
+
+
+def cosine_topk_tokens_prefiltered_top(tw, qn, tokens, xn, tail, rowp, k, combine, top_t, eps, idx_offset, out_s, out_i, redo, thr0=None,
+                                       ws=None):
+    """``cosine_topk_tokens_prefiltered`` under the top-t combine (``top_t`` 0: that call; include/skyemb.h): 'min' scores an image
+    by its top_t-th best token, 'max' is the plain max."""
+    Q, D = tw.shape
+    N, P = tokens.shape[:2]
+    code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered_top")
+    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_tokens_prefiltered_top(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp), N, P, D, k, combine,
+                                                          top_t, eps, idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i),
+                                                          _p(redo), _stream()), "skyemb_cosine_topk_tokens_prefiltered_top")
+    return ws
+
+
+def cosine_topk_tokens_prefiltered_top_sel(tw, qn, tokens, xn, tail, prepared, direct_end, k, combine, top_t, eps, idx_offset, out_s, out_i,
+                                           redo, thr0=None, ws=None):
+    """``cosine_topk_tokens_prefiltered_sel`` under the top-t combine (``top_t`` 0: that call; include/skyemb.h)."""
+    Q, D = tw.shape
+    N, P = tokens.shape[:2]
+    rowp_sel, tiles, n_live, last_live = prepared[:4]
+    code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered_top_sel")
+    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    check(lib().skyemb_cosine_topk_tokens_prefiltered_top_sel(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp_sel), _p(tiles),
+                                                              n_live, last_live, direct_end, N, P, D, k, combine, top_t, eps, idx_offset,
+                                                              _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
+          "skyemb_cosine_topk_tokens_prefiltered_top_sel")
+    return ws
+
+
 def prefilter_select_prepare(words, N, rowp):
     """What the two-stage search needs of a selection (packed ``words`` of ``pack_select``) over a bank of N rows with row constants
     ``rowp`` (``bank16_prepare`` / ``bank16_rowp_lp``): (rowp_sel, tiles, n_live, last_live) -- the masked copy of the constants (a

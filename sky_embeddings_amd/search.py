@@ -873,6 +873,13 @@ def _topk_tokens(rq: TokenRequest, sc, queries, prune, stats, process_group, wor
 
 TOKEN_PREFILTER_MIN_Q = 256    # fewest queries sent through the two-stage token route (measured: DESIGN.md section 6, item 17)
 TOKEN_MEAN_PREFILTER_MIN_Q = 256   # ... under combine 'mean': the smallest measured Q that beats the grouped route
+# ... under 'min' with 1 <= top_t < P: the smallest measured Q that beats the grouped route on every
+# leg, measured on banks of 3.07e9 elements (250 000 x 16 x 768 and 62 500 x 64 x 768).  About 4.3 ms of a two-stage call shrink
+# neither with Q nor with the bank while a grouped pass shrinks with the bank (at 0.77e9 elements the plain search lost at 64, item
+# 19), so a bank below the measured size waits for the Q from which the plain search was measured to win
+TOKEN_TOPT_PREFILTER_MIN_Q = 64
+TOKEN_TOPT_PREFILTER_MIN_ELEMENTS = 62500 * 64 * 768      # N P D of the smallest bank the constant above was measured on
+TOKEN_TOPT_PREFILTER_MIN_Q_SMALL = 256                     # smaller banks
 
 
 def _token_prefilter_refusal(rq: TokenRequest):
@@ -886,8 +893,8 @@ def _token_prefilter_refusal(rq: TokenRequest):
     if rq.metric is not None:
         return "a distance metric"
     mean = rq.combine == ops.COMBINE_CODES['mean']
-    if rq.top_t != 0:
-        return "top_t"
+    if rq.top_t != 0 and mean:
+        return "top_t under combine 'mean'"
     if mean and rq.select is not None:
         return "select under combine 'mean'"
     if rq.select is not None and not isinstance(rq.select, Selection):
@@ -902,7 +909,20 @@ def _token_prefilter_refusal(rq: TokenRequest):
         if rq.Q < TOKEN_MEAN_PREFILTER_MIN_Q:
             return f"Q = {rq.Q} < TOKEN_MEAN_PREFILTER_MIN_Q = {TOKEN_MEAN_PREFILTER_MIN_Q}"
         return ops.token_mean_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
-    if rq.Q < TOKEN_PREFILTER_MIN_Q:
+    if rq.top_t != 0:
+        why = ops.token_topt_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k, rq.combine, rq.top_t)
+        if why is not None:
+            return why
+    # 'max' under any top_t and 'min' under top_t == P ARE the plain search (ops.token_topt_folds): its threshold; the top-t folds
+    # have their own
+    if rq.top_t != 0 and ops.token_topt_folds(rq.P, rq.combine, rq.top_t)[1] == 'top':
+        if rq.N * rq.P * rq.D >= TOKEN_TOPT_PREFILTER_MIN_ELEMENTS:
+            if rq.Q < TOKEN_TOPT_PREFILTER_MIN_Q:
+                return f"Q = {rq.Q} < TOKEN_TOPT_PREFILTER_MIN_Q = {TOKEN_TOPT_PREFILTER_MIN_Q}"
+        elif rq.Q < TOKEN_TOPT_PREFILTER_MIN_Q_SMALL:
+            return (f"Q = {rq.Q} < TOKEN_TOPT_PREFILTER_MIN_Q_SMALL = {TOKEN_TOPT_PREFILTER_MIN_Q_SMALL} (a bank of fewer than "
+                    f"TOKEN_TOPT_PREFILTER_MIN_ELEMENTS = {TOKEN_TOPT_PREFILTER_MIN_ELEMENTS} elements)")
+    elif rq.Q < TOKEN_PREFILTER_MIN_Q:
         return f"Q = {rq.Q} < TOKEN_PREFILTER_MIN_Q = {TOKEN_PREFILTER_MIN_Q}"
     why = ops.token_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
     if why is None and rq.select is not None:
@@ -917,7 +937,9 @@ def _bootstrap_floor(rq: TokenRequest, tw, qn, eps):
     """[Q] the k-th best combined score of every query over a strided sample of min(N, max(16 k, 256)) whole images, scored by
     the grouped kernels, one ulp lower: the two-stage route's first threshold, a lower bound of the k-th best over the bank.  Under
     a selection the sample is min(count, max(16 k, 256)) SELECTED images (``Selection.sample``, kept there per bank and weights
-    version): a lower bound of the k-th best selected score."""
+    version): a lower bound of the k-th best selected score.  The sample is scored under the request's ``top_t``: d[top_t-1] of
+    a sample is a lower bound of the k-th best d[top_t-1] over the bank, and -- d[top_t-1] >= the plain min -- a higher floor than the
+    plain min's, which would be valid too but admit every image whose top_t-th token, not its worst, reaches the sample's k-th worst."""
     tb, k = rq.bank, rq.k
     if rq.select is not None:
         S = min(rq.select.count, max(16 * k, 256))
@@ -932,7 +954,7 @@ def _bootstrap_floor(rq: TokenRequest, tw, qn, eps):
     keys = torch.empty(16, S, device=tw.device)
     for lo in range(0, rq.Q, 16):
         g = min(16, rq.Q - lo)
-        ops.cosine_token_scores(tw[lo:lo + g], qn[lo:lo + g], st, sn, rq.combine, eps, keys[:g], 0, None)
+        ops.cosine_token_scores(tw[lo:lo + g], qn[lo:lo + g], st, sn, rq.combine, eps, keys[:g], rq.top_t, None)
         ops.kth_largest_floor(keys[:g], k, floor[lo:lo + g])
     return floor
 
@@ -952,6 +974,10 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
     if rq.combine == ops.COMBINE_CODES['mean']:            # stage 1 over the pooled image (never under a selection)
         pooled, tail, rowp = tb.stage1_mean()
         ops.cosine_topk_tokens_mean_prefiltered(tw, qn, tb.bank, tb.norms, pooled, tail, rowp, k, eps, rq.idx_offset, out_s, out_i, redo, thr0)
+    elif sel is None and rq.top_t != 0:
+        tail, rowp = tb.stage1()
+        ops.cosine_topk_tokens_prefiltered_top(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, rq.top_t, eps, rq.idx_offset, out_s, out_i,
+                                               redo, thr0)
     elif sel is None:
         tail, rowp = tb.stage1()
         ops.cosine_topk_tokens_prefiltered(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, eps, rq.idx_offset, out_s, out_i, redo, thr0)
@@ -960,17 +986,23 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
         prepared = sel.token_prefilter(tb)
         n_live, cum = prepared[2], prepared[4]
         direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)
-        ops.cosine_topk_tokens_prefiltered_sel(tw, qn, tb.bank, tb.norms, tail, prepared, direct_end, k, rq.combine, eps, rq.idx_offset,
-                                               out_s, out_i, redo, thr0)
+        if rq.top_t != 0:
+            ops.cosine_topk_tokens_prefiltered_top_sel(tw, qn, tb.bank, tb.norms, tail, prepared, direct_end, k, rq.combine, rq.top_t, eps,
+                                                       rq.idx_offset, out_s, out_i, redo, thr0)
+        else:
+            ops.cosine_topk_tokens_prefiltered_sel(tw, qn, tb.bank, tb.norms, tail, prepared, direct_end, k, rq.combine, eps, rq.idx_offset,
+                                                   out_s, out_i, redo, thr0)
     again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
     if again.numel():
-        rq2 = dataclasses.replace(rq, Q=int(again.numel()))
+        rq2 = dataclasses.replace(rq, Q=int(again.numel()))    # (every other field, top_t and select among them, is carried over)
         s2, i2 = _topk_tokens(rq2, _CosineScorer.of(rq2, eps), q.index_select(0, again), prune, None, None, 1)
         out_s.index_copy_(0, again, s2)
         out_i.index_copy_(0, again, i2)
     if stats is not None:
         stats.update(path="prefiltered", redone=int(again.numel()),
                      combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+        if rq.top_t != 0:
+            stats.update(top_t=rq.top_t)
         if sel is not None:
             stats.update(selected=sel.count, tiles=(n_live, (rq.N * rq.P + 255) // 256))
     if world_size > 1:
@@ -1029,7 +1061,7 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     (Q > 16 runs ceil(Q / 16) passes) -- the grouped route, ``stats['path'] == 'tokens'``.
 
     Two-stage route (``stats['path'] == 'prefiltered'``): a ``TokenBank.resident(bank)`` (fp16 / bf16) with ``combine`` 'min' or
-    'max', no ``top_t``, shared weights, P a divisor of 64, at least ``TOKEN_PREFILTER_MIN_Q`` queries, a shape the
+    'max', shared weights, P a divisor of 64, at least ``TOKEN_PREFILTER_MIN_Q`` queries, a shape the
     library takes (D % 32 == 0, 128 <= D <= 4096, 2048 <= N P < 2^31, k <= 256, k <= N) and SKYEMB_TOPK_PREFILTER not 0 is searched
     in ONE pass for all queries: the bank's rows are multiplied on the 16-bit matrix cores with a proven error bound, an image is
     a candidate when every ('min') / some ('max') token of it can still reach the query's threshold, and every candidate is
@@ -1046,8 +1078,15 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     candidate image's P tokens are re-scored exactly, folded in token order with the one division -- bit for bit the grouped
     route.  Its rule: no ``select``, no ``top_t``, shared weights, P a divisor of 64, at least ``TOKEN_MEAN_PREFILTER_MIN_Q``
     queries, D % 32 == 0, 128 <= D <= 4096, N >= 2048 images, N P < 2^31, k <= 256, k <= N.  Everything else is served by the grouped
-    route as ever, never refused.  Out of scope for the two-stage route: ``top_t``, per-query weights, the distance metrics, fp32
-    token banks, P not dividing 64, and ``select`` under 'mean'.
+    route as ever, never refused.  ``top_t`` under 'min' and 'max', alone and with ``select``, takes the route too: 'max' with any
+    ``top_t`` and 'min' with ``top_t == P`` are the plain search; 'min' with 1 <= top_t < P scores d[top_t-1], which reaches a
+    threshold only when at least top_t tokens do, so an image is a candidate when the COUNT of its rows that pass the row test is
+    >= top_t, and stage 2 sorts its exact token scores with the grouped kernels' own network -- bit for bit the grouped route; the
+    first threshold comes from a sample scored under the same ``top_t``, a re-run keeps it, ``stats`` gains ``top_t``, and the
+    smallest Q is ``TOKEN_TOPT_PREFILTER_MIN_Q`` (a bank of fewer than ``TOKEN_TOPT_PREFILTER_MIN_ELEMENTS`` elements:
+    ``TOKEN_TOPT_PREFILTER_MIN_Q_SMALL``).  Out of scope for the two-stage route: ``top_t`` under 'mean' (the mean of the
+    top_t best is not bounded by a count), per-query weights, the distance metrics, fp32 token banks, P not dividing 64, and
+    ``select`` under 'mean'.
 
     Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
