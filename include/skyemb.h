@@ -708,6 +708,60 @@ int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const float *qn,
                                                const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
                                                float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
                                                float *out_s, int64_t *out_i, int *redo, const void *pooled16, void *stream);
+/* Read-only query of the launch plan of every two-stage search above (csrc/prefilter_plan.h): what the entry point serving `req`
+ * decides on the host -- variant, slices, kernel instances, LDS bytes -- and then launches.  Host arithmetic only, touches no device.
+ * Returns 0 and fills *out, or 1 with the text (skyemb_last_error) and under the name of the entry point that would refuse the
+ * same request; pointer arguments (null, alignment, tail tile, workspace size) are the entry points' own business.
+ *   kind        SKYEMB_PF_ROWS: skyemb_cosine_topk_prefiltered (_lp, _resident, _sel); SKYEMB_PF_TOKENS: skyemb_cosine_topk_tokens_
+ *               prefiltered (_top, _sel); SKYEMB_PF_TOKENS_MEAN: skyemb_cosine_topk_tokens_mean_prefiltered
+ *   bank        SKYEMB_PF_BANK_F32 (rows only: an fp32 bank and its fp16 image), _F16, _BF16 (a resident 16-bit bank)
+ *   N           rows of the bank; images on the token routes.  P, combine, top_t: token routes (P = 1, top_t = 0 otherwise)
+ *   sel         the search runs under a selection: n_live, last_live (the prepare call's info), direct_sel (tokens: direct_end)
+ *   lo          0 / 1: SKYEMB_PREFILTER_LO=0 / =1; SKYEMB_PF_LO_UNSET; -1: what the process's environment says now
+ * The plan: slices in launch order; a slice is one stage-1 launch over positions [t0, t1) -- MODE mode of prefilter_kernel<mode,
+ * use_lo, sel, bf, tok, cnt> --, bucket_kernel when `bucket`, the tail tile's launch when `tail` (MODE 1 over position tail_pos, with
+ * the SEL instance when tail_sel) and select_kernel (rows) / the token re-score, told `final`. */
+#define SKYEMB_PF_ROWS 0
+#define SKYEMB_PF_TOKENS 1
+#define SKYEMB_PF_TOKENS_MEAN 2
+#define SKYEMB_PF_BANK_F32 0
+#define SKYEMB_PF_BANK_F16 1
+#define SKYEMB_PF_BANK_BF16 2
+#define SKYEMB_PF_LO_UNSET 2
+#define SKYEMB_PF_MAX_SLICES 6
+typedef struct {
+    int32_t kind, bank;
+    int32_t Q, P, D, k;
+    int64_t N;
+    int32_t combine, top_t;
+    int32_t has_thr0;
+    int32_t sel, n_live, last_live, direct_sel;
+    int32_t lo;
+    float eps;
+} skyemb_prefilter_request_t;
+typedef struct {
+    int32_t mode, t0, t1;            /* stage 1 */
+    int32_t bucket;
+    int32_t tail, tail_sel, tail_pos;
+    int32_t final;
+} skyemb_prefilter_slice_t;
+typedef struct {
+    int32_t use_lo, cap;
+    int32_t T, T_tail, has_tail;     /* positions the slices walk; the tile the tail stands for; a tail launch happens */
+    int32_t first, first_rows;       /* tiles / list slots of the take-all slice (0 on the token routes) */
+    int32_t direct_end, ends[SKYEMB_PF_MAX_SLICES];
+    int32_t sel, bf, tok, cnt;       /* the stage-1 instance family */
+    int32_t tok_word, lgp, fold, top_t;   /* prefilter_kernel's `tok`; log2 P; 0 min 1 max 2 mean; top_t normalised (max, top_t == P: 0) */
+    int32_t q_padded;
+    int32_t lds_stage1, lds_close, lds_rescore;          /* dynamic LDS bytes: stage 1; select_kernel / token re-score; final re-score */
+    int32_t lds_stage1_limit, lds_close_limit;           /* what the instances' dynamic-LDS limit is raised to */
+    float eps_a_f32, gfac;           /* the float handed to query16_kernel; mean: eps / eps_m raised (else -1) */
+    double eps_a;                    /* before the (1 + 1e-6) factor */
+    int64_t rows;                    /* rows stage 1 walks: N, N P on the min / max token route */
+    int32_t n_slices;
+    skyemb_prefilter_slice_t slice[SKYEMB_PF_MAX_SLICES];
+} skyemb_prefilter_plan_t;
+int skyemb_prefilter_plan(const skyemb_prefilter_request_t *req, skyemb_prefilter_plan_t *out);
 /* Attention pooling with one learned query (timm AttentionPoolLatent as built at utils/mim_vit.py:246-249 and applied at
  * :426-427; SimMIM models with attn_pool = True).  q [D] = Wq latent + bq is sample-independent (skyemb_attnpool_q);
  * kv [B, N, 2, H, hd] is the kv projection's output (compute dtype); fwd: out [B, D] (compute dtype) = softmax(scale q.k) v

@@ -27,6 +27,10 @@ METRIC_MSE, METRIC_MAE = 1, 2                          # SKYEMB_METRIC_*: the di
 # SKYEMB_MHA_*: kernel families of skyemb_mha_plan, and its switch bits
 MHA_LDS, MHA_STREAM, MHA_MFMA_PACKED, MHA_MFMA_SINGLE, MHA_MFMA_STRIP, MHA_MFMA_LONG = range(6)
 MHA_SW_NO_MFMA, MHA_SW_WPB1, MHA_SW_WPB4 = 1, 2, 4
+# SKYEMB_PF_*: skyemb_prefilter_plan's request kinds, bank kinds and the "SKYEMB_PREFILTER_LO is unset" value of its lo switch
+PF_ROWS, PF_TOKENS, PF_TOKENS_MEAN = range(3)
+PF_BANK_F32, PF_BANK_F16, PF_BANK_BF16 = range(3)
+PF_LO_UNSET, PF_MAX_SLICES = 2, 6
 PROBE_CHUNKS, PROBE_MAX_F, PROBE_MIN_K, PROBE_MAX_K = 32, 4096, 3, 16   # SKYEMB_PROBE_*: limits of the linear-probe fits
 
 
@@ -70,6 +74,28 @@ class MhaPlan(ctypes.Structure):
     """skyemb_mha_plan_t (include/skyemb.h): the launch skyemb_mha_fwd / skyemb_mha_bwd makes for a shape."""
     _fields_ = [("family", c_i32), ("hd", c_i32), ("waves", c_i32), ("per_wave_floats", c_i32), ("nheads", c_i32),
                 ("grid_x", c_i32), ("grid_y", c_i32), ("block", c_i32), ("lds_bytes", c_i64), ("lds_limit", c_i64)]
+
+
+class PrefilterRequest(ctypes.Structure):
+    """skyemb_prefilter_request_t (include/skyemb.h): one call of a two-stage search entry point, without its pointers."""
+    _fields_ = [("kind", c_i32), ("bank", c_i32), ("Q", c_i32), ("P", c_i32), ("D", c_i32), ("k", c_i32), ("N", c_i64), ("combine", c_i32),
+                ("top_t", c_i32), ("has_thr0", c_i32), ("sel", c_i32), ("n_live", c_i32), ("last_live", c_i32), ("direct_sel", c_i32),
+                ("lo", c_i32), ("eps", c_f32)]
+
+
+class PrefilterSlice(ctypes.Structure):
+    _fields_ = [("mode", c_i32), ("t0", c_i32), ("t1", c_i32), ("bucket", c_i32), ("tail", c_i32), ("tail_sel", c_i32), ("tail_pos", c_i32),
+                ("final", c_i32)]
+
+
+class PrefilterPlan(ctypes.Structure):
+    """skyemb_prefilter_plan_t (include/skyemb.h): what the entry point serving a request decides and launches."""
+    _fields_ = [("use_lo", c_i32), ("cap", c_i32), ("T", c_i32), ("T_tail", c_i32), ("has_tail", c_i32), ("first", c_i32),
+                ("first_rows", c_i32), ("direct_end", c_i32), ("ends", c_i32 * 6), ("sel", c_i32), ("bf", c_i32), ("tok", c_i32),
+                ("cnt", c_i32), ("tok_word", c_i32), ("lgp", c_i32), ("fold", c_i32), ("top_t", c_i32), ("q_padded", c_i32),
+                ("lds_stage1", c_i32), ("lds_close", c_i32), ("lds_rescore", c_i32), ("lds_stage1_limit", c_i32),
+                ("lds_close_limit", c_i32), ("eps_a_f32", c_f32), ("gfac", c_f32), ("eps_a", c_f64), ("rows", c_i64), ("n_slices", c_i32),
+                ("slice", PrefilterSlice * 6)]
 
 
 class GemmGroupInfo(ctypes.Structure):
@@ -194,6 +220,8 @@ PROTOTYPES = {
                                                               c_vp, c_vp, c_vp, c_vp]),
     # ... and with combine mean, over the pooled image of the bank: additive again
     "skyemb_token_mean_pool": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    # read-only query of the two-stage searches' launch plan: additive to ABI version 111
+    "skyemb_prefilter_plan": (c_i32, [ctypes.POINTER(PrefilterRequest), ctypes.POINTER(PrefilterPlan)]),
     "skyemb_token_mean_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),
     "skyemb_token_mean_prefilter_ws_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "skyemb_token_mean_prefilter_eps_m": (c_f64, [c_i32, c_i32, c_i32]),

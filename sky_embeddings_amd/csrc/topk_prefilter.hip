@@ -81,9 +81,12 @@
 // |tw_d| >= 2^79), is flagged by init_state_kernel and re-run by the caller; its dot^ are never trusted.  Nothing else changes:
 // same bytes, same tiles, ring, swizzle, candidate test, lists, phases, selection handling, tail tile; stage 2 widens bf16 rows.
 #include "common.h"
+#include "prefilter_plan.h"
 #include "token_combine.h"
+#include <array>
 #include <math.h>
 #include <stdlib.h>
+#include <utility>
 
 namespace {
 
@@ -115,6 +118,7 @@ __device__ __forceinline__ void glds16(const void *src, char *lds_wave_base) {
 // lo: the query enters as hi + lo (see the header); without lo its own fp16 rounding (2^-11 relative, + the cross term) joins
 // the row's
 // resident: the rows are a resident fp16 bank, exact in stage 1 (file header): their 2^-11 and their half of the subnormal term go
+// (prefilter_plan.h's eps_of restates this, eps_a_bf16_of and eps_m_of for the searches: they MOVE TOGETHER; test_prefilter_plan_cpu.py compares)
 __host__ __device__ inline double eps_a_of(int D, bool lo, bool resident = false) {
     if (resident) return (lo ? 0x1p-21 : 0x1p-11 + 0x1p-21) + 6.06 * D * 0x1p-24 + sqrt((double)D) * 0x1p-27;
     return (lo ? 0x1p-11 + 0x1p-21 : 0x1p-10 + 0x1p-21) + 6.06 * D * 0x1p-24 + 2.0 * sqrt((double)D) * 0x1p-27;
@@ -1387,11 +1391,7 @@ int64_t carve(char *base, int Q, int D, int cap, Workspace *w) {
 
 }  // namespace
 
-extern "C" int skyemb_topk_prefilter_applicable(int Q, int64_t N, int D, int k) {
-    // the fp16 pass pays from a few query tiles on; the re-score list must leave room above k
-    return Q >= 17 && D % BK == 0 && D >= 4 * BK && D <= 4096 && k >= 1 && k <= RESCORE_MAX - 64 && N >= 8 * BT && N < (1ll << 31);
-}
-static int skyemb_topk_prefilter_cap(int k) { return k <= 128 ? 4096 : 8192; }
+extern "C" int skyemb_topk_prefilter_applicable(int Q, int64_t N, int D, int k) { return pfplan::rows_shape_ok(Q, N, D, k); }
 
 extern "C" int64_t skyemb_bank16_bytes(int64_t N, int D) { return ceil_div64(N, BT) * BT * D * 2; }   // whole tiles of BT rows
 
@@ -1413,35 +1413,33 @@ extern "C" double skyemb_topk_prefilter_eps_a_resident(int D, int lo, int dtype)
     return dtype == SKYEMB_BF16 ? eps_a_bf16_of(D, lo != 0) : eps_a_of(D, lo != 0, true);
 }
 
-extern "C" int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
-    SKY_CHECK_ARG(bank16 && xn && rowp && N > 0 && D > 0 && D % BK == 0, "skyemb_bank16_rowp_lp: bad arguments");
-    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_bank16_rowp_lp: N = %lld is no whole number of %d-row tiles: a tail tile [%d, D] is needed",
-                  (long long)N, BT, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_bank16_rowp_lp: the bank and the tail tile must be 16-byte aligned");
+static int resident_rowp(const char *who, bool bf, const void *bank16, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
+    SKY_CHECK_ARG(bank16 && xn && rowp && N > 0 && D > 0 && D % BK == 0, "%s: bad arguments", who);
+    SKY_CHECK_ARG(N % BT == 0 || tail, "%s: N = %lld is no whole number of %d-row tiles: a tail tile [%d, D] is needed", who, (long long)N, BT, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "%s: the bank and the tail tile must be 16-byte aligned", who);
     const int64_t padded = skyemb_bank16_rowp_rows(N);
-    // one set of row constants serves both variants: the smaller eps_a (hi + lo) gives the larger, always valid, term
+    const dim3 grid((unsigned)ceil_div64(padded, 4));
+    // fp16: one set of row constants serves both variants: the smaller eps_a (hi + lo) gives the larger, always valid, term
     const float sub_scale = (float)(0x1p-14 / eps_a_of(D, true, true) * (1.0 + 1e-6));
-    hipLaunchKernelGGL(bank16_rowp_lp_kernel, dim3((unsigned)ceil_div64(padded, 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const half_t *)bank16, xn, N, D, (float4 *)rowp, padded, N % BT ? (half_t *)tail : nullptr, N / BT * BT, sub_scale);
-    SKY_LAUNCH_CHECK("skyemb_bank16_rowp_lp");
+    if (bf) hipLaunchKernelGGL(bankbf16_rowp_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short *)bank16, xn, N, D,
+                               (float4 *)rowp, padded, N % BT ? (unsigned short *)tail : nullptr, N / BT * BT);
+    else hipLaunchKernelGGL(bank16_rowp_lp_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const half_t *)bank16, xn, N, D, (float4 *)rowp,
+                            padded, N % BT ? (half_t *)tail : nullptr, N / BT * BT, sub_scale);
+    SKY_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int skyemb_bank16_rowp_lp(const void *bank16, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
+    return resident_rowp("skyemb_bank16_rowp_lp", false, bank16, xn, N, D, rowp, tail, stream);
 }
 
 extern "C" int skyemb_resident_rowp(const void *bank16, int dtype, const float *xn, int64_t N, int D, float *rowp, void *tail, void *stream) {
     SKY_CHECK_ARG(sky_is_lp(dtype), "skyemb_resident_rowp: dtype " RESIDENT_DTYPE_MSG, dtype);
-    if (dtype == SKYEMB_F16) return skyemb_bank16_rowp_lp(bank16, xn, N, D, rowp, tail, stream);
-    SKY_CHECK_ARG(bank16 && xn && rowp && N > 0 && D > 0 && D % BK == 0, "skyemb_resident_rowp: bad arguments");
-    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_resident_rowp: N = %lld is no whole number of %d-row tiles: a tail tile [%d, D] is needed",
-                  (long long)N, BT, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_resident_rowp: the bank and the tail tile must be 16-byte aligned");
-    const int64_t padded = skyemb_bank16_rowp_rows(N);
-    hipLaunchKernelGGL(bankbf16_rowp_kernel, dim3((unsigned)ceil_div64(padded, 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned short *)bank16, xn, N, D, (float4 *)rowp, padded, N % BT ? (unsigned short *)tail : nullptr, N / BT * BT);
-    SKY_LAUNCH_CHECK("skyemb_resident_rowp");
-    return 0;
+    return resident_rowp(dtype == SKYEMB_F16 ? "skyemb_bank16_rowp_lp" : "skyemb_resident_rowp", dtype == SKYEMB_BF16, bank16, xn, N, D, rowp, tail,
+                         stream);
 }
 
-extern "C" int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k) { return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr); }
+extern "C" int64_t skyemb_topk_prefilter_ws_bytes(int Q, int D, int k) { return carve(nullptr, Q, D, pfplan::cap_of(k), nullptr); }
 
 // Test and diagnostic hook (host arithmetic only, nothing is launched): where carve puts each array of the workspace.  carve
 // itself is run over a base that is only ever subtracted again -- never read or written -- so the two cannot drift.
@@ -1452,7 +1450,7 @@ extern "C" int skyemb_topk_prefilter_ws_layout(int Q, int D, int k, int64_t *out
     SKY_CHECK_ARG(out && n == FIELDS + 2, "skyemb_topk_prefilter_ws_layout: out must hold %d values (14 offsets, cap, capw), got n = %d",
                   FIELDS + 2, n);
     SKY_CHECK_ARG(Q >= 1 && D >= 1 && k >= 1, "skyemb_topk_prefilter_ws_layout: bad shape (Q=%d D=%d k=%d)", Q, D, k);
-    const int cap = skyemb_topk_prefilter_cap(k);
+    const int cap = pfplan::cap_of(k);
     alignas(256) static char anchor[256];                      // an address to count from: carve adds offsets to it, nothing more
     Workspace w;
     carve(anchor, Q, D, cap, &w);
@@ -1463,212 +1461,6 @@ extern "C" int skyemb_topk_prefilter_ws_layout(int Q, int D, int k, int64_t *out
     out[FIELDS] = cap;
     out[FIELDS + 1] = w.capw;
     return 0;
-}
-
-// which of its two variants a bf16 search runs when SKYEMB_PREFILTER_LO is unset: the one measured faster
-constexpr bool BF16_DEFAULT_LO = false;
-
-// The pipeline of all entry points.  bank: the fp32 rows stage 2 re-scores, bank16 their fp16 image (skyemb_bank16_prepare) --
-// or bank NULL: bank16 is a resident fp16 bank that both stages read, its last N % BT rows through `tail` (skyemb_bank16_rowp_lp).
-// tiles (NULL: no selection): the search runs under a selection prepared by skyemb_prefilter_select_prepare -- rowp is then the
-// masked copy, tiles the n_live live tiles of all ceil(N / BT), last_live says whether the last of those is one of them.  The phase
-// schedule runs over the live tiles; a resident bank's tail tile is launched only when it is live.
-// bf (bank NULL only): the resident bank is bf16 -- bf16 query images, the BF instances of stage 1, the bf16 re-score.
-static int topk_prefiltered(const char *who, const float *tw, const float *qn, int Q, const float *bank, const float *xn,
-                            const void *bank16, const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
-                            int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
-                            int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0, bool bf = false) {
-    const bool resident = bank == nullptr;
-    const bool sel = tiles != nullptr;
-    SKY_CHECK_ARG(skyemb_topk_prefilter_applicable(Q, N, D, k), "%s: outside the prefiltered subset "
-                  "(Q >= 17, D %% 32 == 0, k <= %d, N >= %d)", who, RESCORE_MAX - 64, 8 * BT);
-    // one fp16 pass (hi only) by default: half the matrix work, 3/4 of the LDS-DMA bytes, intervals ~1.6x wider -- on
-    // embedding-like data a few dozen more candidates per query.  SKYEMB_PREFILTER_LO=1 keeps the hi + lo passes.
-    // (read per call on purpose: a getenv is a sub-microsecond scan next to a multi-millisecond search, and the tests switch it)
-    const char *lo_env = getenv("SKYEMB_PREFILTER_LO");
-    // a bf16 bank: SKYEMB_PREFILTER_LO=0 forces hi only as well; unset, the variant measured faster
-    const bool use_lo = bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
-    // stage 1 counts an XCD's work items (its bank tiles x the query tiles) and a workgroup's k-steps in 32-bit integers
-    SKY_CHECK_ARG(ceil_div64(ceil_div64(N, BT), 8) * ceil_div64(Q, qtile(use_lo)) * (D / BK) < (1ll << 31),
-                  "%s: Q x N too large: ceil(N / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31, the range of stage 1's work-item "
-                  "and k-step counters (Q=%d N=%lld D=%d); search the queries in batches", who, qtile(use_lo), Q, (long long)N, D);
-    const int cap = skyemb_topk_prefilter_cap(k);
-    SKY_CHECK_ARG(ws_bytes >= skyemb_topk_prefilter_ws_bytes(Q, D, k), "%s: workspace too small", who);
-    hipStream_t st = (hipStream_t)stream;
-    Workspace w;
-    carve((char *)ws, Q, D, cap, &w);
-    const float eps_a = (float)((bf ? eps_a_bf16_of(D, use_lo) : eps_a_of(D, use_lo, resident)) * (1.0 + 1e-6));
-    const dim3 qgrid((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4));
-    if (bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
-    else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
-    // tiles the phases below walk: all of them -- of a resident bank the whole ones, the last N % BT rows follow from `tail`
-    const int T_tail = (int)(N / BT);                          // the tile a resident bank's tail stands for
-    const bool has_tail = resident && N % BT != 0 && (!sel || last_live);
-    const int T = sel ? n_live - (resident && N % BT != 0 && last_live ? 1 : 0) : resident ? T_tail : (int)ceil_div64(N, BT);
-    if (sel) {
-        SKY_CHECK_ARG(n_live >= 1 && n_live <= ceil_div64(N, BT) && (last_live == 0 || last_live == 1),
-                      "%s: n_live = %d, last_live = %d: expected 1 .. %lld live tiles and a flag (skyemb_prefilter_select_prepare's info)",
-                      who, n_live, last_live, (long long)ceil_div64(N, BT));
-        SKY_CHECK_ARG(T >= 1, "%s: the selection's only live tile is the resident bank's tail tile; the phases need a whole live tile", who);
-    }
-    bool tail_done = false;
-    // phases: [0, first) is taken whole unless a floor came in; then slices ending at 1/128, 1/32, 1/8, 1/2 and all of the tiles
-    int first = (int)(cap / 2 / BT);                           // rows of the take-everything slice <= cap / 2
-    if (first < 1) first = 1;
-    if (first > T) first = T;
-    // (under a selection the slots are positions in the live list x BT: all of them are written, see prefilter_kernel)
-    const int64_t first_rows = sel || (int64_t)first * BT < N ? (int64_t)first * BT : N;
-    const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
-    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
-                       w.qpar, w.tau, w.cnt, w.overflow, (int)first_rows, bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
-                       bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
-    const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
-    constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
-    int rc = 0;
-#define PF_ATTR(M, L)                                                                                             \
-    if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false>, smem_max, who);       \
-    if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true>, smem_max, who); \
-    if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true>, smem_max, who);  \
-    if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true>, smem_max, who)
-    PF_ATTR(0, false); PF_ATTR(1, false); PF_ATTR(2, false); PF_ATTR(0, true); PF_ATTR(1, true); PF_ATTR(2, true);
-#undef PF_ATTR
-    if (rc == 0) rc = sky_set_lds_limit((const void *)select_kernel<false>, 2 * 8192 * 4 + 272 * 4, who);
-    if (rc == 0 && sel) rc = sky_set_lds_limit((const void *)select_kernel<true>, 2 * 8192 * 4 + 272 * 4, who);
-    if (rc != 0) return rc;
-    // (the slice right after the first one meets a threshold that still passes ~5 % of the pairs -- k of the ~2000 rows seen --
-    // so it is kept short, to ~96 k rows or 1/128 of the tiles, and appends directly; from then on the threshold passes ~1 %
-    // or less and a workgroup's candidates fit its staging list and region)
-    int direct_end = (int)ceil_div64((int64_t)96 * k, BT);
-    if (direct_end < T / 128) direct_end = T / 128;
-    if (direct_end < first + 1) direct_end = first + 1;
-    int ends[6] = {first, direct_end, T / 32, T / 8, T / 2, T};
-    int t0 = 0;
-    bool thresholded_once = thr0 != nullptr;                   // a caller's floor comes from 256 k sampled rows: tight enough
-    const size_t smem_sel = (size_t)2 * cap * 4 + 272 * 4;
-    for (int p = 0; p < 6; ++p) {
-        int t1 = ends[p];
-        if (p == 0 && thr0) continue;                          // a valid floor is as good as the first slice
-        if (t1 <= t0) continue;
-        if (t1 > T) t1 = T;
-#if defined(PF_STAMP) || defined(PF_CLOCK)
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) { hipMalloc(&dbg, 32 * 8); }
-        hipMemsetAsync(dbg, 0, 32 * 8, st);
-#define PF_DBG , dbg
-#else
-#define PF_DBG
-#endif
-#define PF_ARGS(B, T0, T1, TL) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, TL, w.qpar, Q, N, D, T0, T1, cap, w.cnt, w.cand_i, \
-                               w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, 0 PF_DBG
-#define PF_LAUNCH_AS(M, L, S, B, T0, T1, TL)                                                                                   \
-    do {                                                                                                                       \
-        if (bf) hipLaunchKernelGGL((prefilter_kernel<M, L, S, true>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL)); \
-        else hipLaunchKernelGGL((prefilter_kernel<M, L, S>), dim3(PF_GRID), dim3(NT), smem1, st, PF_ARGS(B, T0, T1, TL));      \
-    } while (0)
-// TL: the live-tile list the positions [T0, T1) index, or NULL: they are the bank tiles themselves
-#define PF_LAUNCH(M, B, T0, T1, TL)                                                              \
-    do {                                                                                         \
-        const int *tl_ = (TL);                                                                   \
-        if (tl_ && use_lo) PF_LAUNCH_AS(M, true, true, B, T0, T1, tl_);                          \
-        else if (tl_) PF_LAUNCH_AS(M, false, true, B, T0, T1, tl_);                              \
-        else if (use_lo) PF_LAUNCH_AS(M, true, false, B, T0, T1, (const int *)nullptr);          \
-        else PF_LAUNCH_AS(M, false, false, B, T0, T1, (const int *)nullptr);                     \
-    } while (0)
-        if (p == 0) {
-            PF_LAUNCH(0, bank16, t0, t1, tiles);
-        } else if (!thresholded_once) {
-            PF_LAUNCH(1, bank16, t0, t1, tiles);
-            thresholded_once = true;
-        } else {
-            PF_LAUNCH(2, bank16, t0, t1, tiles);
-            hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count,
-                               w.capw, cap, w.cnt, w.cand_i, w.cand_d);
-        }
-        if (has_tail && t1 == T && !tail_done) {
-            tail_done = true;                                  // (a later, empty phase may end at T once more)
-            // The last N % BT rows of a resident bank, before the final selection: tile T, read from the padded copy.  The kernel
-            // addresses tile t at base + t * BT rows, so the base handed over is the one that puts tile T on `tail` (an address
-            // only: tile T is the single tile of this launch).  Direct appends under the last phase's threshold -- at most BT
-            // candidates per query behind whatever the lists hold (after a take-all phase: behind its first_rows slots).
-            // (under a selection too the tail is bank tile N / BT itself, no list: its masked constants are all it needs)
-            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T_tail * BT * D * sizeof(half_t));
-            PF_LAUNCH(1, tail_base, T_tail, T_tail + 1, (const int *)nullptr);
-        }
-#undef PF_LAUNCH
-#undef PF_LAUNCH_AS
-#undef PF_ARGS
-#ifdef PF_CLOCK
-        {
-            unsigned long long h[32];
-            hipStreamSynchronize(st);
-            hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-            if (h[23])
-                fprintf(stderr, "[clock] phase %d (%s): in-kernel clock %.3f GHz over %.2f ms, %.0f shader cycles per k-step (256 MFMAs = 64 per SIMD x 16 cycles = 1024 at the "
-                                "matrix pipe's rate), steps/wg %.0f\n",
-                        p, p == 0 ? "take-all" : p == 1 ? "direct append" : "staged", (double)h[20] / (double)h[21] * 0.1, (double)h[21] / h[23] * 1e-5,
-                        (double)h[20] / (double)h[22], (double)h[22] / h[23]);
-        }
-#endif
-#ifdef PF_STAMP
-        {
-            unsigned long long h[32];
-            hipStreamSynchronize(st);
-            hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-            const double n = (double)h[16] * 4.0;     // steps summed over workgroups x 4 waves per group
-            if (p >= 2) {
-                int hc[PF_GRID];
-                hipMemcpy(hc, w.wg_count, sizeof(hc), hipMemcpyDeviceToHost);
-                long tot = 0; int mx = 0;
-                for (int i = 0; i < PF_GRID; ++i) { tot += hc[i]; if (hc[i] > mx) mx = hc[i]; }
-                fprintf(stderr, "[stamp] phase %d staged candidates: total %ld (%.1f per query), max per workgroup %d of %d\n", p, tot, (double)tot / Q, mx, w.capw);
-            }
-            fprintf(stderr, "[stamp] phase %d steps/wg %.0f | early: wait %.0f P0 %.0f read+issue %.0f P1 %.0f mult %.0f | late: wait %.0f P0 %.0f read+issue %.0f P1 %.0f mult %.0f (cycles of s_memtime per k-step)\n",
-                    p, (double)h[16] / 256.0, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[12] / n);
-            const double ni = (double)h[17] * 4.0;    // items summed over workgroups x 4 waves per group
-            fprintf(stderr, "[stamp] phase %d items/wg %.0f | item epilogue, cycles per item: early tests %.0f appends %.0f zero %.0f | late tests %.0f appends %.0f zero %.0f\n",
-                    p, (double)h[17] / 256.0, h[5] / ni, h[6] / ni, h[7] / ni, h[13] / ni, h[14] / ni, h[15] / ni);
-        }
-#endif
-        const int final = t1 == T;
-#define SELECT_ARGS Q, k, cap, eps, w.qbase, (const float4 *)rowp, xn, w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, final, w.sel_i, \
-                    w.nsel, w.bound
-        if (sel) hipLaunchKernelGGL(select_kernel<true>, dim3((unsigned)Q), dim3(256), smem_sel, st, SELECT_ARGS);
-        else hipLaunchKernelGGL(select_kernel<false>, dim3((unsigned)Q), dim3(256), smem_sel, st, SELECT_ARGS);
-#undef SELECT_ARGS
-        t0 = t1;
-    }
-    const size_t smem_re = (size_t)D * 4 + RESCORE_MAX * 8;
-#define RESCORE_ARGS(B) tw, qn, B, xn, Q, D, k, eps, idx_offset, w.sel_i, w.nsel, w.bound, w.overflow, out_s, out_i, redo
-    if (bf && sel) hipLaunchKernelGGL(rescore_bf_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const bf16_t *)bank16));
-    else if (bf) hipLaunchKernelGGL(rescore_bf_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const bf16_t *)bank16));
-    else if (resident && sel) hipLaunchKernelGGL(rescore_lp_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
-    else if (resident) hipLaunchKernelGGL(rescore_lp_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS((const half_t *)bank16));
-    else if (sel) hipLaunchKernelGGL(rescore_kernel<true>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS(bank));
-    else hipLaunchKernelGGL(rescore_kernel<false>, dim3((unsigned)Q), dim3(256), smem_re, st, RESCORE_ARGS(bank));
-#undef RESCORE_ARGS
-    SKY_LAUNCH_CHECK(who);
-    return 0;
-}
-
-extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, int Q, const float *bank, const float *xn,
-                                              const void *bank16, const float *rowp, int64_t N, int D, int k, float eps,
-                                              int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
-                                              int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && bank16 && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered: null argument");
-    return topk_prefiltered("skyemb_cosine_topk_prefiltered", tw, qn, Q, bank, xn, bank16, nullptr, rowp, N, D, k, eps, idx_offset, thr0, ws,
-                            ws_bytes, out_s, out_i, redo, stream);
-}
-
-extern "C" int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *qn, int Q, const void *bank16, const float *xn,
-                                                 const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
-                                                 int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
-                                                 int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered_lp: null argument");
-    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_lp: N = %lld is no whole number of %d-row tiles: the tail tile of "
-                  "skyemb_bank16_rowp_lp is needed", (long long)N, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_lp: the bank and the tail tile must be 16-byte aligned");
-    return topk_prefiltered("skyemb_cosine_topk_prefiltered_lp", tw, qn, Q, nullptr, xn, bank16, tail, rowp, N, D, k, eps, idx_offset, thr0,
-                            ws, ws_bytes, out_s, out_i, redo, stream);
 }
 
 // ---- the same searches under a selection of the bank's rows ---------------------------------------------------------------------
@@ -1683,65 +1475,6 @@ extern "C" int skyemb_prefilter_select_prepare(const uint32_t *words, int64_t N,
                        info);
     SKY_LAUNCH_CHECK("skyemb_prefilter_select_prepare");
     return 0;
-}
-
-extern "C" int skyemb_cosine_topk_prefiltered_sel(const float *tw, const float *qn, int Q, const float *bank, const float *xn,
-                                                  const void *bank16, const float *rowp_sel, const int *tiles, int n_live, int last_live,
-                                                  int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
-                                                  float *out_s, int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank && xn && bank16 && rowp_sel && tiles && ws && out_s && out_i && redo,
-                  "skyemb_cosine_topk_prefiltered_sel: null argument");
-    return topk_prefiltered("skyemb_cosine_topk_prefiltered_sel", tw, qn, Q, bank, xn, bank16, nullptr, rowp_sel, N, D, k, eps, idx_offset,
-                            nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live);
-}
-
-extern "C" int skyemb_cosine_topk_prefiltered_lp_sel(const float *tw, const float *qn, int Q, const void *bank16, const float *xn,
-                                                     const void *tail, const float *rowp_sel, const int *tiles, int n_live,
-                                                     int last_live, int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws,
-                                                     int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp_sel && tiles && ws && out_s && out_i && redo,
-                  "skyemb_cosine_topk_prefiltered_lp_sel: null argument");
-    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_lp_sel: N = %lld is no whole number of %d-row tiles: the tail tile "
-                  "of skyemb_bank16_rowp_lp is needed", (long long)N, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_lp_sel: the bank and the tail tile must be 16-byte aligned");
-    return topk_prefiltered("skyemb_cosine_topk_prefiltered_lp_sel", tw, qn, Q, nullptr, xn, bank16, tail, rowp_sel, N, D, k, eps, idx_offset,
-                            nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live);
-}
-
-// ---- a resident 16-bit bank of either format: dtype SKYEMB_F16 is the _lp entry point itself, SKYEMB_BF16 the bf16 search ------------
-extern "C" int skyemb_cosine_topk_prefiltered_resident(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
-                                                       const float *xn, const void *tail, const float *rowp, int64_t N, int D, int k,
-                                                       float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
-                                                       float *out_s, int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(sky_is_lp(dtype), "skyemb_cosine_topk_prefiltered_resident: dtype " RESIDENT_DTYPE_MSG, dtype);
-    if (dtype == SKYEMB_F16)
-        return skyemb_cosine_topk_prefiltered_lp(tw, qn, Q, bank16, xn, tail, rowp, N, D, k, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i,
-                                                 redo, stream);
-    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "skyemb_cosine_topk_prefiltered_resident: null argument");
-    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_resident: N = %lld is no whole number of %d-row tiles: the tail tile "
-                  "of skyemb_resident_rowp is needed", (long long)N, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail), "skyemb_cosine_topk_prefiltered_resident: the bank and the tail tile must be 16-byte aligned");
-    return topk_prefiltered("skyemb_cosine_topk_prefiltered_resident", tw, qn, Q, nullptr, xn, bank16, tail, rowp, N, D, k, eps, idx_offset,
-                            thr0, ws, ws_bytes, out_s, out_i, redo, stream, nullptr, 0, 0, true);
-}
-
-extern "C" int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
-                                                           const float *xn, const void *tail, const float *rowp_sel, const int *tiles,
-                                                           int n_live, int last_live, int64_t N, int D, int k, float eps,
-                                                           int64_t idx_offset, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
-                                                           int *redo, void *stream) {
-    SKY_CHECK_ARG(sky_is_lp(dtype), "skyemb_cosine_topk_prefiltered_resident_sel: dtype " RESIDENT_DTYPE_MSG, dtype);
-    if (dtype == SKYEMB_F16)
-        return skyemb_cosine_topk_prefiltered_lp_sel(tw, qn, Q, bank16, xn, tail, rowp_sel, tiles, n_live, last_live, N, D, k, eps, idx_offset,
-                                                     ws, ws_bytes, out_s, out_i, redo, stream);
-    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp_sel && tiles && ws && out_s && out_i && redo,
-                  "skyemb_cosine_topk_prefiltered_resident_sel: null argument");
-    SKY_CHECK_ARG(N % BT == 0 || tail, "skyemb_cosine_topk_prefiltered_resident_sel: N = %lld is no whole number of %d-row tiles: the tail "
-                  "tile of skyemb_resident_rowp is needed", (long long)N, BT);
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail),
-                  "skyemb_cosine_topk_prefiltered_resident_sel: the bank and the tail tile must be 16-byte aligned");
-    return topk_prefiltered("skyemb_cosine_topk_prefiltered_resident_sel", tw, qn, Q, nullptr, xn, bank16, tail, rowp_sel, N, D, k, eps,
-                            idx_offset, nullptr, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live, true);
 }
 
 // ---- Patch-token banks: the same two stages over a resident 16-bit token bank [N, P, D], per-image combine min | max -------------------
@@ -2194,8 +1927,7 @@ inline int log2_of(int P) {
 #define TOKEN_PREFILTER_MSG "many-query patch-token search: needs P a divisor of 64, D %% 32 == 0, 128 <= D <= 4096, 1 <= k <= %d, " \
                             "k <= N, 2048 <= N * P < 2^31 rows and Q >= 1 (Q=%d N=%lld P=%d D=%d k=%d)"
 extern "C" int skyemb_token_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
-    const bool ok = Q >= 1 && N >= 1 && P >= 1 && P <= 64 && 64 % P == 0 && D % BK == 0 && D >= 4 * BK && D <= 4096 && k >= 1 &&
-                    k <= TOK_KMAX && k <= N && N * P >= 8 * BT && N * P < (1ll << 31);
+    const bool ok = pfplan::tokens_shape_ok(Q, N, P, D, k);
     if (!ok) skyemb_set_error(TOKEN_PREFILTER_MSG, TOK_KMAX, Q, (long long)N, P, D, k);
     return ok ? 1 : 0;
 }
@@ -2220,15 +1952,14 @@ extern "C" int skyemb_token_topt_prefilter_applicable(int Q, int64_t N, int P, i
 }
 
 extern "C" int64_t skyemb_token_prefilter_ws_bytes(int Q, int D, int k) {
-    return carve(nullptr, Q, D, skyemb_topk_prefilter_cap(k), nullptr) + align256((int64_t)Q * TOK_KMAX * 8);
+    return carve(nullptr, Q, D, pfplan::cap_of(k), nullptr) + align256((int64_t)Q * TOK_KMAX * 8);
 }
 
 // ---- combine 'mean': the limits of the token route with rows = images (stage 1 walks the pooled image's N rows)
 #define TOKEN_MEAN_PREFILTER_MSG "many-query patch-token search, combine mean: needs P a divisor of 64, D %% 32 == 0, 128 <= D <= 4096, " \
                                  "1 <= k <= %d, k <= N, N >= 2048 images, N * P < 2^31 rows and Q >= 1 (Q=%d N=%lld P=%d D=%d k=%d)"
 extern "C" int skyemb_token_mean_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
-    const bool ok = Q >= 1 && P >= 1 && P <= 64 && 64 % P == 0 && D % BK == 0 && D >= 4 * BK && D <= 4096 && k >= 1 && k <= TOK_KMAX &&
-                    k <= N && N >= 8 * BT && N * P < (1ll << 31);
+    const bool ok = pfplan::mean_shape_ok(Q, N, P, D, k);
     if (!ok) skyemb_set_error(TOKEN_MEAN_PREFILTER_MSG, TOK_KMAX, Q, (long long)N, P, D, k);
     return ok ? 1 : 0;
 }
@@ -2262,223 +1993,6 @@ extern "C" int skyemb_token_mean_pool(const void *bank16, int dtype, const float
     return 0;
 }
 
-// The pipeline of both entry points.  tiles (NULL: no selection): the search runs under a selection of images prepared by
-// skyemb_token_prefilter_select_prepare -- rowp is then the masked copy, [0, n_live) the positions of the live-tile list the slices
-// walk (the SEL instances of stage 1), last_live says whether the bank's last tile is one of them, and the first (direct-append)
-// slice ends at position direct_sel, which the caller takes from the cumulative counts of selected images.
-// mo (NULL: min / max): combine 'mean' -- stage 1 runs as the ROW search over the pooled image of skyemb_token_mean_pool (a row is an
-// image: no TOK fold), under the mean bound's constants; stage 2 re-scores the candidate images' tokens from the bank as ever.
-// top_t (0: all tokens, the search as ever; the `_top` entries): only the top_t best token scores of an image count.  'max' is d[0]
-// whatever top_t is and 'min' with top_t == P is the plain min: both ARE the plain search, same kernels.  'min' with 1 <= top_t < P:
-// an image is a candidate iff at least top_t of its rows pass the row test -- top_t == 1 is the OR fold of 'max', else the CNT
-// instances of stage 1 count -- and stage 2 scores d[top_t - 1] (the TOPT re-score kernels).
-struct MeanOperands { const void *pooled, *tail; const float *rowp; };
-static int topk_tokens_prefiltered(const char *who, const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
-                                   const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
-                                   int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
-                                   int *redo, void *stream, const int *tiles = nullptr, int n_live = 0, int last_live = 0,
-                                   int direct_sel = 0, const MeanOperands *mo = nullptr, int top_t = 0) {
-    const bool sel = tiles != nullptr, mean = mo != nullptr;
-    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
-    SKY_CHECK_ARG(tw && qn && bank16 && xn && rowp && ws && out_s && out_i && redo, "%s: null argument", who);
-    if (mean) {
-        SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MEAN, "%s: combine code %d: this entry combines by mean (min and max are served by "
-                      "skyemb_cosine_topk_tokens_prefiltered)", who, combine);
-        SKY_CHECK_ARG(skyemb_token_mean_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_MEAN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
-    } else {
-        SKY_CHECK_ARG(top_t == 0 || combine != SKYEMB_COMBINE_MEAN, "%s: " TOKEN_TOPT_MEAN_MSG, who);
-        SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: this entry combines by min or "
-                      "max (mean is served by skyemb_cosine_topk_tokens_mean_prefiltered)", who, combine);
-        SKY_CHECK_ARG(skyemb_token_prefilter_applicable(Q, N, P, D, k), "%s: " TOKEN_PREFILTER_MSG, who, TOK_KMAX, Q, (long long)N, P, D, k);
-        SKY_CHECK_ARG(top_t >= 0 && top_t <= (P < 16 ? P : 16), "%s: top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)", who,
-                      top_t, P);
-    }
-    if (combine == SKYEMB_COMBINE_MAX || top_t == P) top_t = 0;   // d[0] is the max and d[P - 1] the min: the plain search
-    const bool topt = top_t != 0, cnt = top_t > 1;             // stage 2 selects d[top_t - 1]; stage 1 counts (top_t == 1: the OR fold)
-    const int64_t R = mean ? N : N * P;                        // stage 1's rows -- token rows: whole images, P | 64 | BT; mean: images
-    if (mean) {                                                // from here on stage 1's operands are the pooled image's
-        rowp = mo->rowp;
-        tail = mo->tail;
-    }
-    const void *s1_bank = mean ? mo->pooled : bank16;
-    SKY_CHECK_ARG(R % BT == 0 || tail, "%s: %lld rows are no whole number of %d-row tiles: the tail tile of %s is needed", who, (long long)R, BT,
-                  mean ? "skyemb_token_mean_pool" : "skyemb_resident_rowp");
-    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail) && aligned16(s1_bank), "%s: the bank and the tail tile must be 16-byte aligned", who);
-    const int T_tail = (int)(R / BT);                          // whole tiles; the last R % BT rows follow from `tail` as tile T_tail
-    const bool tail_live = R % BT != 0 && (!sel || last_live != 0);
-    const int T = sel ? n_live - (tail_live ? 1 : 0) : T_tail; // positions the slices walk
-    if (sel) {
-        SKY_CHECK_ARG(n_live >= 1 && n_live <= ceil_div64(R, BT) && (last_live == 0 || last_live == 1),
-                      "%s: n_live = %d, last_live = %d: expected 1 .. %lld live tiles and a flag (skyemb_token_prefilter_select_prepare's "
-                      "info)", who, n_live, last_live, (long long)ceil_div64(R, BT));
-        SKY_CHECK_ARG(T >= 1, "%s: the selection's only live tile is the bank's tail tile; the slices need a whole live tile", who);
-        SKY_CHECK_ARG(direct_sel >= 1 && direct_sel <= n_live, "%s: the first slice ends at position %d, expected 1 .. n_live = %d", who,
-                      direct_sel, n_live);
-    }
-    const bool bf = dtype == SKYEMB_BF16;
-    const char *lo_env = getenv("SKYEMB_PREFILTER_LO");        // the variant rule of topk_prefiltered
-    // mean: hi + lo unless SKYEMB_PREFILTER_LO=0 -- stage 1 is P times smaller than the token route's and stage 2, P rows per
-    // candidate, is what the search costs: the tighter bound pays
-    const bool use_lo = mean ? !(lo_env && lo_env[0] == '0')
-                             : bf && !(lo_env && (lo_env[0] == '0' || lo_env[0] == '1')) ? BF16_DEFAULT_LO : lo_env && lo_env[0] == '1';
-    SKY_CHECK_ARG(ceil_div64(ceil_div64(R, BT), 8) * ceil_div64(Q, qtile(use_lo)) * (D / BK) < (1ll << 31),
-                  "%s: Q x N P too large: ceil(N P / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31 (Q=%d N=%lld P=%d D=%d); search the "
-                  "queries in batches", who, qtile(use_lo), Q, (long long)N, P, D);
-    const int cap = skyemb_topk_prefilter_cap(k);
-    SKY_CHECK_ARG(ws_bytes >= skyemb_token_prefilter_ws_bytes(Q, D, k), "%s: workspace too small", who);
-    hipStream_t st = (hipStream_t)stream;
-    Workspace w;
-    const int64_t used = carve((char *)ws, Q, D, cap, &w);
-    unsigned long long *list = (unsigned long long *)((char *)ws + used);
-    int *rn = w.nsel;
-    const double eps_a_d = (mean ? eps_m_of(D, use_lo, bf) : bf ? eps_a_bf16_of(D, use_lo) : eps_a_of(D, use_lo, true)) * (1.0 + 1e-6);
-    const float eps_a = (float)eps_a_d;
-    // mean: eps / eps_m, raised (the query's third test parameter is N_q eps / qn = (eps_m N_q) gfac / qn); NaN flags every query
-    const float gfac = !mean ? -1.0f : eps >= 0.f && eps < INFINITY ? (float)((double)eps / eps_a_d * (1.0 + 1e-6)) : NAN;
-    const dim3 qgrid((unsigned)(((Q + QPAD - 1) / QPAD * QPAD + 3) / 4));
-    if (bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
-    else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, tw, qn, Q, D, w.qh, w.ql, w.qbase, eps_a);
-    const int Q_padded = (Q + QPAD - 1) / QPAD * QPAD;
-    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((Q_padded + 255) / 256)), dim3(256), 0, st, Q, Q_padded, thr0, w.qbase, eps,
-                       w.qpar, w.tau, w.cnt, w.overflow, 0, bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f, bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
-    hipLaunchKernelGGL(token_state_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, Q, (const float4 *)w.qbase, w.tau, rn, w.overflow,
-                       gfac, w.qpar);
-    const int smem1 = NSTAGE * stage_bytes(use_lo) + (qtile(use_lo) + BT) * 16 + SCAP * 8 + 16;
-    constexpr int smem_max = NSTAGE * stage_bytes(true) + (256 + BT) * 16 + SCAP * 8 + 16;
-    const int smem_re = (TOK_KMAX + cap + TOK_KMAX) * 8 + D * 4 + 264 * 4;
-    int rc = 0;
-#define TK_ATTR(M, L)                                                                                                             \
-    if (rc == 0 && !bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, true>, smem_max, who);   \
-    if (rc == 0 && bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true>, smem_max, who);     \
-    if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, false, true>, smem_max, who);     \
-    if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true, true>, smem_max, who)
-    if (!mean && !cnt) { TK_ATTR(1, false); TK_ATTR(2, false); TK_ATTR(1, true); TK_ATTR(2, true); }
-#undef TK_ATTR
-#define TC_ATTR(M, L)                                                                                                                 \
-    if (rc == 0 && !bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, true, true>, smem_max, who);  \
-    if (rc == 0 && bf && !sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, true, true>, smem_max, who);    \
-    if (rc == 0 && !bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, false, true, true>, smem_max, who);    \
-    if (rc == 0 && bf && sel) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, true, true, true, true>, smem_max, who)
-    if (cnt) { TC_ATTR(1, false); TC_ATTR(2, false); TC_ATTR(1, true); TC_ATTR(2, true); }
-#undef TC_ATTR
-#define TM_ATTR(M, L)                                                                                                 \
-    if (rc == 0 && !bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, false, false>, smem_max, who); \
-    if (rc == 0 && bf) rc = sky_set_lds_limit((const void *)prefilter_kernel<M, L, false, true, false>, smem_max, who)
-    if (mean) { TM_ATTR(1, false); TM_ATTR(2, false); TM_ATTR(1, true); TM_ATTR(2, true); }
-#undef TM_ATTR
-    const void *rescore = topt ? (bf ? (const void *)token_rescore_top_bf_kernel : (const void *)token_rescore_top_lp_kernel)
-                               : (bf ? (const void *)token_rescore_bf_kernel : (const void *)token_rescore_lp_kernel);
-    if (rc == 0) rc = sky_set_lds_limit(rescore, (2 * TOK_KMAX + 8192) * 8 + 4096 * 4 + 264 * 4, who);
-    if (rc != 0) return rc;
-    const int lgp = log2_of(P), fold = mean ? TOK_MEAN : combine == SKYEMB_COMBINE_MAX ? TOK_MAX : TOK_MIN;
-    // (the instances without CNT read every bit above bit 7 as "is max": top_t travels only to those that count)
-    const int tok = lgp | ((fold == TOK_MAX || top_t == 1 ? 1 : 0) << 8) | (cnt ? top_t << 16 : 0);
-    const int rpi = mean ? 1 : P;                              // stage 1's rows per image
-    // the slices of topk_prefiltered's schedule, the first counted in images (96 k of them: the floor comes from a sample of a small
-    // multiple of k images and still passes several per cent of them, so that slice appends directly); no take-all slice.  Under a
-    // selection the fractions are taken of the live tiles and the caller has counted the 96 k SELECTED images.
-    int direct_end;
-    if (sel) {
-        direct_end = direct_sel < T ? direct_sel : T;
-    } else {
-        direct_end = (int)(ceil_div64((int64_t)96 * k * rpi, BT) < T ? ceil_div64((int64_t)96 * k * rpi, BT) : T);
-        if (direct_end < T / 128) direct_end = T / 128;
-        if (direct_end < 1) direct_end = 1;
-    }
-    const int ends[5] = {direct_end, T / 32, T / 8, T / 2, T};
-#define TK_ARGS(B, T0, T1) w.qh, w.ql, (const half_t *)(B), (const float4 *)rowp, tiles, w.qpar, Q, R, D, T0, T1, cap, w.cnt, \
-                           w.cand_i, w.cand_d, w.wg_list, w.wg_count, w.capw, w.overflow, tok
-#define TK_LAUNCH_AS(M, L, S, F, B, T0, T1) \
-    hipLaunchKernelGGL((prefilter_kernel<M, L, S, F, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
-#define TC_LAUNCH_AS(M, L, S, F, B, T0, T1) \
-    hipLaunchKernelGGL((prefilter_kernel<M, L, S, F, true, true>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
-#define TM_LAUNCH_AS(M, L, F, B, T0, T1) \
-    hipLaunchKernelGGL((prefilter_kernel<M, L, false, F, false>), dim3(PF_GRID), dim3(NT), smem1, st, TK_ARGS(B, T0, T1))
-#define TK_LAUNCH(M, B, T0, T1)                                                     \
-    do {                                                                            \
-        if (mean) {                                                                 \
-            if (bf && use_lo) TM_LAUNCH_AS(M, true, true, B, T0, T1);               \
-            else if (bf) TM_LAUNCH_AS(M, false, true, B, T0, T1);                   \
-            else if (use_lo) TM_LAUNCH_AS(M, true, false, B, T0, T1);               \
-            else TM_LAUNCH_AS(M, false, false, B, T0, T1);                          \
-        } else if (cnt && sel) {                                                    \
-            if (bf && use_lo) TC_LAUNCH_AS(M, true, true, true, B, T0, T1);         \
-            else if (bf) TC_LAUNCH_AS(M, false, true, true, B, T0, T1);             \
-            else if (use_lo) TC_LAUNCH_AS(M, true, true, false, B, T0, T1);         \
-            else TC_LAUNCH_AS(M, false, true, false, B, T0, T1);                    \
-        } else if (cnt) {                                                           \
-            if (bf && use_lo) TC_LAUNCH_AS(M, true, false, true, B, T0, T1);        \
-            else if (bf) TC_LAUNCH_AS(M, false, false, true, B, T0, T1);            \
-            else if (use_lo) TC_LAUNCH_AS(M, true, false, false, B, T0, T1);        \
-            else TC_LAUNCH_AS(M, false, false, false, B, T0, T1);                   \
-        } else if (sel) {                                                                  \
-            if (bf && use_lo) TK_LAUNCH_AS(M, true, true, true, B, T0, T1);         \
-            else if (bf) TK_LAUNCH_AS(M, false, true, true, B, T0, T1);             \
-            else if (use_lo) TK_LAUNCH_AS(M, true, true, false, B, T0, T1);         \
-            else TK_LAUNCH_AS(M, false, true, false, B, T0, T1);                    \
-        } else {                                                                    \
-            if (bf && use_lo) TK_LAUNCH_AS(M, true, false, true, B, T0, T1);        \
-            else if (bf) TK_LAUNCH_AS(M, false, false, true, B, T0, T1);            \
-            else if (use_lo) TK_LAUNCH_AS(M, true, false, false, B, T0, T1);        \
-            else TK_LAUNCH_AS(M, false, false, false, B, T0, T1);                   \
-        }                                                                           \
-    } while (0)
-    int t0 = 0;
-    bool direct_done = false;
-    for (int p = 0; p < 5; ++p) {
-        const int t1 = ends[p];
-        if (t1 <= t0) continue;
-        if (!direct_done) {
-            TK_LAUNCH(1, s1_bank, t0, t1);
-            direct_done = true;
-        } else {
-            TK_LAUNCH(2, s1_bank, t0, t1);
-            hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count, w.capw,
-                               cap, w.cnt, w.cand_i, w.cand_d);
-        }
-        const int final = t1 == T;
-        if (final && tail_live) {
-            // the last R % BT rows, tile T_tail from the padded copy (topk_prefiltered's tail launch): direct appends behind the
-            // slice's.  Under a selection it is the list's own last position, n_live - 1 = T, which holds T_tail.
-            const half_t *tail_base = (const half_t *)((uintptr_t)tail - (uintptr_t)T_tail * BT * D * sizeof(half_t));
-            TK_LAUNCH(1, tail_base, sel ? T : T_tail, (sel ? T : T_tail) + 1);
-        }
-#define TK_RESCORE(B) tw, qn, B, xn, N, D, lgp, fold, gfac, k, eps, idx_offset, cap, (const float4 *)w.qbase, w.cnt, (const int *)w.cand_i, list, rn, \
-                      w.qpar, w.tau, w.overflow, final, out_s, out_i, redo
-        if (topt && bf) hipLaunchKernelGGL(token_rescore_top_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16), top_t);
-        else if (topt) hipLaunchKernelGGL(token_rescore_top_lp_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const half_t *)bank16), top_t);
-        else if (bf) hipLaunchKernelGGL(token_rescore_bf_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const bf16_t *)bank16));
-        else hipLaunchKernelGGL(token_rescore_lp_kernel, dim3((unsigned)Q), dim3(256), smem_re, st, TK_RESCORE((const half_t *)bank16));
-#undef TK_RESCORE
-        t0 = t1;
-    }
-#undef TK_LAUNCH
-#undef TK_LAUNCH_AS
-#undef TC_LAUNCH_AS
-#undef TM_LAUNCH_AS
-#undef TK_ARGS
-    SKY_LAUNCH_CHECK(who);
-    return 0;
-}
-
-extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
-                                                     const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
-                                                     float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
-                                                     float *out_s, int64_t *out_i, int *redo, void *stream) {
-    return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered", tw, qn, Q, bank16, dtype, xn, tail, rowp, N, P, D, k, combine, eps,
-                                   idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
-}
-
-// ... under top_t (0: the call above)
-extern "C" int skyemb_cosine_topk_tokens_prefiltered_top(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
-                                                         const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
-                                                         int top_t, float eps, int64_t idx_offset, const float *thr0, void *ws,
-                                                         int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
-    return topk_tokens_prefiltered(top_t ? "skyemb_cosine_topk_tokens_prefiltered_top" : "skyemb_cosine_topk_tokens_prefiltered", tw, qn, Q, bank16,
-                                   dtype, xn, tail, rowp, N, P, D, k, combine, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
-                                   nullptr, 0, 0, 0, nullptr, top_t);
-}
-
 // ---- the same search under a selection of the bank's images ---------------------------------------------------------------------------
 extern "C" int skyemb_token_prefilter_select_prepare(const uint32_t *words, int64_t N, int P, const float *rowp, float *rowp_sel,
                                                      int *tiles, int *cum, int *info, void *stream) {
@@ -2496,38 +2010,361 @@ extern "C" int skyemb_token_prefilter_select_prepare(const uint32_t *words, int6
     return 0;
 }
 
-extern "C" int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
-                                                         const float *xn, const void *tail, const float *rowp_sel, const int *tiles,
-                                                         int n_live, int last_live, int direct_end, int64_t N, int P, int D, int k,
-                                                         int combine, float eps, int64_t idx_offset, const float *thr0, void *ws,
-                                                         int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
-    SKY_CHECK_ARG(tiles, "skyemb_cosine_topk_tokens_prefiltered_sel: null argument");
-    return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_prefiltered_sel", tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, N, P, D, k,
-                                   combine, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream, tiles, n_live, last_live,
-                                   direct_end);
+// ---- The host layer of every search entry point: one plan (prefilter_plan.h), one driver ------------------------------------------------
+// An entry point states its call as a request and its pointers; sky_prefilter_plan decides everything (variant, slices, instances, LDS
+// bytes, constants); `search` checks the pointers, carves the workspace and launches what the plan says.
+//   rows     bank: the fp32 rows stage 2 re-scores, bank16 their fp16 image (skyemb_bank16_prepare) -- or bank NULL: bank16 is a resident
+//            16-bit bank that both stages read, its last N % BT rows through `tail`.  Stage 2: select_kernel after every slice, one exact
+//            re-score at the end.
+//   tokens   bank16 the resident token bank [N, P, D]; stage 1 the TOK (top_t > 1: CNT) instances over its flat rows, stage 2 a token
+//            re-score after every slice -- d[top_t - 1] by the TOPT kernels under 'min' with 1 <= top_t < P.
+//   mean     stage 1 is the ROW search over the pooled image of skyemb_token_mean_pool (`pooled`, with ITS tail and rowp: a row is an image,
+//            no TOK fold) under the mean bound's constants; stage 2 re-scores the candidate images' tokens from bank16 as ever.
+// tiles (a search under a selection, the two select_prepare calls): rowp is the masked copy, the slices walk the live-tile list (SEL).
+namespace {
+
+static_assert(pfplan::BT == BT && pfplan::BK == BK && pfplan::QPAD == QPAD && pfplan::NSTAGE == NSTAGE && pfplan::SCAP == SCAP &&
+                  pfplan::RESCORE_MAX == RESCORE_MAX && pfplan::TOK_KMAX == TOK_KMAX && pfplan::STAGE_BYTES == stage_bytes(false) &&
+                  pfplan::STAGE_BYTES == stage_bytes(true) && pfplan::qtile(false) == qtile(false) && pfplan::qtile(true) == qtile(true) &&
+                  TOK_MIN == 0 && TOK_MAX == 1 && TOK_MEAN == 2, "prefilter_plan.h restates the kernels' geometry");
+// Stage 1: the 56 instances of prefilter_kernel, each named once.  Row (sel, bf) x MODE 0 1 2 x LO; TOK and TOK + CNT: MODE 1 and 2 only.
+constexpr int stage1_index(int mode, bool lo, bool sel, bool bf, bool tok, bool cnt) { return ((((tok + cnt) * 3 + mode) * 2 + lo) * 2 + sel) * 2 + bf; }
+template <int I>
+constexpr auto stage1_instance() {
+    constexpr int family = I / 24, mode = I / 8 % 3;
+    constexpr bool lo = I / 4 % 2, sel = I / 2 % 2, bf = I % 2;
+    if constexpr (family > 0 && mode == 0) return nullptr;
+    else return &prefilter_kernel<mode, lo, sel, bf, (family > 0), (family > 1)>;
+}
+using Stage1Fn = decltype(stage1_instance<0>());
+template <int... I>
+constexpr std::array<Stage1Fn, sizeof...(I)> stage1_table(std::integer_sequence<int, I...>) { return {{stage1_instance<I>()...}}; }
+constexpr auto STAGE1 = stage1_table(std::make_integer_sequence<int, 72>{});
+
+// Stage 2's instances.  The re-scores differ in their bank's element type, so they are launched through their addresses (launch_like).
+using SelectFn = decltype(&select_kernel<false>);
+constexpr SelectFn SELECT[2] = {select_kernel<false>, select_kernel<true>};                                        // [sel]
+const void *const RESCORE[3][2] = {{(const void *)rescore_kernel<false>, (const void *)rescore_kernel<true>},      // [bank][few = sel]
+                                   {(const void *)rescore_lp_kernel<false>, (const void *)rescore_lp_kernel<true>},
+                                   {(const void *)rescore_bf_kernel<false>, (const void *)rescore_bf_kernel<true>}};
+const void *const TOKEN_RESCORE[2][2] = {{(const void *)token_rescore_lp_kernel, (const void *)token_rescore_bf_kernel},     // [topt][bf]
+                                         {(const void *)token_rescore_top_lp_kernel, (const void *)token_rescore_top_bf_kernel}};
+
+// the pointer arguments of an entry point; NULL where it has none
+struct SearchArgs {
+    const float *tw, *qn, *bank, *xn;
+    const void *bank16;
+    int dtype;                                 // of bank16 as the caller gave it (a request's bank is -1 when it is neither 16-bit format)
+    const void *tail, *pooled;
+    const float *rowp;
+    const int *tiles;
+    int64_t idx_offset;
+    const float *thr0;
+    void *ws;
+    int64_t ws_bytes;
+    float *out_s;
+    int64_t *out_i;
+    int *redo;
+    void *stream;
+};
+
+int bank_of(int dtype) { return dtype == SKYEMB_BF16 ? SKYEMB_PF_BANK_BF16 : dtype == SKYEMB_F16 ? SKYEMB_PF_BANK_F16 : -1; }
+// the entry point a request is reported under (dtype SKYEMB_F16 of a `_resident` entry IS the `_lp` entry; top_t == 0 IS the plain one)
+const char *who_of(const skyemb_prefilter_request_t &r) {
+    if (r.kind == SKYEMB_PF_TOKENS_MEAN) return "skyemb_cosine_topk_tokens_mean_prefiltered";
+    if (r.kind == SKYEMB_PF_TOKENS)
+        return r.sel ? (r.top_t ? "skyemb_cosine_topk_tokens_prefiltered_top_sel" : "skyemb_cosine_topk_tokens_prefiltered_sel")
+                     : (r.top_t ? "skyemb_cosine_topk_tokens_prefiltered_top" : "skyemb_cosine_topk_tokens_prefiltered");
+    if (r.bank == SKYEMB_PF_BANK_F32) return r.sel ? "skyemb_cosine_topk_prefiltered_sel" : "skyemb_cosine_topk_prefiltered";
+    if (r.bank == SKYEMB_PF_BANK_F16) return r.sel ? "skyemb_cosine_topk_prefiltered_lp_sel" : "skyemb_cosine_topk_prefiltered_lp";
+    return r.sel ? "skyemb_cosine_topk_prefiltered_resident_sel" : "skyemb_cosine_topk_prefiltered_resident";
 }
 
-// ... under top_t (0: the call above)
+// SKYEMB_PREFILTER_LO as the planner takes it (read per call on purpose: a sub-microsecond scan, and the tests switch it)
+int lo_of_env() {
+    const char *lo_env = getenv("SKYEMB_PREFILTER_LO");
+    return lo_env && lo_env[0] == '0' ? 0 : lo_env && lo_env[0] == '1' ? 1 : SKYEMB_PF_LO_UNSET;
+}
+
+// sky_prefilter_plan with its refusals put into words; no device is touched
+int plan_or_refuse(const skyemb_prefilter_request_t &r, const char *who, skyemb_prefilter_plan_t *p) {
+    const bool rows = r.kind == SKYEMB_PF_ROWS;
+    const long long N = (long long)r.N, tiles_all = (long long)ceil_div64(rows ? r.N : r.N * r.P, BT);
+    const int code = pfplan::sky_prefilter_plan(r, p);
+    const char *prepare = rows ? "skyemb_prefilter_select_prepare" : "skyemb_token_prefilter_select_prepare";
+    if (code == pfplan::PF_OK) return 0;
+    if (code == pfplan::PF_ROWS_SHAPE)
+        skyemb_set_error("%s: outside the prefiltered subset (Q >= 17, D %% 32 == 0, k <= %d, N >= %d)", who, RESCORE_MAX - 64, 8 * BT);
+    else if (code == pfplan::PF_MEAN_COMBINE)
+        skyemb_set_error("%s: combine code %d: this entry combines by mean (min and max are served by skyemb_cosine_topk_tokens_prefiltered)",
+                         who, r.combine);
+    else if (code == pfplan::PF_MEAN_SHAPE) skyemb_set_error("%s: " TOKEN_MEAN_PREFILTER_MSG, who, TOK_KMAX, r.Q, N, r.P, r.D, r.k);
+    else if (code == pfplan::PF_TOPT_MEAN) skyemb_set_error("%s: " TOKEN_TOPT_MEAN_MSG, who);
+    else if (code == pfplan::PF_TOKENS_COMBINE)
+        skyemb_set_error("%s: combine code %d: this entry combines by min or max (mean is served by "
+                         "skyemb_cosine_topk_tokens_mean_prefiltered)", who, r.combine);
+    else if (code == pfplan::PF_TOKENS_SHAPE) skyemb_set_error("%s: " TOKEN_PREFILTER_MSG, who, TOK_KMAX, r.Q, N, r.P, r.D, r.k);
+    else if (code == pfplan::PF_TOPT_RANGE)
+        skyemb_set_error("%s: top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)", who, r.top_t, r.P);
+    else if (code == pfplan::PF_SEL_INFO)
+        skyemb_set_error("%s: n_live = %d, last_live = %d: expected 1 .. %lld live tiles and a flag (%s's info)", who, r.n_live, r.last_live,
+                         tiles_all, prepare);
+    else if (code == pfplan::PF_SEL_ONLY_TAIL && rows)
+        skyemb_set_error("%s: the selection's only live tile is the resident bank's tail tile; the phases need a whole live tile", who);
+    else if (code == pfplan::PF_SEL_ONLY_TAIL)
+        skyemb_set_error("%s: the selection's only live tile is the bank's tail tile; the slices need a whole live tile", who);
+    else if (code == pfplan::PF_SEL_DIRECT)
+        skyemb_set_error("%s: the first slice ends at position %d, expected 1 .. n_live = %d", who, r.direct_sel, r.n_live);
+    else if (code == pfplan::PF_TOO_LARGE && rows)
+        skyemb_set_error("%s: Q x N too large: ceil(N / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31, the range of stage 1's work-item "
+                         "and k-step counters (Q=%d N=%lld D=%d); search the queries in batches", who, qtile(p->use_lo), r.Q, N, r.D);
+    else if (code == pfplan::PF_TOO_LARGE)
+        skyemb_set_error("%s: Q x N P too large: ceil(N P / 2048) * ceil(Q / %d) * (D / 32) must stay below 2^31 (Q=%d N=%lld P=%d D=%d); search the "
+                         "queries in batches", who, qtile(p->use_lo), r.Q, N, r.P, r.D);
+    else
+        skyemb_set_error("skyemb_prefilter_plan: no entry point takes this request (kind=%d bank=%d lo=%d sel=%d has_thr0=%d)", r.kind, r.bank,
+                         r.lo, r.sel, r.has_thr0);
+    return 1;
+}
+
+// Launch `kernel` through its address with the parameter list of `like`: the arguments convert to like's parameter types, so number and types are
+// checked at compile time (a re-score table's kernels share one *_PARAMS text and differ only in the bank's element type; errors: SKY_LAUNCH_CHECK)
+template <typename... P>
+void launch_like(void (*like)(P...), const void *kernel, unsigned grid, size_t lds, hipStream_t st, std::common_type_t<P>... a) {
+    void *args[] = {(void *)&a...};
+    (void)hipLaunchKernel(kernel, dim3(grid), dim3(256), args, lds, st);
+}
+
+#if defined(PF_STAMP) || defined(PF_CLOCK)
+// the diagnostic builds (-DPF_CLOCK / -DPF_STAMP): stage 1 adds to 32 counters, zeroed before every slice, read back and printed after it
+unsigned long long *pf_dbg() {
+    static unsigned long long *dbg = nullptr;
+    if (!dbg) { hipMalloc(&dbg, 32 * 8); }
+    return dbg;
+}
+void pf_dbg_report(hipStream_t st, int p, int mode, int Q, const Workspace &w) {
+    unsigned long long h[32];
+    hipStreamSynchronize(st);
+    hipMemcpy(h, pf_dbg(), sizeof(h), hipMemcpyDeviceToHost);
+#ifdef PF_CLOCK
+    if (h[23])
+        fprintf(stderr, "[clock] phase %d (%s): in-kernel clock %.3f GHz over %.2f ms, %.0f shader cycles per k-step (256 MFMAs = 64 per SIMD x 16 cycles = 1024 at the "
+                        "matrix pipe's rate), steps/wg %.0f\n",
+                p, mode == 0 ? "take-all" : mode == 1 ? "direct append" : "staged", (double)h[20] / (double)h[21] * 0.1, (double)h[21] / h[23] * 1e-5,
+                (double)h[20] / (double)h[22], (double)h[22] / h[23]);
+#endif
+#ifdef PF_STAMP
+    const double n = (double)h[16] * 4.0;     // steps summed over workgroups x 4 waves per group
+    if (mode == 2) {
+        int hc[PF_GRID];
+        hipMemcpy(hc, w.wg_count, sizeof(hc), hipMemcpyDeviceToHost);
+        long tot = 0; int mx = 0;
+        for (int i = 0; i < PF_GRID; ++i) { tot += hc[i]; if (hc[i] > mx) mx = hc[i]; }
+        fprintf(stderr, "[stamp] phase %d staged candidates: total %ld (%.1f per query), max per workgroup %d of %d\n", p, tot, (double)tot / Q, mx, w.capw);
+    }
+    fprintf(stderr, "[stamp] phase %d steps/wg %.0f | early: wait %.0f P0 %.0f read+issue %.0f P1 %.0f mult %.0f | late: wait %.0f P0 %.0f read+issue %.0f P1 %.0f mult %.0f (cycles of s_memtime per k-step)\n",
+            p, (double)h[16] / 256.0, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[12] / n);
+    const double ni = (double)h[17] * 4.0;    // items summed over workgroups x 4 waves per group
+    fprintf(stderr, "[stamp] phase %d items/wg %.0f | item epilogue, cycles per item: early tests %.0f appends %.0f zero %.0f | late tests %.0f appends %.0f zero %.0f\n",
+            p, (double)h[17] / 256.0, h[5] / ni, h[6] / ni, h[7] / ni, h[13] / ni, h[14] / ni, h[15] / ni);
+#endif
+}
+#endif
+
+int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
+    const char *who = who_of(r);
+    const bool rows = r.kind == SKYEMB_PF_ROWS, mean = r.kind == SKYEMB_PF_TOKENS_MEAN;
+    SKY_CHECK_ARG(r.bank >= 0, "%s: dtype " RESIDENT_DTYPE_MSG, who, a.dtype);
+    SKY_CHECK_ARG(a.tw && a.qn && a.xn && a.bank16 && a.rowp && a.ws && a.out_s && a.out_i && a.redo &&
+                      (r.bank != SKYEMB_PF_BANK_F32 || a.bank) && (!r.sel || a.tiles) && (!mean || a.pooled), "%s: null argument", who);
+    r.lo = lo_of_env();
+    skyemb_prefilter_plan_t p;
+    if (plan_or_refuse(r, who, &p)) return 1;
+    const int Q = r.Q, D = r.D, k = r.k, bank = r.bank;
+    const void *s1_bank = mean ? a.pooled : a.bank16;          // the rows stage 1 multiplies
+    if (bank != SKYEMB_PF_BANK_F32) {
+        SKY_CHECK_ARG(p.rows % BT == 0 || a.tail, rows ? "%s: N = %lld is no whole number of %d-row tiles: the tail tile of %s is needed"
+                                                       : "%s: %lld rows are no whole number of %d-row tiles: the tail tile of %s is needed",
+                      who, (long long)p.rows, BT, mean ? "skyemb_token_mean_pool" : rows && bank == SKYEMB_PF_BANK_F16 ? "skyemb_bank16_rowp_lp"
+                                                                                                                      : "skyemb_resident_rowp");
+        SKY_CHECK_ARG(aligned16(a.bank16) && aligned16(a.tail) && aligned16(s1_bank), "%s: the bank and the tail tile must be 16-byte aligned",
+                      who);
+    }
+    SKY_CHECK_ARG(a.ws_bytes >= (rows ? skyemb_topk_prefilter_ws_bytes(Q, D, k) : skyemb_token_prefilter_ws_bytes(Q, D, k)),
+                  "%s: workspace too small", who);
+    hipStream_t st = (hipStream_t)a.stream;
+    Workspace w;
+    const int64_t used = carve((char *)a.ws, Q, D, p.cap, &w);
+    unsigned long long *list = (unsigned long long *)((char *)a.ws + used);     // token routes: the running lists (lengths: nsel) follow
+    // the LDS limits this request's instances need: both variants of every mode of its family, as ever
+    int rc = 0;
+    for (int mode = rows ? 0 : 1; mode <= 2; ++mode)
+        for (int lo = 0; lo <= 1; ++lo)
+            for (int s = rows ? 0 : p.sel; s <= p.sel; ++s)    // (a row search under a selection launches its tail through the non-SEL instance)
+                if (rc == 0) rc = sky_set_lds_limit((const void *)STAGE1[stage1_index(mode, lo, s, p.bf, p.tok, p.cnt)], p.lds_stage1_limit, who);
+    const void *token_rescore = TOKEN_RESCORE[p.top_t != 0][p.bf];
+    if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, p.lds_close_limit, who);
+    if (rc == 0 && rows && p.sel) rc = sky_set_lds_limit((const void *)SELECT[1], p.lds_close_limit, who);
+    if (rc != 0) return rc;
+    const dim3 qgrid((unsigned)((p.q_padded + 3) / 4));
+    if (p.bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
+    else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
+    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((p.q_padded + 255) / 256)), dim3(256), 0, st, Q, p.q_padded, a.thr0, w.qbase, r.eps,
+                       w.qpar, w.tau, w.cnt, w.overflow, p.first_rows, p.bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
+                       p.bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
+    if (!rows)
+        hipLaunchKernelGGL(token_state_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, Q, (const float4 *)w.qbase, w.tau, w.nsel,
+                           w.overflow, p.gfac, w.qpar);
+    // one stage-1 launch over positions [t0, t1) of `base`: of the live-tile list with the SEL instance, else the bank tiles themselves
+    auto stage1 = [&](int mode, bool sel, const void *base, int t0, int t1) {
+        const Stage1Fn kernel = STAGE1[stage1_index(mode, p.use_lo, sel, p.bf, p.tok, p.cnt)];
+        auto go = [&](auto... dbg) {
+            hipLaunchKernelGGL(kernel, dim3(PF_GRID), dim3(NT), p.lds_stage1, st, w.qh, w.ql, (const half_t *)base, (const float4 *)a.rowp,
+                               sel ? a.tiles : (const int *)nullptr, w.qpar, Q, p.rows, D, t0, t1, p.cap, w.cnt, w.cand_i, w.cand_d, w.wg_list,
+                               w.wg_count, w.capw, w.overflow, p.tok_word, dbg...);
+        };
+#if defined(PF_STAMP) || defined(PF_CLOCK)
+        go(pf_dbg());
+#else
+        go();
+#endif
+    };
+    auto token_rescore_as = [&](auto like, int final, auto... top_t) {
+        launch_like(like, token_rescore, Q, p.lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, r.N, D, p.lgp, p.fold, p.gfac, k, r.eps,
+                    a.idx_offset, p.cap, w.qbase, w.cnt, w.cand_i, list, w.nsel, w.qpar, w.tau, w.overflow, final, a.out_s, a.out_i, a.redo, top_t...);
+    };
+    // The kernel addresses tile t at base + t * BT rows, so the base handed over for the tail is the one that puts tile T_tail on
+    // `tail` (an address only: it is the single tile of that launch, and under SEL the list's last entry holds T_tail).
+    const void *tail_base = (const void *)((uintptr_t)a.tail - (uintptr_t)p.T_tail * BT * D * sizeof(half_t));
+    for (int i = 0; i < p.n_slices; ++i) {
+        const skyemb_prefilter_slice_t &s = p.slice[i];
+#if defined(PF_STAMP) || defined(PF_CLOCK)
+        hipMemsetAsync(pf_dbg(), 0, 32 * 8, st);
+#endif
+        stage1(s.mode, p.sel, s1_bank, s.t0, s.t1);
+        if (s.bucket)
+            hipLaunchKernelGGL(bucket_kernel, dim3(8, PF_GRID), dim3(256), 0, st, (const uint4 *)w.wg_list, (const int *)w.wg_count, w.capw, p.cap,
+                               w.cnt, w.cand_i, w.cand_d);
+        // the tail tile: direct appends under the slice's threshold -- at most BT candidates per query behind whatever the lists hold
+        if (s.tail) stage1(1, s.tail_sel, tail_base, s.tail_pos, s.tail_pos + 1);
+#if defined(PF_STAMP) || defined(PF_CLOCK)
+        pf_dbg_report(st, i, s.mode, Q, w);
+#endif
+        if (rows)
+            hipLaunchKernelGGL(SELECT[p.sel], dim3((unsigned)Q), dim3(256), p.lds_close, st, Q, k, p.cap, r.eps, w.qbase, (const float4 *)a.rowp, a.xn,
+                               w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, s.final, w.sel_i, w.nsel, w.bound);
+        else if (p.top_t) token_rescore_as(token_rescore_top_lp_kernel, s.final, p.top_t);      // the TOPT kernels take top_t last
+        else token_rescore_as(token_rescore_lp_kernel, s.final);
+    }
+    if (rows)
+        launch_like(rescore_kernel<false>, RESCORE[bank][p.sel], Q, p.lds_rescore, st, a.tw, a.qn,
+                    (const float *)(bank == SKYEMB_PF_BANK_F32 ? a.bank : a.bank16), a.xn, Q, D, k, r.eps, a.idx_offset, w.sel_i, w.nsel, w.bound,
+                    w.overflow, a.out_s, a.out_i, a.redo);
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+skyemb_prefilter_request_t request(int kind, int bank, int Q, int64_t N, int P, int D, int k, int combine, int top_t, float eps, const float *thr0,
+                                   bool sel = false, int n_live = 0, int last_live = 0, int direct_sel = 0) {
+    return {kind, bank, Q, P, D, k, N, combine, top_t, thr0 != nullptr, sel, n_live, last_live, direct_sel, 0, eps};
+}
+
+}  // namespace
+
+extern "C" int skyemb_prefilter_plan(const skyemb_prefilter_request_t *req, skyemb_prefilter_plan_t *out) {
+    if (!req || !out) return skyemb_set_error("skyemb_prefilter_plan: null argument"), 1;
+    skyemb_prefilter_request_t r = *req;
+    if (r.lo == -1) r.lo = lo_of_env();
+    return plan_or_refuse(r, who_of(r), out);
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered(const float *tw, const float *qn, int Q, const float *bank, const float *xn, const void *bank16,
+                                              const float *rowp, int64_t N, int D, int k, float eps, int64_t idx_offset, const float *thr0,
+                                              void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return search(request(SKYEMB_PF_ROWS, SKYEMB_PF_BANK_F32, Q, N, 1, D, k, 0, 0, eps, thr0),
+                  {tw, qn, bank, xn, bank16, SKYEMB_F32, nullptr, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream});
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_sel(const float *tw, const float *qn, int Q, const float *bank, const float *xn, const void *bank16,
+                                                  const float *rowp_sel, const int *tiles, int n_live, int last_live, int64_t N, int D, int k,
+                                                  float eps, int64_t idx_offset, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                  int *redo, void *stream) {
+    return search(request(SKYEMB_PF_ROWS, SKYEMB_PF_BANK_F32, Q, N, 1, D, k, 0, 0, eps, nullptr, true, n_live, last_live),
+                  {tw, qn, bank, xn, bank16, SKYEMB_F32, nullptr, nullptr, rowp_sel, tiles, idx_offset, nullptr, ws, ws_bytes, out_s, out_i, redo, stream});
+}
+
+// ---- a resident 16-bit bank of either format (dtype SKYEMB_F16: the _lp entry points, SKYEMB_BF16: the bf16 search) --------------------
+extern "C" int skyemb_cosine_topk_prefiltered_resident(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                       const void *tail, const float *rowp, int64_t N, int D, int k, float eps,
+                                                       int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                       int64_t *out_i, int *redo, void *stream) {
+    return search(request(SKYEMB_PF_ROWS, bank_of(dtype), Q, N, 1, D, k, 0, 0, eps, thr0),
+                  {tw, qn, nullptr, xn, bank16, dtype, tail, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream});
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_resident_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                           const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
+                                                           int64_t N, int D, int k, float eps, int64_t idx_offset, void *ws, int64_t ws_bytes,
+                                                           float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return search(request(SKYEMB_PF_ROWS, bank_of(dtype), Q, N, 1, D, k, 0, 0, eps, nullptr, true, n_live, last_live),
+                  {tw, qn, nullptr, xn, bank16, dtype, tail, nullptr, rowp_sel, tiles, idx_offset, nullptr, ws, ws_bytes, out_s, out_i, redo, stream});
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_lp(const float *tw, const float *qn, int Q, const void *bank16, const float *xn, const void *tail,
+                                                 const float *rowp, int64_t N, int D, int k, float eps, int64_t idx_offset, const float *thr0,
+                                                 void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return skyemb_cosine_topk_prefiltered_resident(tw, qn, Q, bank16, SKYEMB_F16, xn, tail, rowp, N, D, k, eps, idx_offset, thr0, ws, ws_bytes,
+                                                   out_s, out_i, redo, stream);
+}
+
+extern "C" int skyemb_cosine_topk_prefiltered_lp_sel(const float *tw, const float *qn, int Q, const void *bank16, const float *xn, const void *tail,
+                                                     const float *rowp_sel, const int *tiles, int n_live, int last_live, int64_t N, int D, int k,
+                                                     float eps, int64_t idx_offset, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                     int *redo, void *stream) {
+    return skyemb_cosine_topk_prefiltered_resident_sel(tw, qn, Q, bank16, SKYEMB_F16, xn, tail, rowp_sel, tiles, n_live, last_live, N, D, k, eps,
+                                                       idx_offset, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// ---- patch-token banks: min / max, under top_t (0: the plain call), under a selection of images; mean -----------------------------------
+extern "C" int skyemb_cosine_topk_tokens_prefiltered_top(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                         const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                                         int top_t, float eps, int64_t idx_offset, const float *thr0, void *ws,
+                                                         int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N, P, D, k, combine, top_t, eps, thr0),
+                  {tw, qn, nullptr, xn, bank16, dtype, tail, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream});
+}
+
+extern "C" int skyemb_cosine_topk_tokens_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                     const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine, float eps,
+                                                     int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                     int64_t *out_i, int *redo, void *stream) {
+    return skyemb_cosine_topk_tokens_prefiltered_top(tw, qn, Q, bank16, dtype, xn, tail, rowp, N, P, D, k, combine, 0, eps, idx_offset, thr0, ws,
+                                                     ws_bytes, out_s, out_i, redo, stream);
+}
+
 extern "C" int skyemb_cosine_topk_tokens_prefiltered_top_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
                                                              const float *xn, const void *tail, const float *rowp_sel, const int *tiles,
                                                              int n_live, int last_live, int direct_end, int64_t N, int P, int D, int k,
-                                                             int combine, int top_t, float eps, int64_t idx_offset, const float *thr0,
-                                                             void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
-                                                             void *stream) {
-    const char *who = top_t ? "skyemb_cosine_topk_tokens_prefiltered_top_sel" : "skyemb_cosine_topk_tokens_prefiltered_sel";
-    SKY_CHECK_ARG(tiles, "%s: null argument", who);
-    return topk_tokens_prefiltered(who, tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, N, P, D, k, combine, eps, idx_offset, thr0, ws, ws_bytes,
-                                   out_s, out_i, redo, stream, tiles, n_live, last_live, direct_end, nullptr, top_t);
+                                                             int combine, int top_t, float eps, int64_t idx_offset, const float *thr0, void *ws,
+                                                             int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N, P, D, k, combine, top_t, eps, thr0, true, n_live, last_live, direct_end),
+                  {tw, qn, nullptr, xn, bank16, dtype, tail, nullptr, rowp_sel, tiles, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream});
 }
 
-// ---- combine 'mean': the same pipeline over the pooled image of skyemb_token_mean_pool --------------------------------------------------
-extern "C" int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
-                                                          const float *xn, const void *tail, const float *rowp, int64_t N, int P, int D,
-                                                          int k, int combine, float eps, int64_t idx_offset, const float *thr0, void *ws,
-                                                          int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, const void *pooled16,
-                                                          void *stream) {
-    SKY_CHECK_ARG(pooled16, "skyemb_cosine_topk_tokens_mean_prefiltered: null argument");
-    const MeanOperands mo = {pooled16, tail, rowp};
-    return topk_tokens_prefiltered("skyemb_cosine_topk_tokens_mean_prefiltered", tw, qn, Q, bank16, dtype, xn, tail, rowp, N, P, D, k, combine,
-                                   eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream, nullptr, 0, 0, 0, &mo);
+extern "C" int skyemb_cosine_topk_tokens_prefiltered_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                         const void *tail, const float *rowp_sel, const int *tiles, int n_live, int last_live,
+                                                         int direct_end, int64_t N, int P, int D, int k, int combine, float eps,
+                                                         int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                         int64_t *out_i, int *redo, void *stream) {
+    return skyemb_cosine_topk_tokens_prefiltered_top_sel(tw, qn, Q, bank16, dtype, xn, tail, rowp_sel, tiles, n_live, last_live, direct_end, N, P,
+                                                         D, k, combine, 0, eps, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// (tail and rowp are those of skyemb_token_mean_pool: stage 1's operands are the pooled image's)
+extern "C" int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                          const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
+                                                          float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                          float *out_s, int64_t *out_i, int *redo, const void *pooled16, void *stream) {
+    return search(request(SKYEMB_PF_TOKENS_MEAN, bank_of(dtype), Q, N, P, D, k, combine, 0, eps, thr0),
+                  {tw, qn, nullptr, xn, bank16, dtype, tail, pooled16, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream});
 }

@@ -738,6 +738,19 @@ def cosine_topk_prefiltered_sel(tw, qn, bank, xn, bank16, tail, prepared, k, eps
     return ws
 
 
+def prefilter_plan(kind, bank, Q, N, D, k, P=1, combine=0, top_t=0, thr0=False, n_live=None, last_live=0, direct_sel=0, lo=-1, eps=1e-6):
+    """The launch plan of the two-stage search entry point serving this call, as a `_lib.PrefilterPlan`; touches no device.  kind:
+    `_lib.PF_ROWS` / `PF_TOKENS` / `PF_TOKENS_MEAN`; bank: `_lib.PF_BANK_*`; N: rows, images on the token routes; n_live (None: no
+    selection), last_live, direct_sel: the selection as the `_sel` entries take it; lo: 0, 1, `_lib.PF_LO_UNSET`, or -1 = what
+    SKYEMB_PREFILTER_LO says now.  Raises SkyembError with the entry point's own text where it would refuse."""
+    from ._lib import PrefilterPlan, PrefilterRequest
+    r = PrefilterRequest(kind, bank, Q, P, D, k, N, combine, top_t, int(bool(thr0)), int(n_live is not None), n_live or 0, last_live,
+                         direct_sel, lo, eps)
+    p = PrefilterPlan()
+    check(lib().skyemb_prefilter_plan(r, p), "skyemb_prefilter_plan")
+    return p
+
+
 def topk_merge(in_s, in_i, Q, nlists, k, out_s, out_i, ws=None):
     """ws: optional int32 [Q] scratch enabling the gather + block-sort path for many short lists."""
     check(lib().skyemb_topk_merge(_p(in_s), _p(in_i), Q, nlists, k, _p(out_s), _p(out_i), _p(ws), _stream()),

@@ -173,7 +173,7 @@ class TokenSearch:
     FILL32 is a candidate some slice appended; those whose image lies in the LAST slice's range are that slice's complete set,
     the others are what is left of an earlier slice's."""
     def __init__(self, ops, fmt, tw, qn, xw, xn, k, combine, thr0=None, flags=None, idx_offset=0):
-        import bisect
+        from tests import token_prefilter_select_reference as tps
         L = ops.lib()
         Q, D = tw.shape
         N, P = xw.shape[:2]
@@ -198,7 +198,7 @@ class TokenSearch:
             words = dev(np.packbits(bits, bitorder="little").view(np.uint32).view(np.int32))
             rowp_sel, tiles, n_live, last_live, cum = ops.token_prefilter_select_prepare(words, N, P, rowp.t(torch.float32, -1, 4))
             self.tiles, self.cum, self.last_live = tiles.cpu().numpy()[:n_live], cum, last_live
-            self.direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)     # search.py's rule
+            self.direct_end = tps.direct_end(cum, n_live, k)            # search.py's rule
             rc = L.skyemb_cosine_topk_tokens_prefiltered_sel(ptr(tw_d), ptr(qn_d), Q, ptr(bank), code, ptr(xn_d), tail, ptr(rowp_sel),
                                                              ptr(tiles), n_live, last_live, self.direct_end, N, P, D, k, comb, EPS, idx_offset,
                                                              ptr(thr_d), ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(), stream())

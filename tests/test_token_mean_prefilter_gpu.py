@@ -10,6 +10,7 @@ from sky_embeddings_amd import ops, search
 from tests import prefilter_gpu_harness as h
 from tests import prefilter_stage1_reference as sr
 from tests import token_mean_prefilter_reference as mr
+from tests import token_prefilter_stage_reference as stage
 from tests import token_search_reference as tsr
 
 pytestmark = pytest.mark.gpu
@@ -66,7 +67,7 @@ def no_staging_list_fills(bank, q, w, fmt, k, lo=True, eps=1e-6, contract=None):
         rq = search._token_request("cosine_topk_tokens", q, tb, k, "mean", search._COSINE, None, None, None)
         floor = search._bootstrap_floor(rq, tw, qn, eps).cpu().numpy()
     else:
-        first = max(-(-96 * k // 256), N // 256 // 128, 1) * 256          # images of the direct-append slice
+        first = stage.token_schedule(N, 1, k)["direct_end"] * 256         # images of the direct-append slice (rows = images)
         floor = -np.sort(-contract[:, :first], axis=1)[:, k - 1]
     pref = mr.pool(bank.float().cpu().numpy(), tb.norms.cpu().numpy(), fmt)
     qref = mr.query_side(tw.cpu().numpy(), qn.cpu().numpy(), fmt, D, lo, eps)
