@@ -124,7 +124,9 @@ int skyemb_gemm(const skyemb_gemm_args *args, void *stream);
  * block fill the chip together: no split-K, no reduce launch).
  * skyemb_gemm_group_plan validates the problems and fills a HOST blob of skyemb_gemm_group_blob_bytes(n) bytes; the
  * caller copies it to device memory once (pointers inside are fixed) and replays skyemb_gemm_group_launch.
- * plan returns -1 (with skyemb_last_error set) when a problem is outside the subset: launch them singly then. */
+ * plan returns -1 (with skyemb_last_error set) when a problem is outside the subset: launch them singly then.
+ * A plan that returns 0 names a launch that is built: skyemb_gemm_group_launch of its blob and info does not refuse the group for its
+ * tile, class mask or format (a KC.RC + RC.RC mix on a tile without the mixed instance, 9128128, is refused by the plan). */
 typedef struct skyemb_gemm_group_info {
     int32_t total_blocks; /* grid size of the launch                                                          */
     int32_t tile;         /* tile code the plan chose (BM * 1000 + BN): 64064, 128064, 128128 or 256256        */

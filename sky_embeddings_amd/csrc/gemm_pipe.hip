@@ -1345,6 +1345,11 @@ extern "C" int skyemb_gemm_group_plan(const skyemb_gemm_args *args, int n, int t
         skyemb_set_error("skyemb_gemm_group_plan: operand-layout mix %d is not built (single class, or KC.RC with RC.RC)", mask);
         return -1;
     }
+    // (a plan that answers 0 launches: the mixed instance exists on the tiles with MIXED only, so refuse here, not in the launch)
+    if (mask == 6 && !(d->forms & MIXED)) {
+        skyemb_set_error("skyemb_gemm_group_plan: tile %d is not built for groups that mix KC.RC with RC.RC problems (class mask %d)", tile, mask);
+        return -1;
+    }
     h->starts[n] = start;
     h->n = n;
     h->total = start;

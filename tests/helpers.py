@@ -44,6 +44,75 @@ def load_simmim_case(name):
     return z, cfg, state, torch.from_numpy(z["imgs"].copy()), torch.from_numpy(z["pixel_mask"].copy()), ra_dec
 
 
+# ---- guarded device buffers of the per-element GEMM tests (test_gemm_elementwise_gpu.py, test_gemm_group_elementwise_gpu.py)
+DEV = "cuda"
+SENT = 12.5
+NAN = float("nan")
+
+
+def guarded_in(x, dtype, ld):
+    """2-D x as a view into a NaN buffer [rows + 2, ld]: a NaN row before and after, NaN columns beyond x's."""
+    R, C = x.shape
+    buf = torch.full((R + 2, ld), NAN, device=DEV, dtype=dtype)
+    v = buf[1:R + 1, :C]
+    v.copy_(x.to(DEV, dtype))
+    return v
+
+
+def guarded_vec(x, dtype, fill, pad):
+    buf = torch.full((x.numel() + 2 * pad,), fill, device=DEV, dtype=dtype)
+    v = buf[pad:pad + x.numel()]
+    v.copy_(x.to(DEV, dtype))
+    return v
+
+
+class Out:
+    """An output view [R, C] (NaN) inside a sentinel buffer [R + 2, ld]."""
+
+    def __init__(self, R, C, dtype, ld):
+        self.buf = torch.full((R + 2, ld), SENT, device=DEV, dtype=dtype)
+        self.view = self.buf[1:R + 1, :C]
+        self.view.fill_(NAN)
+
+    def outside_intact(self):
+        b = self.buf.clone()
+        b[1:-1, :self.view.shape[1]] = SENT
+        return bool((b == SENT).all())
+
+    def bits(self):
+        return self.view.contiguous().view(torch.int32 if self.view.dtype == torch.float32 else torch.int16)
+
+
+def gemm_device_inputs(c, t):
+    """The operands gemm_reference.inputs(c) made, on the device behind guards: {"A", "B", "kw": the epilogue's arguments of
+    ops.gemm / ops.gemm_args}.  A and B are views with ld beyond the contiguous extent into NaN buffers; the same for resid, aux,
+    table and bias; tab_row and dst_row have guard entries around them that name a valid but wrong row whose row is NaN."""
+    from tests import gemm_reference as gr
+    ld = gr.lds(c)
+    Mo = gr.out_rows(c)
+    d = {"A": guarded_in(t["A"] if c.al == gr.KC else t["A"].T, c.dtype, ld["lda"]),
+         "B": guarded_in(t["B"] if c.bl == gr.KC else t["B"].T, c.dtype, ld["ldb"])}
+    kw = {}
+    if "bias" in t:
+        kw["bias"] = guarded_vec(t["bias"], torch.float32, NAN, 4)
+    if "table" in t:
+        table = torch.cat([t["table"], torch.full((1, c.N), NAN)])           # the last row: NaN, named by tab_row's guard entries
+        kw.update(table=guarded_in(table, torch.float32, ld["ldt"]), ldt=ld["ldt"],
+                  tab_row=guarded_vec(t["tab_row"], torch.int32, gr.TABLE_ROWS, 1))
+    resid = t.get("resid")
+    if "dst_row" in t:
+        unmapped = sorted(set(range(Mo)) - set(t["dst_row"].tolist()))
+        kw["dst_row"] = guarded_vec(t["dst_row"], torch.int32, unmapped[0], 1)   # guard entries: an unmapped row (its residual row is NaN)
+        resid = resid.clone()
+        resid[unmapped] = NAN                                                # (a row of dst_row = -1 may request row 0 and drops it)
+    if resid is not None:
+        kw.update(resid=guarded_in(resid, torch.float32, ld["ldr"]), ldr=ld["ldr"])
+    if "aux" in t:
+        kw.update(aux=guarded_in(t["aux"], c.dtype, ld["ldaux"]), ldaux=ld["ldaux"])
+    d["kw"] = kw
+    return d
+
+
 def record_parity(name, values):
     """Achieved errors of a parity test, merged into gpurun_out/parity_errors.json (scratch; `tests/parity_report.py` copies
     the file into profiles/ after a GPU run) and printed: the bars in the tests are set at 2x these figures."""

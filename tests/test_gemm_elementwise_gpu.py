@@ -30,45 +30,10 @@ pytestmark = pytest.mark.gpu
 
 from tests import gemm_reference as gr
 from tests.gemm_reference import CASES, F16, F32, KC, RC, cid, has
-from tests.helpers import record_parity
+from tests.helpers import DEV, NAN, Out, record_parity
+from tests.helpers import gemm_device_inputs as device_inputs
 
-DEV = "cuda"
-SENT = 12.5
 BIAS = 0.1
-NAN = float("nan")
-
-
-def guarded_in(x, dtype, ld):
-    """2-D x as a view into a NaN buffer [rows + 2, ld]: a NaN row before and after, NaN columns beyond x's."""
-    R, C = x.shape
-    buf = torch.full((R + 2, ld), NAN, device=DEV, dtype=dtype)
-    v = buf[1:R + 1, :C]
-    v.copy_(x.to(DEV, dtype))
-    return v
-
-
-def guarded_vec(x, dtype, fill, pad):
-    buf = torch.full((x.numel() + 2 * pad,), fill, device=DEV, dtype=dtype)
-    v = buf[pad:pad + x.numel()]
-    v.copy_(x.to(DEV, dtype))
-    return v
-
-
-class Out:
-    """An output view [R, C] (NaN) inside a sentinel buffer [R + 2, ld]."""
-
-    def __init__(self, R, C, dtype, ld):
-        self.buf = torch.full((R + 2, ld), SENT, device=DEV, dtype=dtype)
-        self.view = self.buf[1:R + 1, :C]
-        self.view.fill_(NAN)
-
-    def outside_intact(self):
-        b = self.buf.clone()
-        b[1:-1, :self.view.shape[1]] = SENT
-        return bool((b == SENT).all())
-
-    def bits(self):
-        return self.view.contiguous().view(torch.int32 if self.view.dtype == F32 else torch.int16)
 
 
 def launch(ops, c, t, dev_in):
@@ -94,31 +59,6 @@ def launch(ops, c, t, dev_in):
     ops.gemm(dev_in["A"], dev_in["B"], M=c.M, N=c.N, K=c.K, a_layout=c.al, b_layout=c.bl, lda=ld["lda"], ldb=ld["ldb"],
              alpha=t["alpha"], act=act, tile=c.tile, split_k=c.split, **dev_in["kw"], **kw)
     return outs
-
-
-def device_inputs(c, t):
-    ld = gr.lds(c)
-    Mo = gr.out_rows(c)
-    d = {"A": guarded_in(t["A"] if c.al == KC else t["A"].T, c.dtype, ld["lda"]),
-         "B": guarded_in(t["B"] if c.bl == KC else t["B"].T, c.dtype, ld["ldb"])}
-    kw = {}
-    if "bias" in t:
-        kw["bias"] = guarded_vec(t["bias"], F32, NAN, 4)
-    if "table" in t:
-        table = torch.cat([t["table"], torch.full((1, c.N), NAN)])           # the last row: NaN, named by tab_row's guard entries
-        kw.update(table=guarded_in(table, F32, ld["ldt"]), ldt=ld["ldt"], tab_row=guarded_vec(t["tab_row"], torch.int32, gr.TABLE_ROWS, 1))
-    resid = t.get("resid")
-    if "dst_row" in t:
-        unmapped = sorted(set(range(Mo)) - set(t["dst_row"].tolist()))
-        kw["dst_row"] = guarded_vec(t["dst_row"], torch.int32, unmapped[0], 1)   # guard entries: an unmapped row (its residual row is NaN)
-        resid = resid.clone()
-        resid[unmapped] = NAN                                                # (a row of dst_row = -1 may request row 0 and drops it)
-    if resid is not None:
-        kw.update(resid=guarded_in(resid, F32, ld["ldr"]), ldr=ld["ldr"])
-    if "aux" in t:
-        kw.update(aux=guarded_in(t["aux"], c.dtype, ld["ldaux"]), ldaux=ld["ldaux"])
-    d["kw"] = kw
-    return d
 
 
 def check_case(ops, c, worst=None):
