@@ -447,12 +447,22 @@ def bank16_prepare(bank, xn):
     return bank16, rowp
 
 
+def _workspace(ws, need, device):
+    """``ws`` when it holds ``need`` bytes, else a fresh workspace: what every two-stage wrapper returns for the next call."""
+    return ws if ws is not None and ws.numel() >= need else torch.empty(need, device=device, dtype=torch.uint8)
+
+
+def _check_aligned16(bank, who, what, verb="must start"):
+    """ValueError, in the words of ``who``, unless the 16-bit ``bank`` (named ``what`` in the text) starts 16-byte aligned."""
+    if bank.data_ptr() % 16:
+        raise ValueError(f"{who}: {what} bank {verb} 16-byte aligned (the search reads it by 16-byte LDS-DMA); this tensor starts at "
+                         "an odd offset of its storage -- clone() it")
+
+
 def cosine_topk_prefiltered(tw, qn, bank, xn, bank16, rowp, k, eps, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
     Q, D = tw.shape
     N = bank.shape[0]
-    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_topk_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_prefiltered(_p(tw), _p(qn), Q, _p(bank), _p(xn), _p(bank16), _p(rowp), N, D, k, eps, idx_offset,
                                                _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
           "skyemb_cosine_topk_prefiltered")
@@ -470,9 +480,7 @@ def bank16_rowp_lp(bank16, xn):
     N % 256 rows (None when there are none), are all the memory it takes.  ValueError when the bank is not 16-byte aligned."""
     N, D = bank16.shape
     assert bank16.dtype == torch.float16 and bank16.is_contiguous()
-    if bank16.data_ptr() % 16:
-        raise ValueError("bank16_rowp_lp: the fp16 bank must be 16-byte aligned (the search reads it by 16-byte LDS-DMA); "
-                         "this tensor starts at an odd offset of its storage -- clone() it")
+    _check_aligned16(bank16, "bank16_rowp_lp", "the fp16", "must be")
     rows = lib().skyemb_bank16_rowp_rows(N)
     rowp = torch.empty(rows, 4, device=bank16.device, dtype=torch.float32)
     tail = torch.empty(rows - N // 256 * 256, D, device=bank16.device, dtype=torch.float16) if rows != N else None
@@ -484,9 +492,7 @@ def cosine_topk_prefiltered_lp(tw, qn, bank16, xn, tail, rowp, k, eps, idx_offse
     """``cosine_topk_prefiltered`` over a resident fp16 bank and the (tail, rowp) of ``bank16_rowp_lp``."""
     Q, D = tw.shape
     N = bank16.shape[0]
-    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_topk_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_prefiltered_lp(_p(tw), _p(qn), Q, _p(bank16), _p(xn), _p(tail), _p(rowp), N, D, k, eps, idx_offset,
                                                   _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
           "skyemb_cosine_topk_prefiltered_lp")
@@ -512,9 +518,7 @@ def resident_rowp(bank16, xn):
     N, D = bank16.shape
     code = resident_dtype_code(bank16.dtype, "resident_rowp")
     assert bank16.is_contiguous()
-    if bank16.data_ptr() % 16:
-        raise ValueError("resident_rowp: the 16-bit bank must be 16-byte aligned (the search reads it by 16-byte LDS-DMA); "
-                         "this tensor starts at an odd offset of its storage -- clone() it")
+    _check_aligned16(bank16, "resident_rowp", "the 16-bit", "must be")
     rows = lib().skyemb_bank16_rowp_rows(N)
     rowp = torch.empty(rows, 4, device=bank16.device, dtype=torch.float32)
     tail = torch.empty(rows - N // 256 * 256, D, device=bank16.device, dtype=bank16.dtype) if rows != N else None
@@ -527,9 +531,7 @@ def cosine_topk_prefiltered_resident(tw, qn, bank16, xn, tail, rowp, k, eps, idx
     Q, D = tw.shape
     N = bank16.shape[0]
     code = resident_dtype_code(bank16.dtype, "cosine_topk_prefiltered_resident")
-    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_topk_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_prefiltered_resident(_p(tw), _p(qn), Q, _p(bank16), code, _p(xn), _p(tail), _p(rowp), N, D, k, eps,
                                                         idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
                                                         _stream()), "skyemb_cosine_topk_prefiltered_resident")
@@ -557,9 +559,7 @@ def cosine_topk_tokens_prefiltered(tw, qn, tokens, xn, tail, rowp, k, combine, e
     Q, D = tw.shape
     N, P = tokens.shape[:2]
     code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered")
-    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_tokens_prefiltered(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp), N, P, D, k, combine,
                                                       eps, idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
                                                       _stream()), "skyemb_cosine_topk_tokens_prefiltered")
@@ -599,9 +599,7 @@ def cosine_topk_tokens_mean_prefiltered(tw, qn, tokens, xn, pooled, tail, rowp, 
     Q, D = tw.shape
     N, P = tokens.shape[:2]
     code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_mean_prefiltered")
-    need = lib().skyemb_token_mean_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_token_mean_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_tokens_mean_prefiltered(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp), N, P, D, k,
                                                            COMBINE_CODES['mean'], eps, idx_offset, _p(thr0), _p(ws), ws.numel(),
                                                            _p(out_s), _p(out_i), _p(redo), _p(pooled), _stream()),
@@ -635,9 +633,7 @@ def cosine_topk_tokens_prefiltered_sel(tw, qn, tokens, xn, tail, prepared, direc
     N, P = tokens.shape[:2]
     rowp_sel, tiles, n_live, last_live = prepared[:4]
     code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered_sel")
-    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_tokens_prefiltered_sel(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp_sel), _p(tiles),
                                                           n_live, last_live, direct_end, N, P, D, k, combine, eps, idx_offset, _p(thr0),
                                                           _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
@@ -671,9 +667,7 @@ def cosine_topk_tokens_prefiltered_top(tw, qn, tokens, xn, tail, rowp, k, combin
     Q, D = tw.shape
     N, P = tokens.shape[:2]
     code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered_top")
-    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_tokens_prefiltered_top(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp), N, P, D, k, combine,
                                                           top_t, eps, idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i),
                                                           _p(redo), _stream()), "skyemb_cosine_topk_tokens_prefiltered_top")
@@ -687,9 +681,7 @@ def cosine_topk_tokens_prefiltered_top_sel(tw, qn, tokens, xn, tail, prepared, d
     N, P = tokens.shape[:2]
     rowp_sel, tiles, n_live, last_live = prepared[:4]
     code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_prefiltered_top_sel")
-    need = lib().skyemb_token_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), tw.device)
     check(lib().skyemb_cosine_topk_tokens_prefiltered_top_sel(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail), _p(rowp_sel), _p(tiles),
                                                               n_live, last_live, direct_end, N, P, D, k, combine, top_t, eps, idx_offset,
                                                               _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
@@ -719,22 +711,15 @@ def cosine_topk_prefiltered_sel(tw, qn, bank, xn, bank16, tail, prepared, k, eps
     Q, D = tw.shape
     rowp_sel, tiles, n_live, last_live = prepared
     N = xn.shape[0]
-    need = lib().skyemb_topk_prefilter_ws_bytes(Q, D, k)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=tw.device, dtype=torch.uint8)
-    if bank is not None:
-        check(lib().skyemb_cosine_topk_prefiltered_sel(_p(tw), _p(qn), Q, _p(bank), _p(xn), _p(bank16), _p(rowp_sel), _p(tiles), n_live,
-                                                       last_live, N, D, k, eps, idx_offset, _p(ws), ws.numel(), _p(out_s), _p(out_i),
-                                                       _p(redo), _stream()), "skyemb_cosine_topk_prefiltered_sel")
+    ws = _workspace(ws, lib().skyemb_topk_prefilter_ws_bytes(Q, D, k), tw.device)
+    if bank is not None:                                   # the entry point and its arguments between Q and the masked row constants
+        entry, lead = "skyemb_cosine_topk_prefiltered_sel", (_p(bank), _p(xn), _p(bank16))
     elif bank16.dtype == torch.bfloat16:
-        check(lib().skyemb_cosine_topk_prefiltered_resident_sel(_p(tw), _p(qn), Q, _p(bank16), dtype_code(bank16.dtype), _p(xn), _p(tail),
-                                                                _p(rowp_sel), _p(tiles), n_live, last_live, N, D, k, eps, idx_offset,
-                                                                _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
-              "skyemb_cosine_topk_prefiltered_resident_sel")
+        entry, lead = "skyemb_cosine_topk_prefiltered_resident_sel", (_p(bank16), dtype_code(bank16.dtype), _p(xn), _p(tail))
     else:
-        check(lib().skyemb_cosine_topk_prefiltered_lp_sel(_p(tw), _p(qn), Q, _p(bank16), _p(xn), _p(tail), _p(rowp_sel), _p(tiles), n_live,
-                                                          last_live, N, D, k, eps, idx_offset, _p(ws), ws.numel(), _p(out_s), _p(out_i),
-                                                          _p(redo), _stream()), "skyemb_cosine_topk_prefiltered_lp_sel")
+        entry, lead = "skyemb_cosine_topk_prefiltered_lp_sel", (_p(bank16), _p(xn), _p(tail))
+    check(getattr(lib(), entry)(_p(tw), _p(qn), Q, *lead, _p(rowp_sel), _p(tiles), n_live, last_live, N, D, k, eps, idx_offset, _p(ws),
+                                ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()), entry)
     return ws
 
 

@@ -19,6 +19,9 @@ import torch
 from . import ops
 
 
+_AN_LP = {torch.float16: "an fp16", torch.bfloat16: "an bf16"}     # a 16-bit bank as the alignment refusals name it
+
+
 def _sample_index(images: int, n: int, device):
     """The strided sample every pruning floor draws: ``images`` of n rows / images / selected images, n // images apart."""
     return torch.arange(images, device=device) * (n // images)
@@ -66,9 +69,8 @@ class PreparedBank:
         return self
 
     def _init(self, bank, weights, idx_offset):
-        if bank.dtype in ops.LP_DTYPES and bank.data_ptr() % 16:
-            raise ValueError(f"PreparedBank: an {'fp16' if bank.dtype == torch.float16 else 'bf16'} bank must start 16-byte aligned "
-                             "(the search reads it by 16-byte LDS-DMA); this tensor starts at an odd offset of its storage -- clone() it")
+        if bank.dtype in ops.LP_DTYPES:
+            ops._check_aligned16(bank, "PreparedBank", _AN_LP[bank.dtype])
         assert bank.is_cuda and bank.dtype in ops.BANK_DTYPES and bank.is_contiguous() and bank.dim() == 2
         self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self._sample = None
@@ -124,6 +126,26 @@ class PreparedBank:
                 self.tail_tile, rowp = ops.resident_rowp(self.bank, self.norms)
                 self._half = (self.bank, rowp)
         return self._half
+
+    def two_stage(self, tw, qn, k, eps, out_s, out_i, redo, prepared=None):
+        """Launch the two-stage search (csrc/topk_prefilter.hip) of this bank's dtype into (out_s, out_i, redo) -- under a selection
+        when ``prepared`` is ``Selection.prefilter`` of this bank.  With ``half_image`` the one place that tells the three banks
+        apart on that path."""
+        bank16, rowp = self.half_image()
+        if prepared is not None:
+            ops.cosine_topk_prefiltered_sel(tw, qn, self.bank if self.dtype == torch.float32 else None, self.norms, bank16, self.tail_tile,
+                                            prepared, k, eps, self.idx_offset, out_s, out_i, redo)
+        elif self.dtype == torch.float32:
+            ops.cosine_topk_prefiltered(tw, qn, self.bank, self.norms, bank16, rowp, k, eps, self.idx_offset, out_s, out_i, redo)
+        else:
+            op = ops.cosine_topk_prefiltered_lp if self.dtype == torch.float16 else ops.cosine_topk_prefiltered_resident
+            op(tw, qn, bank16, self.norms, self.tail_tile, rowp, k, eps, self.idx_offset, out_s, out_i, redo)
+
+    def whole_live_tiles(self, prepared):
+        """The live whole 256-row tiles of a prepared selection: a 16-bit bank's partial last tile, read from ``tail_tile``, is not
+        one (what SELECT_MIN_LIVE_TILES is compared with)."""
+        n_live, last_live = prepared[2], prepared[3]
+        return n_live - (1 if self.dtype != torch.float32 and self.bank.shape[0] % 256 and last_live else 0)
 
     def sample(self, rows: int):
         """A strided row sample (bank rows + norms) used to derive the pruning floor of a search."""
@@ -205,92 +227,93 @@ def _prefilter_enabled():
     return os.environ.get("SKYEMB_TOPK_PREFILTER", "1") != "0"
 
 
-def _local_topk_prefiltered(tw, qn, pb: "PreparedBank", k, eps, q=None, prune=True):
-    """Two-stage exact top-k of this rank's shard (csrc/topk_prefilter.hip); queries the second stage could not certify
-    (redo flags) go through the exact fp32 kernel -- over a resident fp16 / bf16 bank (``q``: the raw queries): through the token
-    search with one token per row, those queries only, on the bank's own norms."""
-    Q = tw.shape[0]
-    dev = tw.device
-    bank16, rowp = pb.half_image()
-    out_s = torch.empty(Q, k, device=dev)
-    out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
-    redo = torch.empty(Q, device=dev, dtype=torch.int32)
-    if pb.dtype == torch.float32:
-        ops.cosine_topk_prefiltered(tw, qn, pb.bank, pb.norms, bank16, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
-    elif pb.dtype == torch.float16:
-        ops.cosine_topk_prefiltered_lp(tw, qn, bank16, pb.norms, pb.tail_tile, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
-    else:
-        ops.cosine_topk_prefiltered_resident(tw, qn, bank16, pb.norms, pb.tail_tile, rowp, k, eps, pb.idx_offset, out_s, out_i, redo)
+def _two_stage(Q, k, device, launch, rerun):
+    """The two-stage driver every route shares: allocate the result and the redo flags, ``launch(out_s, out_i, redo)`` stages 1 + 2,
+    read the flags once, have ``rerun(again)`` -> (scores, indices) search the flagged queries ``again`` (i64, ascending) exactly,
+    copy those rows back.  -> (out_s, out_i, number of queries re-run)."""
+    out_s = torch.empty(Q, k, device=device)
+    out_i = torch.empty(Q, k, device=device, dtype=torch.int64)
+    redo = torch.empty(Q, device=device, dtype=torch.int32)
+    launch(out_s, out_i, redo)
     again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
-    if again.numel() and pb.dtype != torch.float32:
-        s2, i2 = cosine_topk_tokens(q.index_select(0, again), pb._tokens, k, 'min', None, eps, prune=prune)
-        out_s.index_copy_(0, again, s2)
-        out_i.index_copy_(0, again, i2)
-    elif again.numel():
-        tw2, qn2 = tw.index_select(0, again).contiguous(), qn.index_select(0, again).contiguous()
-        thr0 = pruning_floor(tw2, qn2, pb, k, eps)
-        s2, i2 = _local_topk(tw2, qn2, pb.bank, pb.norms, k, eps, pb.idx_offset, thr0)
+    if again.numel():
+        s2, i2 = rerun(again)
         out_s.index_copy_(0, again, s2)
         out_i.index_copy_(0, again, i2)
     return out_s, out_i, int(again.numel())
 
 
+def _gather_merge(out_s, out_i, Q, k, world_size, process_group):
+    """Every rank's [Q, k] lists all-gathered over RCCL -> [Q, world, k] and merged into (out_s, out_i); one rank: as they are."""
+    if world_size > 1:
+        from .distributed import gather_topk
+        gs, gi = gather_topk(out_s, out_i, world_size, process_group)
+        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    return out_s, out_i
+
+
 SELECT_MIN_LIVE_TILES = 8      # fewer live whole 256-row tiles than this: a PreparedBank search under a selection takes the token route
 
 
-def _cosine_topk_selected(queries, pb: "PreparedBank", k, select, eps, process_group, world_size, prune, stats):
-    """``cosine_topk`` over a PreparedBank under a selection (see there): the two-stage path over the live tiles, its uncertified
-    queries -- and a selection of fewer than SELECT_MIN_LIVE_TILES live tiles -- through the token search with one token per row."""
-    # where the two-stage route does not apply the call is refused as it ever was, before anything else is looked at (16 queries or
-    # fewer never take it, whatever the bank)
-    if queries.shape[0] <= 16 or not (_prefilter_enabled() and ops.topk_prefilter_applicable(queries.shape[0], pb.bank.shape[0],
-                                                                                           queries.shape[1], k)):
-        raise ValueError("cosine_topk: select is served by the token search (cosine_topk_tokens with one token per row); pass "
+@dataclasses.dataclass(frozen=True)
+class RowRequest:
+    """One ``cosine_topk`` call as it stands before the first launch: everything ``_row_request`` decides."""
+    route: str                          # 'empty' | 'tokens' | 'exact' | 'prefiltered'
+    Q: int
+    N: int
+    D: int
+    k: int
+    bank: object                        # 'tokens': what cosine_topk_tokens searches; else the PreparedBank (or the flat fp32 tensor)
+    weights: torch.Tensor | None        # 'tokens' over a flat tensor: the caller's; else None (a PreparedBank carries its own)
+    select: object                      # 'tokens': the caller's, as given; else None | the Selection
+    rerun: str | None                   # 'prefiltered': what searches its uncertified queries, 'exact' | 'tokens'
+
+
+def _row_request(who, queries, bank, k, weights, select, world_size=1) -> RowRequest:
+    """Validate a ``cosine_topk`` call and decide its route.  No device work, except that a bool-tensor ``select`` over a PreparedBank
+    is packed into a Selection (one short launch).  Every ValueError of ``cosine_topk`` that is not ``cosine_topk_tokens``'s own is
+    raised here, in this order: [Q, D] weights over anything but a flat tensor; ``select`` over neither a flat tensor nor a
+    PreparedBank.  Then a flat tensor with [Q, D] weights, with ``select`` or of a 16-bit dtype is route 'tokens' (one token per
+    row; ``cosine_topk_tokens`` validates it).  A PreparedBank under ``select``: the two-stage path does not apply (Q <= 16 -- Q = 0
+    and k < 1 included --, the shape, the switch); k > N; the token search's shape rule; the selection.  Any other bank: k < 1;
+    k > N; then Q = 0 is route 'empty', a 16-bit bank off the two-stage path route 'tokens' (its one-token TokenBank), and on it the
+    token search's shape rule (its uncertified queries go there: ``rerun``; an fp32 bank without a selection re-runs them by the
+    exact kernel).  One decision waits for ``Selection.prefilter``'s read-back: the fall of a 'prefiltered' request under a
+    selection to the token route below SELECT_MIN_LIVE_TILES (``cosine_topk``)."""
+    pb = bank if isinstance(bank, PreparedBank) else None
+    flat = isinstance(bank, torch.Tensor) and bank.dim() == 2
+    per_query = isinstance(weights, torch.Tensor) and weights.dim() == 2
+    Q, D = queries.shape
+    if per_query and not flat:
+        raise ValueError(f"{who}: per-query weights [Q, D] are served by the token search (cosine_topk_tokens with one "
+                         "token per row); pass the flat [N, D] tensor, not a PreparedBank")
+    if select is not None and pb is None and not flat:
+        raise ValueError(f"{who}: select needs a flat [N, D] bank tensor")
+    if flat and (per_query or select is not None or bank.dtype in ops.LP_DTYPES):
+        return RowRequest('tokens', Q, bank.shape[0], D, k, bank.unsqueeze(1), weights, select, None)
+    # where the two-stage route does not apply a selection is refused as it ever was, before anything else is looked at (16 queries
+    # or fewer never take it, whatever the bank)
+    if select is not None and (Q <= 16 or not (_prefilter_enabled() and ops.topk_prefilter_applicable(Q, pb.bank.shape[0], D, k))):
+        raise ValueError(f"{who}: select is served by the token search (cosine_topk_tokens with one token per row); pass "
                          "the flat [N, D] tensor, not a PreparedBank -- the prefiltered many-query route takes no selection")
-    q = queries.to(pb.bank.device, torch.float32).contiguous()
-    Q, D = q.shape
-    N = pb.bank.shape[0]
-    assert D == pb.bank.shape[1]
+    rows = bank if pb is None else pb.bank
+    N = rows.shape[0]
+    assert D == rows.shape[1]
+    if select is None and k < 1:
+        raise ValueError(f"{who}: k = {k}")
     if world_size == 1 and k > N:
-        raise ValueError(f"cosine_topk: k = {k} exceeds the {N} rows of the bank")
-    _check_token_shape("cosine_topk", Q, 1, D, k)          # the limits of the route the uncertified queries and small selections take
-    sel = _selection_arg(select, N, "cosine_topk", pb.bank.device)
-    dev = q.device
-    tiles_all = (N + 255) // 256
-    if sel.count == 0:                                      # nothing is eligible: no stage-1 launch
-        out_s = torch.full((Q, k), float("-inf"), device=dev)
-        out_i = torch.full((Q, k), -1, device=dev, dtype=torch.int64)
-        if stats is not None:
-            stats.update(path="prefiltered", redone=0, selected=0, tiles=(0, tiles_all))
-    else:
-        prepared = sel.prefilter(pb)
-        n_live, last_live = prepared[2], prepared[3]
-        tail_live = 1 if (pb.dtype != torch.float32 and N % 256 and last_live) else 0
-        if n_live - tail_live < SELECT_MIN_LIVE_TILES:
-            st = {}
-            out = cosine_topk_tokens(q, pb.row_tokens(), k, 'min', None, eps, process_group, world_size, prune, st, select=sel)
-            if stats is not None:
-                stats.update(st, selected=sel.count, tiles=(n_live, tiles_all))
-            return out
-        tw, qn = prepare_queries(q, pb.weights)
-        bank16 = pb.half_image()[0]
-        out_s = torch.empty(Q, k, device=dev)
-        out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
-        redo = torch.empty(Q, device=dev, dtype=torch.int32)
-        ops.cosine_topk_prefiltered_sel(tw, qn, pb.bank if pb.dtype == torch.float32 else None, pb.norms, bank16, pb.tail_tile, prepared,
-                                        k, eps, pb.idx_offset, out_s, out_i, redo)
-        again = torch.nonzero(redo).squeeze(1)             # host sync: a handful of bytes per search
-        if again.numel():                                   # the exact fp32 kernel takes no selection: the token search, both dtypes
-            s2, i2 = cosine_topk_tokens(q.index_select(0, again), pb.row_tokens(), k, 'min', None, eps, prune=prune, select=sel)
-            out_s.index_copy_(0, again, s2)
-            out_i.index_copy_(0, again, i2)
-        if stats is not None:
-            stats.update(path="prefiltered", redone=int(again.numel()), selected=sel.count, tiles=(n_live, tiles_all))
-    if world_size > 1:
-        from .distributed import gather_topk
-        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
-        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
-    return out_s, out_i
+        raise ValueError(f"{who}: k = {k} exceeds the {N} rows of the bank")
+    lp = rows.dtype != torch.float32
+    if select is not None:
+        _check_token_shape(who, Q, 1, D, k)                # the limits of the route the uncertified queries and small selections take
+        return RowRequest('prefiltered', Q, N, D, k, bank, None, _selection_arg(select, N, who, rows.device), 'tokens')
+    if Q == 0:                                             # nothing to search for (an empty target list): empty result, no launch
+        return RowRequest('empty', Q, N, D, k, bank, None, None, None)
+    if not (_prefilter_enabled() and ops.topk_prefilter_applicable(Q, N, D, k)):
+        return RowRequest('tokens', Q, N, D, k, pb._tokens, None, None, None) if lp else RowRequest('exact', Q, N, D, k, bank, None, None, None)
+    if lp:
+        _check_token_shape(who, Q, 1, D, k)                # the limits of the route its uncertified queries take
+    return RowRequest('prefiltered', Q, N, D, k, bank, None, None, 'tokens' if lp else 'exact')
 
 
 def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | None = None, eps: float = 1e-6,
@@ -341,50 +364,52 @@ def cosine_topk(queries: torch.Tensor, bank, k: int, weights: torch.Tensor | Non
     ``weights`` [Q, D] (one row per query; [D] or None: nothing above changes): a flat [N,D] bank is served the same way, as
     ``cosine_topk_tokens`` with per-query weights and one token per row (``stats['path'] == 'tokens'``); a PreparedBank is a
     ValueError (per-query weights on the two-stage path are out of scope), with or without ``select``."""
-    flat = isinstance(bank, torch.Tensor) and bank.dim() == 2
-    per_query = isinstance(weights, torch.Tensor) and weights.dim() == 2
-    if per_query and not flat:
-        raise ValueError("cosine_topk: per-query weights [Q, D] are served by the token search (cosine_topk_tokens with one "
-                         "token per row); pass the flat [N, D] tensor, not a PreparedBank")
-    if select is not None and not per_query:
-        if isinstance(bank, PreparedBank):
-            return _cosine_topk_selected(queries, bank, k, select, eps, process_group, world_size, prune, stats)
-        if not flat:
-            raise ValueError("cosine_topk: select needs a flat [N, D] bank tensor")
-    if per_query or select is not None or (flat and bank.dtype in ops.LP_DTYPES):     # served by the token search, one token per row
-        return cosine_topk_tokens(queries, bank.unsqueeze(1), k, 'min', weights, eps, process_group, world_size, prune, stats,
-                                  select=select)
-    pb = bank if isinstance(bank, PreparedBank) else PreparedBank(bank, weights)
-    q = queries.to(pb.bank.device, torch.float32).contiguous()
-    Q, D = q.shape
-    N = pb.bank.shape[0]
-    assert D == pb.bank.shape[1]
-    if k < 1:
-        raise ValueError(f"cosine_topk: k = {k}")
-    if world_size == 1 and k > N:
-        raise ValueError(f"cosine_topk: k = {k} exceeds the {N} rows of the bank")
-    if Q == 0:                                      # nothing to search for (an empty target list): empty result, no launch
-        return (torch.empty(0, k, device=q.device), torch.empty(0, k, device=q.device, dtype=torch.int64))
-    two_stage = _prefilter_enabled() and ops.topk_prefilter_applicable(Q, N, D, k)
-    if pb.dtype != torch.float32:                   # a resident fp16 / bf16 bank: the two-stage path on its rows, or the token search
-        if not two_stage:
-            return cosine_topk_tokens(q, pb._tokens, k, 'min', None, eps, process_group, world_size, prune, stats)
-        _check_token_shape("cosine_topk", Q, 1, D, k)      # the limits of the route its uncertified queries take
+    if not isinstance(bank, PreparedBank) and select is None and not (isinstance(weights, torch.Tensor) and weights.dim() == 2) \
+            and not (isinstance(bank, torch.Tensor) and bank.dim() == 2 and bank.dtype in ops.LP_DTYPES):
+        # an fp32 tensor searched on its own is a PreparedBank from here on.  Built before the request is validated, as it ever
+        # was: the norm pass precedes even a refusal of k
+        bank = PreparedBank(bank, weights)
+    rq = _row_request("cosine_topk", queries, bank, k, weights, select, world_size)
+    if rq.route == 'tokens':                               # served by the token search, one token per row
+        return cosine_topk_tokens(queries, rq.bank, k, 'min', rq.weights, eps, process_group, world_size, prune, stats, select=rq.select)
+    pb, sel, Q, dev, prepared = rq.bank, rq.select, rq.Q, rq.bank.bank.device, None
+    if rq.route == 'empty':
+        return torch.empty(0, k, device=dev), torch.empty(0, k, device=dev, dtype=torch.int64)
+    q = queries.to(dev, torch.float32).contiguous()
+    if sel is not None:
+        tiles_all = (rq.N + 255) // 256
+        if sel.count == 0:                                 # nothing is eligible: no stage-1 launch
+            if stats is not None:
+                stats.update(path="prefiltered", redone=0, selected=0, tiles=(0, tiles_all))
+            return _gather_merge(torch.full((Q, k), float("-inf"), device=dev), torch.full((Q, k), -1, device=dev, dtype=torch.int64), Q, k,
+                                 world_size, process_group)
+        prepared = sel.prefilter(pb)
+        if pb.whole_live_tiles(prepared) < SELECT_MIN_LIVE_TILES:      # the token search serves the whole call, gather included
+            st = {}
+            out = cosine_topk_tokens(q, pb.row_tokens(), k, 'min', None, eps, process_group, world_size, prune, st, select=sel)
+            if stats is not None:
+                stats.update(st, selected=sel.count, tiles=(prepared[2], tiles_all))
+            return out
     tw, qn = prepare_queries(q, pb.weights)
-    if two_stage:
-        out_s, out_i, n_redo = _local_topk_prefiltered(tw, qn, pb, k, eps, q, prune)
-        if stats is not None:
-            stats.update(path="prefiltered", redone=n_redo)
-    else:
+    if rq.route == 'exact':
         thr0 = pruning_floor(tw, qn, pb, k, eps) if prune else None
         out_s, out_i = _local_topk(tw, qn, pb.bank, pb.norms, k, eps, pb.idx_offset, thr0)
-        if stats is not None:
-            stats.update(path="exact", redone=0)
-    if world_size > 1:
-        from .distributed import gather_topk
-        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
-        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
-    return out_s, out_i
+        n_redo = 0
+    else:
+        def rerun_exact(again):                            # the exact fp32 kernel, under a floor of its own whatever ``prune`` says
+            tw2, qn2 = tw.index_select(0, again).contiguous(), qn.index_select(0, again).contiguous()
+            return _local_topk(tw2, qn2, pb.bank, pb.norms, k, eps, pb.idx_offset, pruning_floor(tw2, qn2, pb, k, eps))
+
+        def rerun_tokens(again):                           # the token search with one token per row, under the same selection
+            return cosine_topk_tokens(q.index_select(0, again), pb.row_tokens(), k, 'min', None, eps, prune=prune, select=sel)
+
+        out_s, out_i, n_redo = _two_stage(Q, k, dev, lambda *out: pb.two_stage(tw, qn, k, eps, *out, prepared),
+                                          rerun_exact if rq.rerun == 'exact' else rerun_tokens)
+    if stats is not None:
+        stats.update(path=rq.route, redone=n_redo)
+        if sel is not None:
+            stats.update(selected=sel.count, tiles=(prepared[2], tiles_all))
+    return _gather_merge(out_s, out_i, Q, k, world_size, process_group)
 
 
 def cosine_scores(queries: torch.Tensor, bank, weights: torch.Tensor | None = None, eps: float = 1e-6):
@@ -420,9 +445,8 @@ class TokenBank:
         assert bank.is_cuda and bank.is_contiguous() and bank.dim() == 3
         self.bank, self.idx_offset, self.dtype = bank, int(idx_offset), bank.dtype
         self.norms = torch.empty(bank.shape[0] * bank.shape[1], device=bank.device)
-        self._sample = None
         self._resident = False                             # True: made by TokenBank.resident
-        self._stage1 = self._boot = None                   # (tail tile, rowp) / the bootstrap sample of the two-stage route
+        self._stage1 = None                                # (tail tile, rowp) of the two-stage route
         self._stage1_mean = None                           # (pooled image, its tail tile, rowp) of the route under combine 'mean'
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
@@ -438,9 +462,7 @@ class TokenBank:
         if bank.dim() != 3 or not bank.is_contiguous():
             raise ValueError(f"TokenBank.resident: the bank must be a contiguous [N, P, D] tensor, got shape {tuple(bank.shape)}, "
                              f"strides {tuple(bank.stride())}")
-        if bank.data_ptr() % 16:
-            raise ValueError(f"TokenBank.resident: an {'fp16' if bank.dtype == torch.float16 else 'bf16'} bank must start 16-byte aligned "
-                             "(the search reads it by 16-byte LDS-DMA); this tensor starts at an odd offset of its storage -- clone() it")
+        ops._check_aligned16(bank, "TokenBank.resident", _AN_LP[bank.dtype])
         self = cls(bank, weights, idx_offset)
         self._resident = True
         return self
@@ -469,19 +491,23 @@ class TokenBank:
             ops.weighted_norms(rows, self.weights, self.norms)
         else:
             ops.weighted_norms_lp(rows, self.weights, self.norms)
-        self._sample = None
-        self._stage1 = self._boot = self._stage1_mean = None
+        self._sample = None                                # user -> its sample (see ``sample``)
+        self._stage1 = self._stage1_mean = None
 
-    def sample(self, images: int):
+    def sample(self, images: int, user: str = "floor"):
         """A strided sample of WHOLE images (tokens [S, P, D] in the bank's dtype + the norms of their S * P rows) used to
-        derive the pruning floor of a search."""
+        derive the pruning floor of a search.  One sample is kept per ``user`` -- the grouped route's floor and the two-stage
+        route's bootstrap floor ask for different sizes, and a re-run alternates between them -- until the size or the weights change."""
         N, P, _ = self.bank.shape
         images = min(images, N)
-        if self._sample is None or self._sample[0].shape[0] != images:
+        if self._sample is None:
+            self._sample = {}
+        got = self._sample.get(user)
+        if got is None or got[0].shape[0] != images:
             idx = _sample_index(images, N, self.bank.device)
-            self._sample = (self.bank.index_select(0, idx).contiguous(),
-                            self.norms.view(N, P).index_select(0, idx).contiguous().view(-1))
-        return self._sample
+            got = self._sample[user] = (self.bank.index_select(0, idx).contiguous(),
+                                        self.norms.view(N, P).index_select(0, idx).contiguous().view(-1))
+        return got
 
 
 class Selection:
@@ -864,10 +890,7 @@ def _topk_tokens(rq: TokenRequest, sc, queries, prune, stats, process_group, wor
             stats.update(top_t=rq.top_t)
         if rq.select is not None:
             stats.update(selected=rq.select.count)
-    if world_size > 1:
-        from .distributed import gather_topk
-        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather of keys -> [Q, world, k]
-        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
+    _gather_merge(out_s, out_i, Q, k, world_size, process_group)        # (of keys)
     return (out_s.neg_() if sc.negate else out_s), out_i                # distances: (-inf, -1) becomes (+inf, -1)
 
 
@@ -946,10 +969,7 @@ def _bootstrap_floor(rq: TokenRequest, tw, qn, eps):
         st, sn = rq.select.sample(tb, S)
     else:
         S = min(rq.N, max(16 * k, 256))
-        if tb._boot is None or tb._boot[0] != S:
-            idx = _sample_index(S, rq.N, tb.bank.device)
-            tb._boot = (S, tb.bank.index_select(0, idx).contiguous(), tb.norms.view(rq.N, rq.P).index_select(0, idx).contiguous().view(-1))
-        _, st, sn = tb._boot
+        st, sn = tb.sample(S, "bootstrap")
     floor = torch.empty(rq.Q, device=tw.device)
     keys = torch.empty(16, S, device=tw.device)
     for lo in range(0, rq.Q, 16):
@@ -968,48 +988,34 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
     q = queries.to(dev, torch.float32).contiguous()
     tw, qn = prepare_queries(q, tb.weights)
     thr0 = _bootstrap_floor(rq, tw, qn, eps)
-    out_s = torch.empty(Q, k, device=dev)
-    out_i = torch.empty(Q, k, device=dev, dtype=torch.int64)
-    redo = torch.empty(Q, device=dev, dtype=torch.int32)
-    if rq.combine == ops.COMBINE_CODES['mean']:            # stage 1 over the pooled image (never under a selection)
-        pooled, tail, rowp = tb.stage1_mean()
-        ops.cosine_topk_tokens_mean_prefiltered(tw, qn, tb.bank, tb.norms, pooled, tail, rowp, k, eps, rq.idx_offset, out_s, out_i, redo, thr0)
-    elif sel is None and rq.top_t != 0:
+    prepared = None if sel is None else sel.token_prefilter(tb)
+    head, eps_off = (tw, qn, tb.bank, tb.norms), (eps, rq.idx_offset)
+
+    def launch(*out):                                      # ``top_t`` follows ``combine`` in the calls that take it
+        if rq.combine == ops.COMBINE_CODES['mean']:        # stage 1 over the pooled image (never under a selection)
+            return ops.cosine_topk_tokens_mean_prefiltered(*head, *tb.stage1_mean(), k, *eps_off, *out, thr0)
         tail, rowp = tb.stage1()
-        ops.cosine_topk_tokens_prefiltered_top(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, rq.top_t, eps, rq.idx_offset, out_s, out_i,
-                                               redo, thr0)
-    elif sel is None:
-        tail, rowp = tb.stage1()
-        ops.cosine_topk_tokens_prefiltered(tw, qn, tb.bank, tb.norms, tail, rowp, k, rq.combine, eps, rq.idx_offset, out_s, out_i, redo, thr0)
-    else:
-        tail, rowp = tb.stage1()
-        prepared = sel.token_prefilter(tb)
+        fold = (rq.combine,) if rq.top_t == 0 else (rq.combine, rq.top_t)
+        if sel is None:
+            op = ops.cosine_topk_tokens_prefiltered if rq.top_t == 0 else ops.cosine_topk_tokens_prefiltered_top
+            return op(*head, tail, rowp, k, *fold, *eps_off, *out, thr0)
         n_live, cum = prepared[2], prepared[4]
         direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)
-        if rq.top_t != 0:
-            ops.cosine_topk_tokens_prefiltered_top_sel(tw, qn, tb.bank, tb.norms, tail, prepared, direct_end, k, rq.combine, rq.top_t, eps,
-                                                       rq.idx_offset, out_s, out_i, redo, thr0)
-        else:
-            ops.cosine_topk_tokens_prefiltered_sel(tw, qn, tb.bank, tb.norms, tail, prepared, direct_end, k, rq.combine, eps, rq.idx_offset,
-                                                   out_s, out_i, redo, thr0)
-    again = torch.nonzero(redo).squeeze(1)                 # host sync: a handful of bytes per search
-    if again.numel():
-        rq2 = dataclasses.replace(rq, Q=int(again.numel()))    # (every other field, top_t and select among them, is carried over)
-        s2, i2 = _topk_tokens(rq2, _CosineScorer.of(rq2, eps), q.index_select(0, again), prune, None, None, 1)
-        out_s.index_copy_(0, again, s2)
-        out_i.index_copy_(0, again, i2)
+        op = ops.cosine_topk_tokens_prefiltered_sel if rq.top_t == 0 else ops.cosine_topk_tokens_prefiltered_top_sel
+        op(*head, tail, prepared, direct_end, k, *fold, *eps_off, *out, thr0)
+
+    def rerun(again):                                      # the grouped route; every other field, top_t and select among them, is carried over
+        rq2 = dataclasses.replace(rq, Q=int(again.numel()))
+        return _topk_tokens(rq2, _CosineScorer.of(rq2, eps), q.index_select(0, again), prune, None, None, 1)
+
+    out_s, out_i, n_redo = _two_stage(Q, k, dev, launch, rerun)
     if stats is not None:
-        stats.update(path="prefiltered", redone=int(again.numel()),
-                     combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+        stats.update(path="prefiltered", redone=n_redo, combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
         if rq.top_t != 0:
             stats.update(top_t=rq.top_t)
         if sel is not None:
-            stats.update(selected=sel.count, tiles=(n_live, (rq.N * rq.P + 255) // 256))
-    if world_size > 1:
-        from .distributed import gather_topk
-        gs, gi = gather_topk(out_s, out_i, world_size, process_group)   # RCCL all-gather -> [Q, world, k]
-        ops.topk_merge(gs, gi, Q, world_size, k, out_s, out_i)
-    return out_s, out_i
+            stats.update(selected=sel.count, tiles=(prepared[2], (rq.N * rq.P + 255) // 256))
+    return _gather_merge(out_s, out_i, Q, k, world_size, process_group)
 
 
 def _score_tokens(rq: TokenRequest, sc, queries):

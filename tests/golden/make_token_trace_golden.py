@@ -10,7 +10,8 @@ Usage (on a machine with a GPU, at the commit whose behaviour is the reference):
 Matrix: the four public functions x bank (fp32 tensor, fp16 tensor, TokenBank with weights of its own) x weights (None, [D], [Q, D]) x select (None,
 bool tensor, Selection; 4096 of the 4608 images, so the floor still engages) x top_t (None, 2) x Q (0, 1, 17) x prune (on, off;
 the two top-k functions), at N = 4608, P = 4, D = 64, k = 1.  Extras: a Selection of 1000 images (the size rule turns the floor
-off) and a bank of N = 64 images (no floor).  ``cases()``, ``Fixture``, ``Recorder`` and ``run_case`` are what the test imports.
+off) and a bank of N = 64 images (no floor).  ``cases()``, ``Fixture``, ``Recorder`` and ``run_case`` are what the test imports; ``Recorder``, ``describe``, ``digest`` and ``Table``
+serve tests/golden/make_row_trace_golden.py too.
 
 File: {"ops": [distinct call records], "traces": [distinct sequences of indices into ops], "digests": [distinct digests],
 "cases": [[trace index, digest index], ...] in the order of ``cases()``} -- sequences and digests repeat a lot, so each is stored
@@ -79,11 +80,15 @@ _SHORT = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16", to
           torch.bool: "bool"}
 
 
-def _describe(x):
+def describe(x):
     if x is None or isinstance(x, (bool, int, float, str)):
         return x
     if isinstance(x, torch.Tensor):                       # (shape, dtype) as one short string: "f32[4608,4,64]"
         return f"{_SHORT[x.dtype]}[{','.join(str(n) for n in x.shape)}]"
+    if isinstance(x, (tuple, list)):                      # a prepared selection and the like: item by item; a long host list: its length
+        if len(x) > 8 and all(isinstance(v, (int, float)) for v in x):
+            return f"list[{len(x)}]"
+        return [describe(v) for v in x]
     return str(x)
 
 
@@ -108,10 +113,19 @@ class Recorder:
 
     def _wrap(self, name, fn):
         def logged(*args, **kw):
-            self.log.append([name, _bound(sig, [_describe(a) for a in args], {key: _describe(v) for key, v in kw.items()})])
+            self.log.append([name, _bound(sig, [describe(a) for a in args], {key: describe(v) for key, v in kw.items()})])
             return fn(*args, **kw)
         sig = inspect.signature(fn)
         return logged
+
+
+def digest(got):
+    """SHA-256 over shape, dtype and bytes of the returned tensor(s)."""
+    h = hashlib.sha256()
+    for x in (got if isinstance(got, tuple) else (got,)):
+        h.update(repr((tuple(x.shape), str(x.dtype))).encode())
+        h.update(x.cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
 
 
 def run_case(fx, rec, case):
@@ -124,14 +138,10 @@ def run_case(fx, rec, case):
     del rec.log[:]
     got = getattr(search, fn)(fx.q[:Qn], fx.banks[bank], **kw)
     trace = list(rec.log) + [["stats", [], dict(sorted(stats.items()))]]        # a last pseudo-call: the stats dict
-    h = hashlib.sha256()
-    for x in (got if isinstance(got, tuple) else (got,)):
-        h.update(repr((tuple(x.shape), str(x.dtype))).encode())
-        h.update(x.cpu().contiguous().numpy().tobytes())
-    return trace, h.hexdigest()
+    return trace, digest(got)
 
 
-class _Table:
+class Table:
     def __init__(self):
         self.items, self.index = [], {}
 
@@ -152,7 +162,7 @@ def main():
         setattr(obj, name, value)
 
     rec = Recorder(put)
-    ops_t, traces_t, digests_t, table = _Table(), _Table(), _Table(), []
+    ops_t, traces_t, digests_t, table = Table(), Table(), Table(), []
     try:
         for case in cases():
             trace, digest = run_case(fx, rec, case)
