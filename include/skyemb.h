@@ -371,6 +371,32 @@ int skyemb_grad_probe(const void *g, int grad_dtype, int64_t n, uint32_t *state,
 int skyemb_adamw_guarded(float *p, void *g, float *m, float *v, void *p_lp, int dtype, int64_t n, int64_t n_decay,
                          const float *hyper, float lr, float bc1, float bc2, float beta1, float beta2, float eps, float wd,
                          float grad_scale, int zero_grad, int grad_dtype, const uint32_t *skip, void *stream);
+/* Multi-tensor AdamW: one launch steps any set of disjoint segments of a flat buffer, each with the scalars of its parameter group
+ * (the downstream predictor: layer-wise lr decay, linear probes, the head's own buffer).  Additive to ABI version 111.  Per segment
+ * the result is bit-identical to skyemb_adamw over that segment with the group's lr, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, beta1,
+ * beta2, eps, wd and n_decay = n (decayed != 0) or 0; nothing outside the segments is written and g is only read.
+ * skyemb_adamw_segments_limits: three compile-time constants -- the most groups of one launch (they travel by value in the
+ *   kernel arguments), the most elements of one work item, and the most workgroups of a launch.
+ * skyemb_adamw_segments_plan: HOST function, no stream and no device: checks the segments (offsets and lengths in ELEMENTS of the
+ *   flat buffer of buffer_n elements: multiples of 4, length > 0, inside the buffer, disjoint in any input order, group in
+ *   [0, n_groups), n_groups in 1 .. max_groups; a refusal names the input index of the offending segment and the value) and writes
+ *   the table the launch walks: (1) the segments sorted by offset, (2) neighbours that touch and share a group joined into one
+ *   run, (3) every run cut from its start into work items of chunk_elems elements, the remainder (if any) last.  The table is
+ *   n_work records of skyemb_adamw_work (16 bytes each, in that order); *need_bytes = 16 n_work.  table_host == NULL: only
+ *   *need_bytes and *n_work are reported; a table of fewer than *need_bytes bytes is refused.
+ * skyemb_adamw_segments: the launch.  p, g, m, v: the fp32 flat buffers; p_lp: the compute-dtype shadow (`dtype` SKYEMB_F32 /
+ *   SKYEMB_BF16 / SKYEMB_F16; required); table_dev: a device copy of the planned table (16-byte aligned); groups: n_groups HOST
+ *   structs, copied into the kernel arguments by the call (the caller may reuse them at once); grad_scale as skyemb_adamw's; skip:
+ *   NULL, or the state of skyemb_grad_probe -- skip[0] != 0: the launch writes nothing, skip[0] == 0: the same bits as NULL.
+ *   Workgroups of 256 threads stride over the work items, min(n_work, max_grid) of them. */
+typedef struct skyemb_adamw_group { float lr, bc1, bc2, beta1, beta2, eps, wd; int32_t decayed; } skyemb_adamw_group;   /* 32 bytes */
+typedef struct skyemb_adamw_segment { int64_t offset, n; int32_t group, reserved; } skyemb_adamw_segment;               /* 24 bytes */
+typedef struct skyemb_adamw_work { int64_t offset; int32_t n, group; } skyemb_adamw_work;       /* 16 bytes: elements [offset, offset + n) */
+int skyemb_adamw_segments_limits(int32_t *max_groups, int32_t *chunk_elems, int32_t *max_grid);
+int skyemb_adamw_segments_plan(const skyemb_adamw_segment *segs, int n_segs, int n_groups, int64_t buffer_n, void *table_host,
+                               int64_t table_bytes, int64_t *need_bytes, int32_t *n_work);
+int skyemb_adamw_segments(float *p, const float *g, float *m, float *v, void *p_lp, int dtype, const void *table_dev, int32_t n_work,
+                          const skyemb_adamw_group *groups, int n_groups, float grad_scale, const uint32_t *skip, void *stream);
 
 /* ------------------------------------------------------------ input feeder -
  * utils/dataloaders.py:285-328 (H5Dataset.__getitem__): the reference opens the file and reads ONE cutout per python

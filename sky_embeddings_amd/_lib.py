@@ -98,6 +98,17 @@ class PrefilterPlan(ctypes.Structure):
                 ("slice", PrefilterSlice * 6)]
 
 
+class AdamwGroup(ctypes.Structure):
+    """skyemb_adamw_group (include/skyemb.h): the scalars of one parameter group of a segmented AdamW launch."""
+    _fields_ = [("lr", c_f32), ("bc1", c_f32), ("bc2", c_f32), ("beta1", c_f32), ("beta2", c_f32), ("eps", c_f32), ("wd", c_f32),
+                ("decayed", c_i32)]
+
+
+class AdamwSegment(ctypes.Structure):
+    """skyemb_adamw_segment: elements [offset, offset + n) of a flat buffer and the group that steps them."""
+    _fields_ = [("offset", c_i64), ("n", c_i64), ("group", c_i32), ("reserved", c_i32)]
+
+
 class GemmGroupInfo(ctypes.Structure):
     _fields_ = [("total_blocks", c_i32), ("tile", c_i32), ("class_mask", c_i32), ("reserved", c_i32)]
 
@@ -166,6 +177,10 @@ PROTOTYPES = {
     "skyemb_grad_probe": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp]),
     "skyemb_adamw_guarded": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_f32, c_f32, c_f32, c_f32,
                                      c_f32, c_f32, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp]),
+    # multi-tensor AdamW over segments of a flat buffer (csrc/adamw_segments.hip): additive again
+    "skyemb_adamw_segments_limits": (c_i32, [c_vp, c_vp, c_vp]),
+    "skyemb_adamw_segments_plan": (c_i32, [c_vp, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "skyemb_adamw_segments": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_standardise": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "skyemb_weighted_norms": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "skyemb_cosine_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32]),

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -346,6 +347,60 @@ def adamw_guarded(p, g, m, v, p_lp, n, n_decay, hyper, beta1, beta2, eps, wd, sk
     check(lib().skyemb_adamw_guarded(_p(p), _p(g), _p(m), _p(v), _p(p_lp), code, n, n_decay, _p(hyper), lr, bc1, bc2, beta1,
                                      beta2, eps, wd, grad_scale, int(zero_grad), dtype_code(g.dtype), _p(skip), _stream()),
           "skyemb_adamw_guarded")
+
+
+# skyemb_adamw_work: one work item of a segmented AdamW launch, 16 bytes
+ADAMW_WORK_DTYPE = np.dtype([("offset", "<i8"), ("n", "<i4"), ("group", "<i4")])
+
+
+def adamw_segments_limits():
+    """(max_groups, chunk_elems, max_grid) of skyemb_adamw_segments: the most groups of one launch, the most elements of one work
+    item, the most workgroups of a launch."""
+    out = (ctypes.c_int32 * 3)()
+    base = ctypes.addressof(out)
+    check(lib().skyemb_adamw_segments_limits(base, base + 4, base + 8), "skyemb_adamw_segments_limits")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def adamw_segments_plan(segments, n_groups, buffer_n):
+    """segments: [(offset, n, group)] in elements of a flat buffer of buffer_n elements, in any order -> (table, n_work): the host
+    table of skyemb_adamw_segments (numpy, ADAMW_WORK_DTYPE; see include/skyemb.h for how it is built).  No device is touched.
+    ValueError with the library's text when the segments are refused."""
+    segs = (_lib.AdamwSegment * max(len(segments), 1))()
+    for s, (offset, n, group) in zip(segs, segments):
+        s.offset, s.n, s.group = int(offset), int(n), int(group)
+    need, n_work = ctypes.c_int64(0), ctypes.c_int32(0)
+    L = lib()
+
+    def call(table, nbytes):
+        if L.skyemb_adamw_segments_plan(ctypes.addressof(segs), len(segments), int(n_groups), int(buffer_n), table, nbytes,
+                                        ctypes.addressof(need), ctypes.addressof(n_work)) != 0:
+            raise ValueError(L.skyemb_last_error().decode())
+    call(None, 0)
+    table = np.zeros(n_work.value, dtype=ADAMW_WORK_DTYPE)
+    call(table.ctypes.data, table.nbytes)
+    return table, int(n_work.value)
+
+
+def adamw_groups(groups):
+    """[(lr, bc1, bc2, beta1, beta2, eps, wd, decayed)] -> the skyemb_adamw_group array a launch takes (host memory)."""
+    arr = (_lib.AdamwGroup * len(groups))()
+    for a, (lr, bc1, bc2, beta1, beta2, eps, wd, decayed) in zip(arr, groups):
+        a.lr, a.bc1, a.bc2, a.beta1, a.beta2, a.eps, a.wd, a.decayed = lr, bc1, bc2, beta1, beta2, eps, wd, int(bool(decayed))
+    return arr
+
+
+def adamw_segments(p, g, m, v, p_lp, table, n_work, groups, grad_scale=1.0, skip=None):
+    """One AdamW launch over the segments planned into `table` (device copy of adamw_segments_plan's, int32 view) of the flat
+    buffers p, g, m, v (fp32) and the shadow p_lp; groups: adamw_groups(...) or the tuples it takes; skip: None or the state of
+    grad_probe (the launch writes nothing when skip[0] != 0)."""
+    assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32 and p.numel() == g.numel() == m.numel() == v.numel() == p_lp.numel()
+    assert table.is_cuda and table.numel() * table.element_size() >= 16 * n_work
+    assert skip is None or skip.dtype == torch.int32
+    if not isinstance(groups, ctypes.Array):
+        groups = adamw_groups(groups)
+    check(lib().skyemb_adamw_segments(_p(p), _p(g), _p(m), _p(v), _p(p_lp), dtype_code(p_lp.dtype), _p(table), int(n_work),
+                                      ctypes.addressof(groups), len(groups), grad_scale, _p(skip), _stream()), "skyemb_adamw_segments")
 
 
 def set_scalars(dst, a, b=0.0, c=0.0, d=0.0):

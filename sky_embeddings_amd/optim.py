@@ -16,6 +16,24 @@ import torch
 from . import ops
 
 
+def segmented_launches(segments, max_groups):
+    """The launches of one segmented AdamW step (ops.adamw_segments).  segments: [(store_key, offset, n, group_index)] -- which
+    elements of which flat buffer belong to which parameter group -> [(store_key, [group_index, ...], [(offset, n, k), ...])]: one
+    launch per store when the groups touching it number at most max_groups, otherwise consecutive launches over at most max_groups
+    groups each, in ascending group order; k is the position of the segment's group in the launch's own list.  Stores come in the
+    order of their first segment; a group without segments takes part in nothing.  Pure: nothing here touches a device."""
+    by_store = {}
+    for store_key, offset, n, group in segments:
+        by_store.setdefault(store_key, {}).setdefault(group, []).append((offset, n))
+    launches = []
+    for store_key, groups in by_store.items():
+        ids = sorted(groups)
+        for lo in range(0, len(ids), max_groups):
+            part = ids[lo:lo + max_groups]
+            launches.append((store_key, part, [(offset, n, k) for k, gi in enumerate(part) for offset, n in groups[gi]]))
+    return launches
+
+
 class FusedAdamW:
     def __init__(self, engine, lr=1e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.05, process_group=None):
         self.engine = engine

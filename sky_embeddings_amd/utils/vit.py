@@ -30,6 +30,7 @@ from .. import ops
 from ..engine import MAEEngine
 from ..loss_scale import make_loss_scaler
 from ..model_config import MODEL_TYPES, config_for
+from ..optim import segmented_launches
 from ..predictor_head import PredictorHead
 from .lr_decay import param_groups_lrd
 from .mim_vit import _DataParallelShim, _PatchEmbedInfo, _compute_dtype
@@ -294,9 +295,12 @@ class PredictorOptimizer:
     stepped by the AdamW kernel on its slice of the flat buffers it lives in (fp32 master + the compute-dtype shadow the GEMMs
     read).  groups: [{'params': [names], 'lr', 'weight_decay'(, 'betas')}]; eps = torch's default, as the reference.
     state_dict / load_state_dict use torch.optim.AdamW's layout (integer parameter ids in group order, per-parameter
-    'step' / 'exp_avg' / 'exp_avg_sq'), so predictor checkpoints interchange with the reference's."""
+    'step' / 'exp_avg' / 'exp_avg_sq'), so predictor checkpoints interchange with the reference's.
+    segmented=True: one launch per flat buffer steps every tensor of it (ops.adamw_segments: a table of segments planned once, the
+    groups' scalars as kernel arguments of every step) -- the same bits as segmented=False, the per-tensor launches.
+    last_step_launches: the AdamW launches the last step() made."""
 
-    def __init__(self, model, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, model, groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, segmented=True):
         self.model = model
         self.defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.param_groups = []
@@ -309,6 +313,9 @@ class PredictorOptimizer:
             self.param_groups.append(g)
         self.step_count = 0
         self._ranges = None
+        self.segmented = bool(segmented)
+        self.last_step_launches = 0
+        self._seg_key, self._seg_launches = None, None
 
     def zero_grad(self, set_to_none=True):
         """Nothing to do: every backward overwrites the gradient buffers (engine and head) it computes."""
@@ -357,21 +364,52 @@ class PredictorOptimizer:
             for r in self._probe_ranges():
                 scaler.probe(r)
             unscale = 1.0 / self.model._backward_scale
-        for g in self.param_groups:
-            lr, wd = g["lr"], g["weight_decay"]
-            b1, b2 = g["betas"]
-            bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-            for name in g["params"]:
-                (p, gr, m, v, p_lp), _ = self._buffers(name)
-                n = p.numel()
-                if scaler is None:
-                    ops.adamw(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, lr=lr, bc1=bc1, bc2=bc2)
-                else:
-                    ops.adamw_guarded(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, scaler.state,
-                                      grad_scale=unscale, lr=lr, bc1=bc1, bc2=bc2)
+        if self.segmented:
+            launches = self._segment_launches()
+            for store, group_ids, table, n_work in launches:
+                scalars = []
+                for g in (self.param_groups[i] for i in group_ids):
+                    b1, b2 = g["betas"]
+                    scalars.append((g["lr"], 1.0 - b1 ** t, 1.0 - b2 ** t, b1, b2, eps, g["weight_decay"], g["weight_decay"] != 0.0))
+                ops.adamw_segments(store.p, store.g, store.m, store.v, store.p_lp, table, n_work, scalars,
+                                   grad_scale=1.0 if scaler is None else unscale, skip=None if scaler is None else scaler.state)
+            self.last_step_launches = len(launches)
+        else:
+            for g in self.param_groups:
+                lr, wd = g["lr"], g["weight_decay"]
+                b1, b2 = g["betas"]
+                bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+                for name in g["params"]:
+                    (p, gr, m, v, p_lp), _ = self._buffers(name)
+                    n = p.numel()
+                    if scaler is None:
+                        ops.adamw(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, lr=lr, bc1=bc1, bc2=bc2)
+                    else:
+                        ops.adamw_guarded(p, gr, m, v, p_lp, n, n if wd != 0.0 else 0, None, b1, b2, eps, wd, scaler.state,
+                                          grad_scale=unscale, lr=lr, bc1=bc1, bc2=bc2)
+            self.last_step_launches = len(self._names())
         # a skipped step does not count: its retry uses the same t (bias corrections) -- the lr schedule moves on regardless
         if scaler is None or scaler.finish_step():
             self.step_count = t
+
+    def _segment_launches(self):
+        """[(store, group indices, device table, n_work)]: the launches of a segmented step, planned and uploaded once per set of
+        parameter names per group (a changed set -- another `trainable` -- plans again)."""
+        key = tuple(tuple(g["params"]) for g in self.param_groups)
+        if key != self._seg_key:
+            stores, segs = {}, []
+            for gi, names in enumerate(key):
+                for name in names:
+                    (p, _, _, _, _), store = self._buffers(name)
+                    stores[id(store)] = store
+                    segs.append((id(store), p.storage_offset(), p.numel(), gi))
+            self._seg_launches = []
+            for sk, group_ids, local in segmented_launches(segs, ops.adamw_segments_limits()[0]):
+                store = stores[sk]
+                table, n_work = ops.adamw_segments_plan(local, len(group_ids), store.p.numel())
+                self._seg_launches.append((store, group_ids, torch.from_numpy(table.view(np.int32)).to(store.p.device), n_work))
+            self._seg_key = key
+        return self._seg_launches
 
     def _names(self):
         return [n for g in self.param_groups for n in g["params"]]
@@ -471,14 +509,15 @@ class LinearLR:
         self._apply()
 
 
-def build_optimizer(model, train_method, init_lr, weight_decay, layer_decay):
-    """utils/vit.py:134-172 on a VisionTransformer of this module (``model`` = the object behind ``.module``)."""
+def build_optimizer(model, train_method, init_lr, weight_decay, layer_decay, segmented=True):
+    """utils/vit.py:134-172 on a VisionTransformer of this module (``model`` = the object behind ``.module``).  segmented: see
+    PredictorOptimizer."""
     if train_method in ('finetune', 'ft'):
         print('\nUsing the fine-tuning training method...')
         # utils/vit.py:141-143 passes (model, weight_decay, ...) POSITIONALLY to param_groups_lrd(model, init_lr, weight_decay=0.05, ...):
         # the configured weight decay becomes the base lr of the groups and their weight decay stays 0.05.  Mirrored as written.
         groups, _ = param_groups_lrd(model, weight_decay, no_weight_decay_list=model.no_weight_decay(), layer_decay=layer_decay)
-        return PredictorOptimizer(model, groups)                 # (the groups' own rates are what utils/vit.py:174 hands OneCycleLR)
+        return PredictorOptimizer(model, groups, segmented=segmented)    # (the groups' own rates are what utils/vit.py:174 hands OneCycleLR)
     if train_method in ('linearprobe', 'lp'):
         print('\nUsing the linear probing training method...')
         comps = ["norm.", "fc_norm.", "head."]
@@ -489,12 +528,13 @@ def build_optimizer(model, train_method, init_lr, weight_decay, layer_decay):
         model.trainable = {k for g in groups for k in g["params"]}      # everything else: requires_grad = False
         model.frozen_encoder = True
         # (one group per component, as the reference builds them -- fc_norm's is empty unless the pooling is 'avg')
-        return PredictorOptimizer(model, groups, lr=init_lr, weight_decay=weight_decay)
+        return PredictorOptimizer(model, groups, lr=init_lr, weight_decay=weight_decay, segmented=segmented)
     print('\nUsing the fully supervised training method...')
     # timm's param_groups_weight_decay: 1-D tensors and biases are not decayed, everything else is (cls_token and patch_mask_values too)
     no_decay = [k for k, nd in model.trainable_tensors() if nd <= 1 or k.endswith(".bias")]
     decay = [k for k, nd in model.trainable_tensors() if not (nd <= 1 or k.endswith(".bias"))]
-    return PredictorOptimizer(model, [{"params": no_decay, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}], lr=init_lr)
+    return PredictorOptimizer(model, [{"params": no_decay, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}], lr=init_lr,
+                              segmented=segmented)
 
 
 def build_model(config, mae_config, model_filename, mae_filename, device, build_optimizer=False):
