@@ -736,6 +736,34 @@ int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const float *qn,
                                                const void *tail, const float *rowp, int64_t N, int P, int D, int k, int combine,
                                                float eps, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
                                                float *out_s, int64_t *out_i, int *redo, const void *pooled16, void *stream);
+/* Combine mean under a selection of images, by COMPACTION: stage 1 under mean never reads the bank, only the pooled image and its row
+ * constants, so the selected images' rows of both are gathered once into a compact image [S, D] and stage 1 is the unselected pass
+ * above over S rows, not N -- its work falls with the selection however the selected images are scattered over the bank.  A deselected
+ * image appears nowhere: nothing it holds (NaN, inf, huge values) can matter.  Scores and image indices are bit for bit those of
+ * skyemb_cosine_token_topk_sel (lp) + skyemb_topk_merge under mean and the same words.
+ *   skyemb_token_mean_select_gather   one launch per selection, bank and weights version.  pooled16 [N, D] and rowp are those of
+ *                           skyemb_token_mean_pool (dtype: the bank's); idx [S] the selected images, ASCENDING, 0 <= idx < N (an entry
+ *                           outside is never followed: its row becomes padding).  Writes pooled_sel [S, D], row j = the bits of pooled
+ *                           row idx[j]; rowp_sel [skyemb_bank16_rowp_rows(S), 4], row j = rowp row idx[j] bit for bit -- the {0, inf, 1, 0}
+ *                           of an unboundable image included: it stays a candidate of every query, decided by stage 2 --, rows past S
+ *                           the padding sentinel {0, NaN, 0, 0}; tail_sel (NULL when S % 256 == 0, then untouched): a zero-padded
+ *                           [256, D] copy of the last S % 256 rows; map int32 [S] = idx.  pooled16, pooled_sel and tail_sel 16-byte
+ *                           aligned.  Extra memory: 2 D + 20 bytes per selected image and the tail tile.
+ *   skyemb_cosine_topk_tokens_mean_prefiltered_sel   the arguments of skyemb_cosine_topk_tokens_mean_prefiltered with tail / rowp /
+ *                           pooled16 the COMPACTED ones, and S and map behind N.  N stays the bank's image count (the bank's bounds,
+ *                           N P < 2^31).  It plans as the request {SKYEMB_PF_TOKENS_MEAN, N = S, sel = 0} of skyemb_prefilter_plan; stage
+ *                           2 reads candidate c's tokens at image map[c] of the bank, and keys and out_i carry idx_offset + map[c] (map
+ *                           ascending keeps the order (score desc, image asc)).  Refused before any launch, under this entry's name:
+ *                           combine not mean, S < 2048, k > S, S > N, N P >= 2^31, a null map, pooled_sel or tail_sel not 16-byte
+ *                           aligned, no tail_sel when S % 256 != 0, and whatever the plan refuses.  thr0: a floor of the k-th best
+ *                           SELECTED score.  redo[q] != 0: as above -- the caller runs the query through skyemb_cosine_token_topk_sel. */
+int skyemb_token_mean_select_gather(const void *pooled16, const float *rowp, const int64_t *idx, int64_t N, int64_t S, int D, int dtype,
+                                    void *pooled_sel, float *rowp_sel, void *tail_sel, int *map, void *stream);
+int skyemb_cosine_topk_tokens_mean_prefiltered_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype, const float *xn,
+                                                   const void *tail_sel, const float *rowp_sel, int64_t N, int64_t S, const int *map, int P,
+                                                   int D, int k, int combine, float eps, int64_t idx_offset, const float *thr0, void *ws,
+                                                   int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, const void *pooled_sel,
+                                                   void *stream);
 /* Read-only query of the launch plan of every two-stage search above (csrc/prefilter_plan.h): what the entry point serving `req`
  * decides on the host -- variant, slices, kernel instances, LDS bytes -- and then launches.  Host arithmetic only, touches no device.
  * Returns 0 and fills *out, or 1 with the text (skyemb_last_error) and under the name of the entry point that would refuse the

@@ -242,6 +242,11 @@ PROTOTYPES = {
     "skyemb_token_mean_prefilter_eps_m": (c_f64, [c_i32, c_i32, c_i32]),
     "skyemb_cosine_topk_tokens_mean_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
                                                            c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # ... and mean under a selection of images, over the compacted pooled image: additive again
+    "skyemb_token_mean_select_gather": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_cosine_topk_tokens_mean_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32,
+                                                               c_i32, c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                                               c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

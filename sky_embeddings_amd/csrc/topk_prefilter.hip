@@ -1707,14 +1707,19 @@ __global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, floa
 // carried; here the tiles sit side by side on 32 / 64 lanes: each is sorted in its own 16 lanes, then tiles 1, 2, 3 are merged, in
 // that order, into the lanes of tile 0 (top_tile's step with the carry in tile 0's lanes and the new tile fetched across).
 // Without TOPT top_t is not read: the instruction stream of the kernels without it.
-template <typename X, bool TOPT = false>
+// MAP ('mean' under a selection, the `_mean_prefiltered_sel` entry; fold is TOK_MEAN): stage 1 ran over the COMPACTED pooled image of
+// skyemb_token_mean_select_gather, so a candidate is a position c in [0, S) of it and the image is map[c]; its token rows are read from
+// the full bank and the keys carry the image, so the lists, the threshold and the result are those of the unmapped search (map is
+// ascending: (score desc, image asc) is (score desc, position asc)).  Without MAP neither map nor S is read.
+template <typename X, bool TOPT = false, bool MAP = false>
 __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank,
                                                    const float *__restrict__ xn, int64_t N, int D, int lgp, int fold, float gfac, int k,
                                                    float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase, int *__restrict__ cnt,
                                                    const int *__restrict__ cand_i, unsigned long long *__restrict__ list,
                                                    int *__restrict__ rn, float4 *__restrict__ qpar, float *__restrict__ tau_q,
                                                    int *__restrict__ overflow, int final, float *__restrict__ out_s,
-                                                   int64_t *__restrict__ out_i, int *__restrict__ redo, int top_t = 0) {
+                                                   int64_t *__restrict__ out_i, int *__restrict__ redo, int top_t = 0,
+                                                   const int *__restrict__ map = nullptr, int S = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *keys = (unsigned long long *)smem;     // [TOK_KMAX + cap] the running list, then the slice's candidates
     unsigned long long *kept = keys + TOK_KMAX + cap;          // [TOK_KMAX] the new running list
@@ -1736,6 +1741,10 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
     for (int base = 0; base < n; base += G) {                  // (uniform trip count: every lane takes part in the shuffles)
         const int c = base + g;
         int img = c < n ? cand_i[(int64_t)q * cap + c] : 0;
+        if constexpr (MAP) {
+            if (img < 0 || img >= S) { img = 0; bad = true; }  // never read outside the map (stage 1 appends positions of real rows only)
+            img = map[img];
+        }
         if (img < 0 || img >= N) { img = 0; bad = true; }      // never read outside the bank (stage 1 appends images of real rows only)
         const int64_t row = (int64_t)img * P + p;
         const X *x = bank + row * D;
@@ -1846,8 +1855,43 @@ __global__ __launch_bounds__(256) void token_rescore_top_lp_kernel(TOKEN_RESCORE
 __global__ __launch_bounds__(256) void token_rescore_top_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), int top_t) {
     token_rescore_body<bf16_t, true>(TOKEN_RESCORE_PASS, top_t);
 }
+__global__ __launch_bounds__(256) void token_rescore_map_lp_kernel(TOKEN_RESCORE_PARAMS(half_t), const int *__restrict__ map, int S) {
+    token_rescore_body<half_t, false, true>(TOKEN_RESCORE_PASS, 0, map, S);
+}
+__global__ __launch_bounds__(256) void token_rescore_map_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const int *__restrict__ map, int S) {
+    token_rescore_body<bf16_t, false, true>(TOKEN_RESCORE_PASS, 0, map, S);
+}
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
+
+// ---- 'mean' under a selection of images: the compacted pooled image (skyemb_token_mean_select_gather) ------------------------------
+// Stage 1 under 'mean' never reads the bank, only the pooled image [N, D] and its constants, so a selection is served by COMPACTING
+// them: row j of pooled_sel / rowp_sel is row idx[j] of pooled / rowp bit for bit (the {0, inf, 1, 0} of an unboundable image
+// included: it stays a candidate of every query), and stage 1 is the unselected pass over S rows.  A deselected image appears
+// nowhere.  One wave per compacted row, 16 bytes per lane and step (D % 32 == 0: whole vectors); rows S .. rows_padded-1: the padding
+// sentinel, zeros in the tail tile (bank16_rowp_lp_kernel's layout: tail_first = S rounded down to whole tiles).  An idx outside
+// [0, N) is never followed: its row is padding.
+__global__ __launch_bounds__(256) void token_mean_select_gather_kernel(const unsigned short *__restrict__ pooled, const float4 *__restrict__ rowp,
+                                                                        const int64_t *__restrict__ idx, int64_t N, int64_t S, int D,
+                                                                        unsigned short *__restrict__ pooled_sel, float4 *__restrict__ rowp_sel,
+                                                                        int64_t rows_padded, unsigned short *__restrict__ tail,
+                                                                        int64_t tail_first, int *__restrict__ map) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= rows_padded) return;
+    unsigned short *t = tail && j >= tail_first ? tail + (j - tail_first) * D : nullptr;
+    const int64_t src = j < S ? idx[j] : -1;
+    const bool on = src >= 0 && src < N;
+    for (int d = lane * 8; d < D; d += 512) {
+        const uint4 v = on ? *(const uint4 *)(pooled + src * D + d) : make_uint4(0u, 0u, 0u, 0u);
+        if (j < S) *(uint4 *)(pooled_sel + j * D + d) = v;
+        if (t) *(uint4 *)(t + d) = v;
+    }
+    if (lane == 0) {
+        rowp_sel[j] = on ? rowp[src] : make_float4(0.f, NAN, 0.f, 0.f);
+        if (j < S) map[j] = on ? (int)src : 0;
+    }
+}
 
 // ---- a selection of the bank's IMAGES (skyemb_token_prefilter_select_prepare) -------------------------------------------------------
 // words: bit i & 31 of word i >> 5 is IMAGE i, padding bits zero (skyemb_pack_select); the row constants and the tiles are per
@@ -2020,6 +2064,7 @@ extern "C" int skyemb_token_prefilter_select_prepare(const uint32_t *words, int6
 //            re-score after every slice -- d[top_t - 1] by the TOPT kernels under 'min' with 1 <= top_t < P.
 //   mean     stage 1 is the ROW search over the pooled image of skyemb_token_mean_pool (`pooled`, with ITS tail and rowp: a row is an image,
 //            no TOK fold) under the mean bound's constants; stage 2 re-scores the candidate images' tokens from bank16 as ever.
+//            Under a selection (`map`): the same request over the S rows of the COMPACTED pooled image; stage 2 follows map to the bank.
 // tiles (a search under a selection, the two select_prepare calls): rowp is the masked copy, the slices walk the live-tile list (SEL).
 namespace {
 
@@ -2049,6 +2094,7 @@ const void *const RESCORE[3][2] = {{(const void *)rescore_kernel<false>, (const 
                                    {(const void *)rescore_bf_kernel<false>, (const void *)rescore_bf_kernel<true>}};
 const void *const TOKEN_RESCORE[2][2] = {{(const void *)token_rescore_lp_kernel, (const void *)token_rescore_bf_kernel},     // [topt][bf]
                                          {(const void *)token_rescore_top_lp_kernel, (const void *)token_rescore_top_bf_kernel}};
+const void *const TOKEN_RESCORE_MAP[2] = {(const void *)token_rescore_map_lp_kernel, (const void *)token_rescore_map_bf_kernel};   // [bf]
 
 // the pointer arguments of an entry point; NULL where it has none
 struct SearchArgs {
@@ -2066,6 +2112,11 @@ struct SearchArgs {
     int64_t *out_i;
     int *redo;
     void *stream;
+    // 'mean' over a compacted selection (skyemb_cosine_topk_tokens_mean_prefiltered_sel; NULL / 0 everywhere else): the request's N is
+    // the S compacted rows stage 1 walks, map their images, bank_N the bank's image count, who the entry's own name
+    const int *map;
+    int64_t bank_N;
+    const char *who;
 };
 
 int bank_of(int dtype) { return dtype == SKYEMB_BF16 ? SKYEMB_PF_BANK_BF16 : dtype == SKYEMB_F16 ? SKYEMB_PF_BANK_F16 : -1; }
@@ -2172,7 +2223,7 @@ void pf_dbg_report(hipStream_t st, int p, int mode, int Q, const Workspace &w) {
 #endif
 
 int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
-    const char *who = who_of(r);
+    const char *who = a.who ? a.who : who_of(r);
     const bool rows = r.kind == SKYEMB_PF_ROWS, mean = r.kind == SKYEMB_PF_TOKENS_MEAN;
     SKY_CHECK_ARG(r.bank >= 0, "%s: dtype " RESIDENT_DTYPE_MSG, who, a.dtype);
     SKY_CHECK_ARG(a.tw && a.qn && a.xn && a.bank16 && a.rowp && a.ws && a.out_s && a.out_i && a.redo &&
@@ -2185,7 +2236,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
     if (bank != SKYEMB_PF_BANK_F32) {
         SKY_CHECK_ARG(p.rows % BT == 0 || a.tail, rows ? "%s: N = %lld is no whole number of %d-row tiles: the tail tile of %s is needed"
                                                        : "%s: %lld rows are no whole number of %d-row tiles: the tail tile of %s is needed",
-                      who, (long long)p.rows, BT, mean ? "skyemb_token_mean_pool" : rows && bank == SKYEMB_PF_BANK_F16 ? "skyemb_bank16_rowp_lp"
+                      who, (long long)p.rows, BT, a.map ? "skyemb_token_mean_select_gather" : mean ? "skyemb_token_mean_pool" : rows && bank == SKYEMB_PF_BANK_F16 ? "skyemb_bank16_rowp_lp"
                                                                                                                       : "skyemb_resident_rowp");
         SKY_CHECK_ARG(aligned16(a.bank16) && aligned16(a.tail) && aligned16(s1_bank), "%s: the bank and the tail tile must be 16-byte aligned",
                       who);
@@ -2202,7 +2253,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
         for (int lo = 0; lo <= 1; ++lo)
             for (int s = rows ? 0 : p.sel; s <= p.sel; ++s)    // (a row search under a selection launches its tail through the non-SEL instance)
                 if (rc == 0) rc = sky_set_lds_limit((const void *)STAGE1[stage1_index(mode, lo, s, p.bf, p.tok, p.cnt)], p.lds_stage1_limit, who);
-    const void *token_rescore = TOKEN_RESCORE[p.top_t != 0][p.bf];
+    const void *token_rescore = a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
     if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, p.lds_close_limit, who);
     if (rc == 0 && rows && p.sel) rc = sky_set_lds_limit((const void *)SELECT[1], p.lds_close_limit, who);
     if (rc != 0) return rc;
@@ -2229,8 +2280,8 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
         go();
 #endif
     };
-    auto token_rescore_as = [&](auto like, int final, auto... top_t) {
-        launch_like(like, token_rescore, Q, p.lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, r.N, D, p.lgp, p.fold, p.gfac, k, r.eps,
+    auto token_rescore_as = [&](auto like, int final, auto... top_t) {               // (top_t: what the instance takes behind redo)
+        launch_like(like, token_rescore, Q, p.lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, a.map ? a.bank_N : r.N, D, p.lgp, p.fold, p.gfac, k, r.eps,
                     a.idx_offset, p.cap, w.qbase, w.cnt, w.cand_i, list, w.nsel, w.qpar, w.tau, w.overflow, final, a.out_s, a.out_i, a.redo, top_t...);
     };
     // The kernel addresses tile t at base + t * BT rows, so the base handed over for the tail is the one that puts tile T_tail on
@@ -2253,6 +2304,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
         if (rows)
             hipLaunchKernelGGL(SELECT[p.sel], dim3((unsigned)Q), dim3(256), p.lds_close, st, Q, k, p.cap, r.eps, w.qbase, (const float4 *)a.rowp, a.xn,
                                w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, s.final, w.sel_i, w.nsel, w.bound);
+        else if (a.map) token_rescore_as(token_rescore_map_lp_kernel, s.final, a.map, (int)r.N);   // the MAP kernels take map and S last
         else if (p.top_t) token_rescore_as(token_rescore_top_lp_kernel, s.final, p.top_t);      // the TOPT kernels take top_t last
         else token_rescore_as(token_rescore_lp_kernel, s.final);
     }
@@ -2367,4 +2419,44 @@ extern "C" int skyemb_cosine_topk_tokens_mean_prefiltered(const float *tw, const
                                                           float *out_s, int64_t *out_i, int *redo, const void *pooled16, void *stream) {
     return search(request(SKYEMB_PF_TOKENS_MEAN, bank_of(dtype), Q, N, P, D, k, combine, 0, eps, thr0),
                   {tw, qn, nullptr, xn, bank16, dtype, tail, pooled16, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream});
+}
+
+// ---- 'mean' under a selection of images: the compacted pooled image, then the unselected search over it ----------------------------------
+extern "C" int skyemb_token_mean_select_gather(const void *pooled16, const float *rowp, const int64_t *idx, int64_t N, int64_t S, int D,
+                                               int dtype, void *pooled_sel, float *rowp_sel, void *tail_sel, int *map, void *stream) {
+    const char *who = "skyemb_token_mean_select_gather";
+    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
+    SKY_CHECK_ARG(pooled16 && rowp && idx && pooled_sel && rowp_sel && map, "%s: null argument", who);
+    SKY_CHECK_ARG(S >= 1 && S <= N && N < (1ll << 31) && D % BK == 0 && D >= BK && D <= 4096,
+                  "%s: expected 1 <= S <= N < 2^31 images, D %% 32 == 0 and D <= 4096 (N=%lld S=%lld D=%d)", who, (long long)N, (long long)S, D);
+    SKY_CHECK_ARG(S % BT == 0 || tail_sel, "%s: S = %lld is no whole number of %d-image tiles: a tail tile [%d, D] is needed", who, (long long)S,
+                  BT, BT);
+    SKY_CHECK_ARG(aligned16(pooled16) && aligned16(pooled_sel) && aligned16(tail_sel), "%s: the pooled image, its compacted copy and the tail "
+                  "tile must be 16-byte aligned", who);
+    const int64_t padded = skyemb_bank16_rowp_rows(S);
+    hipLaunchKernelGGL(token_mean_select_gather_kernel, dim3((unsigned)(padded / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned short *)pooled16, (const float4 *)rowp, idx, N, S, D, (unsigned short *)pooled_sel, (float4 *)rowp_sel, padded,
+                       S % BT ? (unsigned short *)tail_sel : nullptr, S / BT * BT, map);
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// (tail_sel, rowp_sel, pooled_sel and map are those of skyemb_token_mean_select_gather; the plan is the unselected mean request over S rows)
+extern "C" int skyemb_cosine_topk_tokens_mean_prefiltered_sel(const float *tw, const float *qn, int Q, const void *bank16, int dtype,
+                                                              const float *xn, const void *tail_sel, const float *rowp_sel, int64_t N,
+                                                              int64_t S, const int *map, int P, int D, int k, int combine, float eps,
+                                                              int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                              int64_t *out_i, int *redo, const void *pooled_sel, void *stream) {
+    const char *who = "skyemb_cosine_topk_tokens_mean_prefiltered_sel";
+    SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MEAN, "%s: combine code %d: this entry combines by mean (min and max under a selection are served "
+                  "by skyemb_cosine_topk_tokens_prefiltered_sel)", who, combine);
+    SKY_CHECK_ARG(S >= 8 * BT, "%s: S = %lld selected images: stage 1 needs S >= %d (the grouped search serves a smaller selection)", who,
+                  (long long)S, 8 * BT);
+    SKY_CHECK_ARG(k <= S, "%s: k = %d exceeds the S = %lld selected images", who, k, (long long)S);
+    SKY_CHECK_ARG(S <= N, "%s: S = %lld selected images of a bank of N = %lld", who, (long long)S, (long long)N);
+    SKY_CHECK_ARG(P >= 1 && N * P < (1ll << 31), "%s: N * P must stay below 2^31 token rows (N=%lld P=%d)", who, (long long)N, P);
+    SKY_CHECK_ARG(map, "%s: null argument (map)", who);
+    return search(request(SKYEMB_PF_TOKENS_MEAN, bank_of(dtype), Q, S, P, D, k, combine, 0, eps, thr0),
+                  {tw, qn, nullptr, xn, bank16, dtype, tail_sel, pooled_sel, rowp_sel, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
+                   map, N, who});
 }

@@ -662,6 +662,48 @@ def cosine_topk_tokens_mean_prefiltered(tw, qn, tokens, xn, pooled, tail, rowp, 
     return ws
 
 
+def token_mean_select_prefilter_refusal(Q, S, P, D, k):
+    """None when the two-stage token search with combine mean takes a selection of ``S`` images as the bank stage 1 walks (its
+    compacted pooled image: the rule of ``token_mean_prefilter_refusal`` with the selected images for the bank's), else the
+    library's own statement of those limits."""
+    return token_mean_prefilter_refusal(Q, S, P, D, k)
+
+
+def token_mean_select_gather(pooled, rowp, idx):
+    """(pooled_sel, tail_sel, rowp_sel, map) of ``skyemb_token_mean_select_gather``: the rows ``idx`` (i64 [S], ascending) of the
+    pooled image [N, D] and of the row constants of ``token_mean_pool``, compacted -- the image [S, D] in the bank's dtype, its
+    zero-padded tail tile (None when S % 256 == 0), the constants f32 [ceil(S / 256) * 256, 4] and compacted position -> image
+    (i32 [S]).  One short launch; 2 D + 20 bytes per selected image and the tail tile."""
+    N, D = pooled.shape
+    S = int(idx.numel())
+    code = resident_dtype_code(pooled.dtype, "token_mean_select_gather")
+    assert pooled.is_contiguous() and idx.dtype == torch.int64 and idx.is_contiguous() and idx.device == pooled.device
+    rows = lib().skyemb_bank16_rowp_rows(S)
+    pooled_sel = torch.empty(S, D, device=pooled.device, dtype=pooled.dtype)
+    rowp_sel = torch.empty(rows, 4, device=pooled.device, dtype=torch.float32)
+    tail_sel = torch.empty(256, D, device=pooled.device, dtype=pooled.dtype) if rows != S else None
+    cmap = torch.empty(S, device=pooled.device, dtype=torch.int32)
+    check(lib().skyemb_token_mean_select_gather(_p(pooled), _p(rowp), _p(idx), N, S, D, code, _p(pooled_sel), _p(rowp_sel), _p(tail_sel),
+                                                _p(cmap), _stream()), "skyemb_token_mean_select_gather")
+    return pooled_sel, tail_sel, rowp_sel, cmap
+
+
+def cosine_topk_tokens_mean_prefiltered_sel(tw, qn, tokens, xn, pooled_sel, tail_sel, rowp_sel, cmap, k, eps, idx_offset, out_s, out_i, redo,
+                                            thr0=None, ws=None):
+    """``cosine_topk_tokens_mean_prefiltered`` under a selection of images: (pooled_sel, tail_sel, rowp_sel, cmap) is
+    ``token_mean_select_gather``'s result over the pooled image of ``tokens`` (include/skyemb.h)."""
+    Q, D = tw.shape
+    N, P = tokens.shape[:2]
+    S = pooled_sel.shape[0]
+    code = resident_dtype_code(tokens.dtype, "cosine_topk_tokens_mean_prefiltered_sel")
+    ws = _workspace(ws, lib().skyemb_token_mean_prefilter_ws_bytes(Q, D, k), tw.device)
+    check(lib().skyemb_cosine_topk_tokens_mean_prefiltered_sel(_p(tw), _p(qn), Q, _p(tokens), code, _p(xn), _p(tail_sel), _p(rowp_sel), N, S,
+                                                               _p(cmap), P, D, k, COMBINE_CODES['mean'], eps, idx_offset, _p(thr0), _p(ws),
+                                                               ws.numel(), _p(out_s), _p(out_i), _p(redo), _p(pooled_sel), _stream()),
+          "skyemb_cosine_topk_tokens_mean_prefiltered_sel")
+    return ws
+
+
 def token_prefilter_select_prepare(words, N, P, rowp):
     """What the two-stage token search needs of a selection of IMAGES (packed ``words`` of ``pack_select`` over the N images) over
     a resident token bank of N x P rows with row constants ``rowp`` (``resident_rowp`` over the flat rows): (rowp_sel, tiles, n_live,

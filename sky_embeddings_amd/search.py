@@ -532,6 +532,7 @@ class Selection:
         self._sample = None                                # bank -> (its weights version, images, the floor's sample)
         self._prefilter = None                             # PreparedBank -> (its version, its row constants, what stage 1 needs)
         self._token_prefilter = None                       # resident TokenBank -> the same
+        self._mean = None                                  # resident TokenBank -> (its version, its pooled image, the compacted one)
 
     def prefilter(self, pb: "PreparedBank"):
         """What the two-stage many-query search needs of this selection over ``pb`` (``ops.prefilter_select_prepare``: the masked row
@@ -558,6 +559,37 @@ class Selection:
         if got is None or got[0] != tb._version or got[1] is not rowp:
             got = (tb._version, rowp, ops.token_prefilter_select_prepare(self.words, tb.bank.shape[0], tb.bank.shape[1], rowp))
             self._token_prefilter[tb] = got
+        return got[2]
+
+    def prepare_mean(self, tb: "TokenBank"):
+        """Ask this selection to hold, for the resident ``tb``, what the two-stage search under combine 'mean' reads in stage 1: the
+        selected images' rows of ``tb.stage1_mean()`` compacted into an image [count, D] with its tail tile, row constants and the
+        map compacted position -> image (``ops.token_mean_select_gather``: one short launch, 2 D + 20 bytes per selected image and
+        one 256-row tail tile).  Only a Selection asked so takes that route (``cosine_topk_tokens``): the compaction pays when
+        searches repeat under one Selection.  Kept per bank like ``token_prefilter``; once asked for a bank, an entry made stale by
+        ``set_weights`` is rebuilt by the next search, not dropped.  Returns ``self``: ``Selection(flags).prepare_mean(tb)``."""
+        if not isinstance(tb, TokenBank) or not tb._resident:
+            raise ValueError("Selection.prepare_mean: the bank must be made by TokenBank.resident")
+        if tb.bank.shape[0] != self.N:
+            raise ValueError(f"Selection.prepare_mean: the selection describes {self.N} images, the bank has {tb.bank.shape[0]}")
+        if self.words.device != tb.bank.device:
+            raise ValueError(f"Selection.prepare_mean: the Selection was packed on {self.words.device}, the bank is on {tb.bank.device}")
+        if self.count == 0:
+            return self                                    # nothing to compact: the grouped route answers (-inf, -1)
+        if self._mean is None:
+            self._mean = weakref.WeakKeyDictionary()
+        self._mean.setdefault(tb, None)
+        self.mean_prefilter(tb)
+        return self
+
+    def mean_prefilter(self, tb: "TokenBank"):
+        """(pooled_sel, tail_sel, rowp_sel, map) of ``prepare_mean`` for ``tb``, rebuilt when the bank's weights version or its pooled
+        image changed since."""
+        pooled = tb.stage1_mean()
+        got = self._mean.get(tb)
+        if got is None or got[0] != tb._version or got[1] is not pooled:
+            got = (tb._version, pooled, ops.token_mean_select_gather(pooled[0], pooled[2], self.indices()))
+            self._mean[tb] = got
         return got[2]
 
     def sample(self, tb: "TokenBank", images: int):
@@ -896,6 +928,9 @@ def _topk_tokens(rq: TokenRequest, sc, queries, prune, stats, process_group, wor
 
 TOKEN_PREFILTER_MIN_Q = 256    # fewest queries sent through the two-stage token route (measured: DESIGN.md section 6, item 17)
 TOKEN_MEAN_PREFILTER_MIN_Q = 256   # ... under combine 'mean': the smallest measured Q that beats the grouped route
+# ... under combine 'mean' with a Selection that holds the compacted pooled image (Selection.prepare_mean).  NOT MEASURED yet: the
+# unselected constant stands in until tools/bench_token_mean_select.py has run
+TOKEN_MEAN_SELECT_PREFILTER_MIN_Q = TOKEN_MEAN_PREFILTER_MIN_Q
 # ... under 'min' with 1 <= top_t < P: the smallest measured Q that beats the grouped route on every
 # leg, measured on banks of 3.07e9 elements (250 000 x 16 x 768 and 62 500 x 64 x 768).  About 4.3 ms of a two-stage call shrink
 # neither with Q nor with the bank while a grouped pass shrinks with the bank (at 0.77e9 elements the plain search lost at 64, item
@@ -919,7 +954,10 @@ def _token_prefilter_refusal(rq: TokenRequest):
     if rq.top_t != 0 and mean:
         return "top_t under combine 'mean'"
     if mean and rq.select is not None:
-        return "select under combine 'mean'"
+        held = getattr(rq.select, "_mean", None)           # (getattr: a Selection may be built without __init__)
+        if not isinstance(rq.select, Selection) or held is None or tb not in held:
+            return ("select under combine 'mean' without the compacted pooled image of this bank (opt in once per Selection and bank: "
+                    "Selection.prepare_mean)")
     if rq.select is not None and not isinstance(rq.select, Selection):
         return "select is not a Selection"
     if rq.per_query:
@@ -928,6 +966,14 @@ def _token_prefilter_refusal(rq: TokenRequest):
         return f"P = {rq.P} does not divide 64"
     if not _prefilter_enabled():
         return "SKYEMB_TOPK_PREFILTER=0"
+    if mean and rq.select is not None:                     # stage 1 walks the selected images' compacted pooled rows
+        if rq.Q < TOKEN_MEAN_SELECT_PREFILTER_MIN_Q:
+            return f"Q = {rq.Q} < TOKEN_MEAN_SELECT_PREFILTER_MIN_Q = {TOKEN_MEAN_SELECT_PREFILTER_MIN_Q}"
+        why = ops.token_mean_prefilter_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k)
+        if why is None:
+            why = ops.token_mean_select_prefilter_refusal(rq.Q, rq.select.count, rq.P, rq.D, rq.k)
+            why = why if why is None else "the selected images alone: " + why
+        return why
     if mean:                                               # its own size and shape rule: stage 1 walks images, not token rows
         if rq.Q < TOKEN_MEAN_PREFILTER_MIN_Q:
             return f"Q = {rq.Q} < TOKEN_MEAN_PREFILTER_MIN_Q = {TOKEN_MEAN_PREFILTER_MIN_Q}"
@@ -983,16 +1029,21 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
     """The two-stage driver (csrc/topk_prefilter.hip, "Patch-token banks"): one bootstrap floor, one stage-1 pass with exact
     re-scoring after every slice; flagged queries go through the grouped route, those queries only.  Under a selection stage 1
     walks the live tiles of ``Selection.token_prefilter``; its first slice ends at the first live-tile position whose count of
-    selected images reaches 96 k (never less than n_live / 128 positions, never less than 1), and the re-run keeps the selection."""
+    selected images reaches 96 k (never less than n_live / 128 positions, never less than 1), and the re-run keeps the selection.
+    Under 'mean' a selection is served by compaction instead (``Selection.mean_prefilter``): stage 1 is the unselected mean pass over
+    the selected images' pooled rows, stage 2 follows the map back to the bank."""
     tb, Q, k, dev, sel = rq.bank, rq.Q, rq.k, rq.tokens.device, rq.select
+    mean = rq.combine == ops.COMBINE_CODES['mean']
     q = queries.to(dev, torch.float32).contiguous()
     tw, qn = prepare_queries(q, tb.weights)
     thr0 = _bootstrap_floor(rq, tw, qn, eps)
-    prepared = None if sel is None else sel.token_prefilter(tb)
+    prepared = None if sel is None or mean else sel.token_prefilter(tb)
     head, eps_off = (tw, qn, tb.bank, tb.norms), (eps, rq.idx_offset)
 
     def launch(*out):                                      # ``top_t`` follows ``combine`` in the calls that take it
-        if rq.combine == ops.COMBINE_CODES['mean']:        # stage 1 over the pooled image (never under a selection)
+        if mean and sel is not None:                       # stage 1 over the selected images' compacted pooled rows
+            return ops.cosine_topk_tokens_mean_prefiltered_sel(*head, *sel.mean_prefilter(tb), k, *eps_off, *out, thr0)
+        if mean:                                           # stage 1 over the pooled image
             return ops.cosine_topk_tokens_mean_prefiltered(*head, *tb.stage1_mean(), k, *eps_off, *out, thr0)
         tail, rowp = tb.stage1()
         fold = (rq.combine,) if rq.top_t == 0 else (rq.combine, rq.top_t)
@@ -1013,7 +1064,9 @@ def _topk_tokens_prefiltered(rq: TokenRequest, eps, queries, prune, stats, proce
         stats.update(path="prefiltered", redone=n_redo, combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
         if rq.top_t != 0:
             stats.update(top_t=rq.top_t)
-        if sel is not None:
+        if sel is not None and mean:
+            stats.update(selected=sel.count, compacted=(sel.count, rq.N))
+        elif sel is not None:
             stats.update(selected=sel.count, tiles=(prepared[2], (rq.N * rq.P + 255) // 256))
     return _gather_merge(out_s, out_i, Q, k, world_size, process_group)
 
@@ -1082,8 +1135,16 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     ``eps`` and rounding, one dot product with the image's pooled unit tokens, so the matrix cores multiply a derived 16-bit image
     [N, D] of them (``TokenBank.stage1_mean``, one launch per bank and weights version) under a proven bound U >= mean, and every
     candidate image's P tokens are re-scored exactly, folded in token order with the one division -- bit for bit the grouped
-    route.  Its rule: no ``select``, no ``top_t``, shared weights, P a divisor of 64, at least ``TOKEN_MEAN_PREFILTER_MIN_Q``
-    queries, D % 32 == 0, 128 <= D <= 4096, N >= 2048 images, N P < 2^31, k <= 256, k <= N.  Everything else is served by the grouped
+    route.  Its rule: no ``top_t``, shared weights, P a divisor of 64, at least ``TOKEN_MEAN_PREFILTER_MIN_Q``
+    queries, D % 32 == 0, 128 <= D <= 4096, N >= 2048 images, N P < 2^31, k <= 256, k <= N.  ``select`` under 'mean' takes the route
+    by opt-in only: a ``Selection`` that was asked to hold the compacted pooled image of this bank
+    (``Selection(flags).prepare_mean(bank)``: the selected images' pooled rows and constants gathered into an image [count, D] by one
+    short launch, 2 D + 20 bytes per selected image and one 256-row tail tile, kept per bank and rebuilt when its weights change).
+    Stage 1 is then the unselected mean pass over ``count`` rows, not N -- its work falls with the selection however the images are
+    scattered --, a deselected image appears nowhere, stage 2 follows the map back to the bank; ``stats`` gains ``selected`` and
+    ``compacted`` = (count, N).  Its rule: the rule above on the bank, the same rule with ``count`` for N (count >= 2048, k <= count)
+    and at least ``TOKEN_MEAN_SELECT_PREFILTER_MIN_Q`` queries.  A bool tensor or a Selection never asked keeps the grouped route:
+    the gather costs memory and a launch that only repeated searches under one Selection amortise.  Everything else is served by the grouped
     route as ever, never refused.  ``top_t`` under 'min' and 'max', alone and with ``select``, takes the route too: 'max' with any
     ``top_t`` and 'min' with ``top_t == P`` are the plain search; 'min' with 1 <= top_t < P scores d[top_t-1], which reaches a
     threshold only when at least top_t tokens do, so an image is a candidate when the COUNT of its rows that pass the row test is
@@ -1092,7 +1153,7 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     smallest Q is ``TOKEN_TOPT_PREFILTER_MIN_Q`` (a bank of fewer than ``TOKEN_TOPT_PREFILTER_MIN_ELEMENTS`` elements:
     ``TOKEN_TOPT_PREFILTER_MIN_Q_SMALL``).  Out of scope for the two-stage route: ``top_t`` under 'mean' (the mean of the
     top_t best is not bounded by a count), per-query weights, the distance metrics, fp32 token banks, P not dividing 64, and
-    ``select`` under 'mean'.
+    ``select`` under 'mean' without ``Selection.prepare_mean``.
 
     Images whose combined score is -inf (a NaN token under min / mean)
     are never returned; missing entries are (-inf, -1).  ``weights`` is used only when ``bank`` is a plain tensor: a TokenBank
