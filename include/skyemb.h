@@ -764,6 +764,47 @@ int skyemb_cosine_topk_tokens_mean_prefiltered_sel(const float *tw, const float 
                                                    int D, int k, int combine, float eps, int64_t idx_offset, const float *thr0, void *ws,
                                                    int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, const void *pooled_sel,
                                                    void *stream);
+/* Weighted MSE over a resident 16-bit token bank in the same two stages (additive to ABI version 111): the many-query form of
+ * skyemb_distance_token_topk with metric SKYEMB_METRIC_MSE, combine min | max, shared weights c [D], no top_t, no selection.
+ * Scores are the distance contract's below ("weighted MSE / MAE": 16 partial sums, four folds, one division), keys are
+ * key = -dist; out_s [Q, k] holds KEYS (descending; the caller negates), out_i the images, order (key desc, image asc), missing
+ * entries (-inf, -1): bit for bit skyemb_distance_token_topk + skyemb_topk_merge over the same bank.
+ * In real arithmetic D dist = A_q + B_r - 2 (c o t_q) . x_r with A_q = sum c_d t_d^2, B_r = sum c_d x_d^2: one dot product with
+ * tw = fl(c o t), which stage 1 multiplies on the 16-bit matrix cores under the resident bound above,
+ *   |dot^ - 2^-f sum tw_d x_d| <= eps_mse ||q'|| nx,   eps_mse = eps_a (resident, dtype, hi | hi + lo) + 2^-22 (tw's own rounding),
+ * so D dist_real >= A_dn + B_dn - 2 2^f (dot^ + eps_mse ||q'|| nx) with A_dn, B_dn the fp32 sums lowered by D 2^-22 relative (0 below
+ * 2^-100).  With c >= 0 every term of the contract's sum is non-negative, so its n = 4 ceil(D / 64) + 9 roundings (the subtraction,
+ * square, product, the additions into a partial, four folds, the division) each move it by at most 2^-24 relative: a token can
+ * reach the distance threshold theta only if that lower bound is <= D theta (1 + gamma) + 2^-126, gamma = (4 ceil(D / 64) + 12) 2^-24.
+ * Distance min: an image is a candidate when SOME token can (key-space max); distance max: when EVERY token can (key-space min).
+ * Every candidate image's P tokens are re-scored by the contract's chain after each slice, which makes the threshold exact.
+ *   skyemb_token_mse_prefilter_applicable   1 / 0 (+ text): the shape rule of skyemb_token_prefilter_applicable
+ *   skyemb_token_mse_prefilter_eps / _gamma eps_mse (lo: 0 hi only, 1 hi + lo) and gamma, before the (1 + 1e-6) raise: host arithmetic
+ *   skyemb_token_mse_rowp   one launch per (bank, c): rowp [skyemb_bank16_rowp_rows(R), 4] over the R = N P flat rows, row i =
+ *                           {B_dn, nx, 1, 0}: B_dn the lower bound of B_r under this c, nx the norm slot of skyemb_resident_rowp
+ *                           (rounded up; fp16: + sqrt(nsub) 2^-14 / eps_mse; bf16: rule (R)); an unboundable row -- an inf / NaN
+ *                           element, a bf16 element outside [2^-60, 2^120), B^ negative, not finite or >= 2^36 (fp16) / 2^96
+ *                           (bf16) -- holds {0, inf, 1, 0}: a candidate of every query; padding rows the sentinel {0, NaN, 0, 0};
+ *                           tail (NULL when R % 256 == 0): the zero-padded tile [256, D] of the last R % 256 rows.
+ *   skyemb_distance_topk_tokens_prefiltered   c [D], t [Q, D] the raw queries (both 16-byte aligned), rowp / tail those of
+ *                           skyemb_token_mse_rowp for this c, combine the DISTANCE combine (min | max; anything else is
+ *                           refused); thr0 NULL or [Q] floors of the k-th best KEY; ws: skyemb_token_prefilter_ws_bytes(Q, D, k).
+ *                           It plans as the request {SKYEMB_PF_TOKENS, combine = the key-space code (min -> max, max -> min)} of
+ *                           skyemb_prefilter_plan for the variant, the slices and the stage-1 instances.  Three launch values are NOT
+ *                           the plan's: stage 1's eps is eps_mse (skyemb_token_mse_prefilter_eps), not eps_a / eps_a_f32; the token
+ *                           re-score takes lds_close + 4 D bytes of dynamic LDS (c [D] beside t) and its limit is raised to
+ *                           lds_close_limit + 16384; gfac (-1 in the plan) carries gamma.  redo[q] != 0: a full candidate list, tw = 0, a scale 2^-f outside (0, 2^90)
+ *                           (fp16) / (2^-100, 2^30) (bf16), A_q not finite, a test parameter outside fp32's range, or any c_d
+ *                           negative, NaN or above 2^10 (then every query): the caller runs the query through
+ *                           skyemb_distance_token_topk. */
+int skyemb_token_mse_prefilter_applicable(int Q, int64_t N, int P, int D, int k);
+double skyemb_token_mse_prefilter_eps(int D, int lo, int dtype);
+double skyemb_token_mse_prefilter_gamma(int D);
+int skyemb_token_mse_rowp(const void *bank16, int dtype, const float *c, int64_t R, int D, float *rowp, void *tail, void *stream);
+int skyemb_distance_topk_tokens_prefiltered(const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp,
+                                            const void *tail, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
+                                            const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
+                                            void *stream);
 /* Read-only query of the launch plan of every two-stage search above (csrc/prefilter_plan.h): what the entry point serving `req`
  * decides on the host -- variant, slices, kernel instances, LDS bytes -- and then launches.  Host arithmetic only, touches no device.
  * Returns 0 and fills *out, or 1 with the text (skyemb_last_error) and under the name of the entry point that would refuse the

@@ -209,7 +209,15 @@ def main():
                 scores, idx = search.cosine_topk_tokens(queries, tokens, min(k, bank.shape[0]), combine=args.combine,
                                                         weights=w, top_t=args.n_top_sims, select=select)
             else:
-                scores, idx = search.distance_topk_tokens(queries, bank, min(k, bank.shape[0]), metric=args.metric,
+                tokens = bank
+                kk = min(k, bank.shape[0])
+                if (bank.dtype != torch.float32 and bank.data_ptr() % 16 == 0
+                        and search.token_mse_route_refusal(queries.shape[0], *bank.shape, kk, args.metric, args.combine, args.n_top_sims,
+                                                           select is not None, args.per_target) is None):
+                    # many targets under weighted MSE over a 16-bit bank, and the two-stage route will take them (decided first: the
+                    # wrapper costs a norm pass over the bank that the distance route never reads): identical results by contract
+                    tokens = search.TokenBank.resident(bank, w)
+                scores, idx = search.distance_topk_tokens(queries, tokens, min(k, bank.shape[0]), metric=args.metric,
                                                           combine=args.combine, weights=w, top_t=args.n_top_sims, select=select)
         ds = test_dataloader.dataset
 

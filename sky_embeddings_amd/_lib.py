@@ -247,6 +247,13 @@ PROTOTYPES = {
     "skyemb_cosine_topk_tokens_mean_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32,
                                                                c_i32, c_i32, c_i32, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                                                c_vp]),
+    # weighted MSE (min | max) over a resident 16-bit token bank in the same two stages: additive again
+    "skyemb_token_mse_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),
+    "skyemb_token_mse_prefilter_eps": (c_f64, [c_i32, c_i32, c_i32]),
+    "skyemb_token_mse_prefilter_gamma": (c_f64, [c_i32]),
+    "skyemb_token_mse_rowp": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "skyemb_distance_topk_tokens_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64,
+                                                        c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -32,6 +32,7 @@
 // the single-c call with that row.  LDS: 8 Q D <= 128 D for t and c, so these calls answer to skyemb_cosine_token_pq_applicable.
 #include "topk_stream.h"
 #include "token_combine.h"
+#include "distance_chain.h"
 
 #pragma clang fp contract(off)
 
@@ -61,13 +62,7 @@ __device__ __forceinline__ float4 row4<f16_t>(const f16_t *p) {
     return v;
 }
 
-// p = p + c * v(x - t): sub, abs or square, times c, add -- four roundings (abs is exact), no fma
-template <int METRIC>
-__device__ __forceinline__ float dist_term(float p, float x, float t, float c) {
-    const float d = __fsub_rn(x, t);
-    const float v = METRIC == SKYEMB_METRIC_MSE ? __fmul_rn(d, d) : fabsf(d);
-    return __fadd_rn(p, __fmul_rn(c, v));
-}
+// (the chain's term, its folds and its division: distance_chain.h, shared with the two-stage MSE search's re-score)
 
 // KCOMBINE is the combine in KEY space (see the head of this file); the other switches are cosine_token_kernel's.
 // c [D] (PQC: [Q, D]), t [Q, D]; LDS: t, (PQC: c,) then [DWAVES][Q][k] list scores and [DWAVES][Q][k] list images.
@@ -186,12 +181,7 @@ __global__ __launch_bounds__(DWAVES * 64) void distance_token_kernel(const float
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
                         if (q >= Q) continue;                       // wave-uniform
-                        float v = p[q];
-                        v = __fadd_rn(v, lane_xor(v, 8));
-                        v = __fadd_rn(v, lane_xor(v, 4));
-                        v = __fadd_rn(v, lane_xor(v, 2));
-                        v = __fadd_rn(v, lane_xor(v, 1));
-                        const float dist = __fdiv_rn(v, fD);
+                        const float dist = dist_finish(dist_fold_lanes(p[q]), fD);
                         const float kq = (row_ok && dist == dist) ? -dist : -INFINITY;
                         const float got = __shfl(kq, from_lane, 64);
                         if (mine && g == (q >> 2)) key[q & 3] = got;

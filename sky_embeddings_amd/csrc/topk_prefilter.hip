@@ -83,6 +83,7 @@
 #include "common.h"
 #include "prefilter_plan.h"
 #include "token_combine.h"
+#include "distance_chain.h"
 #include <array>
 #include <math.h>
 #include <stdlib.h>
@@ -1551,6 +1552,244 @@ __device__ __forceinline__ float4 mean_test_row(float tau, float4 qb, float gfac
     return test_row(a, -g, qb.y);
 }
 
+// ---- Weighted MSE (skyemb_token_mse_rowp / skyemb_distance_topk_tokens_prefiltered): the distance contract's MSE over the same bank ----
+// Contract (include/skyemb.h, distance_chain.h): dist = (1/D) sum_d c_d (x_d - t_d)^2, c = fp32(w / sum w) shared by all queries, every
+// operation rounded on its own, 16 partial sums / 4 folds / one division; keys are key = -dist, so distance 'min' is the key-space
+// MAX fold (an image is a candidate when SOME token can reach the threshold) and distance 'max' the MIN fold (EVERY token must).
+// In real arithmetic  D dist = A_q + B_r - 2 G,  A_q = sum c_d t_d^2,  B_r = sum c_d x_d^2,  G = sum (c_d t_d) x_d: ONE dot product of the
+// row with tw = fl(c o t), the operand shape of the cosine search.  Stage 1 multiplies q' = tw 2^-f, split hi / lo exactly as
+// query16_kernel splits it, by the stored rows; the file header's bound holds against the real sum, |dot^ - 2^-f sum tw_d x_d| <=
+// eps_a ||q'|| ||x|| (its accumulation term prices dot^ against the real sum and then adds the chain's own roundings), and
+//   eps_mse = eps_a (resident fp16 / bf16, hi or hi + lo) + 2^-22
+// pays for tw itself: tw_d = c_d t_d (1 + d), |d| <= 2^-24, or an absolute 2^-150 where the product is subnormal -- against ||tw|| >=
+// 2^-77 (fp16, scale below 2^90) or 2^-51 (bf16, scale below 2^30) that is below sqrt(D) 2^-73 ||tw|| ||x||.  Hence
+//   D dist_real >= A_dn + B_dn - 2 2^f (dot^ + eps_mse ||q'|| nx) =: L,    nx the row's norm slot (>= ||x||, with the fp16 subnormal term)
+// with A_dn <= A_q and B_dn <= B_r: the fp32 sums of D non-negative terms (c >= 0) are within (D + 3) 2^-24 of the real ones in any
+// order, so A_dn = A^ (1 - D 2^-22) and B_dn = B^ (1 - D 2^-22), and 0 when the sum is below 2^-100 (where subnormal terms could have
+// rounded UP by an absolute D 2^-150).
+// The contract's own roundings: with c >= 0 every term and every partial sum is non-negative, so each of the chain's roundings moves
+// the value by at most 2^-24 relative.  Counted along the longest path to the result: the subtraction, whose error is squared (2), the
+// square (1), the product with c (1); the additions into a partial -- partial j takes EVERY element with (d >> 2) & 15 == j, four per
+// 64-element step, so m = 4 ceil(D / 64) terms (D / 16 when 64 | D) and at most m rounded additions; four folds; one division:
+// n = m + 9 = 4 ceil(D / 64) + 9 (17 at D = 128, 57 at D = 768), dist^ >= dist_real (1 - 2^-24)^n -- and squares or products that
+// underflow lose at most (1 + c_d) 2^-149 each, in all below 2^-126 for c_d <= 2^10.  A token can reach the distance threshold
+// theta = -tau only if dist^ <= theta, hence only if  L <= D theta (1 + gamma) + 2^-126,  gamma = (4 ceil(D / 64) + 12) 2^-24  (raised):
+// (1 - 2^-24)^-n <= 1 + (n + 3) 2^-24 for every n <= 265, i.e. D <= 4096.
+// The test is the instruction of prefilter_kernel as it stands, t = dot^ - a R0 + c R1 + g R2 >= 0 with
+//     rowp[i] = {B_dn, nx, 1, 0}      qpar[q] = {-a, c, g, 0},  a = 2^-(f+1) (lowered),  c = eps_mse ||q'|| (raised),
+//                                                              g = 2^-(f+1) (D theta (1 + gamma) + 2^-126 - A_dn) (raised)
+// each by 2^-19 relative for the instruction's own fp32 chain (prefilter_kernel's argument: the slack covers it term by term).  So
+// stage 1 runs the TOK instances unchanged; only the constants differ.
+// A row is UNBOUNDABLE -- {0, inf, 1, 0}: a candidate of every query, decided by stage 2 -- when it has an inf / NaN element (bf16: a
+// nonzero element outside [2^-60, 2^120)), or when B^ is not a finite number below 2^36 (fp16) / 2^96 (bf16) or is negative: with
+// the query windows below a R0 then stays finite.  A query is flagged (redo: the grouped search answers it) when tw is zero, its
+// scale 2^-f is outside (0, 2^90) (fp16) / (2^-100, 2^30) (bf16), A^ is not finite, g is not finite, or ANY c_d is negative, NaN or
+// above 2^10 -- then every query is flagged, since no row constant is a bound.
+__host__ __device__ inline double eps_mse_of(int D, bool lo, bool bf) { return (bf ? eps_a_bf16_of(D, lo) : eps_a_of(D, lo, true)) + 0x1p-22; }
+__host__ __device__ inline double gamma_mse_of(int D) { return (4 * ((D + 63) / 64) + 12) * 0x1p-24; }
+constexpr int MSE_SCALE_HI_F16 = 90, MSE_B_HI_F16 = 36, MSE_B_HI_BF16 = 96;
+
+// the query's row of the test's A operand under MSE (see above); qb = {A_dn, eps_mse ||q'||, 2^-f, flag}; *bad: g left fp32's range
+__device__ __forceinline__ float4 mse_test_row(float tau, float4 qb, float fD, float gamma, bool *bad) {
+    const float theta = tau > -3.0e38f ? -tau : 3.0e38f;       // the distance threshold; no threshold yet: everything passes
+    float T = theta * fD;
+    T = fmaf(fabsf(T), gamma, T) + 0x1p-126f;                  // D theta (1 + gamma) + 2^-126 (the slack below covers these roundings)
+    if (!(T < 3.0e38f)) T = 3.0e38f;
+    const float h = 0.5f * qb.z;                               // 2^-(f+1), exact
+    float g = h * (T - qb.x);
+    g += fabsf(g) * 0x1p-19f;
+    if (g > 3.0e38f) g = 3.0e38f;                              // no threshold yet (or a loose one times a large scale): a R0 < 2^125, all pass
+    *bad = !(g >= -3.0e38f);                                   // -inf or NaN: the test of an unboundable row would not be a number
+    return make_float4(-(h - h * 0x1p-19f), qb.y * (1.0f + 0x1p-19f), g, 0.f);
+}
+
+// eight consecutive elements of a 16-bit row as fp32 (exact)
+template <bool BF>
+__device__ __forceinline__ void widen8(const uint4 raw, float (&a)[8]) {
+    const unsigned int u[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (BF) {
+            a[2 * j] = __uint_as_float(u[j] << 16);
+            a[2 * j + 1] = __uint_as_float(u[j] & 0xFFFF0000u);
+        } else {
+            typedef __attribute__((ext_vector_type(2))) _Float16 half2_t;
+            const half2_t h = __builtin_bit_cast(half2_t, u[j]);
+            a[2 * j] = (float)h[0];
+            a[2 * j + 1] = (float)h[1];
+        }
+    }
+}
+
+// Row constants under MSE: one wave per row, 16 bytes per lane and load.  rowp[i] = {B_dn, nx, 1, 0}; nx, the tail tile and the
+// padding sentinel are those of bank16_rowp_lp_kernel (fp16: sub_scale = 2^-14 / eps_mse(hi + lo), raised) and bankbf16_rowp_kernel
+// (bf16: the norm of the row scaled by a power of two, a second pass over the row in L2).  D % 8 == 0.
+template <bool BF>
+__global__ __launch_bounds__(256) void mse_rowp_kernel(const unsigned short *__restrict__ bank, const float *__restrict__ cw, int64_t N, int D,
+                                                        float4 *__restrict__ rowp, int64_t rows_padded, unsigned short *__restrict__ tail,
+                                                        int64_t tail_first, float sub_scale) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows_padded) return;
+    unsigned short *t = tail && row >= tail_first ? tail + (row - tail_first) * D : nullptr;
+    if (row >= N) {
+        if (t)
+            for (int d = lane * 8; d < D; d += 512) *(uint4 *)(t + d) = make_uint4(0u, 0u, 0u, 0u);
+        if (lane == 0) rowp[row] = make_float4(0.f, NAN, 0.f, 0.f);
+        return;
+    }
+    const unsigned short *x = bank + row * D;
+    float B = 0.f, ss = 0.f, nsub = 0.f, bad = 0.f, mx = 0.f;
+    for (int d = lane * 8; d < D; d += 512) {
+        const uint4 raw = *(const uint4 *)(x + d);
+        if (t) *(uint4 *)(t + d) = raw;
+        float a[8];
+        widen8<BF>(raw, a);
+        const float4 c0 = *(const float4 *)(cw + d), c1 = *(const float4 *)(cw + d + 4);
+        const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float m = fabsf(a[j]);
+            if (BF) bad = (!(m < ldexpf(1.0f, BF_ROW_HI)) || (m > 0.f && m < ldexpf(1.0f, -BF_ROW_LO))) ? 1.f : bad;
+            else bad = !(m < INFINITY) ? 1.f : bad;
+            const float sq = a[j] * a[j];                      // exact where it neither overflows nor underflows (window / B^ rule)
+            B = fmaf(c[j], sq, B);
+            if (!BF) {
+                ss += sq;
+                nsub += (m > 0.f && m < 0x1p-14f) ? 1.f : 0.f;
+            }
+            mx = fmaxf(mx, m);
+        }
+    }
+    B = wave_sum(B);
+    bad = wave_max(bad);
+    if (!(B >= 0.f && B < ldexpf(1.0f, BF ? MSE_B_HI_BF16 : MSE_B_HI_F16))) bad = 1.f;
+    if (bad != 0.f) {
+        if (lane == 0) rowp[row] = make_float4(0.f, INFINITY, 1.0f, 0.f);
+        return;
+    }
+    float nx;
+    if (BF) {
+        mx = wave_max(mx);
+        int e = 0;
+        if (mx > 0.f) (void)frexpf(mx, &e);
+        const float s = ldexpf(1.0f, -e);
+        for (int d = lane * 8; d < D; d += 512) {
+            float a[8];
+            widen8<true>(*(const uint4 *)(x + d), a);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss = fmaf(a[j] * s, a[j] * s, ss);
+        }
+        ss = wave_sum(ss);
+        nx = ldexpf(sqrtf(ss) * (1.0f + (float)D * 0x1p-22f) * (1.0f + 0x1p-21f), e);
+    } else {
+        ss = wave_sum(ss);
+        nsub = wave_sum(nsub);                                 // <= D <= 4096: exact
+        nx = fmaf(sqrtf(nsub), sub_scale, sqrtf(ss) * (1.0f + (float)D * 0x1p-22f)) * (1.0f + 0x1p-21f);
+    }
+    if (lane == 0) {
+        const float Bdn = B < 0x1p-100f ? 0.f : B * (1.0f - (float)D * 0x1p-22f);
+        rowp[row] = make_float4(Bdn, nx, 1.0f, 0.f);
+    }
+}
+
+// Queries under MSE: tw = fl(c o t) -> qh, ql exactly as query16_kernel writes them (same scale rule, same padding rows);
+// qbase[q] = {A_dn, eps_mse ||q'|| (1 + D 2^-22), 2^-f, flag}, flag != 0: a weight outside [0, 2^10] or A^ not finite
+template <bool BF>
+__global__ __launch_bounds__(256) void mse_query_kernel(const float *__restrict__ cw, const float *__restrict__ tq, int Q, int D,
+                                                         half_t *__restrict__ qh, half_t *__restrict__ ql, float4 *__restrict__ qbase,
+                                                         float eps_mse) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q) {
+        if (q < (Q + QPAD - 1) / QPAD * QPAD)
+            for (int d = lane * 4; d < D; d += 256) {
+                *(uint2 *)(qh + (int64_t)q * D + d) = make_uint2(0u, 0u);
+                *(uint2 *)(ql + (int64_t)q * D + d) = make_uint2(0u, 0u);
+            }
+        return;
+    }
+    const float *x = tq + (int64_t)q * D;
+    float mx = 0.f, A = 0.f, cbad = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const float4 v = *(const float4 *)(x + d), c = *(const float4 *)(cw + d);
+        const float tv[4] = {v.x, v.y, v.z, v.w}, cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float w = __fmul_rn(cv[j], tv[j]);
+            mx = fmaxf(mx, fabsf(w));
+            A += __fmul_rn(w, tv[j]);
+            cbad = !(cv[j] >= 0.f && cv[j] <= 0x1p10f) ? 1.f : cbad;
+        }
+    }
+    mx = wave_max(mx);
+    A = wave_sum(A);
+    cbad = wave_max(cbad);
+    int e = 0;
+    if (mx > 0.f && mx < INFINITY) {
+        (void)frexpf(mx, &e);
+        e -= BF ? BF_QMAX_EXP : 14;
+    }
+    if (e < -126) e = -126;             // (query16_kernel's clamps: such a query is flagged by mse_state_kernel)
+    if (BF && e > BF_SCALE_LO) e = BF_SCALE_LO;
+    const float s = ldexpf(1.0f, -e);
+    float ss = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const float4 v = *(const float4 *)(x + d), c = *(const float4 *)(cw + d);
+        const float a[4] = {__fmul_rn(c.x, v.x) * s, __fmul_rn(c.y, v.y) * s, __fmul_rn(c.z, v.z) * s, __fmul_rn(c.w, v.w) * s};
+        if (BF) {
+            bf16x4 h, l;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ss = fmaf(a[j], a[j], ss);
+                h[j] = (bf16_t)a[j];
+                l[j] = (bf16_t)(a[j] - (float)h[j]);
+            }
+            *(bf16x4 *)(qh + (int64_t)q * D + d) = h;
+            *(bf16x4 *)(ql + (int64_t)q * D + d) = l;
+            continue;
+        }
+        typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+        half4 h, l;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ss = fmaf(a[j], a[j], ss);
+            h[j] = (half_t)a[j];
+            l[j] = (half_t)(a[j] - (float)h[j]);
+        }
+        *(half4 *)(qh + (int64_t)q * D + d) = h;
+        *(half4 *)(ql + (int64_t)q * D + d) = l;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) {
+        const float nq = sqrtf(ss) * (1.0f + (float)D * 0x1p-22f);
+        const bool flag = cbad != 0.f || !(A >= 0.f && A < INFINITY);
+        const float Adn = !(A >= 0x1p-100f) ? 0.f : A * (1.0f - (float)D * 0x1p-22f);
+        qbase[q] = make_float4(flag ? 0.f : Adn, eps_mse * nq, s, flag ? 1.f : 0.f);
+    }
+}
+
+// init_state_kernel and token_state_kernel under MSE: the first threshold (a floor that is not a number counts as none), empty lists,
+// the first test row, and the queries stage 1 cannot serve (see above)
+__global__ void mse_state_kernel(int Q, int Q_padded, const float *__restrict__ thr0, const float4 *__restrict__ qbase, float fD, float gamma,
+                                 float4 *__restrict__ qpar, float *__restrict__ tau_q, int *__restrict__ cnt, int *__restrict__ rn,
+                                 int *__restrict__ overflow, float scale_lo, float scale_hi) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) {
+        if (q < Q_padded) qpar[q] = make_float4(NAN, NAN, NAN, NAN);   // padding of the last query tile: t = NaN, no pair passes
+        return;
+    }
+    float tau = thr0 ? thr0[q] : -INFINITY;
+    if (!(tau == tau)) tau = -INFINITY;
+    tau_q[q] = tau;
+    cnt[q] = 0;
+    rn[q] = 0;
+    const float4 qb = qbase[q];
+    bool out;
+    qpar[q] = mse_test_row(tau, qb, fD, gamma, &out);
+    overflow[q] = out || qb.w != 0.f || qb.z >= scale_hi || qb.z <= scale_lo || !(qb.y > 0.f && qb.y < 0x1p60f) ? 1 : 0;
+}
+
 // One wave per image: the pooled row and its constants (the derivation above).  tail / tail_first / the padding sentinel: as in
 // bank16_rowp_lp_kernel, with images for rows.  kfac = kappa / eps_m (hi + lo), raised.
 template <bool BF>
@@ -1711,7 +1950,11 @@ __global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, floa
 // skyemb_token_mean_select_gather, so a candidate is a position c in [0, S) of it and the image is map[c]; its token rows are read from
 // the full bank and the keys carry the image, so the lists, the threshold and the result are those of the unmapped search (map is
 // ascending: (score desc, image asc) is (score desc, position asc)).  Without MAP neither map nor S is read.
-template <typename X, bool TOPT = false, bool MAP = false>
+// DIST (the weighted-MSE search, "Weighted MSE" below; fold is TOK_MIN or TOK_MAX in KEY space): tw holds the raw queries t, cw the
+// weights c [D], and a token's score is key = -dist by the distance contract's chain (distance_chain.h; a NaN distance is key -inf);
+// qn, xn and eps are not read, gfac is the widening of the threshold and the next test row is mse_test_row's.  Without DIST cw is
+// not read: the instruction stream of the cosine kernels.
+template <typename X, bool TOPT = false, bool MAP = false, bool DIST = false>
 __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank,
                                                    const float *__restrict__ xn, int64_t N, int D, int lgp, int fold, float gfac, int k,
                                                    float eps, int64_t idx_offset, int cap, const float4 *__restrict__ qbase, int *__restrict__ cnt,
@@ -1719,26 +1962,31 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
                                                    int *__restrict__ rn, float4 *__restrict__ qpar, float *__restrict__ tau_q,
                                                    int *__restrict__ overflow, int final, float *__restrict__ out_s,
                                                    int64_t *__restrict__ out_i, int *__restrict__ redo, int top_t = 0,
-                                                   const int *__restrict__ map = nullptr, int S = 0) {
+                                                   const int *__restrict__ map = nullptr, int S = 0,
+                                                   const float *__restrict__ cw = nullptr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *keys = (unsigned long long *)smem;     // [TOK_KMAX + cap] the running list, then the slice's candidates
     unsigned long long *kept = keys + TOK_KMAX + cap;          // [TOK_KMAX] the new running list
-    float *sq = (float *)(kept + TOK_KMAX);                    // [D] weighted query
+    float *sq = (float *)(kept + TOK_KMAX);                    // [D] weighted query (DIST: the raw query t)
     int *hist = (int *)(sq + D);                               // [260] + two counters
+    float *sc = (float *)(hist + 264);                         // DIST: [D] the weights c (16-byte aligned: 264 ints)
     const int tid = threadIdx.x, q = blockIdx.x;
     const int raw = cnt[q];
     const int n = raw < cap ? raw : cap;
     const int r0 = rn[q];                                      // <= k <= TOK_KMAX
     bool bad = raw > cap;                                      // more candidates than the list holds: the grouped search decides
     for (int d = tid; d < D; d += 256) sq[d] = tw[(int64_t)q * D + d];
+    if constexpr (DIST)
+        for (int d = tid; d < D; d += 256) sc[d] = cw[d];
     unsigned long long *mine = list + (int64_t)q * TOK_KMAX;
     for (int e = tid; e < r0; e += 256) keys[e] = mine[e];
     if (tid == 0) { hist[260] = 0; hist[261] = 0; }
     __syncthreads();
     const int P = 1 << lgp, G = 256 >> lgp;
     const int g = tid >> lgp, p = tid & (P - 1);
-    const float qnv = qn[q];
-    for (int base = 0; base < n; base += G) {                  // (uniform trip count: every lane takes part in the shuffles)
+    float qnv = 0.f;
+    if constexpr (!DIST) qnv = qn[q];
+    for (int base = 0; base < n; base += G) {                // (uniform trip count: every lane takes part in the shuffles)
         const int c = base + g;
         int img = c < n ? cand_i[(int64_t)q * cap + c] : 0;
         if constexpr (MAP) {
@@ -1748,15 +1996,21 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
         if (img < 0 || img >= N) { img = 0; bad = true; }      // never read outside the bank (stage 1 appends images of real rows only)
         const int64_t row = (int64_t)img * P + p;
         const X *x = bank + row * D;
-        float acc = 0.f;
-        for (int d = 0; d < D; d += 4) {                       // explicit fmaf only: the contract's chain, d ascending
-            const float4 v = row4(x + d);
-            acc = fmaf(sq[d], v.x, acc);
-            acc = fmaf(sq[d + 1], v.y, acc);
-            acc = fmaf(sq[d + 2], v.z, acc);
-            acc = fmaf(sq[d + 3], v.w, acc);
+        float s;
+        if constexpr (DIST) {
+            const float dist = dist_row_serial<SKYEMB_METRIC_MSE>([&](int d) { return row4(x + d); }, sq, sc, D);
+            s = dist == dist ? -dist : -INFINITY;              // key space; a NaN distance ranks as distance +inf
+        } else {
+            float acc = 0.f;
+            for (int d = 0; d < D; d += 4) {                   // explicit fmaf only: the contract's chain, d ascending
+                const float4 v = row4(x + d);
+                acc = fmaf(sq[d], v.x, acc);
+                acc = fmaf(sq[d + 1], v.y, acc);
+                acc = fmaf(sq[d + 2], v.z, acc);
+                acc = fmaf(sq[d + 3], v.w, acc);
+            }
+            s = finish_score(acc, qnv, xn[row], eps);          // a NaN score is -inf: out under min and mean, ignored under max
         }
-        float s = finish_score(acc, qnv, xn[row], eps);        // a NaN score is -inf: out under min and mean, ignored under max
         if constexpr (TOPT) {
             const int ln = tid & 63, tp = P < 16 ? P : 16, n16 = ln & 15;
             float v = sort_desc(s, ln & (tp - 1), tp);         // every tile of 16 (or image of P < 16) tokens, descending over its lanes
@@ -1810,7 +2064,11 @@ __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw,
         if (kk == k) tau = fmaxf(tau, unorderable((unsigned int)(kth >> 32)));   // k images decided: their k-th best exact score
         tau_q[q] = tau;
         const float4 qb = qbase[q];
-        if (fold == TOK_MEAN) {
+        if constexpr (DIST) {
+            bool out;
+            qpar[q] = mse_test_row(tau, qb, (float)D, gfac, &out);
+            if (out) overflow[q] = 1;                          // a test parameter left fp32's range: the grouped search decides
+        } else if (fold == TOK_MEAN) {
             bool out;
             qpar[q] = mean_test_row(tau, qb, gfac, &out);
             if (out) overflow[q] = 1;                          // tau qn' left fp32's range: the grouped search decides
@@ -1860,6 +2118,12 @@ __global__ __launch_bounds__(256) void token_rescore_map_lp_kernel(TOKEN_RESCORE
 }
 __global__ __launch_bounds__(256) void token_rescore_map_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const int *__restrict__ map, int S) {
     token_rescore_body<bf16_t, false, true>(TOKEN_RESCORE_PASS, 0, map, S);
+}
+__global__ __launch_bounds__(256) void token_rescore_mse_lp_kernel(TOKEN_RESCORE_PARAMS(half_t), const float *__restrict__ cw) {
+    token_rescore_body<half_t, false, false, true>(TOKEN_RESCORE_PASS, 0, nullptr, 0, cw);
+}
+__global__ __launch_bounds__(256) void token_rescore_mse_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const float *__restrict__ cw) {
+    token_rescore_body<bf16_t, false, false, true>(TOKEN_RESCORE_PASS, 0, nullptr, 0, cw);
 }
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
@@ -2095,6 +2359,7 @@ const void *const RESCORE[3][2] = {{(const void *)rescore_kernel<false>, (const 
 const void *const TOKEN_RESCORE[2][2] = {{(const void *)token_rescore_lp_kernel, (const void *)token_rescore_bf_kernel},     // [topt][bf]
                                          {(const void *)token_rescore_top_lp_kernel, (const void *)token_rescore_top_bf_kernel}};
 const void *const TOKEN_RESCORE_MAP[2] = {(const void *)token_rescore_map_lp_kernel, (const void *)token_rescore_map_bf_kernel};   // [bf]
+const void *const TOKEN_RESCORE_MSE[2] = {(const void *)token_rescore_mse_lp_kernel, (const void *)token_rescore_mse_bf_kernel};   // [bf]
 
 // the pointer arguments of an entry point; NULL where it has none
 struct SearchArgs {
@@ -2117,6 +2382,9 @@ struct SearchArgs {
     const int *map;
     int64_t bank_N;
     const char *who;
+    // weighted MSE (skyemb_distance_topk_tokens_prefiltered; NULL everywhere else): the weights c [D]; tw then holds the raw queries
+    // t, rowp is skyemb_token_mse_rowp's, qn and xn are NULL, and the result is in key space (key = -distance)
+    const float *cw;
 };
 
 int bank_of(int dtype) { return dtype == SKYEMB_BF16 ? SKYEMB_PF_BANK_BF16 : dtype == SKYEMB_F16 ? SKYEMB_PF_BANK_F16 : -1; }
@@ -2226,7 +2494,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
     const char *who = a.who ? a.who : who_of(r);
     const bool rows = r.kind == SKYEMB_PF_ROWS, mean = r.kind == SKYEMB_PF_TOKENS_MEAN;
     SKY_CHECK_ARG(r.bank >= 0, "%s: dtype " RESIDENT_DTYPE_MSG, who, a.dtype);
-    SKY_CHECK_ARG(a.tw && a.qn && a.xn && a.bank16 && a.rowp && a.ws && a.out_s && a.out_i && a.redo &&
+    SKY_CHECK_ARG(a.tw && (a.cw || (a.qn && a.xn)) && a.bank16 && a.rowp && a.ws && a.out_s && a.out_i && a.redo &&
                       (r.bank != SKYEMB_PF_BANK_F32 || a.bank) && (!r.sel || a.tiles) && (!mean || a.pooled), "%s: null argument", who);
     r.lo = lo_of_env();
     skyemb_prefilter_plan_t p;
@@ -2253,17 +2521,28 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
         for (int lo = 0; lo <= 1; ++lo)
             for (int s = rows ? 0 : p.sel; s <= p.sel; ++s)    // (a row search under a selection launches its tail through the non-SEL instance)
                 if (rc == 0) rc = sky_set_lds_limit((const void *)STAGE1[stage1_index(mode, lo, s, p.bf, p.tok, p.cnt)], p.lds_stage1_limit, who);
-    const void *token_rescore = a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
-    if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, p.lds_close_limit, who);
+    const bool mse = a.cw != nullptr;                          // weighted MSE: its own constants and re-score, [D] more floats of LDS for c
+    const void *token_rescore = mse ? TOKEN_RESCORE_MSE[p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
+    const int lds_close = p.lds_close + (mse ? D * 4 : 0), lds_close_limit = p.lds_close_limit + (mse ? 4096 * 4 : 0);
+    const float gamma_mse = (float)(gamma_mse_of(D) * (1.0 + 1e-6));
+    if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, lds_close_limit, who);
     if (rc == 0 && rows && p.sel) rc = sky_set_lds_limit((const void *)SELECT[1], p.lds_close_limit, who);
     if (rc != 0) return rc;
     const dim3 qgrid((unsigned)((p.q_padded + 3) / 4));
-    if (p.bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
+    if (mse) {
+        const float eps_mse = (float)(eps_mse_of(D, p.use_lo, p.bf) * (1.0 + 1e-6));
+        if (p.bf) hipLaunchKernelGGL(mse_query_kernel<true>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, D, w.qh, w.ql, w.qbase, eps_mse);
+        else hipLaunchKernelGGL(mse_query_kernel<false>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, D, w.qh, w.ql, w.qbase, eps_mse);
+        hipLaunchKernelGGL(mse_state_kernel, dim3((unsigned)((p.q_padded + 255) / 256)), dim3(256), 0, st, Q, p.q_padded, a.thr0, (const float4 *)w.qbase,
+                           (float)D, gamma_mse, w.qpar, w.tau, w.cnt, w.nsel, w.overflow, p.bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
+                           ldexpf(1.0f, p.bf ? BF_SCALE_HI : MSE_SCALE_HI_F16));
+    } else if (p.bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
     else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
-    hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((p.q_padded + 255) / 256)), dim3(256), 0, st, Q, p.q_padded, a.thr0, w.qbase, r.eps,
-                       w.qpar, w.tau, w.cnt, w.overflow, p.first_rows, p.bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
-                       p.bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
-    if (!rows)
+    if (!mse)
+        hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((p.q_padded + 255) / 256)), dim3(256), 0, st, Q, p.q_padded, a.thr0, w.qbase, r.eps,
+                           w.qpar, w.tau, w.cnt, w.overflow, p.first_rows, p.bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
+                           p.bf ? ldexpf(1.0f, BF_SCALE_HI) : 0x1p126f);
+    if (!rows && !mse)
         hipLaunchKernelGGL(token_state_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, Q, (const float4 *)w.qbase, w.tau, w.nsel,
                            w.overflow, p.gfac, w.qpar);
     // one stage-1 launch over positions [t0, t1) of `base`: of the live-tile list with the SEL instance, else the bank tiles themselves
@@ -2281,7 +2560,8 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
 #endif
     };
     auto token_rescore_as = [&](auto like, int final, auto... top_t) {               // (top_t: what the instance takes behind redo)
-        launch_like(like, token_rescore, Q, p.lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, a.map ? a.bank_N : r.N, D, p.lgp, p.fold, p.gfac, k, r.eps,
+        launch_like(like, token_rescore, Q, lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, a.map ? a.bank_N : r.N, D, p.lgp, p.fold,
+                    mse ? gamma_mse : p.gfac, k, r.eps,
                     a.idx_offset, p.cap, w.qbase, w.cnt, w.cand_i, list, w.nsel, w.qpar, w.tau, w.overflow, final, a.out_s, a.out_i, a.redo, top_t...);
     };
     // The kernel addresses tile t at base + t * BT rows, so the base handed over for the tail is the one that puts tile T_tail on
@@ -2306,6 +2586,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
                                w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, s.final, w.sel_i, w.nsel, w.bound);
         else if (a.map) token_rescore_as(token_rescore_map_lp_kernel, s.final, a.map, (int)r.N);   // the MAP kernels take map and S last
         else if (p.top_t) token_rescore_as(token_rescore_top_lp_kernel, s.final, p.top_t);      // the TOPT kernels take top_t last
+        else if (mse) token_rescore_as(token_rescore_mse_lp_kernel, s.final, a.cw);                 // the MSE kernels take c last
         else token_rescore_as(token_rescore_lp_kernel, s.final);
     }
     if (rows)
@@ -2459,4 +2740,56 @@ extern "C" int skyemb_cosine_topk_tokens_mean_prefiltered_sel(const float *tw, c
     return search(request(SKYEMB_PF_TOKENS_MEAN, bank_of(dtype), Q, S, P, D, k, combine, 0, eps, thr0),
                   {tw, qn, nullptr, xn, bank16, dtype, tail_sel, pooled_sel, rowp_sel, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
                    map, N, who});
+}
+
+// ---- weighted MSE over a resident token bank (min | max): the constants and the search ("Weighted MSE" above) -----------------------------
+#define TOKEN_MSE_PREFILTER_MSG "many-query weighted-MSE patch-token search: needs P a divisor of 64, D %% 32 == 0, 128 <= D <= 4096, " \
+                                "1 <= k <= %d, k <= N, 2048 <= N * P < 2^31 rows and Q >= 1 (Q=%d N=%lld P=%d D=%d k=%d)"
+extern "C" int skyemb_token_mse_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
+    const bool ok = pfplan::tokens_shape_ok(Q, N, P, D, k);
+    if (!ok) skyemb_set_error(TOKEN_MSE_PREFILTER_MSG, TOK_KMAX, Q, (long long)N, P, D, k);
+    return ok ? 1 : 0;
+}
+
+extern "C" double skyemb_token_mse_prefilter_eps(int D, int lo, int dtype) { return eps_mse_of(D, lo != 0, dtype == SKYEMB_BF16); }
+
+extern "C" double skyemb_token_mse_prefilter_gamma(int D) { return gamma_mse_of(D); }
+
+extern "C" int skyemb_token_mse_rowp(const void *bank16, int dtype, const float *c, int64_t R, int D, float *rowp, void *tail, void *stream) {
+    const char *who = "skyemb_token_mse_rowp";
+    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
+    SKY_CHECK_ARG(bank16 && c && rowp && R > 0 && D > 0 && D % BK == 0 && D <= 4096, "%s: bad arguments", who);
+    SKY_CHECK_ARG(R % BT == 0 || tail, "%s: %lld rows are no whole number of %d-row tiles: a tail tile [%d, D] is needed", who, (long long)R, BT, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(tail) && aligned16(c), "%s: the bank, the tail tile and c must be 16-byte aligned", who);
+    const int64_t padded = skyemb_bank16_rowp_rows(R);
+    const dim3 grid((unsigned)ceil_div64(padded, 4));
+    // fp16: one set of row constants serves both variants: the smaller eps_mse (hi + lo) gives the larger, always valid, term
+    const float sub_scale = (float)(0x1p-14 / eps_mse_of(D, true, false) * (1.0 + 1e-6));
+#define MSE_ROWP_ARGS (const unsigned short *)bank16, c, R, D, (float4 *)rowp, padded, R % BT ? (unsigned short *)tail : nullptr, R / BT * BT, sub_scale
+    if (dtype == SKYEMB_BF16) hipLaunchKernelGGL(mse_rowp_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, MSE_ROWP_ARGS);
+    else hipLaunchKernelGGL(mse_rowp_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, MSE_ROWP_ARGS);
+#undef MSE_ROWP_ARGS
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// (combine is the DISTANCE combine: min -> the key-space MAX fold, max -> the key-space MIN fold; out_s holds keys = -distance)
+extern "C" int skyemb_distance_topk_tokens_prefiltered(const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp,
+                                                       const void *tail, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
+                                                       const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                       int *redo, void *stream) {
+    const char *who = "skyemb_distance_topk_tokens_prefiltered";
+    SKY_CHECK_ARG(c && aligned16(c) && aligned16(t), "%s: c and t must be given and 16-byte aligned", who);
+    SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: this entry combines by min or max "
+                  "(mean is served by skyemb_distance_token_topk)", who, combine);
+    if (!skyemb_token_mse_prefilter_applicable(Q, N, P, D, k)) {
+        char why[512];
+        snprintf(why, sizeof why, "%s", skyemb_last_error());
+        skyemb_set_error("%s: %s", who, why);
+        return 1;
+    }
+    const int key_combine = combine == SKYEMB_COMBINE_MIN ? SKYEMB_COMBINE_MAX : SKYEMB_COMBINE_MIN;
+    return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N, P, D, k, key_combine, 0, 0.f, thr0),
+                  {t, nullptr, nullptr, nullptr, bank16, dtype, tail, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
+                   nullptr, 0, who, c});
 }

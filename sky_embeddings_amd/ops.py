@@ -621,6 +621,53 @@ def cosine_topk_tokens_prefiltered(tw, qn, tokens, xn, tail, rowp, k, combine, e
     return ws
 
 
+def token_mse_prefilter_refusal(Q, N, P, D, k):
+    """None when the two-stage weighted-MSE token search takes the shape, else the library's own statement of its limits.  Host
+    arithmetic only."""
+    L = lib()
+    return None if L.skyemb_token_mse_prefilter_applicable(Q, N, P, D, k) else L.skyemb_last_error().decode()
+
+
+def token_mse_prefilter_eps(D, dtype, lo=False):
+    """eps_mse of the two-stage weighted-MSE search over a ``dtype`` bank (host arithmetic only; include/skyemb.h)."""
+    return lib().skyemb_token_mse_prefilter_eps(D, int(lo), resident_dtype_code(dtype, "token_mse_prefilter_eps"))
+
+
+def token_mse_prefilter_gamma(D):
+    """gamma, the widening of the distance threshold for the contract's own roundings (host arithmetic only; include/skyemb.h)."""
+    return lib().skyemb_token_mse_prefilter_gamma(D)
+
+
+def token_mse_rowp(tokens, c):
+    """(tail, rowp) of the two-stage weighted-MSE search: the row constants of a resident 16-bit token bank ``tokens`` [N, P, D]
+    (or its flat rows [R, D]) under the weights ``c`` [D] (``prepare_distance_weights``), and the zero-padded tail tile [256, D]
+    of the last R % 256 rows (None when there are none).  One launch per (bank, c)."""
+    D = tokens.shape[-1]
+    R = tokens.numel() // D
+    code = resident_dtype_code(tokens.dtype, "token_mse_rowp")
+    assert tokens.is_contiguous() and c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (D,)
+    _check_aligned16(tokens, "token_mse_rowp", "the 16-bit", "must be")
+    rows = lib().skyemb_bank16_rowp_rows(R)
+    rowp = torch.empty(rows, 4, device=tokens.device, dtype=torch.float32)
+    tail = torch.empty(256, D, device=tokens.device, dtype=tokens.dtype) if rows != R else None
+    check(lib().skyemb_token_mse_rowp(_p(tokens), code, _p(c), R, D, _p(rowp), _p(tail), _stream()), "skyemb_token_mse_rowp")
+    return tail, rowp
+
+
+def distance_topk_tokens_prefiltered(c, t, tokens, tail, rowp, k, combine, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """The two-stage many-query weighted-MSE search over a resident 16-bit token bank ``tokens`` [N, P, D] and the (tail, rowp) of
+    ``token_mse_rowp`` under the same ``c``; ``combine``: COMBINE_CODES['min'] or ['max'] of the DISTANCES.  ``out_s`` receives
+    keys = -distance (include/skyemb.h)."""
+    Q, D = t.shape
+    N, P = tokens.shape[:2]
+    code = resident_dtype_code(tokens.dtype, "distance_topk_tokens_prefiltered")
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), t.device)
+    check(lib().skyemb_distance_topk_tokens_prefiltered(_p(c), _p(t), Q, _p(tokens), code, _p(rowp), _p(tail), N, P, D, k, combine,
+                                                        idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
+                                                        _stream()), "skyemb_distance_topk_tokens_prefiltered")
+    return ws
+
+
 def token_mean_prefilter_refusal(Q, N, P, D, k):
     """None when the two-stage token search with combine mean takes the shape, else the library's own statement of its limits."""
     L = lib()

@@ -448,6 +448,7 @@ class TokenBank:
         self._resident = False                             # True: made by TokenBank.resident
         self._stage1 = None                                # (tail tile, rowp) of the two-stage route
         self._stage1_mean = None                           # (pooled image, its tail tile, rowp) of the route under combine 'mean'
+        self._stage1_mse = None                            # (c, tail tile, rowp) of the weighted-MSE route, for the last c seen
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
 
@@ -482,6 +483,17 @@ class TokenBank:
         if self._stage1_mean is None:
             self._stage1_mean = ops.token_mean_pool(self.bank, self.norms)
         return self._stage1_mean
+
+    def stage1_mse(self, c):
+        """(tail, rowp) of ``ops.token_mse_rowp`` under the distance weights ``c`` [D]: what stage 1 of the two-stage weighted-MSE
+        route (``distance_topk_tokens``) reads besides the bank itself -- 16 bytes per token row and one 256-row tail tile.  Kept
+        for the last ``c`` seen: the cache is keyed by the vector itself (compared element by element -- one small device-to-host
+        read per search, next to the redo flags' --, so ``set_weights`` need not clear it); a different vector rebuilds them, one
+        launch over the bank."""
+        held = self._stage1_mse
+        if held is None or not torch.equal(held[0], c):
+            held = self._stage1_mse = (c.clone(), *ops.token_mse_rowp(self.bank, c))
+        return held[1], held[2]
 
     def set_weights(self, weights):
         self._version += 1
@@ -940,16 +952,64 @@ TOKEN_TOPT_PREFILTER_MIN_ELEMENTS = 62500 * 64 * 768      # N P D of the smalles
 TOKEN_TOPT_PREFILTER_MIN_Q_SMALL = 256                     # smaller banks
 
 
+# fewest queries sent through the two-stage weighted-MSE route: the smallest Q of tools/mse_prefilter_crossover.py's grid at which it
+# is at least 10 % faster than the grouped route, row-constants launch included (profiles/mse_prefilter_crossover.json; DESIGN.md
+# section 6, item 22): 2.0x at 64 (1.05x - 1.07x at 32), measured on a bank of 15 625 x 64 x 768 = 0.77e9 elements.  A two-stage call
+# costs about 10 ms there whatever Q is, and that does not shrink with the bank, while a grouped pass does: a bank below the measured
+# size has NOT been measured and waits for the grid's largest Q
+TOKEN_MSE_PREFILTER_MIN_Q = 64
+TOKEN_MSE_PREFILTER_MIN_ELEMENTS = 15625 * 64 * 768       # N P D of the bank the constant above was measured on
+TOKEN_MSE_PREFILTER_MIN_Q_SMALL = 1024                    # smaller banks
+
+
+def _token_mse_prefilter_refusal(rq: TokenRequest):
+    """``_token_prefilter_refusal`` for a distance request over a resident 16-bit bank: None when ``distance_topk_tokens`` serves it
+    by the two-stage route (metric MSE, combine min | max, no top_t, no select, shared weights, P a divisor of 64, the library's
+    shape rule, the switch on, enough queries), else the first reason why the grouped route serves it."""
+    name = next((n for n, code in ops.METRIC_CODES.items() if code == rq.metric), rq.metric_name)
+    return token_mse_route_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k, name, rq.combine, rq.top_t, rq.select is not None,
+                                   rq.per_query)
+
+
+def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=False, per_query=False):
+    """The same decision from the request's plain facts, for a caller that has not wrapped its bank yet (``similarity_search.py``
+    builds a ``TokenBank.resident`` -- a norm pass over the bank -- only when this returns None): ``metric`` a name, ``combine`` a
+    name or an ``ops.COMBINE_CODES`` code, ``top_t`` None / 0 for all tokens, ``select`` whether there is a selection.  The bank is
+    taken to be a 16-byte aligned fp16 / bf16 tensor.  No device work."""
+    combine = ops.COMBINE_CODES.get(combine, combine)
+    if metric != 'MSE':
+        return f"metric {metric} (a distance that is no dot product)"
+    if combine == ops.COMBINE_CODES['mean']:
+        return "combine 'mean' under a distance metric"
+    if top_t:
+        return "top_t under a distance metric"
+    if select:
+        return "select under a distance metric"
+    if per_query:
+        return "per-query weights"
+    if P < 1 or 64 % P:
+        return f"P = {P} does not divide 64"
+    if not _prefilter_enabled():
+        return "SKYEMB_TOPK_PREFILTER=0"
+    if N * P * D >= TOKEN_MSE_PREFILTER_MIN_ELEMENTS:
+        if Q < TOKEN_MSE_PREFILTER_MIN_Q:
+            return f"Q = {Q} < TOKEN_MSE_PREFILTER_MIN_Q = {TOKEN_MSE_PREFILTER_MIN_Q}"
+    elif Q < TOKEN_MSE_PREFILTER_MIN_Q_SMALL:
+        return (f"Q = {Q} < TOKEN_MSE_PREFILTER_MIN_Q_SMALL = {TOKEN_MSE_PREFILTER_MIN_Q_SMALL} (a bank of fewer than "
+                f"TOKEN_MSE_PREFILTER_MIN_ELEMENTS = {TOKEN_MSE_PREFILTER_MIN_ELEMENTS} elements)")
+    return ops.token_mse_prefilter_refusal(Q, N, P, D, k)
+
+
 def _token_prefilter_refusal(rq: TokenRequest):
-    """None when ``cosine_topk_tokens`` serves the request by the two-stage route, else the first reason why the grouped route
-    serves it.  A pure function of the request (and the bank it names): no device work."""
+    """None when ``cosine_topk_tokens`` (a distance request: ``distance_topk_tokens``) serves the request by the two-stage route,
+    else the first reason why the grouped route serves it.  A pure function of the request (and the bank it names): no device work."""
     tb = rq.bank
     if tb is not None and getattr(tb, "dtype", None) == torch.float32:
         return "an fp32 token bank"
     if tb is None or not getattr(tb, "_resident", False):
         return "the bank was not made by TokenBank.resident"
     if rq.metric is not None:
-        return "a distance metric"
+        return _token_mse_prefilter_refusal(rq)
     mean = rq.combine == ops.COMBINE_CODES['mean']
     if rq.top_t != 0 and mean:
         return "top_t under combine 'mean'"
@@ -1152,7 +1212,7 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     first threshold comes from a sample scored under the same ``top_t``, a re-run keeps it, ``stats`` gains ``top_t``, and the
     smallest Q is ``TOKEN_TOPT_PREFILTER_MIN_Q`` (a bank of fewer than ``TOKEN_TOPT_PREFILTER_MIN_ELEMENTS`` elements:
     ``TOKEN_TOPT_PREFILTER_MIN_Q_SMALL``).  Out of scope for the two-stage route: ``top_t`` under 'mean' (the mean of the
-    top_t best is not bounded by a count), per-query weights, the distance metrics, fp32 token banks, P not dividing 64, and
+    top_t best is not bounded by a count), per-query weights, fp32 token banks, P not dividing 64, and
     ``select`` under 'mean' without ``Selection.prepare_mean``.
 
     Images whose combined score is -inf (a NaN token under min / mean)
@@ -1226,6 +1286,41 @@ def distance_pruning_floor(c, t, bank, k: int, metric: str = 'MAE', combine: str
     return _token_floor(_DistanceScorer(tokens, tb, sel, mcode, ccode, tt), (t, c), k, sample_images)
 
 
+def _topk_tokens_mse_prefiltered(rq: TokenRequest, queries, prune, stats, process_group, world_size):
+    """The two-stage driver of ``distance_topk_tokens`` (csrc/topk_prefilter.hip, "Weighted MSE"): the first threshold is
+    ``distance_pruning_floor``'s -- the k-th best key of a strided sample of min(N, max(16 k, 256)) whole images, scored by the
+    grouped kernel in groups of 16 queries, one ulp lower --, then one stage-1 pass for all queries with exact re-scoring after
+    every slice; flagged queries go through the grouped route, those queries only.  Everything runs in key space (key = -distance)
+    until the result is negated on the way out."""
+    tb, Q, k, dev = rq.bank, rq.Q, rq.k, rq.tokens.device
+    q = queries.to(dev, torch.float32).contiguous()
+    c = prepare_distance_weights(rq.weights, rq.D, dev)
+    S = min(rq.N, max(16 * k, 256))
+    st = tb.sample(S, "bootstrap")[0]
+    thr0 = torch.empty(Q, device=dev)
+    keys = torch.empty(16, S, device=dev)
+    for lo in range(0, Q, 16):
+        g = min(16, Q - lo)
+        ops.distance_token_scores(c, q[lo:lo + g], st, rq.metric, rq.combine, keys[:g])
+        ops.kth_largest_floor(keys[:g].neg_(), k, thr0[lo:lo + g])
+    tail, rowp = tb.stage1_mse(c)
+
+    def launch(*out):
+        return ops.distance_topk_tokens_prefiltered(c, q, tb.bank, tail, rowp, k, rq.combine, rq.idx_offset, *out, thr0)
+
+    def rerun(again):                                      # the grouped route, in key space like ``launch``'s result
+        rq2 = dataclasses.replace(rq, Q=int(again.numel()))
+        s2, i2 = _topk_tokens(rq2, _DistanceScorer.of(rq2), q.index_select(0, again), prune, None, None, 1)
+        return s2.neg_(), i2
+
+    out_s, out_i, n_redo = _two_stage(Q, k, dev, launch, rerun)
+    if stats is not None:
+        stats.update(path="prefiltered", redone=n_redo, metric=rq.metric_name,
+                     combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+    _gather_merge(out_s, out_i, Q, k, world_size, process_group)        # (of keys)
+    return out_s.neg_(), out_i                                          # (-inf, -1) becomes (+inf, -1)
+
+
 def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE', combine: str = 'mean',
                          weights: torch.Tensor | None = None, prune: bool = True, stats: dict | None = None, top_t: int | None = None,
                          select=None, process_group=None, world_size: int = 1):
@@ -1242,6 +1337,19 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     (torch would propagate the NaN): 'min' ignores it, 'max' and 'mean' become +inf, as they do for an image with fewer than top_t
     finite token distances; an image whose combined distance is +inf is never returned.  Missing entries are (+inf, -1).
 
+    Two-stage route (``stats['path'] == 'prefiltered'``): metric 'MSE' with ``combine`` 'min' or 'max' over a
+    ``TokenBank.resident(bank)`` (fp16 / bf16), shared weights, no ``top_t``, no ``select``, P a divisor of 64, at least
+    ``TOKEN_MSE_PREFILTER_MIN_Q`` queries (a bank of fewer than ``TOKEN_MSE_PREFILTER_MIN_ELEMENTS`` elements:
+    ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``), a shape the library takes (D % 32 == 0, 128 <= D <= 4096, 2048 <= N P < 2^31, k <= 256,
+    k <= N) and SKYEMB_TOPK_PREFILTER not 0 is searched in ONE pass for all queries: D dist = A_q + B_r - 2 (c o t) . x is one dot
+    product per token, multiplied on the 16-bit matrix cores with a proven error bound next to a per-query and a per-row constant
+    (the row constants: ``TokenBank.stage1_mse``, one launch per bank and weight vector); an image is a candidate when some ('min')
+    / every ('max') token of it can still reach the query's threshold, and every candidate is re-scored by the contract's own
+    chain after each slice of the bank.  Distances and indices are bit for bit those of the grouped route.  ``stats`` gains
+    ``redone`` (queries re-run by the grouped route: a full candidate list, a zero or out-of-range query, a negative or NaN
+    weight) and ``combine``.  Out of scope for the two-stage route, served by the grouped route as ever: metric 'MAE' (no dot
+    product), ``combine`` 'mean', ``top_t``, ``select``, per-query weights, fp32 banks, P not dividing 64.
+
     ``select``, ``prune``, ``stats``, ``world_size``: as for ``cosine_topk_tokens`` (the floor and the merges work on
     key = -distance).  Every ValueError -- an unknown metric or combine, top_t outside 1 .. min(P, 16), k, a selection of
     another length, a shape the kernels do not take -- is raised before the first launch.
@@ -1252,6 +1360,8 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     the queries run in groups of the largest g <= 16 with 128 D + 32 g k <= 163840, as for ``cosine_topk_tokens``;
     ``stats['per_query_weights']`` is True and ``stats['group']`` is g."""
     rq = _token_request("distance_topk_tokens", queries, bank, k, combine, metric, weights, top_t, select, world_size)
+    if _token_prefilter_refusal(rq) is None:
+        return _topk_tokens_mse_prefiltered(rq, queries, prune, stats, process_group, world_size)
     return _topk_tokens(rq, _DistanceScorer.of(rq), queries, prune, stats, process_group, world_size)
 
 
