@@ -765,7 +765,8 @@ int skyemb_cosine_topk_tokens_mean_prefiltered_sel(const float *tw, const float 
                                                    int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, const void *pooled_sel,
                                                    void *stream);
 /* Weighted MSE over a resident 16-bit token bank in the same two stages (additive to ABI version 111): the many-query form of
- * skyemb_distance_token_topk with metric SKYEMB_METRIC_MSE, combine min | max, shared weights c [D], no top_t, no selection.
+ * skyemb_distance_token_topk with metric SKYEMB_METRIC_MSE, combine min | max, shared weights c [D], no top_t, no selection (those: the
+ * _top / _sel / _top_sel forms below).
  * Scores are the distance contract's below ("weighted MSE / MAE": 16 partial sums, four folds, one division), keys are
  * key = -dist; out_s [Q, k] holds KEYS (descending; the caller negates), out_i the images, order (key desc, image asc), missing
  * entries (-inf, -1): bit for bit skyemb_distance_token_topk + skyemb_topk_merge over the same bank.
@@ -805,6 +806,47 @@ int skyemb_distance_topk_tokens_prefiltered(const float *c, const float *t, int 
                                             const void *tail, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
                                             const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
                                             void *stream);
+/* The weighted-MSE search above under top_t and under a SELECTION of the bank's images (additive to ABI version 111): the many-query
+ * forms of skyemb_distance_token_topk with top_t and with selection words, bit for bit.  The argument lists are those of the cosine
+ * _top / _sel / _top_sel entries with c, t in place of tw, qn, xn and eps (rowp before tail, as in the plain MSE call).
+ * Key space (key = -distance), with a[0] <= a[1] <= ... the token distances of an image, a NaN distance ranking as +inf (key -inf, last):
+ *   top_t == 0               IS the plain call: same checks, same kernels.
+ *   min, any top_t           IS the plain min call (a[0] does not depend on top_t).
+ *   max, top_t == P          IS the plain max call (a[P-1] is the max).
+ *   max, 1 <= top_t < P      a[top_t-1] is the top_t-th LARGEST key: key-space 'min' under top_t.  It reaches the threshold only when at
+ *                            least top_t rows of the image pass the MSE row test, so stage 1 runs the counting fold (top_t == 1: some
+ *                            row passes), and stage 2 computes the P token keys by the distance contract's chain, sorts them by
+ *                            skyemb_distance_token_topk's own network and takes the top_t-th.  An image with fewer than top_t finite
+ *                            token distances scores +inf (key -inf) and is never returned.
+ *   mean                     refused with a text: the grouped search serves it.
+ * They plan as the requests {SKYEMB_PF_TOKENS, key-space combine, top_t (0 under distance min), sel} of skyemb_prefilter_plan -- the
+ * plans of the cosine _top / _sel entries of the same shape -- with the three launch values of the plain MSE call (eps_mse, lds_close +
+ * 4 D, gamma in gfac).
+ * Selection: skyemb_token_prefilter_select_prepare is applied to the rowp of skyemb_token_mse_rowp as it stands.  Its kernel writes
+ * the padding sentinel {0, NaN, 0, 0} into every row of a deselected image whatever rowp held there, the unboundable {0, inf, 1, 0}
+ * included; and the sentinel fails the MSE row test under both folds: t = dot^ - a 0 + c NaN + g 0 is NaN, no pass bit is set, so the row
+ * neither opens the OR fold nor counts.  A selected image keeps its constants, an unboundable row of it stays a candidate of every
+ * query and is decided by stage 2, which re-scores candidates exactly as the unselected call does (they are images of the whole bank).
+ * n_live, last_live, direct_end, tiles: as for skyemb_cosine_topk_tokens_prefiltered_sel (1 <= n_live <= ceil(N P / 256), at least one
+ * live WHOLE tile, 1 <= direct_end <= n_live); thr0: a floor of the k-th best key UNDER THE SAME top_t over a sample of SELECTED images.
+ * Refusals (before any launch, under the entry's name): mean, top_t outside 0 .. min(P, 16), the shape rule, the selection's limits.
+ * redo[q] as for the plain MSE call: the caller re-runs the query through skyemb_distance_token_topk with the same top_t and words.
+ *   skyemb_token_mse_topt_prefilter_applicable   skyemb_token_mse_prefilter_applicable's shape rule, combine min or max and
+ *                            1 <= top_t <= min(P, 16); a refusal leaves its reason as the error text. */
+int skyemb_token_mse_topt_prefilter_applicable(int Q, int64_t N, int P, int D, int k, int combine, int top_t);
+int skyemb_distance_topk_tokens_prefiltered_top(const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp,
+                                                const void *tail, int64_t N, int P, int D, int k, int combine, int top_t,
+                                                int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                int64_t *out_i, int *redo, void *stream);
+int skyemb_distance_topk_tokens_prefiltered_sel(const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp_sel,
+                                                const void *tail, const int *tiles, int n_live, int last_live, int direct_end, int64_t N,
+                                                int P, int D, int k, int combine, int64_t idx_offset, const float *thr0, void *ws,
+                                                int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream);
+int skyemb_distance_topk_tokens_prefiltered_top_sel(const float *c, const float *t, int Q, const void *bank16, int dtype,
+                                                    const float *rowp_sel, const void *tail, const int *tiles, int n_live, int last_live,
+                                                    int direct_end, int64_t N, int P, int D, int k, int combine, int top_t,
+                                                    int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
+                                                    int64_t *out_i, int *redo, void *stream);
 /* Read-only query of the launch plan of every two-stage search above (csrc/prefilter_plan.h): what the entry point serving `req`
  * decides on the host -- variant, slices, kernel instances, LDS bytes -- and then launches.  Host arithmetic only, touches no device.
  * Returns 0 and fills *out, or 1 with the text (skyemb_last_error) and under the name of the entry point that would refuse the

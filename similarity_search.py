@@ -213,10 +213,17 @@ def main():
                 kk = min(k, bank.shape[0])
                 if (bank.dtype != torch.float32 and bank.data_ptr() % 16 == 0
                         and search.token_mse_route_refusal(queries.shape[0], *bank.shape, kk, args.metric, args.combine, args.n_top_sims,
-                                                           select is not None, args.per_target) is None):
+                                                           select is not None, args.per_target, top_t_prepared=True,
+                                                           select_prepared=True,
+                                                           selected=None if select is None else select.count) is None):
                     # many targets under weighted MSE over a 16-bit bank, and the two-stage route will take them (decided first: the
-                    # wrapper costs a norm pass over the bank that the distance route never reads): identical results by contract
+                    # wrapper costs a norm pass over the bank that the distance route never reads): identical results by contract.
+                    # -nts and --bank-select-snr take that route by opt-in, asked for here
                     tokens = search.TokenBank.resident(bank, w)
+                    if args.n_top_sims:
+                        tokens.prepare_mse_top_t()
+                    if select is not None:
+                        select.prepare_mse(tokens)
                 scores, idx = search.distance_topk_tokens(queries, tokens, min(k, bank.shape[0]), metric=args.metric,
                                                           combine=args.combine, weights=w, top_t=args.n_top_sims, select=select)
         ds = test_dataloader.dataset

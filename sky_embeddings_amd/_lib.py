@@ -254,6 +254,15 @@ PROTOTYPES = {
     "skyemb_token_mse_rowp": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "skyemb_distance_topk_tokens_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64,
                                                         c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    # ... under top_t and under a selection of images: the cosine _top / _sel lists with c, t in place of tw, qn, xn, eps
+    "skyemb_token_mse_topt_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "skyemb_distance_topk_tokens_prefiltered_top": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                            c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_distance_topk_tokens_prefiltered_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i32,
+                                                            c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_distance_topk_tokens_prefiltered_top_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64,
+                                                                c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                                c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -1954,6 +1954,10 @@ __global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, floa
 // weights c [D], and a token's score is key = -dist by the distance contract's chain (distance_chain.h; a NaN distance is key -inf);
 // qn, xn and eps are not read, gfac is the widening of the threshold and the next test row is mse_test_row's.  Without DIST cw is
 // not read: the instruction stream of the cosine kernels.
+// DIST with TOPT (distance 'max' under top_t, the `_top` entries of the MSE search; fold is TOK_MIN): with a[0] <= a[1] <= ... an image's
+// token distances, a[top_t - 1] is the top_t-th LARGEST key, so the keys go through the same network and top_finish<MIN>: bit for bit
+// distance_token_kernel's value, which sorts the same keys by the same functions.  A NaN distance is key -inf and sorts last; fewer
+// than top_t finite distances: key -inf, never returned.
 template <typename X, bool TOPT = false, bool MAP = false, bool DIST = false>
 __device__ __forceinline__ void token_rescore_body(const float *__restrict__ tw, const float *__restrict__ qn, const X *__restrict__ bank,
                                                    const float *__restrict__ xn, int64_t N, int D, int lgp, int fold, float gfac, int k,
@@ -2124,6 +2128,12 @@ __global__ __launch_bounds__(256) void token_rescore_mse_lp_kernel(TOKEN_RESCORE
 }
 __global__ __launch_bounds__(256) void token_rescore_mse_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const float *__restrict__ cw) {
     token_rescore_body<bf16_t, false, false, true>(TOKEN_RESCORE_PASS, 0, nullptr, 0, cw);
+}
+__global__ __launch_bounds__(256) void token_rescore_mse_top_lp_kernel(TOKEN_RESCORE_PARAMS(half_t), int top_t, const float *__restrict__ cw) {
+    token_rescore_body<half_t, true, false, true>(TOKEN_RESCORE_PASS, top_t, nullptr, 0, cw);
+}
+__global__ __launch_bounds__(256) void token_rescore_mse_top_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), int top_t, const float *__restrict__ cw) {
+    token_rescore_body<bf16_t, true, false, true>(TOKEN_RESCORE_PASS, top_t, nullptr, 0, cw);
 }
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
@@ -2359,7 +2369,8 @@ const void *const RESCORE[3][2] = {{(const void *)rescore_kernel<false>, (const 
 const void *const TOKEN_RESCORE[2][2] = {{(const void *)token_rescore_lp_kernel, (const void *)token_rescore_bf_kernel},     // [topt][bf]
                                          {(const void *)token_rescore_top_lp_kernel, (const void *)token_rescore_top_bf_kernel}};
 const void *const TOKEN_RESCORE_MAP[2] = {(const void *)token_rescore_map_lp_kernel, (const void *)token_rescore_map_bf_kernel};   // [bf]
-const void *const TOKEN_RESCORE_MSE[2] = {(const void *)token_rescore_mse_lp_kernel, (const void *)token_rescore_mse_bf_kernel};   // [bf]
+const void *const TOKEN_RESCORE_MSE[2][2] = {{(const void *)token_rescore_mse_lp_kernel, (const void *)token_rescore_mse_bf_kernel},   // [topt][bf]
+                                             {(const void *)token_rescore_mse_top_lp_kernel, (const void *)token_rescore_mse_top_bf_kernel}};
 
 // the pointer arguments of an entry point; NULL where it has none
 struct SearchArgs {
@@ -2382,8 +2393,9 @@ struct SearchArgs {
     const int *map;
     int64_t bank_N;
     const char *who;
-    // weighted MSE (skyemb_distance_topk_tokens_prefiltered; NULL everywhere else): the weights c [D]; tw then holds the raw queries
-    // t, rowp is skyemb_token_mse_rowp's, qn and xn are NULL, and the result is in key space (key = -distance)
+    // weighted MSE (skyemb_distance_topk_tokens_prefiltered and its _top / _sel / _top_sel forms; NULL everywhere else): the weights
+    // c [D]; tw then holds the raw queries t, rowp is skyemb_token_mse_rowp's (under a selection: its masked copy), qn and xn are NULL,
+    // and the result is in key space (key = -distance)
     const float *cw;
 };
 
@@ -2522,7 +2534,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
             for (int s = rows ? 0 : p.sel; s <= p.sel; ++s)    // (a row search under a selection launches its tail through the non-SEL instance)
                 if (rc == 0) rc = sky_set_lds_limit((const void *)STAGE1[stage1_index(mode, lo, s, p.bf, p.tok, p.cnt)], p.lds_stage1_limit, who);
     const bool mse = a.cw != nullptr;                          // weighted MSE: its own constants and re-score, [D] more floats of LDS for c
-    const void *token_rescore = mse ? TOKEN_RESCORE_MSE[p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
+    const void *token_rescore = mse ? TOKEN_RESCORE_MSE[p.top_t != 0][p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
     const int lds_close = p.lds_close + (mse ? D * 4 : 0), lds_close_limit = p.lds_close_limit + (mse ? 4096 * 4 : 0);
     const float gamma_mse = (float)(gamma_mse_of(D) * (1.0 + 1e-6));
     if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, lds_close_limit, who);
@@ -2585,6 +2597,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
             hipLaunchKernelGGL(SELECT[p.sel], dim3((unsigned)Q), dim3(256), p.lds_close, st, Q, k, p.cap, r.eps, w.qbase, (const float4 *)a.rowp, a.xn,
                                w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, s.final, w.sel_i, w.nsel, w.bound);
         else if (a.map) token_rescore_as(token_rescore_map_lp_kernel, s.final, a.map, (int)r.N);   // the MAP kernels take map and S last
+        else if (mse && p.top_t) token_rescore_as(token_rescore_mse_top_lp_kernel, s.final, p.top_t, a.cw);   // MSE under top_t: top_t, then c
         else if (p.top_t) token_rescore_as(token_rescore_top_lp_kernel, s.final, p.top_t);      // the TOPT kernels take top_t last
         else if (mse) token_rescore_as(token_rescore_mse_lp_kernel, s.final, a.cw);                 // the MSE kernels take c last
         else token_rescore_as(token_rescore_lp_kernel, s.final);
@@ -2774,11 +2787,13 @@ extern "C" int skyemb_token_mse_rowp(const void *bank16, int dtype, const float 
 }
 
 // (combine is the DISTANCE combine: min -> the key-space MAX fold, max -> the key-space MIN fold; out_s holds keys = -distance)
-extern "C" int skyemb_distance_topk_tokens_prefiltered(const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp,
-                                                       const void *tail, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
-                                                       const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
-                                                       int *redo, void *stream) {
-    const char *who = "skyemb_distance_topk_tokens_prefiltered";
+// One body for the plain call and its _top / _sel / _top_sel forms.  In key space distance 'max' under top_t is 'min' under top_t (the
+// top_t-th largest key: the counting fold, the TOPT re-score); distance 'min' is a[0] whatever top_t says, the plain call.  The request
+// is the cosine one of the same shape, so the planner decides top_t == P and the selection's limits as it does there.
+namespace {
+int mse_search(const char *who, const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp, const void *tail,
+               const int *tiles, bool sel, int n_live, int last_live, int direct_end, int64_t N, int P, int D, int k, int combine, int top_t,
+               int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo, void *stream) {
     SKY_CHECK_ARG(c && aligned16(c) && aligned16(t), "%s: c and t must be given and 16-byte aligned", who);
     SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: this entry combines by min or max "
                   "(mean is served by skyemb_distance_token_topk)", who, combine);
@@ -2788,8 +2803,63 @@ extern "C" int skyemb_distance_topk_tokens_prefiltered(const float *c, const flo
         skyemb_set_error("%s: %s", who, why);
         return 1;
     }
+    SKY_CHECK_ARG(top_t >= 0 && top_t <= (P < 16 ? P : 16), "%s: top_t must be 0 (all tokens) or 1 .. min(P, 16) (top_t=%d P=%d)", who, top_t, P);
     const int key_combine = combine == SKYEMB_COMBINE_MIN ? SKYEMB_COMBINE_MAX : SKYEMB_COMBINE_MIN;
-    return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N, P, D, k, key_combine, 0, 0.f, thr0),
-                  {t, nullptr, nullptr, nullptr, bank16, dtype, tail, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
+    return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N, P, D, k, key_combine, key_combine == SKYEMB_COMBINE_MIN ? top_t : 0, 0.f, thr0,
+                          sel, n_live, last_live, direct_end),
+                  {t, nullptr, nullptr, nullptr, bank16, dtype, tail, nullptr, rowp, tiles, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
                    nullptr, 0, who, c});
+}
+}  // namespace
+
+extern "C" int skyemb_distance_topk_tokens_prefiltered(const float *c, const float *t, int Q, const void *bank16, int dtype, const float *rowp,
+                                                       const void *tail, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
+                                                       const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                       int *redo, void *stream) {
+    return mse_search("skyemb_distance_topk_tokens_prefiltered", c, t, Q, bank16, dtype, rowp, tail, nullptr, false, 0, 0, 0, N, P, D, k, combine, 0,
+                      idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// ---- the same search under top_t (distance 'max': a[top_t - 1]) and under a selection of the bank's images ----------------------------------
+extern "C" int skyemb_token_mse_topt_prefilter_applicable(int Q, int64_t N, int P, int D, int k, int combine, int top_t) {
+    if (combine != SKYEMB_COMBINE_MIN && combine != SKYEMB_COMBINE_MAX) {
+        if (combine == SKYEMB_COMBINE_MEAN)
+            skyemb_set_error("many-query weighted-MSE patch-token search: combine mean is not served by the two-stage route (the mean of token "
+                             "distances is no count of passing rows); the grouped search serves it");
+        else skyemb_set_error("many-query weighted-MSE patch-token search: unknown combine code %d", combine);
+        return 0;
+    }
+    if (!skyemb_token_mse_prefilter_applicable(Q, N, P, D, k)) return 0;     // (its own text)
+    if (top_t < 1 || top_t > (P < 16 ? P : 16)) {
+        skyemb_set_error("many-query weighted-MSE patch-token search: top_t must be 1 .. min(P, 16) (top_t=%d P=%d)", top_t, P);
+        return 0;
+    }
+    return 1;
+}
+
+extern "C" int skyemb_distance_topk_tokens_prefiltered_top(const float *c, const float *t, int Q, const void *bank16, int dtype,
+                                                           const float *rowp, const void *tail, int64_t N, int P, int D, int k, int combine,
+                                                           int top_t, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                           float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return mse_search(top_t ? "skyemb_distance_topk_tokens_prefiltered_top" : "skyemb_distance_topk_tokens_prefiltered", c, t, Q, bank16, dtype, rowp,
+                      tail, nullptr, false, 0, 0, 0, N, P, D, k, combine, top_t, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+extern "C" int skyemb_distance_topk_tokens_prefiltered_top_sel(const float *c, const float *t, int Q, const void *bank16, int dtype,
+                                                               const float *rowp_sel, const void *tail, const int *tiles, int n_live,
+                                                               int last_live, int direct_end, int64_t N, int P, int D, int k, int combine,
+                                                               int top_t, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                               float *out_s, int64_t *out_i, int *redo, void *stream) {
+    return mse_search(top_t ? "skyemb_distance_topk_tokens_prefiltered_top_sel" : "skyemb_distance_topk_tokens_prefiltered_sel", c, t, Q, bank16, dtype,
+                      rowp_sel, tail, tiles, true, n_live, last_live, direct_end, N, P, D, k, combine, top_t, idx_offset, thr0, ws, ws_bytes, out_s,
+                      out_i, redo, stream);
+}
+
+extern "C" int skyemb_distance_topk_tokens_prefiltered_sel(const float *c, const float *t, int Q, const void *bank16, int dtype,
+                                                           const float *rowp_sel, const void *tail, const int *tiles, int n_live, int last_live,
+                                                           int direct_end, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
+                                                           const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                           int *redo, void *stream) {
+    return skyemb_distance_topk_tokens_prefiltered_top_sel(c, t, Q, bank16, dtype, rowp_sel, tail, tiles, n_live, last_live, direct_end, N, P, D, k,
+                                                           combine, 0, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
 }

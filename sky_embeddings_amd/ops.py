@@ -668,6 +668,66 @@ def distance_topk_tokens_prefiltered(c, t, tokens, tail, rowp, k, combine, idx_o
     return ws
 
 
+def token_mse_topt_prefilter_refusal(Q, N, P, D, k, combine, top_t):
+    """None when the two-stage weighted-MSE token search takes the shape under ``top_t`` (``combine``: a COMBINE_CODES value of the
+    DISTANCES), else the library's own reason: the plain search's limits, 1 <= top_t <= min(P, 16), and no mean."""
+    L = lib()
+    return None if L.skyemb_token_mse_topt_prefilter_applicable(Q, N, P, D, k, combine, top_t) else L.skyemb_last_error().decode()
+
+
+def token_mse_topt_folds(P, combine, top_t):
+    """``token_topt_folds`` for the weighted-MSE search, ``combine`` the DISTANCE combine -- the rule of include/skyemb.h restated in
+    key space (key = -distance): distance 'min' is the key-space max whatever ``top_t`` says, distance 'max' the key-space min, so
+    'max' with top_t in (0, P) is the plain search and 'max' with 1 <= top_t < P counts rows and sorts keys."""
+    assert combine in (COMBINE_CODES['min'], COMBINE_CODES['max'])
+    return token_topt_folds(P, COMBINE_CODES['max' if combine == COMBINE_CODES['min'] else 'min'], top_t)
+
+
+def distance_topk_tokens_prefiltered_top(c, t, tokens, tail, rowp, k, combine, top_t, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """``distance_topk_tokens_prefiltered`` under ``top_t`` (0: that call; include/skyemb.h): distance 'max' scores an image by its
+    top_t-th smallest token distance, 'min' is the plain min."""
+    Q, D = t.shape
+    N, P = tokens.shape[:2]
+    code = resident_dtype_code(tokens.dtype, "distance_topk_tokens_prefiltered_top")
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), t.device)
+    check(lib().skyemb_distance_topk_tokens_prefiltered_top(_p(c), _p(t), Q, _p(tokens), code, _p(rowp), _p(tail), N, P, D, k, combine, top_t,
+                                                            idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
+                                                            _stream()), "skyemb_distance_topk_tokens_prefiltered_top")
+    return ws
+
+
+def distance_topk_tokens_prefiltered_top_sel(c, t, tokens, tail, prepared, direct_end, k, combine, top_t, idx_offset, out_s, out_i, redo,
+                                             thr0=None, ws=None):
+    """``distance_topk_tokens_prefiltered_top`` under a selection of images: ``prepared`` is ``token_prefilter_select_prepare``'s result
+    over the rowp of ``token_mse_rowp``, ``direct_end`` the position of the live-tile list at which the first slice ends (``top_t`` 0:
+    the plain search under the selection; include/skyemb.h)."""
+    Q, D = t.shape
+    N, P = tokens.shape[:2]
+    rowp_sel, tiles, n_live, last_live = prepared[:4]
+    code = resident_dtype_code(tokens.dtype, "distance_topk_tokens_prefiltered_top_sel")
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), t.device)
+    check(lib().skyemb_distance_topk_tokens_prefiltered_top_sel(_p(c), _p(t), Q, _p(tokens), code, _p(rowp_sel), _p(tail), _p(tiles), n_live,
+                                                                last_live, direct_end, N, P, D, k, combine, top_t, idx_offset, _p(thr0),
+                                                                _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
+          "skyemb_distance_topk_tokens_prefiltered_top_sel")
+    return ws
+
+
+def distance_topk_tokens_prefiltered_sel(c, t, tokens, tail, prepared, direct_end, k, combine, idx_offset, out_s, out_i, redo, thr0=None,
+                                         ws=None):
+    """``distance_topk_tokens_prefiltered`` under a selection of images (include/skyemb.h)."""
+    Q, D = t.shape
+    N, P = tokens.shape[:2]
+    rowp_sel, tiles, n_live, last_live = prepared[:4]
+    code = resident_dtype_code(tokens.dtype, "distance_topk_tokens_prefiltered_sel")
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, D, k), t.device)
+    check(lib().skyemb_distance_topk_tokens_prefiltered_sel(_p(c), _p(t), Q, _p(tokens), code, _p(rowp_sel), _p(tail), _p(tiles), n_live,
+                                                            last_live, direct_end, N, P, D, k, combine, idx_offset, _p(thr0), _p(ws),
+                                                            ws.numel(), _p(out_s), _p(out_i), _p(redo), _stream()),
+          "skyemb_distance_topk_tokens_prefiltered_sel")
+    return ws
+
+
 def token_mean_prefilter_refusal(Q, N, P, D, k):
     """None when the two-stage token search with combine mean takes the shape, else the library's own statement of its limits."""
     L = lib()

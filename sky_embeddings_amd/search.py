@@ -449,6 +449,7 @@ class TokenBank:
         self._stage1 = None                                # (tail tile, rowp) of the two-stage route
         self._stage1_mean = None                           # (pooled image, its tail tile, rowp) of the route under combine 'mean'
         self._stage1_mse = None                            # (c, tail tile, rowp) of the weighted-MSE route, for the last c seen
+        self._mse_top_t = False                            # True: asked to take that route under top_t too (prepare_mse_top_t)
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
 
@@ -494,6 +495,16 @@ class TokenBank:
         if held is None or not torch.equal(held[0], c):
             held = self._stage1_mse = (c.clone(), *ops.token_mse_rowp(self.bank, c))
         return held[1], held[2]
+
+    def prepare_mse_top_t(self):
+        """Ask this resident bank to take the two-stage weighted-MSE route of ``distance_topk_tokens`` under ``top_t`` as well
+        (distance 'max' with 1 <= top_t < P: stage 1 counts the rows that pass, stage 2 sorts the token distances).  Nothing is built
+        here -- the route reads ``stage1_mse`` as the plain one does --; a bank never asked answers ``top_t`` by the grouped route,
+        as it always has.  Returns ``self``: ``TokenBank.resident(bank).prepare_mse_top_t()``."""
+        if not self._resident:
+            raise ValueError("TokenBank.prepare_mse_top_t: the bank must be made by TokenBank.resident")
+        self._mse_top_t = True
+        return self
 
     def set_weights(self, weights):
         self._version += 1
@@ -545,6 +556,7 @@ class Selection:
         self._prefilter = None                             # PreparedBank -> (its version, its row constants, what stage 1 needs)
         self._token_prefilter = None                       # resident TokenBank -> the same
         self._mean = None                                  # resident TokenBank -> (its version, its pooled image, the compacted one)
+        self._mse = None                                   # resident TokenBank -> None (asked, not built) | (its MSE rowp, what stage 1 needs)
 
     def prefilter(self, pb: "PreparedBank"):
         """What the two-stage many-query search needs of this selection over ``pb`` (``ops.prefilter_select_prepare``: the masked row
@@ -603,6 +615,35 @@ class Selection:
             got = (tb._version, pooled, ops.token_mean_select_gather(pooled[0], pooled[2], self.indices()))
             self._mean[tb] = got
         return got[2]
+
+    def prepare_mse(self, tb: "TokenBank"):
+        """Ask this selection to take the two-stage weighted-MSE route of ``distance_topk_tokens`` over the resident ``tb``.  Only a
+        Selection asked so takes it; a bool tensor or a Selection never asked keeps the grouped route.  What stage 1 reads -- the
+        masked copy of ``tb.stage1_mse(c)``'s row constants, the live tiles and their counts (``ops.token_prefilter_select_prepare``:
+        two short launches, one read-back, 16 bytes per token row) -- depends on the distance weights ``c``, which only a search knows,
+        so it is built by the first search per (bank, c) and kept until ``c`` or the bank's constants change (``mse_prefilter``).
+        Returns ``self``: ``Selection(flags).prepare_mse(tb)``."""
+        if not isinstance(tb, TokenBank) or not tb._resident:
+            raise ValueError("Selection.prepare_mse: the bank must be made by TokenBank.resident")
+        if tb.bank.shape[0] != self.N:
+            raise ValueError(f"Selection.prepare_mse: the selection describes {self.N} images, the bank has {tb.bank.shape[0]}")
+        if self.words.device != tb.bank.device:
+            raise ValueError(f"Selection.prepare_mse: the Selection was packed on {self.words.device}, the bank is on {tb.bank.device}")
+        if self._mse is None:
+            self._mse = weakref.WeakKeyDictionary()
+        self._mse.setdefault(tb, None)
+        return self
+
+    def mse_prefilter(self, tb: "TokenBank", c):
+        """``token_prefilter`` for the weighted-MSE route under the distance weights ``c``: ``ops.token_prefilter_select_prepare`` over
+        the row constants of ``tb.stage1_mse(c)``.  Keyed by those constants themselves: ``stage1_mse`` returns a new tensor exactly
+        when ``c`` differs from the last one seen, and then this is rebuilt."""
+        rowp = tb.stage1_mse(c)[1]
+        got = self._mse.get(tb)
+        if got is None or got[0] is not rowp:
+            got = (rowp, ops.token_prefilter_select_prepare(self.words, tb.bank.shape[0], tb.bank.shape[1], rowp))
+            self._mse[tb] = got
+        return got[1]
 
     def sample(self, tb: "TokenBank", images: int):
         """A strided sample of ``images`` SELECTED whole images of ``tb`` (tokens + the norms of their rows) for the pruning floor.
@@ -960,30 +1001,54 @@ TOKEN_TOPT_PREFILTER_MIN_Q_SMALL = 256                     # smaller banks
 TOKEN_MSE_PREFILTER_MIN_Q = 64
 TOKEN_MSE_PREFILTER_MIN_ELEMENTS = 15625 * 64 * 768       # N P D of the bank the constant above was measured on
 TOKEN_MSE_PREFILTER_MIN_Q_SMALL = 1024                    # smaller banks
+# ... by opt-in (TokenBank.prepare_mse_top_t, Selection.prepare_mse): distance 'max' under 1 <= top_t < P, a selection of images, and
+# both together.  tools/bench_mse_select_topt.py measures them against the grouped route on the bank above (its legs: top_t = 4, a
+# 10 % selection scattered and in runs of 4096 rows, both); each constant is the smallest Q of its grid at which the route is at least
+# 10 % faster on every leg that exercises it, both dtypes, preparation launches included (profiles/mse_select_topt_crossover.json and
+# its repeat).  Measured: 32, the grid's smallest point, for all three -- 1.12x under top_t (in both runs
+# and both dtypes, 1 % above the margin), 1.30x - 1.41x under the scattered selection, 1.88x - 2.09x under the runs.  Smaller banks are
+# NOT MEASURED: TOKEN_MSE_PREFILTER_MIN_Q_SMALL, as above
+TOKEN_MSE_TOPT_PREFILTER_MIN_Q = 32
+TOKEN_MSE_SELECT_PREFILTER_MIN_Q = 32
+TOKEN_MSE_SELECT_TOPT_PREFILTER_MIN_Q = 32
 
 
 def _token_mse_prefilter_refusal(rq: TokenRequest):
     """``_token_prefilter_refusal`` for a distance request over a resident 16-bit bank: None when ``distance_topk_tokens`` serves it
-    by the two-stage route (metric MSE, combine min | max, no top_t, no select, shared weights, P a divisor of 64, the library's
-    shape rule, the switch on, enough queries), else the first reason why the grouped route serves it."""
+    by the two-stage route (metric MSE, combine min | max, shared weights, P a divisor of 64, the library's shape rule, the switch
+    on, enough queries; ``top_t`` only over a bank asked by ``TokenBank.prepare_mse_top_t``, ``select`` only as a Selection asked by
+    ``Selection.prepare_mse`` for this bank), else the first reason why the grouped route serves it."""
     name = next((n for n, code in ops.METRIC_CODES.items() if code == rq.metric), rq.metric_name)
-    return token_mse_route_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k, name, rq.combine, rq.top_t, rq.select is not None,
-                                   rq.per_query)
+    tb, sel = rq.bank, rq.select
+    held = getattr(sel, "_mse", None)                      # (getattr: a Selection may be built without __init__, a bank too)
+    asked = isinstance(sel, Selection) and held is not None and tb in held
+    why = token_mse_route_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k, name, rq.combine, rq.top_t, sel is not None, rq.per_query,
+                                  top_t_prepared=bool(getattr(tb, "_mse_top_t", False)), select_prepared=asked,
+                                  selected=sel.count if asked else None)
+    if why == "select under a distance metric" and isinstance(sel, Selection):
+        why += " without the masked row constants of this bank (opt in once per Selection and bank: Selection.prepare_mse)"
+    return why
 
 
-def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=False, per_query=False):
+def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=False, per_query=False, *, top_t_prepared=False,
+                            select_prepared=False, selected=None):
     """The same decision from the request's plain facts, for a caller that has not wrapped its bank yet (``similarity_search.py``
     builds a ``TokenBank.resident`` -- a norm pass over the bank -- only when this returns None): ``metric`` a name, ``combine`` a
     name or an ``ops.COMBINE_CODES`` code, ``top_t`` None / 0 for all tokens, ``select`` whether there is a selection.  The bank is
-    taken to be a 16-byte aligned fp16 / bf16 tensor.  No device work."""
+    taken to be a 16-byte aligned fp16 / bf16 tensor.  No device work.
+
+    ``top_t_prepared`` / ``select_prepared`` (keyword only; False: the answers as they ever were): the caller will opt in by
+    ``TokenBank.prepare_mse_top_t`` / ``Selection.prepare_mse``, and the request is then decided under ``top_t`` / the selection:
+    the library's range for ``top_t``, the smallest Q of the route the request takes, and with ``selected`` (the number of selected
+    images; None: not looked at) the rule that the selected images are themselves a bank the route takes."""
     combine = ops.COMBINE_CODES.get(combine, combine)
     if metric != 'MSE':
         return f"metric {metric} (a distance that is no dot product)"
     if combine == ops.COMBINE_CODES['mean']:
         return "combine 'mean' under a distance metric"
-    if top_t:
+    if top_t and not top_t_prepared:
         return "top_t under a distance metric"
-    if select:
+    if select and not select_prepared:
         return "select under a distance metric"
     if per_query:
         return "per-query weights"
@@ -991,13 +1056,26 @@ def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=Fals
         return f"P = {P} does not divide 64"
     if not _prefilter_enabled():
         return "SKYEMB_TOPK_PREFILTER=0"
+    if top_t:
+        why = ops.token_mse_topt_prefilter_refusal(Q, N, P, D, k, combine, top_t)
+        if why is not None:
+            return why
+    # distance 'min' under any top_t and 'max' under top_t == P ARE the plain search (ops.token_mse_topt_folds): its smallest Q
+    top = bool(top_t) and ops.token_mse_topt_folds(P, combine, top_t)[1] == 'top'
+    name = "TOKEN_MSE" + ("_SELECT" if select else "") + ("_TOPT" if top else "") + "_PREFILTER_MIN_Q"
     if N * P * D >= TOKEN_MSE_PREFILTER_MIN_ELEMENTS:
-        if Q < TOKEN_MSE_PREFILTER_MIN_Q:
-            return f"Q = {Q} < TOKEN_MSE_PREFILTER_MIN_Q = {TOKEN_MSE_PREFILTER_MIN_Q}"
+        if Q < globals()[name]:
+            return f"Q = {Q} < {name} = {globals()[name]}"
     elif Q < TOKEN_MSE_PREFILTER_MIN_Q_SMALL:
         return (f"Q = {Q} < TOKEN_MSE_PREFILTER_MIN_Q_SMALL = {TOKEN_MSE_PREFILTER_MIN_Q_SMALL} (a bank of fewer than "
                 f"TOKEN_MSE_PREFILTER_MIN_ELEMENTS = {TOKEN_MSE_PREFILTER_MIN_ELEMENTS} elements)")
-    return ops.token_mse_prefilter_refusal(Q, N, P, D, k)
+    why = ops.token_mse_prefilter_refusal(Q, N, P, D, k)
+    if why is None and select and selected is not None:
+        # the selection must itself be a bank the route takes (k <= selected images, selected images x P >= 2048 rows): then the
+        # bootstrap sample exists, and the grouped route is cheap in exactly the cases refused here
+        why = ops.token_mse_prefilter_refusal(Q, selected, P, D, k)
+        why = why if why is None else "the selected images alone: " + why
+    return why
 
 
 def _token_prefilter_refusal(rq: TokenRequest):
@@ -1291,22 +1369,36 @@ def _topk_tokens_mse_prefiltered(rq: TokenRequest, queries, prune, stats, proces
     ``distance_pruning_floor``'s -- the k-th best key of a strided sample of min(N, max(16 k, 256)) whole images, scored by the
     grouped kernel in groups of 16 queries, one ulp lower --, then one stage-1 pass for all queries with exact re-scoring after
     every slice; flagged queries go through the grouped route, those queries only.  Everything runs in key space (key = -distance)
-    until the result is negated on the way out."""
-    tb, Q, k, dev = rq.bank, rq.Q, rq.k, rq.tokens.device
+    until the result is negated on the way out.  Under ``top_t`` the sample is scored under it; under a selection the sample is of
+    SELECTED images, stage 1 walks the live tiles of ``Selection.mse_prefilter`` and its first slice ends where ``cum`` says the
+    cosine driver's would (``_topk_tokens_prefiltered``); the re-run keeps both."""
+    tb, Q, k, dev, sel = rq.bank, rq.Q, rq.k, rq.tokens.device, rq.select
     q = queries.to(dev, torch.float32).contiguous()
     c = prepare_distance_weights(rq.weights, rq.D, dev)
-    S = min(rq.N, max(16 * k, 256))
-    st = tb.sample(S, "bootstrap")[0]
+    tail, rowp = tb.stage1_mse(c)
+    # (a selection that reaches this driver holds at least 2048 token rows -- the route's shape rule on the selected images alone --,
+    # and 7 whole 256-row tiles and a tail tile hold 2047 at most: it has SELECT_MIN_LIVE_TILES live whole tiles, nothing to check)
+    prepared = None if sel is None else sel.mse_prefilter(tb, c)
+    # the floor: the sample of SELECTED images under a selection, scored under the request's top_t (a[top_t-1] of a sample bounds the
+    # k-th best a[top_t-1] of the search)
+    S = min(rq.N if sel is None else sel.count, max(16 * k, 256))
+    st = tb.sample(S, "bootstrap")[0] if sel is None else sel.sample(tb, S)[0]
     thr0 = torch.empty(Q, device=dev)
     keys = torch.empty(16, S, device=dev)
     for lo in range(0, Q, 16):
         g = min(16, Q - lo)
-        ops.distance_token_scores(c, q[lo:lo + g], st, rq.metric, rq.combine, keys[:g])
+        ops.distance_token_scores(c, q[lo:lo + g], st, rq.metric, rq.combine, keys[:g], rq.top_t)
         ops.kth_largest_floor(keys[:g].neg_(), k, thr0[lo:lo + g])
-    tail, rowp = tb.stage1_mse(c)
 
-    def launch(*out):
-        return ops.distance_topk_tokens_prefiltered(c, q, tb.bank, tail, rowp, k, rq.combine, rq.idx_offset, *out, thr0)
+    def launch(*out):                                      # ``top_t`` follows ``combine`` in the calls that take it
+        if sel is None and rq.top_t == 0:
+            return ops.distance_topk_tokens_prefiltered(c, q, tb.bank, tail, rowp, k, rq.combine, rq.idx_offset, *out, thr0)
+        if sel is None:
+            return ops.distance_topk_tokens_prefiltered_top(c, q, tb.bank, tail, rowp, k, rq.combine, rq.top_t, rq.idx_offset, *out, thr0)
+        n_live, cum = prepared[2], prepared[4]
+        direct_end = min(max(bisect.bisect_left(cum, 96 * k) + 1, n_live // 128, 1), n_live)
+        return ops.distance_topk_tokens_prefiltered_top_sel(c, q, tb.bank, tail, prepared, direct_end, k, rq.combine, rq.top_t,
+                                                            rq.idx_offset, *out, thr0)
 
     def rerun(again):                                      # the grouped route, in key space like ``launch``'s result
         rq2 = dataclasses.replace(rq, Q=int(again.numel()))
@@ -1317,6 +1409,10 @@ def _topk_tokens_mse_prefiltered(rq: TokenRequest, queries, prune, stats, proces
     if stats is not None:
         stats.update(path="prefiltered", redone=n_redo, metric=rq.metric_name,
                      combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+        if rq.top_t != 0:
+            stats.update(top_t=rq.top_t)
+        if sel is not None:
+            stats.update(selected=sel.count, tiles=(prepared[2], (rq.N * rq.P + 255) // 256))
     _gather_merge(out_s, out_i, Q, k, world_size, process_group)        # (of keys)
     return out_s.neg_(), out_i                                          # (-inf, -1) becomes (+inf, -1)
 
@@ -1347,8 +1443,22 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     / every ('max') token of it can still reach the query's threshold, and every candidate is re-scored by the contract's own
     chain after each slice of the bank.  Distances and indices are bit for bit those of the grouped route.  ``stats`` gains
     ``redone`` (queries re-run by the grouped route: a full candidate list, a zero or out-of-range query, a negative or NaN
-    weight) and ``combine``.  Out of scope for the two-stage route, served by the grouped route as ever: metric 'MAE' (no dot
-    product), ``combine`` 'mean', ``top_t``, ``select``, per-query weights, fp32 banks, P not dividing 64.
+    weight) and ``combine``.  ``top_t`` and ``select`` take the route BY OPT-IN only; a caller that has not asked gets the grouped
+    route, as ever.  ``TokenBank.resident(bank).prepare_mse_top_t()`` opens it for ``top_t``: 'min' under any ``top_t`` and 'max'
+    under ``top_t == P`` are the plain search; 'max' under 1 <= top_t < P scores a[top_t-1], which reaches a threshold only when at
+    least top_t token distances do, so an image is a candidate when the COUNT of its rows that pass the row test is >= top_t, and
+    stage 2 sorts the image's exact token distances with the grouped kernel's own network; the first threshold comes from a sample
+    scored under the same ``top_t``, a re-run keeps it, ``stats`` gains ``top_t``.  ``Selection(flags).prepare_mse(bank)`` opens it
+    for ``select``: stage 1 reads only the 256-row tiles that hold a selected image, every row of a deselected image fails its test
+    whatever it holds (a masked copy of the row constants, built with the live tiles by the first search per bank and weight vector
+    and kept in the Selection), the first threshold comes from a sample of selected images, a re-run keeps the selection, ``stats``
+    gains ``selected`` and ``tiles`` = (live tiles, all tiles).  The selected images must themselves be a bank the route takes
+    (selected x P >= 2048 rows -- hence 8 live whole tiles --, k <= selected): a smaller selection is served whole by the grouped
+    route, never refused, and fewer than k selected images leave a (+inf, -1) tail.  Smallest Q on a bank of at least
+    ``TOKEN_MSE_PREFILTER_MIN_ELEMENTS`` elements: ``TOKEN_MSE_TOPT_PREFILTER_MIN_Q`` (the top-t fold),
+    ``TOKEN_MSE_SELECT_PREFILTER_MIN_Q`` (a selection), ``TOKEN_MSE_SELECT_TOPT_PREFILTER_MIN_Q`` (both); smaller banks:
+    ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``.  Out of scope for the two-stage route, served by the grouped route as ever: metric 'MAE'
+    (no dot product), ``combine`` 'mean', per-query weights, fp32 banks, P not dividing 64, a bool-tensor ``select``.
 
     ``select``, ``prune``, ``stats``, ``world_size``: as for ``cosine_topk_tokens`` (the floor and the merges work on
     key = -distance).  Every ValueError -- an unknown metric or combine, top_t outside 1 .. min(P, 16), k, a selection of
