@@ -847,6 +847,42 @@ int skyemb_distance_topk_tokens_prefiltered_top_sel(const float *c, const float 
                                                     int direct_end, int64_t N, int P, int D, int k, int combine, int top_t,
                                                     int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes, float *out_s,
                                                     int64_t *out_i, int *redo, void *stream);
+/* The weighted-MSE search with PER-QUERY weights c [Q, D] in the same two stages (additive to ABI version 111): the many-query form of
+ * skyemb_distance_token_topk_pq with metric SKYEMB_METRIC_MSE, combine min | max, no top_t, no selection; bit for bit that call +
+ * skyemb_topk_merge.  B_r = sum c_qd x_d^2 depends on the query, so it joins the dot product: with c_q >= 0, in real arithmetic
+ *   D dist = A_q - 2 u_q . y_x,   u_q = [c_q o t_q ; -c_q / 2],   y_x = [x ; x o x],   A_q = sum c_qd t_qd^2   (2 D numbers each).
+ * Stage 1 runs the same instances over a second resident 16-bit image of the bank, rows [x ; r16(x o x)] of length 2 D (r16: one
+ * round-to-nearest-even of the exact fp32 square; 4 N P D bytes beside the bank's 2 N P D, independent of the weights), under
+ *   |dot^ - 2^-f u_q . y_x| <= eps_pq ||u'|| ny,   eps_pq = eps_a (2 D; resident, dtype, hi | hi + lo) + rho (1 + rho) + 2^-22 (+ kappa),
+ * rho = 2^-11 (fp16) / 2^-8 (bf16), the format's unit roundoff, for the one rounding of each square; bf16 only: kappa = 2^-9 (hi only) /
+ * 2^-16 - 2^-18 (hi + lo) prices the query split at the same unit roundoff (derivation: csrc/topk_prefilter.hip), so
+ * D dist_real >= A_dn - 2 2^f (dot^ + eps_pq ||u'|| ny); the threshold test, gamma (at the real D) and stage 2 are the plain call's,
+ * stage 2 reading row q of c.  Cosine with per-query weights is NOT served this way: its row norm sum w_qd x_d^2 sits under a square
+ * root in the denominator, so the candidate test is no single linear instruction.
+ *   skyemb_token_mse_pq_prefilter_applicable   1 / 0 (+ text): D % 32 == 0, 128 <= D <= 2048, skyemb_token_prefilter_applicable's
+ *                           shape rule on (Q, N, P, 2 D, k), fewer than 2^31 rows after padding to whole 256-row tiles
+ *   skyemb_token_mse_pq_prefilter_eps   eps_pq (lo: 0 hi only, 1 hi + lo), before the (1 + 1e-6) raise: host arithmetic
+ *   skyemb_token_mse_pq_image   one launch per bank: image [skyemb_bank16_rowp_rows(R), 2 D] in the bank's dtype and rowp [the same rows, 4]
+ *                           over the R = N P flat rows; row i = {0, ny, 1, 0}, ny >= ||[x ; r16(x o x)]||_2 rounded up (fp16: + (sqrt(nsub)
+ *                           2^-14 + sqrt(nsq) 2^-25) / eps_pq (hi + lo): nsub the fp16-subnormal elements of both halves, nsq the
+ *                           squares below 2^-14).  An unboundable row -- an inf / NaN element, fp16: an |x| >= 2^8, bf16: a nonzero
+ *                           element whose stored square is outside [2^-60, 2^120), ny not finite -- holds {0, inf, 1, 0} and a ZERO
+ *                           image row: a candidate of every query.  Padding rows: zeros and the sentinel {0, NaN, 0, 0}; no tail tile.
+ *   skyemb_distance_topk_tokens_prefiltered_pq   c [Q, D], t [Q, D], image and rowp those of skyemb_token_mse_pq_image for this bank
+ *                           (all 16-byte aligned); combine, thr0, out_s (KEYS), out_i, redo as for the plain call; ws:
+ *                           skyemb_token_prefilter_ws_bytes(Q, 2 D, k).  It plans as the request {SKYEMB_PF_TOKENS, the bank's format,
+ *                           D' = 2 D, N' = the padded rows / P, the key-space combine} of skyemb_prefilter_plan; stage 1's eps is eps_pq,
+ *                           gfac carries gamma (D), the token re-score takes lds_close as planned (t [D] and c_q [D] fill the plan's
+ *                           2 D floats) and reads the BANK at D.  redo[q] != 0 as for the plain call, except that a negative, NaN or
+ *                           above-2^10 weight flags only the queries whose own row holds it; c_q o t_q = 0 flags the query too.  The
+ *                           caller re-runs flagged queries through skyemb_distance_token_topk_pq. */
+int skyemb_token_mse_pq_prefilter_applicable(int Q, int64_t N, int P, int D, int k);
+double skyemb_token_mse_pq_prefilter_eps(int D, int lo, int dtype);
+int skyemb_token_mse_pq_image(const void *bank16, int dtype, int64_t R, int D, void *image, float *rowp, void *stream);
+int skyemb_distance_topk_tokens_prefiltered_pq(const float *c, const float *t, int Q, const void *bank16, int dtype, const void *image,
+                                               const float *rowp, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
+                                               const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
+                                               void *stream);
 /* Read-only query of the launch plan of every two-stage search above (csrc/prefilter_plan.h): what the entry point serving `req`
  * decides on the host -- variant, slices, kernel instances, LDS bytes -- and then launches.  Host arithmetic only, touches no device.
  * Returns 0 and fills *out, or 1 with the text (skyemb_last_error) and under the name of the entry point that would refuse the

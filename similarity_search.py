@@ -215,11 +215,15 @@ def main():
                         and search.token_mse_route_refusal(queries.shape[0], *bank.shape, kk, args.metric, args.combine, args.n_top_sims,
                                                            select is not None, args.per_target, top_t_prepared=True,
                                                            select_prepared=True,
-                                                           selected=None if select is None else select.count) is None):
+                                                           selected=None if select is None else select.count,
+                                                           per_query_prepared=True) is None):
                     # many targets under weighted MSE over a 16-bit bank, and the two-stage route will take them (decided first: the
                     # wrapper costs a norm pass over the bank that the distance route never reads): identical results by contract.
-                    # -nts and --bank-select-snr take that route by opt-in, asked for here
-                    tokens = search.TokenBank.resident(bank, w)
+                    # -nts, --bank-select-snr and --per-target take that route by opt-in, asked for here (--per-target: a second
+                    # image of the bank, 4 bytes per element; its [T, D] weights travel with the search, not with the bank)
+                    tokens = search.TokenBank.resident(bank, None if args.per_target else w)
+                    if args.per_target:
+                        tokens.prepare_mse_per_query()
                     if args.n_top_sims:
                         tokens.prepare_mse_top_t()
                     if select is not None:

@@ -263,6 +263,12 @@ PROTOTYPES = {
     "skyemb_distance_topk_tokens_prefiltered_top_sel": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64,
                                                                 c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
                                                                 c_vp]),
+    # ... with per-query weights c [Q, D]: a second 16-bit image [x ; x o x] of the bank, additive again
+    "skyemb_token_mse_pq_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),
+    "skyemb_token_mse_pq_prefilter_eps": (c_f64, [c_i32, c_i32, c_i32]),
+    "skyemb_token_mse_pq_image": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "skyemb_distance_topk_tokens_prefiltered_pq": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64,
+                                                           c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

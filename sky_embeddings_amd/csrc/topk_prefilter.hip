@@ -1790,6 +1790,235 @@ __global__ void mse_state_kernel(int Q, int Q_padded, const float *__restrict__ 
     overflow[q] = out || qb.w != 0.f || qb.z >= scale_hi || qb.z <= scale_lo || !(qb.y > 0.f && qb.y < 0x1p60f) ? 1 : 0;
 }
 
+// ---- Weighted MSE with PER-QUERY weights (skyemb_token_mse_pq_image / skyemb_distance_topk_tokens_prefiltered_pq) ------------------------
+// Contract: the same chain with query q's own row of c [Q, D] (skyemb_distance_token_topk_pq).  B_r = sum c_qd x_d^2 now depends on the
+// query, so it cannot ride in a row constant; it joins the dot product instead.  With c_q >= 0, in real arithmetic
+//   D dist = sum_d c_qd (x_d - t_qd)^2 = A_q - 2 u_q . y_x,   u_q = [c_q o t_q ; -c_q / 2],   y_x = [x ; x o x],   A_q = sum c_qd t_qd^2:
+// ONE dot product of length 2 D per token.  Stage 1 therefore runs the TOK instances of prefilter_kernel unchanged over a second
+// resident 16-bit image of the bank, rows y^_i = [x_i ; r16(x_i o x_i)] of length 2 D (mse_pq_image_kernel: 4 N P D bytes beside the
+// bank's 2 N P D, independent of the weights), against query images built from u_q (mse_pq_query_kernel); the row constant B is 0.
+// No power of two is folded into the squares: fp16 rows are admitted up to |x| < 2^8 and bf16 has fp32's range.
+// The image.  x is a 16-bit number, so x * x is exact in fp32 (where it neither overflows nor underflows: the window below) and
+// r16 is ONE round-to-nearest-even to the operand format, rho its unit roundoff: 2^-11 (fp16, 11 significant bits) / 2^-8 (bf16, 8
+// significant bits: numbers of [2^e, 2^(e+1)) are 2^(e-7) apart, half of that is 2^(e-8)).  A square v in [2^e, 2^(e+1)) of the
+// format's normal range moves by at most rho 2^e <= rho min(v, r16(v)); the bound is attained (x = 95.5 in bf16: 9120.25 -> 9152),
+// and by every element of a row at once when they are equal, so nothing below the unit roundoff will do.  fp16 only: a square below 2^-14 (0 < |x| < 2^-7) lands on
+// the subnormal grid and moves by at most 2^-25 absolute instead (to zero below 2^-25).
+// The bound.  u' = 2^-f u_q with u_q the fp32 numbers the kernel forms -- first half fl(c o t), second half -c / 2, exact (a
+// subnormal c loses at most 2^-150) --, split hi / lo as mse_query_kernel splits tw.  Three steps:
+//   (1) the resident bound of the file header on the stored rows y^, length 2 D:  |dot^ - 2^-f sum u_d y^_d| <= eps_a(2 D) ||u'|| ||y^|| + s_i,
+//       s_i = ||u'|| sqrt(nsub_i) 2^-14 (fp16: nsub_i counts the subnormal elements 0 < |y^_d| < 2^-14 of BOTH halves; nothing is
+//       assumed about whether the matrix core flushes them), no additive term for bf16 under (R) on both halves;
+//   (2) the rounding of the squares, Cauchy-Schwarz over the second half:  |2^-f sum_{d >= D} u_d (y^_d - y_d)| <= ||u'|| ||y^ - y||
+//       <= ||u'|| (rho ||y^|| + sqrt(nsq_i) 2^-25), nsq_i the number of fp16 squares rounded on the subnormal grid (0 for bf16).  In the
+//       form the constant is quoted: ||x o x|| <= (1 + rho) ||y^|| and rho ||x o x|| <= rho (1 + rho) ||y^||, which is no smaller;
+//   (3) fl(c o t) against c o t: 2^-22, the argument of eps_mse above (||u|| >= ||tw||, ||y|| >= ||x||);
+//   (4) bf16 only, the query split at the SAME unit roundoff: |q'_d - qh_d| <= 2^-8 |q'_d| and, with lo, |r_d - ql_d| <= 2^-8 |r_d| <=
+//       2^-16 |q'_d|.  eps_a_bf16_of prices these two at 2^-9 and 2^-18; kappa = 2^-9 (hi only) / 2^-16 - 2^-18 (hi + lo) is the
+//       difference, added here so that this bound does not lean on it (attained too: q'_d = 2^-21 (1 + 2^-8) for every d).
+// Together  |dot^ - 2^-f u_q . y_x| <= eps_pq ||u'|| ny,
+//   eps_pq = eps_a(2 D; resident fp16 | bf16; hi | hi + lo) + rho (1 + rho) + 2^-22 (+ kappa, bf16)
+//   ny_i  >= ||y^_i||_2 (1 + 2 D 2^-22) + (sqrt(nsub_i) 2^-14 + sqrt(nsq_i) 2^-25) / eps_pq (hi + lo), rounded up (bf16: no second term).
+// Hence  D dist_real >= A_dn - 2 2^f (dot^ + eps_pq ||u'|| ny)  with A_dn as above, and the candidate test is mse_test_row's with
+// rowp[i] = {0, ny_i, 1, 0} and qbase[q] = {A_dn, eps_pq ||u'||, 2^-f, flag}: mse_state_kernel and the threshold refresh stand as they
+// are, gamma taken at the real D (the contract's chain still has D terms).
+// A row is UNBOUNDABLE -- {0, inf, 1, 0} and a ZERO image row, so that dot^ stays a number and the row is a candidate of every query,
+// decided by stage 2 -- when it has an inf / NaN element, when a square leaves the operand format's range (fp16: |x| >= 2^8; below
+// that r16(x^2) <= 65472 is finite), when a nonzero element has its stored square outside [2^-60, 2^120) (bf16: (R) on the second
+// half, which implies it on the first and keeps x * x exact in fp32), or when ny is not finite.
+// A query is flagged by a negative, NaN or above-2^10 weight IN ITS OWN ROW (the row constants do not depend on the weights, so the
+// others stay served), by c_q o t_q = 0 (as tw = 0 is above), and by mse_state_kernel's windows.
+__host__ __device__ inline double eps_pq_of(int D, bool lo, bool bf) {
+    const double rho = bf ? 0x1p-8 : 0x1p-11;
+    const double eps = (bf ? eps_a_bf16_of(2 * D, lo) : eps_a_of(2 * D, lo, true)) + rho * (1.0 + rho) + 0x1p-22;
+    return bf ? eps + (lo ? 0x1p-16 - 0x1p-18 : 0x1p-9) : eps;
+}
+
+// eight squares of 16-bit elements, rounded once to the operand format: the stored words, and their values as fp32
+template <bool BF>
+__device__ __forceinline__ uint4 squares8(const float (&a)[8], float (&v)[8]) {
+    unsigned int u[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float s0 = a[2 * j] * a[2 * j], s1 = a[2 * j + 1] * a[2 * j + 1];
+        unsigned short h0, h1;
+        if (BF) {
+            h0 = __builtin_bit_cast(unsigned short, (bf16_t)s0);
+            h1 = __builtin_bit_cast(unsigned short, (bf16_t)s1);
+        } else {
+            h0 = __builtin_bit_cast(unsigned short, (half_t)s0);
+            h1 = __builtin_bit_cast(unsigned short, (half_t)s1);
+        }
+        u[j] = (unsigned int)h0 | ((unsigned int)h1 << 16);
+    }
+    const uint4 raw = make_uint4(u[0], u[1], u[2], u[3]);
+    widen8<BF>(raw, v);
+    return raw;
+}
+
+// The image and its row constants: one wave per row, 16 bytes per lane and load.  image [rows_padded, 2 D]: row i = [x_i ; r16(x_i o x_i)],
+// an unboundable row and the padding rows i >= N zeros; rowp[i] = {0, ny_i, 1, 0}, unboundable {0, inf, 1, 0}, padding the sentinel
+// {0, NaN, 0, 0}.  sub_scale = 2^-14 / eps_pq (hi + lo), raised.  D % 8 == 0.
+template <bool BF>
+__global__ __launch_bounds__(256) void mse_pq_image_kernel(const unsigned short *__restrict__ bank, int64_t N, int D,
+                                                            unsigned short *__restrict__ image, float4 *__restrict__ rowp, int64_t rows_padded,
+                                                            float sub_scale) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows_padded) return;
+    unsigned short *o = image + row * 2 * D;
+    if (row >= N) {
+        for (int d = lane * 8; d < 2 * D; d += 512) *(uint4 *)(o + d) = make_uint4(0u, 0u, 0u, 0u);
+        if (lane == 0) rowp[row] = make_float4(0.f, NAN, 0.f, 0.f);
+        return;
+    }
+    const unsigned short *x = bank + row * D;
+    float ss = 0.f, nsub = 0.f, nsq = 0.f, bad = 0.f, mx = 0.f;
+    for (int d = lane * 8; d < D; d += 512) {
+        const uint4 raw = *(const uint4 *)(x + d);
+        float a[8], v[8];
+        widen8<BF>(raw, a);
+        *(uint4 *)(o + d) = raw;
+        *(uint4 *)(o + D + d) = squares8<BF>(a, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float m = fabsf(a[j]);
+            if (BF) {
+                bad = (m != 0.f && !(v[j] >= ldexpf(1.0f, -BF_ROW_LO) && v[j] < ldexpf(1.0f, BF_ROW_HI))) ? 1.f : bad;   // NaN: m != 0
+                mx = fmaxf(mx, fmaxf(m, v[j]));
+            } else {
+                bad = !(m < 0x1p8f) ? 1.f : bad;               // inf, NaN, or a square outside fp16
+                ss = fmaf(a[j], a[j], ss);
+                ss = fmaf(v[j], v[j], ss);
+                nsub += (m > 0.f && m < 0x1p-14f) ? 1.f : 0.f;
+                nsub += (v[j] > 0.f && v[j] < 0x1p-14f) ? 1.f : 0.f;
+                nsq += (m > 0.f && m < 0x1p-7f) ? 1.f : 0.f;
+            }
+        }
+    }
+    bad = wave_max(bad);
+    float ny = INFINITY;
+    if (bad == 0.f) {
+        if (BF) {
+            mx = wave_max(mx);
+            int e = 0;
+            if (mx > 0.f) (void)frexpf(mx, &e);                // mx 2^-e in [0.5, 1); e in (-BF_ROW_LO, BF_ROW_HI]
+            const float s = ldexpf(1.0f, -e);
+            for (int d = lane * 8; d < D; d += 512) {
+                float a[8], v[8];
+                widen8<true>(*(const uint4 *)(x + d), a);
+                (void)squares8<true>(a, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    ss = fmaf(a[j] * s, a[j] * s, ss);
+                    ss = fmaf(v[j] * s, v[j] * s, ss);
+                }
+            }
+            ss = wave_sum(ss);
+            ny = ldexpf(sqrtf(ss) * (1.0f + (float)(2 * D) * 0x1p-22f) * (1.0f + 0x1p-21f), e);
+        } else {
+            ss = wave_sum(ss);                                 // 2 D <= 4096 terms below 2^32 each
+            nsub = wave_sum(nsub);                             // <= 2 D <= 4096: exact
+            nsq = wave_sum(nsq);
+            ny = fmaf(sqrtf(nsub) + sqrtf(nsq) * 0x1p-11f, sub_scale, sqrtf(ss) * (1.0f + (float)(2 * D) * 0x1p-22f)) * (1.0f + 0x1p-21f);
+        }
+    }
+    if (!(ny < INFINITY)) {                                    // unboundable: a zero image row, so that dot^ is a number
+        for (int d = lane * 8; d < D; d += 512) {              // (every lane overwrites the addresses it wrote itself above)
+            *(uint4 *)(o + d) = make_uint4(0u, 0u, 0u, 0u);
+            *(uint4 *)(o + D + d) = make_uint4(0u, 0u, 0u, 0u);
+        }
+        ny = INFINITY;
+    }
+    if (lane == 0) rowp[row] = make_float4(0.f, ny, 1.0f, 0.f);
+}
+
+// Queries under per-query weights: one wave per query.  u_q = [fl(c_q o t_q) ; -c_q / 2] -> qh, ql [Q_padded, 2 D] exactly as
+// mse_query_kernel writes tw (same scale rule over all 2 D elements, same padding rows); qbase[q] = {A_dn, eps_pq ||u'|| (1 + 2 D 2^-22),
+// 2^-f, flag}, flag != 0: a weight of row q outside [0, 2^10], c_q o t_q = 0 or A^ not finite
+template <bool BF>
+__global__ __launch_bounds__(256) void mse_pq_query_kernel(const float *__restrict__ cw, const float *__restrict__ tq, int Q, int D,
+                                                            half_t *__restrict__ qh, half_t *__restrict__ ql, float4 *__restrict__ qbase,
+                                                            float eps_pq) {
+    const int lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int D2 = 2 * D;
+    if (q >= Q) {
+        if (q < (Q + QPAD - 1) / QPAD * QPAD)
+            for (int d = lane * 4; d < D2; d += 256) {
+                *(uint2 *)(qh + (int64_t)q * D2 + d) = make_uint2(0u, 0u);
+                *(uint2 *)(ql + (int64_t)q * D2 + d) = make_uint2(0u, 0u);
+            }
+        return;
+    }
+    const float *x = tq + (int64_t)q * D, *cq = cw + (int64_t)q * D;
+    float mx = 0.f, mw = 0.f, A = 0.f, cbad = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const float4 v = *(const float4 *)(x + d), c = *(const float4 *)(cq + d);
+        const float tv[4] = {v.x, v.y, v.z, v.w}, cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float w = __fmul_rn(cv[j], tv[j]);
+            mw = fmaxf(mw, fabsf(w));
+            mx = fmaxf(mx, fabsf(0.5f * cv[j]));
+            A += __fmul_rn(w, tv[j]);
+            cbad = !(cv[j] >= 0.f && cv[j] <= 0x1p10f) ? 1.f : cbad;
+        }
+    }
+    mw = wave_max(mw);
+    mx = fmaxf(wave_max(mx), mw);
+    A = wave_sum(A);
+    cbad = wave_max(cbad);
+    int e = 0;
+    if (mx > 0.f && mx < INFINITY) {
+        (void)frexpf(mx, &e);
+        e -= BF ? BF_QMAX_EXP : 14;
+    }
+    if (e < -126) e = -126;             // (query16_kernel's clamps: such a query is flagged by mse_state_kernel)
+    if (BF && e > BF_SCALE_LO) e = BF_SCALE_LO;
+    const float s = ldexpf(1.0f, -e);
+    float ss = 0.f;
+    for (int d = lane * 4; d < D2; d += 256) {
+        const int dd = d < D ? d : d - D;                      // (D % 4 == 0: a lane's four elements lie in one half)
+        const float4 v = *(const float4 *)(x + dd), c = *(const float4 *)(cq + dd);
+        float a[4];
+        if (d < D) {
+            a[0] = __fmul_rn(c.x, v.x) * s, a[1] = __fmul_rn(c.y, v.y) * s, a[2] = __fmul_rn(c.z, v.z) * s, a[3] = __fmul_rn(c.w, v.w) * s;
+        } else {
+            a[0] = (-0.5f * c.x) * s, a[1] = (-0.5f * c.y) * s, a[2] = (-0.5f * c.z) * s, a[3] = (-0.5f * c.w) * s;
+        }
+        if (BF) {
+            bf16x4 h, l;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                ss = fmaf(a[j], a[j], ss);
+                h[j] = (bf16_t)a[j];
+                l[j] = (bf16_t)(a[j] - (float)h[j]);
+            }
+            *(bf16x4 *)(qh + (int64_t)q * D2 + d) = h;
+            *(bf16x4 *)(ql + (int64_t)q * D2 + d) = l;
+            continue;
+        }
+        typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+        half4 h, l;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ss = fmaf(a[j], a[j], ss);
+            h[j] = (half_t)a[j];
+            l[j] = (half_t)(a[j] - (float)h[j]);
+        }
+        *(half4 *)(qh + (int64_t)q * D2 + d) = h;
+        *(half4 *)(ql + (int64_t)q * D2 + d) = l;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) {
+        const float nq = sqrtf(ss) * (1.0f + (float)D2 * 0x1p-22f);
+        const bool flag = cbad != 0.f || !(mw > 0.f) || !(A >= 0.f && A < INFINITY);
+        const float Adn = !(A >= 0x1p-100f) ? 0.f : A * (1.0f - (float)D * 0x1p-22f);
+        qbase[q] = make_float4(flag ? 0.f : Adn, eps_pq * nq, s, flag ? 1.f : 0.f);
+    }
+}
+
 // One wave per image: the pooled row and its constants (the derivation above).  tail / tail_first / the padding sentinel: as in
 // bank16_rowp_lp_kernel, with images for rows.  kfac = kappa / eps_m (hi + lo), raised.
 template <bool BF>
@@ -2135,6 +2364,13 @@ __global__ __launch_bounds__(256) void token_rescore_mse_top_lp_kernel(TOKEN_RES
 __global__ __launch_bounds__(256) void token_rescore_mse_top_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), int top_t, const float *__restrict__ cw) {
     token_rescore_body<bf16_t, true, false, true>(TOKEN_RESCORE_PASS, top_t, nullptr, 0, cw);
 }
+// per-query weights ("Weighted MSE with PER-QUERY weights" above): cw is c [Q, D] and the workgroup of query q reads its row
+__global__ __launch_bounds__(256) void token_rescore_mse_pq_lp_kernel(TOKEN_RESCORE_PARAMS(half_t), const float *__restrict__ cw) {
+    token_rescore_body<half_t, false, false, true>(TOKEN_RESCORE_PASS, 0, nullptr, 0, cw + (int64_t)blockIdx.x * D);
+}
+__global__ __launch_bounds__(256) void token_rescore_mse_pq_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const float *__restrict__ cw) {
+    token_rescore_body<bf16_t, false, false, true>(TOKEN_RESCORE_PASS, 0, nullptr, 0, cw + (int64_t)blockIdx.x * D);
+}
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
 
@@ -2369,6 +2605,7 @@ const void *const RESCORE[3][2] = {{(const void *)rescore_kernel<false>, (const 
 const void *const TOKEN_RESCORE[2][2] = {{(const void *)token_rescore_lp_kernel, (const void *)token_rescore_bf_kernel},     // [topt][bf]
                                          {(const void *)token_rescore_top_lp_kernel, (const void *)token_rescore_top_bf_kernel}};
 const void *const TOKEN_RESCORE_MAP[2] = {(const void *)token_rescore_map_lp_kernel, (const void *)token_rescore_map_bf_kernel};   // [bf]
+const void *const TOKEN_RESCORE_MSE_PQ[2] = {(const void *)token_rescore_mse_pq_lp_kernel, (const void *)token_rescore_mse_pq_bf_kernel};   // [bf]
 const void *const TOKEN_RESCORE_MSE[2][2] = {{(const void *)token_rescore_mse_lp_kernel, (const void *)token_rescore_mse_bf_kernel},   // [topt][bf]
                                              {(const void *)token_rescore_mse_top_lp_kernel, (const void *)token_rescore_mse_top_bf_kernel}};
 
@@ -2397,6 +2634,10 @@ struct SearchArgs {
     // c [D]; tw then holds the raw queries t, rowp is skyemb_token_mse_rowp's (under a selection: its masked copy), qn and xn are NULL,
     // and the result is in key space (key = -distance)
     const float *cw;
+    // per-query weights (skyemb_distance_topk_tokens_prefiltered_pq; NULL everywhere else): the image [r.N * r.P, r.D] of
+    // skyemb_token_mse_pq_image, r.D = 2 D twice the bank's row length and r.N its images padded to whole tiles.  Stage 1 multiplies
+    // the image at r.D, stage 2 re-scores the bank [bank_N, P, D] at D; cw is c [Q, D], tw the raw queries t [Q, D]
+    const void *image;
 };
 
 int bank_of(int dtype) { return dtype == SKYEMB_BF16 ? SKYEMB_PF_BANK_BF16 : dtype == SKYEMB_F16 ? SKYEMB_PF_BANK_F16 : -1; }
@@ -2512,7 +2753,9 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
     skyemb_prefilter_plan_t p;
     if (plan_or_refuse(r, who, &p)) return 1;
     const int Q = r.Q, D = r.D, k = r.k, bank = r.bank;
-    const void *s1_bank = mean ? a.pooled : a.bank16;          // the rows stage 1 multiplies
+    const bool pq = a.image != nullptr;                        // per-query weights: stage 1 over the image at D = 2 Dr, stage 2 over the bank at Dr
+    const int Dr = pq ? D / 2 : D;                             // the row length of the bank stage 2 reads
+    const void *s1_bank = pq ? a.image : mean ? a.pooled : a.bank16;          // the rows stage 1 multiplies
     if (bank != SKYEMB_PF_BANK_F32) {
         SKY_CHECK_ARG(p.rows % BT == 0 || a.tail, rows ? "%s: N = %lld is no whole number of %d-row tiles: the tail tile of %s is needed"
                                                        : "%s: %lld rows are no whole number of %d-row tiles: the tail tile of %s is needed",
@@ -2534,19 +2777,22 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
             for (int s = rows ? 0 : p.sel; s <= p.sel; ++s)    // (a row search under a selection launches its tail through the non-SEL instance)
                 if (rc == 0) rc = sky_set_lds_limit((const void *)STAGE1[stage1_index(mode, lo, s, p.bf, p.tok, p.cnt)], p.lds_stage1_limit, who);
     const bool mse = a.cw != nullptr;                          // weighted MSE: its own constants and re-score, [D] more floats of LDS for c
-    const void *token_rescore = mse ? TOKEN_RESCORE_MSE[p.top_t != 0][p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
-    const int lds_close = p.lds_close + (mse ? D * 4 : 0), lds_close_limit = p.lds_close_limit + (mse ? 4096 * 4 : 0);
-    const float gamma_mse = (float)(gamma_mse_of(D) * (1.0 + 1e-6));
+    const void *token_rescore = pq ? TOKEN_RESCORE_MSE_PQ[p.bf] : mse ? TOKEN_RESCORE_MSE[p.top_t != 0][p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
+    // (per-query weights: the plan's t [2 Dr] IS t [Dr] beside c_q [Dr], within LDS_TOKEN_RESCORE_LIMIT as it stands)
+    const int lds_close = p.lds_close + (mse && !pq ? D * 4 : 0), lds_close_limit = p.lds_close_limit + (mse && !pq ? 4096 * 4 : 0);
+    const float gamma_mse = (float)(gamma_mse_of(Dr) * (1.0 + 1e-6));
     if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, lds_close_limit, who);
     if (rc == 0 && rows && p.sel) rc = sky_set_lds_limit((const void *)SELECT[1], p.lds_close_limit, who);
     if (rc != 0) return rc;
     const dim3 qgrid((unsigned)((p.q_padded + 3) / 4));
     if (mse) {
-        const float eps_mse = (float)(eps_mse_of(D, p.use_lo, p.bf) * (1.0 + 1e-6));
-        if (p.bf) hipLaunchKernelGGL(mse_query_kernel<true>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, D, w.qh, w.ql, w.qbase, eps_mse);
+        const float eps_mse = (float)((pq ? eps_pq_of(Dr, p.use_lo, p.bf) : eps_mse_of(D, p.use_lo, p.bf)) * (1.0 + 1e-6));
+        if (pq && p.bf) hipLaunchKernelGGL(mse_pq_query_kernel<true>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, Dr, w.qh, w.ql, w.qbase, eps_mse);
+        else if (pq) hipLaunchKernelGGL(mse_pq_query_kernel<false>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, Dr, w.qh, w.ql, w.qbase, eps_mse);
+        else if (p.bf) hipLaunchKernelGGL(mse_query_kernel<true>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, D, w.qh, w.ql, w.qbase, eps_mse);
         else hipLaunchKernelGGL(mse_query_kernel<false>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, D, w.qh, w.ql, w.qbase, eps_mse);
         hipLaunchKernelGGL(mse_state_kernel, dim3((unsigned)((p.q_padded + 255) / 256)), dim3(256), 0, st, Q, p.q_padded, a.thr0, (const float4 *)w.qbase,
-                           (float)D, gamma_mse, w.qpar, w.tau, w.cnt, w.nsel, w.overflow, p.bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
+                           (float)Dr, gamma_mse, w.qpar, w.tau, w.cnt, w.nsel, w.overflow, p.bf ? ldexpf(1.0f, -BF_SCALE_LO) : 0.f,
                            ldexpf(1.0f, p.bf ? BF_SCALE_HI : MSE_SCALE_HI_F16));
     } else if (p.bf) hipLaunchKernelGGL(query16_kernel<true>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
     else hipLaunchKernelGGL(query16_kernel<false>, qgrid, dim3(256), 0, st, a.tw, a.qn, Q, D, w.qh, w.ql, w.qbase, p.eps_a_f32);
@@ -2572,7 +2818,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
 #endif
     };
     auto token_rescore_as = [&](auto like, int final, auto... top_t) {               // (top_t: what the instance takes behind redo)
-        launch_like(like, token_rescore, Q, lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, a.map ? a.bank_N : r.N, D, p.lgp, p.fold,
+        launch_like(like, token_rescore, Q, lds_close, st, a.tw, a.qn, (const half_t *)a.bank16, a.xn, a.map || pq ? a.bank_N : r.N, Dr, p.lgp, p.fold,
                     mse ? gamma_mse : p.gfac, k, r.eps,
                     a.idx_offset, p.cap, w.qbase, w.cnt, w.cand_i, list, w.nsel, w.qpar, w.tau, w.overflow, final, a.out_s, a.out_i, a.redo, top_t...);
     };
@@ -2597,6 +2843,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
             hipLaunchKernelGGL(SELECT[p.sel], dim3((unsigned)Q), dim3(256), p.lds_close, st, Q, k, p.cap, r.eps, w.qbase, (const float4 *)a.rowp, a.xn,
                                w.cnt, w.cand_i, w.cand_d, w.qpar, w.tau, w.overflow, s.final, w.sel_i, w.nsel, w.bound);
         else if (a.map) token_rescore_as(token_rescore_map_lp_kernel, s.final, a.map, (int)r.N);   // the MAP kernels take map and S last
+        else if (pq) token_rescore_as(token_rescore_mse_pq_lp_kernel, s.final, a.cw);               // c [Q, D] last
         else if (mse && p.top_t) token_rescore_as(token_rescore_mse_top_lp_kernel, s.final, p.top_t, a.cw);   // MSE under top_t: top_t, then c
         else if (p.top_t) token_rescore_as(token_rescore_top_lp_kernel, s.final, p.top_t);      // the TOPT kernels take top_t last
         else if (mse) token_rescore_as(token_rescore_mse_lp_kernel, s.final, a.cw);                 // the MSE kernels take c last
@@ -2862,4 +3109,62 @@ extern "C" int skyemb_distance_topk_tokens_prefiltered_sel(const float *c, const
                                                            int *redo, void *stream) {
     return skyemb_distance_topk_tokens_prefiltered_top_sel(c, t, Q, bank16, dtype, rowp_sel, tail, tiles, n_live, last_live, direct_end, N, P, D, k,
                                                            combine, 0, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream);
+}
+
+// ---- weighted MSE with per-query weights c [Q, D] ("Weighted MSE with PER-QUERY weights" above) --------------------------------------------
+#define TOKEN_MSE_PQ_PREFILTER_MSG "many-query weighted-MSE patch-token search with per-query weights: needs P a divisor of 64, D %% 32 == 0, " \
+                                   "128 <= D <= 2048 (stage 1 multiplies rows of 2 D), 1 <= k <= %d, k <= N, 2048 <= N * P rows, fewer than 2^31 " \
+                                   "rows after padding to whole %d-row tiles, and Q >= 1 (Q=%d N=%lld P=%d D=%d k=%d)"
+extern "C" int skyemb_token_mse_pq_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
+    const bool ok = D >= 4 * BK && D <= 2048 && D % BK == 0 && pfplan::tokens_shape_ok(Q, N, P, 2 * D, k) &&
+                    skyemb_bank16_rowp_rows(N * P) < (1ll << 31);
+    if (!ok) skyemb_set_error(TOKEN_MSE_PQ_PREFILTER_MSG, TOK_KMAX, BT, Q, (long long)N, P, D, k);
+    return ok ? 1 : 0;
+}
+
+extern "C" double skyemb_token_mse_pq_prefilter_eps(int D, int lo, int dtype) { return eps_pq_of(D, lo != 0, dtype == SKYEMB_BF16); }
+
+extern "C" int skyemb_token_mse_pq_image(const void *bank16, int dtype, int64_t R, int D, void *image, float *rowp, void *stream) {
+    const char *who = "skyemb_token_mse_pq_image";
+    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
+    SKY_CHECK_ARG(bank16 && image && rowp && R > 0 && D >= 4 * BK && D % BK == 0 && D <= 2048, "%s: bad arguments (R=%lld, D=%d: D %% 32 == 0, "
+                  "128 <= D <= 2048)", who, (long long)R, D);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(image), "%s: the bank and the image must be 16-byte aligned", who);
+    const int64_t padded = skyemb_bank16_rowp_rows(R);
+    SKY_CHECK_ARG(padded < (1ll << 31), "%s: R = %lld rows: the image must hold fewer than 2^31 rows after padding to whole %d-row tiles", who,
+                  (long long)R, BT);
+    const dim3 grid((unsigned)ceil_div64(padded, 4));
+    // fp16: one image serves both variants: the smaller eps_pq (hi + lo) gives the larger, always valid, term
+    const float sub_scale = (float)(0x1p-14 / eps_pq_of(D, true, false) * (1.0 + 1e-6));
+    if (dtype == SKYEMB_BF16)
+        hipLaunchKernelGGL(mse_pq_image_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short *)bank16, R, D,
+                           (unsigned short *)image, (float4 *)rowp, padded, sub_scale);
+    else
+        hipLaunchKernelGGL(mse_pq_image_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short *)bank16, R, D,
+                           (unsigned short *)image, (float4 *)rowp, padded, sub_scale);
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// (combine is the DISTANCE combine, out_s holds keys = -distance, as for skyemb_distance_topk_tokens_prefiltered.  The request plans as
+// {tokens, resident, D' = 2 D} over the image's padded images: a bank without a ragged tail, whose padding rows pass no test)
+extern "C" int skyemb_distance_topk_tokens_prefiltered_pq(const float *c, const float *t, int Q, const void *bank16, int dtype, const void *image,
+                                                          const float *rowp, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
+                                                          const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i,
+                                                          int *redo, void *stream) {
+    const char *who = "skyemb_distance_topk_tokens_prefiltered_pq";
+    SKY_CHECK_ARG(c && image && aligned16(c) && aligned16(t) && aligned16(image), "%s: c, t and the image must be given and 16-byte aligned", who);
+    SKY_CHECK_ARG(combine == SKYEMB_COMBINE_MIN || combine == SKYEMB_COMBINE_MAX, "%s: combine code %d: this entry combines by min or max "
+                  "(mean is served by skyemb_distance_token_topk_pq)", who, combine);
+    if (!skyemb_token_mse_pq_prefilter_applicable(Q, N, P, D, k)) {
+        char why[640];
+        snprintf(why, sizeof why, "%s", skyemb_last_error());
+        skyemb_set_error("%s: %s", who, why);
+        return 1;
+    }
+    const int key_combine = combine == SKYEMB_COMBINE_MIN ? SKYEMB_COMBINE_MAX : SKYEMB_COMBINE_MIN;
+    const int64_t N_padded = skyemb_bank16_rowp_rows(N * P) / P;
+    return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N_padded, P, 2 * D, k, key_combine, 0, 0.f, thr0),
+                  {t, nullptr, nullptr, nullptr, bank16, dtype, nullptr, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
+                   nullptr, N, who, c, image});
 }

@@ -728,6 +728,53 @@ def distance_topk_tokens_prefiltered_sel(c, t, tokens, tail, prepared, direct_en
     return ws
 
 
+def token_mse_pq_prefilter_refusal(Q, N, P, D, k):
+    """None when the two-stage weighted-MSE token search with per-query weights takes the shape, else the library's own statement
+    of its limits.  Host arithmetic only."""
+    L = lib()
+    return None if L.skyemb_token_mse_pq_prefilter_applicable(Q, N, P, D, k) else L.skyemb_last_error().decode()
+
+
+def token_mse_pq_prefilter_eps(D, dtype, lo=False):
+    """eps_pq of the two-stage weighted-MSE search with per-query weights over a ``dtype`` bank (host arithmetic only;
+    include/skyemb.h)."""
+    return lib().skyemb_token_mse_pq_prefilter_eps(D, int(lo), resident_dtype_code(dtype, "token_mse_pq_prefilter_eps"))
+
+
+def token_mse_pq_image(tokens, image=None, rowp=None):
+    """(image, rowp) of the two-stage weighted-MSE search with per-query weights: the second 16-bit image [rows, 2 D] of a resident
+    token bank ``tokens`` [N, P, D] (or its flat rows [R, D]), rows [x ; r16(x o x)], and its row constants [rows, 4]; rows = R
+    padded to whole 256-row tiles (zero rows, sentinel constants).  One launch per bank: neither depends on the weights.  ``image``
+    / ``rowp``: buffers to write into (the tests' guard buffers), allocated when None."""
+    D = tokens.shape[-1]
+    R = tokens.numel() // D
+    code = resident_dtype_code(tokens.dtype, "token_mse_pq_image")
+    assert tokens.is_contiguous()
+    _check_aligned16(tokens, "token_mse_pq_image", "the 16-bit", "must be")
+    rows = lib().skyemb_bank16_rowp_rows(R)
+    image = torch.empty(rows, 2 * D, device=tokens.device, dtype=tokens.dtype) if image is None else image
+    rowp = torch.empty(rows, 4, device=tokens.device, dtype=torch.float32) if rowp is None else rowp
+    assert image.is_contiguous() and rowp.is_contiguous() and image.numel() == rows * 2 * D and rowp.numel() == rows * 4
+    assert image.dtype == tokens.dtype and rowp.dtype == torch.float32
+    check(lib().skyemb_token_mse_pq_image(_p(tokens), code, R, D, _p(image), _p(rowp), _stream()), "skyemb_token_mse_pq_image")
+    return image, rowp
+
+
+def distance_topk_tokens_prefiltered_pq(c, t, tokens, image, rowp, k, combine, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """The two-stage many-query weighted-MSE search with per-query weights ``c`` [Q, D] (``prepare_distance_weights`` of [Q, D]
+    weights) over a resident 16-bit token bank ``tokens`` [N, P, D] and the (image, rowp) of ``token_mse_pq_image``; ``combine``:
+    COMBINE_CODES['min'] or ['max'] of the DISTANCES.  ``out_s`` receives keys = -distance (include/skyemb.h)."""
+    Q, D = t.shape
+    N, P = tokens.shape[:2]
+    assert tuple(c.shape) == (Q, D) and c.dtype == torch.float32 and c.is_contiguous() and t.is_contiguous()
+    code = resident_dtype_code(tokens.dtype, "distance_topk_tokens_prefiltered_pq")
+    ws = _workspace(ws, lib().skyemb_token_prefilter_ws_bytes(Q, 2 * D, k), t.device)
+    check(lib().skyemb_distance_topk_tokens_prefiltered_pq(_p(c), _p(t), Q, _p(tokens), code, _p(image), _p(rowp), N, P, D, k, combine,
+                                                           idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
+                                                           _stream()), "skyemb_distance_topk_tokens_prefiltered_pq")
+    return ws
+
+
 def token_mean_prefilter_refusal(Q, N, P, D, k):
     """None when the two-stage token search with combine mean takes the shape, else the library's own statement of its limits."""
     L = lib()

@@ -450,6 +450,7 @@ class TokenBank:
         self._stage1_mean = None                           # (pooled image, its tail tile, rowp) of the route under combine 'mean'
         self._stage1_mse = None                            # (c, tail tile, rowp) of the weighted-MSE route, for the last c seen
         self._mse_top_t = False                            # True: asked to take that route under top_t too (prepare_mse_top_t)
+        self._mse_pq = None                                # (image [x ; x o x], rowp) of that route with per-query weights (prepare_mse_per_query)
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
 
@@ -504,6 +505,24 @@ class TokenBank:
         if not self._resident:
             raise ValueError("TokenBank.prepare_mse_top_t: the bank must be made by TokenBank.resident")
         self._mse_top_t = True
+        return self
+
+    def prepare_mse_per_query(self):
+        """Ask this resident bank to take the two-stage weighted-MSE route of ``distance_topk_tokens`` with per-query weights
+        ([Q, D] ``weights``), and build what that route reads: a second 16-bit image [N P padded to whole 256-row tiles, 2 D] of the
+        bank, rows [x ; x o x] with the squares rounded once to the bank's dtype, and its row constants (``ops.token_mse_pq_image``:
+        one pass over the bank, 4 N P D + 16 N P bytes beside the bank's 2 N P D).  Neither depends on the weights -- per-query weights
+        arrive with the search --, so ``set_weights`` keeps them.  A bank never asked answers per-query weights by the grouped route,
+        as it always has.  Cosine with per-query weights keeps the grouped route either way: its row norm sits under a square root
+        in the denominator, which no single dot product holds.  Returns ``self``:
+        ``TokenBank.resident(bank).prepare_mse_per_query()``."""
+        if not self._resident:
+            raise ValueError("TokenBank.prepare_mse_per_query: the bank must be made by TokenBank.resident")
+        N, P, D = self.bank.shape
+        if D % 32 or not 128 <= D <= 2048:
+            raise ValueError(f"TokenBank.prepare_mse_per_query: the image holds rows of 2 D: D % 32 == 0 and 128 <= D <= 2048 (D = {D})")
+        if self._mse_pq is None:
+            self._mse_pq = ops.token_mse_pq_image(self.bank)
         return self
 
     def set_weights(self, weights):
@@ -1011,11 +1030,22 @@ TOKEN_MSE_PREFILTER_MIN_Q_SMALL = 1024                    # smaller banks
 TOKEN_MSE_TOPT_PREFILTER_MIN_Q = 32
 TOKEN_MSE_SELECT_PREFILTER_MIN_Q = 32
 TOKEN_MSE_SELECT_TOPT_PREFILTER_MIN_Q = 32
+# ... with per-query weights [Q, D], by opt-in (TokenBank.prepare_mse_per_query): stage 1 multiplies a second image of the bank with
+# rows of 2 D, twice the k-steps of the shared-weight route, against a grouped route that takes at most 16 queries per bank pass.
+# tools/bench_mse_per_query.py measures it against the grouped per-query route on the bank above (Q in 16 .. 1024, 'min' and 'max',
+# both dtypes, query preparation and the first-threshold sample included, the one-off image build -- about 1 ms -- apart); the
+# constant is the smallest Q of its grid from which the route is at least 10 % faster in both of two runs
+# (profiles/mse_per_query_crossover.json and its repeat).  Measured: 128, decided by bf16 -- 1.51x - 1.52x
+# there (fp16: 2.36x - 2.39x), 2.28x - 2.30x at 256 (3.3x - 3.5x), 1.76x - 1.80x at 1024 (2.9x - 3.0x); at 64 fp16 wins by 1.53x -
+# 1.58x but bf16, whose bound is the wider one (unit roundoff 2^-8), loses (0.89x - 0.91x), and one constant serves both dtypes.
+# Smaller banks are NOT MEASURED: TOKEN_MSE_PREFILTER_MIN_Q_SMALL, as above
+TOKEN_MSE_PQ_PREFILTER_MIN_Q = 128
 
 
 def _token_mse_prefilter_refusal(rq: TokenRequest):
     """``_token_prefilter_refusal`` for a distance request over a resident 16-bit bank: None when ``distance_topk_tokens`` serves it
-    by the two-stage route (metric MSE, combine min | max, shared weights, P a divisor of 64, the library's shape rule, the switch
+    by the two-stage route (metric MSE, combine min | max, shared weights -- per-query weights only over a bank asked by
+    ``TokenBank.prepare_mse_per_query``, without ``top_t`` and ``select`` --, P a divisor of 64, the library's shape rule, the switch
     on, enough queries; ``top_t`` only over a bank asked by ``TokenBank.prepare_mse_top_t``, ``select`` only as a Selection asked by
     ``Selection.prepare_mse`` for this bank), else the first reason why the grouped route serves it."""
     name = next((n for n, code in ops.METRIC_CODES.items() if code == rq.metric), rq.metric_name)
@@ -1024,14 +1054,14 @@ def _token_mse_prefilter_refusal(rq: TokenRequest):
     asked = isinstance(sel, Selection) and held is not None and tb in held
     why = token_mse_route_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k, name, rq.combine, rq.top_t, sel is not None, rq.per_query,
                                   top_t_prepared=bool(getattr(tb, "_mse_top_t", False)), select_prepared=asked,
-                                  selected=sel.count if asked else None)
+                                  selected=sel.count if asked else None, per_query_prepared=getattr(tb, "_mse_pq", None) is not None)
     if why == "select under a distance metric" and isinstance(sel, Selection):
         why += " without the masked row constants of this bank (opt in once per Selection and bank: Selection.prepare_mse)"
     return why
 
 
 def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=False, per_query=False, *, top_t_prepared=False,
-                            select_prepared=False, selected=None):
+                            select_prepared=False, selected=None, per_query_prepared=False):
     """The same decision from the request's plain facts, for a caller that has not wrapped its bank yet (``similarity_search.py``
     builds a ``TokenBank.resident`` -- a norm pass over the bank -- only when this returns None): ``metric`` a name, ``combine`` a
     name or an ``ops.COMBINE_CODES`` code, ``top_t`` None / 0 for all tokens, ``select`` whether there is a selection.  The bank is
@@ -1040,7 +1070,12 @@ def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=Fals
     ``top_t_prepared`` / ``select_prepared`` (keyword only; False: the answers as they ever were): the caller will opt in by
     ``TokenBank.prepare_mse_top_t`` / ``Selection.prepare_mse``, and the request is then decided under ``top_t`` / the selection:
     the library's range for ``top_t``, the smallest Q of the route the request takes, and with ``selected`` (the number of selected
-    images; None: not looked at) the rule that the selected images are themselves a bank the route takes."""
+    images; None: not looked at) the rule that the selected images are themselves a bank the route takes.
+
+    ``per_query_prepared`` (keyword only; False: the answers as they ever were): the caller will opt in by
+    ``TokenBank.prepare_mse_per_query``, and a request with per-query weights is then decided by that route's rule -- no ``top_t`` and
+    no ``select`` (with either the answer stays "per-query weights"), D % 32 == 0 and 128 <= D <= 2048 (stage 1 multiplies rows of
+    2 D), and ``TOKEN_MSE_PQ_PREFILTER_MIN_Q`` as the smallest Q."""
     combine = ops.COMBINE_CODES.get(combine, combine)
     if metric != 'MSE':
         return f"metric {metric} (a distance that is no dot product)"
@@ -1050,12 +1085,20 @@ def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=Fals
         return "top_t under a distance metric"
     if select and not select_prepared:
         return "select under a distance metric"
-    if per_query:
+    if per_query and (not per_query_prepared or top_t or select):
         return "per-query weights"
     if P < 1 or 64 % P:
         return f"P = {P} does not divide 64"
     if not _prefilter_enabled():
         return "SKYEMB_TOPK_PREFILTER=0"
+    if per_query:                                          # its own smallest Q and its own shape rule (rows of 2 D)
+        if N * P * D >= TOKEN_MSE_PREFILTER_MIN_ELEMENTS:
+            if Q < TOKEN_MSE_PQ_PREFILTER_MIN_Q:
+                return f"Q = {Q} < TOKEN_MSE_PQ_PREFILTER_MIN_Q = {TOKEN_MSE_PQ_PREFILTER_MIN_Q}"
+        elif Q < TOKEN_MSE_PREFILTER_MIN_Q_SMALL:
+            return (f"Q = {Q} < TOKEN_MSE_PREFILTER_MIN_Q_SMALL = {TOKEN_MSE_PREFILTER_MIN_Q_SMALL} (a bank of fewer than "
+                    f"TOKEN_MSE_PREFILTER_MIN_ELEMENTS = {TOKEN_MSE_PREFILTER_MIN_ELEMENTS} elements)")
+        return ops.token_mse_pq_prefilter_refusal(Q, N, P, D, k)
     if top_t:
         why = ops.token_mse_topt_prefilter_refusal(Q, N, P, D, k, combine, top_t)
         if why is not None:
@@ -1290,7 +1333,9 @@ def cosine_topk_tokens(queries: torch.Tensor, bank, k: int, combine: str = 'min'
     first threshold comes from a sample scored under the same ``top_t``, a re-run keeps it, ``stats`` gains ``top_t``, and the
     smallest Q is ``TOKEN_TOPT_PREFILTER_MIN_Q`` (a bank of fewer than ``TOKEN_TOPT_PREFILTER_MIN_ELEMENTS`` elements:
     ``TOKEN_TOPT_PREFILTER_MIN_Q_SMALL``).  Out of scope for the two-stage route: ``top_t`` under 'mean' (the mean of the
-    top_t best is not bounded by a count), per-query weights, fp32 token banks, P not dividing 64, and
+    top_t best is not bounded by a count), per-query weights (the row norm sum w_qd x_d^2 sits under a square root in the
+    denominator, so no single dot product bounds the score; ``distance_topk_tokens`` with 'MSE' does take them, by opt-in), fp32
+    token banks, P not dividing 64, and
     ``select`` under 'mean' without ``Selection.prepare_mean``.
 
     Images whose combined score is -inf (a NaN token under min / mean)
@@ -1417,6 +1462,42 @@ def _topk_tokens_mse_prefiltered(rq: TokenRequest, queries, prune, stats, proces
     return out_s.neg_(), out_i                                          # (-inf, -1) becomes (+inf, -1)
 
 
+def _topk_tokens_mse_pq_prefiltered(rq: TokenRequest, queries, prune, stats, process_group, world_size):
+    """``_topk_tokens_mse_prefiltered`` with per-query weights (csrc/topk_prefilter.hip, "Weighted MSE with PER-QUERY weights"):
+    stage 1 multiplies the bank's second image [x ; x o x] (``TokenBank.prepare_mse_per_query``) by query images built from
+    [c_q o t_q ; -c_q / 2], stage 2 re-scores candidates under row q of c.  The first threshold comes from the same strided sample
+    of min(N, max(16 k, 256)) whole images, scored by the grouped per-query kernel in groups of ``rq.step`` (``_pq_group``) queries;
+    flagged queries are re-run by the grouped per-query route, those queries only, each with its own weight row."""
+    tb, Q, k, dev = rq.bank, rq.Q, rq.k, rq.tokens.device
+    q = queries.to(dev, torch.float32).contiguous()
+    W = rq.weights.to(dev, torch.float32).contiguous()
+    c = prepare_distance_weights(W, rq.D, dev)
+    image, rowp = tb._mse_pq
+    S = min(rq.N, max(16 * k, 256))
+    st = tb.sample(S, "bootstrap")[0]
+    thr0 = torch.empty(Q, device=dev)
+    keys = torch.empty(rq.step, S, device=dev)
+    for lo in range(0, Q, rq.step):
+        g = min(rq.step, Q - lo)
+        ops.distance_token_scores_pq(c[lo:lo + g], q[lo:lo + g], st, rq.metric, rq.combine, keys[:g], 0, None)
+        ops.kth_largest_floor(keys[:g].neg_(), k, thr0[lo:lo + g])
+
+    def launch(*out):
+        return ops.distance_topk_tokens_prefiltered_pq(c, q, tb.bank, image, rowp, k, rq.combine, rq.idx_offset, *out, thr0)
+
+    def rerun(again):                                      # the grouped per-query route, in key space like ``launch``'s result
+        rq2 = dataclasses.replace(rq, Q=int(again.numel()), weights=W.index_select(0, again))
+        s2, i2 = _topk_tokens(rq2, _DistanceScorer.of(rq2), q.index_select(0, again), prune, None, None, 1)
+        return s2.neg_(), i2
+
+    out_s, out_i, n_redo = _two_stage(Q, k, dev, launch, rerun)
+    if stats is not None:
+        stats.update(path="prefiltered", per_query_weights=True, redone=n_redo, metric=rq.metric_name,
+                     combine=next(name for name, code in ops.COMBINE_CODES.items() if code == rq.combine))
+    _gather_merge(out_s, out_i, Q, k, world_size, process_group)        # (of keys)
+    return out_s.neg_(), out_i                                          # (-inf, -1) becomes (+inf, -1)
+
+
 def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE', combine: str = 'mean',
                          weights: torch.Tensor | None = None, prune: bool = True, stats: dict | None = None, top_t: int | None = None,
                          select=None, process_group=None, world_size: int = 1):
@@ -1457,8 +1538,20 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     route, never refused, and fewer than k selected images leave a (+inf, -1) tail.  Smallest Q on a bank of at least
     ``TOKEN_MSE_PREFILTER_MIN_ELEMENTS`` elements: ``TOKEN_MSE_TOPT_PREFILTER_MIN_Q`` (the top-t fold),
     ``TOKEN_MSE_SELECT_PREFILTER_MIN_Q`` (a selection), ``TOKEN_MSE_SELECT_TOPT_PREFILTER_MIN_Q`` (both); smaller banks:
-    ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``.  Out of scope for the two-stage route, served by the grouped route as ever: metric 'MAE'
-    (no dot product), ``combine`` 'mean', per-query weights, fp32 banks, P not dividing 64, a bool-tensor ``select``.
+    ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``.  Per-query weights ([Q, D], below) take the route BY OPT-IN too:
+    ``TokenBank.resident(bank).prepare_mse_per_query()`` builds a second 16-bit image of the bank, rows [x ; x o x] of length 2 D with
+    the squares rounded once to the bank's dtype (4 N P D bytes beside the bank's 2 N P D, one pass, independent of the weights and
+    kept across ``set_weights``); then D dist = A_q - 2 [c_q o t_q ; -c_q / 2] . [x ; x o x] is still one dot product per token, the row
+    constant B_r having moved into it, and stage 2 re-scores candidates under row q of c -- bit for bit the grouped per-query route.
+    Its rule: metric 'MSE', 'min' or 'max', no ``top_t`` and no ``select`` (with either the request keeps the grouped route), P a
+    divisor of 64, D % 32 == 0 and 128 <= D <= 2048, the shape rule above on (N, P, 2 D, k), at least
+    ``TOKEN_MSE_PQ_PREFILTER_MIN_Q`` queries (smaller banks: ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``); ``stats`` gains
+    ``per_query_weights``.  A negative, NaN or above-2^10 weight sends back only the queries whose own row holds it; a query with
+    c_q o t_q = 0 is re-run as well.  Out of scope for the two-stage route, served by the grouped route as ever: metric 'MAE' (no dot
+    product), ``combine`` 'mean', per-query weights over a bank never asked or together with ``top_t`` or ``select``, fp32 banks, P
+    not dividing 64, a bool-tensor ``select``.  (Cosine with per-query weights, ``cosine_topk_tokens``, stays on the grouped route as
+    well: its row norm sum w_qd x_d^2 sits under a square root in the denominator, so stage 1's candidate test is no longer one
+    linear instruction.)
 
     ``select``, ``prune``, ``stats``, ``world_size``: as for ``cosine_topk_tokens`` (the floor and the merges work on
     key = -distance).  Every ValueError -- an unknown metric or combine, top_t outside 1 .. min(P, 16), k, a selection of
@@ -1471,7 +1564,8 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     ``stats['per_query_weights']`` is True and ``stats['group']`` is g."""
     rq = _token_request("distance_topk_tokens", queries, bank, k, combine, metric, weights, top_t, select, world_size)
     if _token_prefilter_refusal(rq) is None:
-        return _topk_tokens_mse_prefiltered(rq, queries, prune, stats, process_group, world_size)
+        driver = _topk_tokens_mse_pq_prefiltered if rq.per_query else _topk_tokens_mse_prefiltered
+        return driver(rq, queries, prune, stats, process_group, world_size)
     return _topk_tokens(rq, _DistanceScorer.of(rq), queries, prune, stats, process_group, world_size)
 
 
