@@ -1594,8 +1594,8 @@ __device__ __forceinline__ float4 mse_test_row(float tau, float4 qb, float fD, f
     const float theta = tau > -3.0e38f ? -tau : 3.0e38f;       // the distance threshold; no threshold yet: everything passes
     float T = theta * fD;
     T = fmaf(fabsf(T), gamma, T) + 0x1p-126f;                  // D theta (1 + gamma) + 2^-126 (the slack below covers these roundings)
-    if (!(T < 3.0e38f)) T = 3.0e38f;
-    const float h = 0.5f * qb.z;                               // 2^-(f+1), exact
+    if (T > 3.0e38f) T = 3.0e38f;                              // (a floor of +inf: theta = -inf, T = inf - inf stays NaN -> g NaN -> *bad)
+    const float h = 0.5f * qb.z;                              // 2^-(f+1), exact
     float g = h * (T - qb.x);
     g += fabsf(g) * 0x1p-19f;
     if (g > 3.0e38f) g = 3.0e38f;                              // no threshold yet (or a loose one times a large scale): a R0 < 2^125, all pass

@@ -1,7 +1,8 @@
 """What the per-pair (tests/test_prefilter_stage1_gpu.py) and per-candidate (tests/test_prefilter_stage2_gpu.py) GPU tests of the
 two-stage many-query search share: guarded device buffers, the preparation call, and one search call through the C ABI whose
 workspace is read back through skyemb_topk_prefilter_ws_layout; TokenSearch is the same for the patch-token route
-(tests/test_token_prefilter_stage_gpu.py).  No test lives here."""
+(tests/test_token_prefilter_stage_gpu.py), MseTokenSearch for its weighted-MSE forms (tests/test_token_mse_stage_gpu.py).  No test
+lives here."""
 import numpy as np
 import torch
 
@@ -220,3 +221,95 @@ class TokenSearch:
             return row
         inside = (row >= 0) & (row < self.N)
         return row[inside][images[row[inside]]]
+
+
+def select_words(flags, N):
+    """The packed selection words (one bit per image, little-endian) of a boolean mask [N], on the device."""
+    bits = np.zeros(-(-N // 32) * 32, dtype=np.uint8)
+    bits[:N] = flags
+    return dev(np.packbits(bits, bitorder="little").view(np.uint32).view(np.int32))
+
+
+class MseTokenSearch(TokenSearch):
+    """TokenSearch's twin for the weighted-MSE search: one call of skyemb_distance_topk_tokens_prefiltered, or of its _top (top_t),
+    _sel (flags, a boolean per image), _top_sel or _pq (c of shape [Q, D]: per-query weights) form, over the bank xw [N, P, D]
+    (float32 values of `fmt`), raw queries t [Q, D] and prepared weights c.  combine is the DISTANCE combine; thr0 a floor per query
+    in KEY space (key = -distance).  skyemb_token_mse_rowp / skyemb_token_mse_pq_image write into guarded buffers (.rowp, .image:
+    16-bit patterns [rows, 2 D]); the workspace is read back at ops.token_prefilter_ws_layout(Q, D or 2 D, k).  .ws, .rn, .list,
+    .candidates, .out_s (KEYS), .out_i, .redo, .guards_ok as in TokenSearch, and the FILL32 convention with them."""
+    def __init__(self, ops, fmt, c, t, xw, k, combine, top_t=None, flags=None, thr0=None, idx_offset=0):
+        from tests import token_prefilter_select_reference as tps
+        L = ops.lib()
+        fmt = {"f16": "fp16"}.get(fmt, fmt)
+        Q, D = t.shape
+        N, P = xw.shape[:2]
+        R = N * P
+        self.pq = np.ndim(c) == 2
+        Ds = 2 * D if self.pq else D                                   # the row length stage 1 multiplies
+        self.Q, self.N, self.P, self.D, self.Ds, self.k = Q, N, P, D, Ds, k
+        assert not self.pq or (top_t is None and flags is None)
+        bank = bank_tensor(np.ascontiguousarray(xw.reshape(R, D)), fmt)
+        code, comb = ops.dtype_code(TORCH16[fmt]), ops.COMBINE_CODES[combine]
+        c_d, t_d, thr_d = dev(np.asarray(c, np.float32)), dev(np.asarray(t, np.float32)), dev(thr0)
+        rows = L.skyemb_bank16_rowp_rows(R)
+        rowp, side = Guarded(rows * 16), None
+        if self.pq:
+            side = Guarded(rows * Ds * 2)
+            rc = L.skyemb_token_mse_pq_image(ptr(bank), code, R, D, side.ptr(), rowp.ptr(), stream())
+        else:
+            side = Guarded(256 * D * 2) if R % 256 else None
+            rc = L.skyemb_token_mse_rowp(ptr(bank), code, ptr(c_d), R, D, rowp.ptr(), side.ptr() if side else None, stream())
+        torch.cuda.synchronize()
+        assert rc == 0, L.skyemb_last_error()
+        assert rowp.intact() and (side is None or side.intact())
+        self.rowp = rowp.np(np.float32, -1, 4)
+        self.image = side.np(np.uint16, rows, Ds) if self.pq else None
+        lay = ops.token_prefilter_ws_layout(Q, Ds, k)
+        nbytes = L.skyemb_token_prefilter_ws_bytes(Q, Ds, k)
+        assert lay["list"] == L.skyemb_topk_prefilter_ws_bytes(Q, Ds, k)
+        assert nbytes == lay["list"] + -(-Q * TOK_KMAX * 8 // 256) * 256
+        ws = Guarded(nbytes)
+        out_s, out_i, redo = Guarded(Q * k * 4), Guarded(Q * k * 8), Guarded(Q * 4)
+        tail = side.ptr() if side is not None else None
+        back = (idx_offset, ptr(thr_d), ws.ptr(), nbytes, out_s.ptr(), out_i.ptr(), redo.ptr(), stream())
+        self.tiles = self.cum = None
+        if self.pq:
+            rc = L.skyemb_distance_topk_tokens_prefiltered_pq(ptr(c_d), ptr(t_d), Q, ptr(bank), code, side.ptr(), rowp.ptr(), N, P, D, k, comb,
+                                                              *back)
+        elif flags is None and top_t is None:
+            rc = L.skyemb_distance_topk_tokens_prefiltered(ptr(c_d), ptr(t_d), Q, ptr(bank), code, rowp.ptr(), tail, N, P, D, k, comb, *back)
+        elif flags is None:
+            rc = L.skyemb_distance_topk_tokens_prefiltered_top(ptr(c_d), ptr(t_d), Q, ptr(bank), code, rowp.ptr(), tail, N, P, D, k, comb, top_t,
+                                                               *back)
+        else:
+            rowp_sel, tiles, n_live, last_live, cum = ops.token_prefilter_select_prepare(select_words(flags, N), N, P, rowp.t(torch.float32, -1, 4))
+            self.tiles, self.cum, self.last_live = tiles.cpu().numpy()[:n_live], cum, last_live
+            self.direct_end = tps.direct_end(cum, n_live, k)            # search.py's rule
+            self.rowp = rowp_sel.cpu().numpy()
+            lead = (ptr(c_d), ptr(t_d), Q, ptr(bank), code, ptr(rowp_sel), tail, ptr(tiles), n_live, last_live, self.direct_end, N, P, D, k, comb)
+            if top_t is None:
+                rc = L.skyemb_distance_topk_tokens_prefiltered_sel(*lead, *back)
+            else:
+                rc = L.skyemb_distance_topk_tokens_prefiltered_top_sel(*lead, top_t, *back)
+        torch.cuda.synchronize()
+        assert rc == 0, L.skyemb_last_error()
+        self.guards_ok = all(g.intact() for g in (ws, out_s, out_i, redo, rowp) + ((side,) if side is not None else ()))
+        self.cap = lay["cap"]
+        raw = ws.mem.cpu().numpy()
+        self.ws = ws_arrays(raw, lay, Q, Ds)
+        self.rn = self.ws["nsel"]
+        self.list = raw[lay["list"]:lay["list"] + Q * TOK_KMAX * 8].view(np.uint64).reshape(Q, TOK_KMAX)
+        self.out_s, self.out_i, self.redo = out_s.np(np.float32, Q, k), out_i.np(np.int64, Q, k), redo.np(np.int32, Q)
+
+    def dots(self):
+        """P = 1, a single direct slice: dot^ [Q, R] from cand_i / cand_d (NaN where a row is not listed), and per query the number
+        of slots written -- anything in a list's row that is not the FILL pattern counts, in either array."""
+        assert self.P == 1
+        ci, cd = self.ws["cand_i"], self.ws["cand_d"]
+        used = ci != FILL32
+        d = np.full((self.Q, self.N), np.nan, dtype=np.float32)
+        ok = used & (ci >= 0) & (ci < self.N)
+        qq = np.nonzero(ok)[0]
+        d[qq, ci[ok]] = cd[ok]
+        written = used | (cd.view(np.int32) != FILL32)
+        return d, written.sum(axis=1)
