@@ -883,6 +883,49 @@ int skyemb_distance_topk_tokens_prefiltered_pq(const float *c, const float *t, i
                                                const float *rowp, int64_t N, int P, int D, int k, int combine, int64_t idx_offset,
                                                const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
                                                void *stream);
+/* The weighted-MSE search under combine MEAN in the same two stages (additive to ABI version 111): the many-query form of
+ * skyemb_distance_token_topk with metric SKYEMB_METRIC_MSE, combine SKYEMB_COMBINE_MEAN, shared weights c [D], no top_t, no selection; bit
+ * for bit that call + skyemb_topk_merge.  The mean is linear in the tokens: per image i and query q, in real arithmetic (P a power of two),
+ *   D mean_p dist(q, x_p) = A_q + Bbar_i - 2 (c o t_q) . m_i,   m_i = (1/P) sum_p x_p,   Bbar_i = (1/P) sum_p sum_d c_d x_pd^2,
+ * the operand shape of skyemb_distance_topk_tokens_prefiltered with a row that is an image: stage 1 is the ROW pass over a pooled 16-bit
+ * image [N, D] (P times fewer rows than the bank), stage 2 re-scores every candidate image's P tokens by the contract's chain and folds
+ * the keys -dist_p in token order, (((0 + s_0) + s_1) + ...) / float(P) -- the negation of the contract's mean bit for bit; a sum that is
+ * not a number is key -inf, never returned.  Bound (derivation: csrc/topk_prefilter.hip): the pooled row is m' = m_fl 2^-e, m_fl the fp32
+ * sum of the widened tokens in token order scaled exactly by 1 / P, e the power of two that puts its largest element in [2^13, 2^14),
+ * rounded once to the bank's dtype (bf16: elements below 2^-40 stored as zero), and
+ *   |dot^ - 2^-(f + e) (c o t) . m| <= eps ||q'|| R1,   eps = eps_m (skyemb_token_mean_prefilter_eps_m) + 2^-22,
+ *   R1 = ||m'|| + (kappa / eps_m(hi + lo)) c1 2^-e (raised),   kappa = 1.01 P 2^-24,   c1 = mean_p ||x_p||_2   (the pooling's P - 1 additions),
+ * so D mean_real >= A_dn + Bbar_dn - 2 2^(f + e) (dot^ + eps ||q'|| R1) =: L, and an image can reach the distance threshold theta only if
+ * L <= D theta (1 + gamma) + 2^-126, gamma = skyemb_token_mse_prefilter_gamma(D) + P 2^-24 (the mean's own P - 1 rounded additions).
+ *   skyemb_token_mse_mean_prefilter_applicable   1 / 0 (+ text): skyemb_token_mean_prefilter_applicable's shape rule (N >= 2048 images)
+ *   skyemb_token_mse_mean_prefilter_eps / _gamma  eps (lo: 0 hi only, 1 hi + lo; before the (1 + 1e-6) raise) and gamma: host arithmetic
+ *   skyemb_token_mse_mean_pool   one pass over the bank, independent of the weights: pooled16 [N, D] in the bank's dtype, its zero-padded tail
+ *                           tile [256, D] (needed when N % 256 != 0) and paux f32 [skyemb_bank16_rowp_rows(N), 2] = {R1, 2^-e} per image.
+ *                           An image the bank alone makes unboundable -- an inf / NaN element, bf16: a nonzero element outside
+ *                           [2^-60, 2^120), R1 or 2^-e at or above 2^60 -- holds a ZERO pooled row and {inf, 1}; padding rows {NaN, 0}.
+ *                           An image whose tokens cancel to a zero pooled row is an ordinary image (e = 0).
+ *   skyemb_token_mse_mean_rowp   one more pass over the bank per weight vector c [D] (16-byte aligned): rowp f32 [the same rows, 4] =
+ *                           {Bbar_dn 2^-e, R1, 2^-e, 0}, Bbar_dn = Bbar^ (1 - (n_B + 8) 2^-23) <= Bbar, n_B = 8 P ceil(D / 512) the fused multiply-adds of one lane's chain (0 below 2^-100; a product that
+ *                           underflows is lowered to 0).  Unboundable -- {0, inf, 1, 0}, a candidate of every query -- when paux says so,
+ *                           when Bbar^ is not a number in [0, 2^36) (fp16) / [0, 2^96) (bf16), or when Bbar_dn 2^-e leaves that window.
+ *                           Padding rows: the sentinel {0, NaN, 0, 0}.
+ *   skyemb_distance_topk_tokens_mean_prefiltered   c [D], t [Q, D] (16-byte aligned); pooled16 and tail those of _pool, rowp that of _rowp
+ *                           under the same c; thr0, out_s (KEYS = -distance), out_i, redo as for skyemb_distance_topk_tokens_prefiltered;
+ *                           ws: skyemb_token_mean_prefilter_ws_bytes(Q, D, k).  It plans as the request {SKYEMB_PF_TOKENS_MEAN, the
+ *                           bank's format, D, combine mean} of skyemb_prefilter_plan (hi + lo unless SKYEMB_PREFILTER_LO=0); stage 1's eps
+ *                           is the eps above, the re-score's gfac carries gamma.  redo[q] != 0: a full candidate list, a zero or
+ *                           out-of-range query, a weight that is negative, NaN or above 2^10 (then every query).  The caller re-runs
+ *                           flagged queries through skyemb_distance_token_topk. */
+int skyemb_token_mse_mean_prefilter_applicable(int Q, int64_t N, int P, int D, int k);
+double skyemb_token_mse_mean_prefilter_eps(int D, int lo, int dtype);
+double skyemb_token_mse_mean_prefilter_gamma(int D, int P);
+int skyemb_token_mse_mean_pool(const void *bank16, int dtype, int64_t N, int P, int D, void *pooled16, float *paux, void *tail, void *stream);
+int skyemb_token_mse_mean_rowp(const void *bank16, int dtype, const float *c, const float *paux, int64_t N, int P, int D, float *rowp,
+                               void *stream);
+int skyemb_distance_topk_tokens_mean_prefiltered(const float *c, const float *t, int Q, const void *bank16, int dtype, const void *pooled16,
+                                                 const void *tail, const float *rowp, int64_t N, int P, int D, int k, int64_t idx_offset,
+                                                 const float *thr0, void *ws, int64_t ws_bytes, float *out_s, int64_t *out_i, int *redo,
+                                                 void *stream);
 /* Read-only query of the launch plan of every two-stage search above (csrc/prefilter_plan.h): what the entry point serving `req`
  * decides on the host -- variant, slices, kernel instances, LDS bytes -- and then launches.  Host arithmetic only, touches no device.
  * Returns 0 and fills *out, or 1 with the text (skyemb_last_error) and under the name of the entry point that would refuse the

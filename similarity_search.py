@@ -216,12 +216,15 @@ def main():
                                                            select is not None, args.per_target, top_t_prepared=True,
                                                            select_prepared=True,
                                                            selected=None if select is None else select.count,
-                                                           per_query_prepared=True) is None):
+                                                           per_query_prepared=True, mean_prepared=True) is None):
                     # many targets under weighted MSE over a 16-bit bank, and the two-stage route will take them (decided first: the
                     # wrapper costs a norm pass over the bank that the distance route never reads): identical results by contract.
                     # -nts, --bank-select-snr and --per-target take that route by opt-in, asked for here (--per-target: a second
-                    # image of the bank, 4 bytes per element; its [T, D] weights travel with the search, not with the bank)
+                    # image of the bank, 4 bytes per element; its [T, D] weights travel with the search, not with the bank).
+                    # -c mean takes it by opt-in as well: a pooled image of the bank, one pass, 2 D bytes per image
                     tokens = search.TokenBank.resident(bank, None if args.per_target else w)
+                    if args.combine == 'mean':
+                        tokens.prepare_mse_mean()
                     if args.per_target:
                         tokens.prepare_mse_per_query()
                     if args.n_top_sims:

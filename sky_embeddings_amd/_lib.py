@@ -269,6 +269,14 @@ PROTOTYPES = {
     "skyemb_token_mse_pq_image": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "skyemb_distance_topk_tokens_prefiltered_pq": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64,
                                                            c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    # ... under combine mean: a pooled 16-bit image [N, D] of the bank and its constants, additive again
+    "skyemb_token_mse_mean_prefilter_applicable": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32]),
+    "skyemb_token_mse_mean_prefilter_eps": (c_f64, [c_i32, c_i32, c_i32]),
+    "skyemb_token_mse_mean_prefilter_gamma": (c_f64, [c_i32, c_i32]),
+    "skyemb_token_mse_mean_pool": (c_i32, [c_vp, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "skyemb_token_mse_mean_rowp": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "skyemb_distance_topk_tokens_mean_prefiltered": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i64,
+                                                             c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "skyemb_cosine_scores": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_vp]),
     "skyemb_cosine_token_applicable": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
     "skyemb_cosine_token_topk_chunks": (c_i32, [c_i64, c_i32, c_i32, c_i32, c_i32]),

@@ -1790,6 +1790,186 @@ __global__ void mse_state_kernel(int Q, int Q_padded, const float *__restrict__ 
     overflow[q] = out || qb.w != 0.f || qb.z >= scale_hi || qb.z <= scale_lo || !(qb.y > 0.f && qb.y < 0x1p60f) ? 1 : 0;
 }
 
+// ---- Weighted MSE under combine 'mean' (skyemb_token_mse_mean_pool / _rowp / skyemb_distance_topk_tokens_mean_prefiltered) ---------------
+// Contract: the distance chain per token, then the grouped kernels' fold (((0 + d_0) + d_1) + ...) / float(P) in token order; in key
+// space (key = -dist) that fold of keys is its negation bit for bit, so stage 2 is token_rescore_body with DIST and the TOK_MEAN fold.
+// The mean is LINEAR in the tokens: per image i and query q, in real arithmetic, with P a power of two,
+//   D mean_p dist(q, x_p) = A_q + Bbar_i - 2 (c o t_q) . m_i,   m_i = (1/P) sum_p x_p,   Bbar_i = (1/P) sum_p sum_d c_d x_pd^2,
+// the operand shape of "Weighted MSE" above with a row that is an IMAGE: stage 1 is the ROW pass (prefilter_kernel without TOK) over a
+// pooled 16-bit image [N, D], P times fewer rows than the bank, as under the cosine 'mean'; the query constants, the first state and
+// the threshold refresh are mse_query_kernel's, mse_state_kernel's and mse_test_row's, fed the eps and gamma below.
+// The pooled image (token_mse_mean_pool_kernel; it depends on the bank only): m_fl = fl(sum_p x_p) / P -- the widened tokens summed in
+// fp32 in token order from +0 (the first addition is exact), one exact scale by 1 / P --, then m' = m_fl 2^-e with the largest |m'_d|
+// in [2^13, 2^14) (exact; e = 0 for a zero row) rounded ONCE to the bank's dtype (bf16: elements below 2^-40 stored as zero).  That is
+// the situation of the cosine mean's pooled image, points (b) + (a) there:  |dot^ - q' . m'| <= eps_m ||q'|| ||m'||,  eps_m = eps_m_of.
+//   pooling    per element |fl(sum_p x_pd) - sum_p x_pd| <= 1.01 (P - 1) 2^-24 sum_p |x_pd| (P - 1 <= 63 rounded additions; nothing
+//              underflows: fp16 elements are multiples of 2^-24, bf16 elements of the window multiples of 2^-67), so by the triangle
+//              inequality over the tokens  ||m_fl - m|| <= kappa c1,  kappa = 1.01 P 2^-24,  c1 = mean_p ||x_p||_2.
+//   tw         tw_d = fl(c_d t_d) against c_d t_d: 2^-24 relative (or the absolute 2^-150 of "Weighted MSE"), against
+//              ||m|| <= ||m_fl|| + kappa c1: below 2^-22 ||q'|| R1 2^e with R1 as follows.
+// Together  |dot^ - 2^-(f + e) (c o t) . m| <= eps ||q'|| R1,   eps = eps_m + 2^-22,   R1 = ||m'|| + (kappa / eps_m) c1 2^-e  (raised; the
+// SMALLER eps_m, hi + lo, so one image serves both variants), hence
+//   D mean_real >= A_dn + Bbar_dn - 2 2^(f + e) (dot^ + eps ||q'|| R1) =: L.
+// Bbar_dn <= Bbar in the manner of B_dn: token_mse_mean_rowp_kernel adds the P D non-negative terms c_d x_pd^2 lane by lane.  A lane
+// takes 8 consecutive elements per 512-element step of a row -- only D / 8 lanes have any when D < 512 --, so an active lane's chain is
+// n_B = 8 P ceil(D / 512) fused multiply-adds into one accumulator (the squares exact inside the windows; P D / 64 of them only when
+// 512 divides D: 8 P at D = 128), and wave_sum folds the 64 lanes in 6 more additions (an idle lane adds an exact 0).  Every term and
+// partial sum is non-negative, so the fp32 sum is within 1.01 (n_B + 6) 2^-24 of the real one (n_B + 6 <= 4102):
+// Bbar_dn = Bbar^ (1 - (n_B + 8) 2^-23), twice that, and 0 below 2^-100.
+// The contract's own roundings: each token distance as above, dist_p^ >= dist_p (1 - 2^-24)^n, n = 4 ceil(D / 64) + 9; the fold adds P
+// non-negative terms with P - 1 rounded additions and divides exactly, so mean^ >= mean_real (1 - 2^-24)^(n + P - 1) - (what
+// underflows: below 2^-126 in units of D dist, the division's 2^-150 included), and an image can reach the distance threshold theta
+// only if  L <= D theta (1 + gamma) + 2^-126,   gamma = gamma_mse_of(D) + P 2^-24 = (4 ceil(D / 64) + 12 + P) 2^-24
+// ((1 - 2^-24)^-n' <= 1 + (n' + 3) 2^-24 for every n' <= 328).  Times 2^-(f + 1 + e) this is the test instruction as it stands,
+//   t = dot^ - a R0 + c R1 + g R2 >= 0,   rowp[i] = {Bbar_dn 2^-e, R1, 2^-e, 0},   qpar[q] = mse_test_row's {-a, c, g, 0}.
+// An image is UNBOUNDABLE -- zeros in the pooled row where the bank alone decides it, and {0, inf, 1, 0}: a candidate of every query,
+// decided by stage 2 -- when a token has an inf / NaN element (bf16: a nonzero element outside [2^-60, 2^120)), when R1 or R2 = 2^-e
+// reach 2^60 (a pooled row of heavy cancellation, bf16 only: fp16 keeps 2^-e <= 2^43), when Bbar^ is not a number in [0, 2^36) (fp16) /
+// [0, 2^96) (bf16), or when R0 leaves that same window: with the query windows of mse_state_kernel a R0 and c R1 then stay finite, and
+// g R2 overflows only where its sign already decides the test.  An image whose tokens cancel to an exactly zero pooled row is an
+// ordinary image: m' = 0, dot^ = 0, R1 the pooling term alone.  Queries are flagged as under "Weighted MSE".
+__host__ __device__ inline double eps_mse_mean_of(int D, bool lo, bool bf) { return eps_m_of(D, lo, bf) + 0x1p-22; }
+__host__ __device__ inline double gamma_mse_mean_of(int D, int P) { return gamma_mse_of(D) + P * 0x1p-24; }
+inline double kappa_mse_mean_of(int P) { return 1.01 * P * 0x1p-24; }
+
+// One wave per image: the pooled row and the bank's share of its constants, paux[i] = {R1, 2^-e}; an unboundable image {inf, 1} and a
+// zero pooled row; padding rows {NaN, 0}.  tail / tail_first: as in token_mean_pool_kernel.  kfac = kappa / eps_m (hi + lo), raised.
+template <bool BF>
+__global__ __launch_bounds__(128) void token_mse_mean_pool_kernel(const unsigned short *__restrict__ bank, int64_t N, int P, int D,
+                                                                   unsigned short *__restrict__ pooled, float2 *__restrict__ paux,
+                                                                   int64_t rows_padded, unsigned short *__restrict__ tail,
+                                                                   int64_t tail_first, float kfac) {
+    __shared__ float sm[2][4096];                             // the image's sums, D <= 4096; a lane only ever touches its own elements
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t img = (int64_t)blockIdx.x * 2 + w;
+    if (img >= rows_padded) return;
+    unsigned short *t = tail && img >= tail_first ? tail + (img - tail_first) * D : nullptr;
+    if (img >= N) {
+        if (t)
+            for (int d = lane * 8; d < D; d += 512) *(uint4 *)(t + d) = make_uint4(0u, 0u, 0u, 0u);
+        if (lane == 0) paux[img] = make_float2(NAN, 0.f);
+        return;
+    }
+    float *m = sm[w];
+    for (int d = lane * 8; d < D; d += 512) {
+        *(float4 *)(m + d) = make_float4(0.f, 0.f, 0.f, 0.f);
+        *(float4 *)(m + d + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float bad = 0.f, c1 = 0.f;
+    for (int p = 0; p < P; ++p) {
+        const unsigned short *x = bank + (img * P + p) * D;
+        float ss = 0.f;
+        for (int d = lane * 8; d < D; d += 512) {
+            float a[8];
+            widen8<BF>(*(const uint4 *)(x + d), a);
+            const float4 s0 = *(const float4 *)(m + d), s1 = *(const float4 *)(m + d + 4);
+            float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float mag = fabsf(a[j]);
+                if (BF) bad = (!(mag < ldexpf(1.0f, BF_ROW_HI)) || (mag > 0.f && mag < ldexpf(1.0f, -BF_ROW_LO))) ? 1.f : bad;
+                else bad = !(mag < INFINITY) ? 1.f : bad;
+                ss = fmaf(a[j], a[j], ss);                     // (bf16: a square may overflow: c1 = inf, R1 = inf, unboundable)
+                s[j] = s[j] + a[j];                            // token order: p ascending
+            }
+            *(float4 *)(m + d) = make_float4(s[0], s[1], s[2], s[3]);
+            *(float4 *)(m + d + 4) = make_float4(s[4], s[5], s[6], s[7]);
+        }
+        c1 += sqrtf(wave_sum(ss));
+    }
+    const float inv_p = 1.0f / (float)P;                      // a power of two
+    float mx = 0.f;
+    for (int d = lane * 8; d < D; d += 512) {
+        const float4 u = *(const float4 *)(m + d), v = *(const float4 *)(m + d + 4);
+        mx = fmaxf(fmaxf(mx, fmaxf(fmaxf(fabsf(u.x), fabsf(u.y)), fmaxf(fabsf(u.z), fabsf(u.w)))),
+                   fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    }
+    mx = wave_max(mx) * inv_p;
+    bad = wave_max(bad);
+    if (!(mx < INFINITY)) bad = 1.f;
+    int e = 0;
+    if (bad == 0.f && mx > 0.f) {
+        (void)frexpf(mx, &e);
+        e -= 14;                                               // mx 2^-e in [2^13, 2^14)
+    }
+    const float s = ldexpf(1.0f, -e);                          // (|e| <= 101 inside the windows: finite)
+    // norms rounded up: the fp32 sums of squares and of P terms, the square roots
+    const float up = (1.0f + (float)(D + 64) * 0x1p-22f) * (1.0f + 0x1p-20f);
+    float ss = 0.f;
+    if (bad == 0.f)
+        for (int d = lane * 8; d < D; d += 512) {
+            const float4 u = *(const float4 *)(m + d), v = *(const float4 *)(m + d + 4);
+            const float a[8] = {u.x * inv_p * s, u.y * inv_p * s, u.z * inv_p * s, u.w * inv_p * s,
+                                v.x * inv_p * s, v.y * inv_p * s, v.z * inv_p * s, v.w * inv_p * s};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss = fmaf(a[j], a[j], ss);
+        }
+    ss = wave_sum(ss);
+    const float r1 = fmaf(kfac * s, c1 * inv_p * up, sqrtf(ss) * up) * (1.0f + 0x1p-21f);
+    if (!(r1 < 0x1p60f) || !(s < 0x1p60f)) bad = 1.f;
+    unsigned short *o = pooled + img * D;
+    for (int d = lane * 8; d < D; d += 512) {
+        const float4 u = *(const float4 *)(m + d), v = *(const float4 *)(m + d + 4);
+        const float a[8] = {u.x * inv_p * s, u.y * inv_p * s, u.z * inv_p * s, u.w * inv_p * s,
+                            v.x * inv_p * s, v.y * inv_p * s, v.z * inv_p * s, v.w * inv_p * s};
+        unsigned int r[4] = {0u, 0u, 0u, 0u};
+        if (bad == 0.f) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                unsigned short h0, h1;
+                if (BF) {
+                    h0 = __builtin_bit_cast(unsigned short, (bf16_t)(fabsf(a[2 * j]) < 0x1p-40f ? 0.f : a[2 * j]));
+                    h1 = __builtin_bit_cast(unsigned short, (bf16_t)(fabsf(a[2 * j + 1]) < 0x1p-40f ? 0.f : a[2 * j + 1]));
+                } else {
+                    h0 = __builtin_bit_cast(unsigned short, (half_t)a[2 * j]);
+                    h1 = __builtin_bit_cast(unsigned short, (half_t)a[2 * j + 1]);
+                }
+                r[j] = (unsigned int)h0 | ((unsigned int)h1 << 16);
+            }
+        }
+        const uint4 raw = make_uint4(r[0], r[1], r[2], r[3]);
+        *(uint4 *)(o + d) = raw;
+        if (t) *(uint4 *)(t + d) = raw;
+    }
+    if (lane == 0) paux[img] = bad != 0.f ? make_float2(INFINITY, 1.0f) : make_float2(r1, s);
+}
+
+// Row constants under the weights c: one wave per image, a second pass over the bank (16 bytes per lane and load).
+// rowp[i] = {Bbar_dn 2^-e, R1, 2^-e, 0} from paux[i] = {R1, 2^-e}; unboundable {0, inf, 1, 0}; padding rows the sentinel {0, NaN, 0, 0}.
+template <bool BF>
+__global__ __launch_bounds__(256) void token_mse_mean_rowp_kernel(const unsigned short *__restrict__ bank, const float *__restrict__ cw,
+                                                                   const float2 *__restrict__ paux, int64_t N, int P, int D,
+                                                                   float4 *__restrict__ rowp, int64_t rows_padded) {
+    const int lane = threadIdx.x & 63;
+    const int64_t img = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (img >= rows_padded) return;
+    if (img >= N) {
+        if (lane == 0) rowp[img] = make_float4(0.f, NAN, 0.f, 0.f);
+        return;
+    }
+    const unsigned short *x = bank + img * P * D;
+    float B = 0.f;
+    for (int p = 0; p < P; ++p, x += D)
+        for (int d = lane * 8; d < D; d += 512) {
+            float a[8];
+            widen8<BF>(*(const uint4 *)(x + d), a);
+            const float4 c0 = *(const float4 *)(cw + d), c1 = *(const float4 *)(cw + d + 4);
+            const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) B = fmaf(c[j], a[j] * a[j], B);    // the square is exact inside the windows (an inf / NaN: B^ fails its own)
+        }
+    B = wave_sum(B) * (1.0f / (float)P);                      // Bbar^; the scale is a power of two
+    if (lane != 0) return;
+    const float2 aux = paux[img];
+    const float hi = ldexpf(1.0f, BF ? MSE_B_HI_BF16 : MSE_B_HI_F16);
+    const int n_b = 8 * P * ((D + 511) / 512);                 // fmas of an active lane's chain (the derivation above), <= 4096
+    const float Bdn = B < 0x1p-100f ? 0.f : B * (1.0f - (float)(n_b + 8) * 0x1p-23f);
+    float r0 = Bdn * aux.y;                                    // exact, a power of two ...
+    if (r0 < 0x1p-126f) r0 = 0.f;                              // ... unless it underflows, where it could round up: lowered to 0
+    const bool ok = B >= 0.f && B < hi && r0 < hi && aux.x < INFINITY;     // (NaN fails every comparison)
+    rowp[img] = ok ? make_float4(r0, aux.x, aux.y, 0.f) : make_float4(0.f, INFINITY, 1.0f, 0.f);
+}
+
 // ---- Weighted MSE with PER-QUERY weights (skyemb_token_mse_pq_image / skyemb_distance_topk_tokens_prefiltered_pq) ------------------------
 // Contract: the same chain with query q's own row of c [Q, D] (skyemb_distance_token_topk_pq).  B_r = sum c_qd x_d^2 now depends on the
 // query, so it cannot ride in a row constant; it joins the dot product instead.  With c_q >= 0, in real arithmetic
@@ -2183,6 +2363,8 @@ __global__ void token_state_kernel(int Q, const float4 *__restrict__ qbase, floa
 // weights c [D], and a token's score is key = -dist by the distance contract's chain (distance_chain.h; a NaN distance is key -inf);
 // qn, xn and eps are not read, gfac is the widening of the threshold and the next test row is mse_test_row's.  Without DIST cw is
 // not read: the instruction stream of the cosine kernels.
+// DIST with fold TOK_MEAN (the weighted-MSE search under combine 'mean'): the mean fold below over the keys -dist_p -- the negation of
+// the contract's mean of distances bit for bit --, and the DIST refresh, which is tested before the fold's.
 // DIST with TOPT (distance 'max' under top_t, the `_top` entries of the MSE search; fold is TOK_MIN): with a[0] <= a[1] <= ... an image's
 // token distances, a[top_t - 1] is the top_t-th LARGEST key, so the keys go through the same network and top_finish<MIN>: bit for bit
 // distance_token_kernel's value, which sorts the same keys by the same functions.  A NaN distance is key -inf and sorts last; fewer
@@ -2370,6 +2552,17 @@ __global__ __launch_bounds__(256) void token_rescore_mse_pq_lp_kernel(TOKEN_RESC
 }
 __global__ __launch_bounds__(256) void token_rescore_mse_pq_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const float *__restrict__ cw) {
     token_rescore_body<bf16_t, false, false, true>(TOKEN_RESCORE_PASS, 0, nullptr, 0, cw + (int64_t)blockIdx.x * D);
+}
+// MSE under combine 'mean' ("Weighted MSE under combine 'mean'" above): DIST with the TOK_MEAN fold -- the keys -dist_p summed in token
+// order from 0, one division by float(P), a sum that is not a number is key -inf; the threshold refresh is the DIST branch's.  The fold is
+// these kernels' own (the `fold` argument is not read), so the min / max branches are not compiled into them.
+__global__ __launch_bounds__(256) void token_rescore_mse_mean_lp_kernel(TOKEN_RESCORE_PARAMS(half_t), const float *__restrict__ cw) {
+    token_rescore_body<half_t, false, false, true>(tw, qn, bank, xn, N, D, lgp, TOK_MEAN, gfac, k, eps, idx_offset, cap, qbase, cnt, cand_i, list, rn,
+                                                   qpar, tau_q, overflow, final, out_s, out_i, redo, 0, nullptr, 0, cw);
+}
+__global__ __launch_bounds__(256) void token_rescore_mse_mean_bf_kernel(TOKEN_RESCORE_PARAMS(bf16_t), const float *__restrict__ cw) {
+    token_rescore_body<bf16_t, false, false, true>(tw, qn, bank, xn, N, D, lgp, TOK_MEAN, gfac, k, eps, idx_offset, cap, qbase, cnt, cand_i, list, rn,
+                                                   qpar, tau_q, overflow, final, out_s, out_i, redo, 0, nullptr, 0, cw);
 }
 #undef TOKEN_RESCORE_PARAMS
 #undef TOKEN_RESCORE_PASS
@@ -2608,6 +2801,7 @@ const void *const TOKEN_RESCORE_MAP[2] = {(const void *)token_rescore_map_lp_ker
 const void *const TOKEN_RESCORE_MSE_PQ[2] = {(const void *)token_rescore_mse_pq_lp_kernel, (const void *)token_rescore_mse_pq_bf_kernel};   // [bf]
 const void *const TOKEN_RESCORE_MSE[2][2] = {{(const void *)token_rescore_mse_lp_kernel, (const void *)token_rescore_mse_bf_kernel},   // [topt][bf]
                                              {(const void *)token_rescore_mse_top_lp_kernel, (const void *)token_rescore_mse_top_bf_kernel}};
+const void *const TOKEN_RESCORE_MSE_MEAN[2] = {(const void *)token_rescore_mse_mean_lp_kernel, (const void *)token_rescore_mse_mean_bf_kernel};   // [bf]
 
 // the pointer arguments of an entry point; NULL where it has none
 struct SearchArgs {
@@ -2632,7 +2826,8 @@ struct SearchArgs {
     const char *who;
     // weighted MSE (skyemb_distance_topk_tokens_prefiltered and its _top / _sel / _top_sel forms; NULL everywhere else): the weights
     // c [D]; tw then holds the raw queries t, rowp is skyemb_token_mse_rowp's (under a selection: its masked copy), qn and xn are NULL,
-    // and the result is in key space (key = -distance)
+    // and the result is in key space (key = -distance).  With a 'mean' request (skyemb_distance_topk_tokens_mean_prefiltered): pooled,
+    // tail and rowp are those of skyemb_token_mse_mean_pool / _rowp, and the constants are the MSE mean bound's
     const float *cw;
     // per-query weights (skyemb_distance_topk_tokens_prefiltered_pq; NULL everywhere else): the image [r.N * r.P, r.D] of
     // skyemb_token_mse_pq_image, r.D = 2 D twice the bank's row length and r.N its images padded to whole tiles.  Stage 1 multiplies
@@ -2759,7 +2954,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
     if (bank != SKYEMB_PF_BANK_F32) {
         SKY_CHECK_ARG(p.rows % BT == 0 || a.tail, rows ? "%s: N = %lld is no whole number of %d-row tiles: the tail tile of %s is needed"
                                                        : "%s: %lld rows are no whole number of %d-row tiles: the tail tile of %s is needed",
-                      who, (long long)p.rows, BT, a.map ? "skyemb_token_mean_select_gather" : mean ? "skyemb_token_mean_pool" : rows && bank == SKYEMB_PF_BANK_F16 ? "skyemb_bank16_rowp_lp"
+                      who, (long long)p.rows, BT, a.map ? "skyemb_token_mean_select_gather" : mean && a.cw ? "skyemb_token_mse_mean_pool" : mean ? "skyemb_token_mean_pool" : rows && bank == SKYEMB_PF_BANK_F16 ? "skyemb_bank16_rowp_lp"
                                                                                                                       : "skyemb_resident_rowp");
         SKY_CHECK_ARG(aligned16(a.bank16) && aligned16(a.tail) && aligned16(s1_bank), "%s: the bank and the tail tile must be 16-byte aligned",
                       who);
@@ -2777,16 +2972,18 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
             for (int s = rows ? 0 : p.sel; s <= p.sel; ++s)    // (a row search under a selection launches its tail through the non-SEL instance)
                 if (rc == 0) rc = sky_set_lds_limit((const void *)STAGE1[stage1_index(mode, lo, s, p.bf, p.tok, p.cnt)], p.lds_stage1_limit, who);
     const bool mse = a.cw != nullptr;                          // weighted MSE: its own constants and re-score, [D] more floats of LDS for c
-    const void *token_rescore = pq ? TOKEN_RESCORE_MSE_PQ[p.bf] : mse ? TOKEN_RESCORE_MSE[p.top_t != 0][p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
+    const void *token_rescore = pq ? TOKEN_RESCORE_MSE_PQ[p.bf] : mse && mean ? TOKEN_RESCORE_MSE_MEAN[p.bf] : mse ? TOKEN_RESCORE_MSE[p.top_t != 0][p.bf] : a.map ? TOKEN_RESCORE_MAP[p.bf] : TOKEN_RESCORE[p.top_t != 0][p.bf];
     // (per-query weights: the plan's t [2 Dr] IS t [Dr] beside c_q [Dr], within LDS_TOKEN_RESCORE_LIMIT as it stands)
     const int lds_close = p.lds_close + (mse && !pq ? D * 4 : 0), lds_close_limit = p.lds_close_limit + (mse && !pq ? 4096 * 4 : 0);
-    const float gamma_mse = (float)(gamma_mse_of(Dr) * (1.0 + 1e-6));
+    const float gamma_mse = (float)((mean ? gamma_mse_mean_of(Dr, r.P) : gamma_mse_of(Dr)) * (1.0 + 1e-6));
     if (rc == 0) rc = sky_set_lds_limit(rows ? (const void *)SELECT[0] : token_rescore, lds_close_limit, who);
     if (rc == 0 && rows && p.sel) rc = sky_set_lds_limit((const void *)SELECT[1], p.lds_close_limit, who);
     if (rc != 0) return rc;
     const dim3 qgrid((unsigned)((p.q_padded + 3) / 4));
     if (mse) {
-        const float eps_mse = (float)((pq ? eps_pq_of(Dr, p.use_lo, p.bf) : eps_mse_of(D, p.use_lo, p.bf)) * (1.0 + 1e-6));
+        // (the plan's own eps_a is the cosine bound's: under MSE the eps of the route is computed here, beside eps_mse_of)
+        const float eps_mse = (float)((pq ? eps_pq_of(Dr, p.use_lo, p.bf) : mean ? eps_mse_mean_of(D, p.use_lo, p.bf) : eps_mse_of(D, p.use_lo, p.bf)) *
+                                      (1.0 + 1e-6));
         if (pq && p.bf) hipLaunchKernelGGL(mse_pq_query_kernel<true>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, Dr, w.qh, w.ql, w.qbase, eps_mse);
         else if (pq) hipLaunchKernelGGL(mse_pq_query_kernel<false>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, Dr, w.qh, w.ql, w.qbase, eps_mse);
         else if (p.bf) hipLaunchKernelGGL(mse_query_kernel<true>, qgrid, dim3(256), 0, st, a.cw, a.tw, Q, D, w.qh, w.ql, w.qbase, eps_mse);
@@ -2846,7 +3043,7 @@ int search(skyemb_prefilter_request_t r, const SearchArgs &a) {
         else if (pq) token_rescore_as(token_rescore_mse_pq_lp_kernel, s.final, a.cw);               // c [Q, D] last
         else if (mse && p.top_t) token_rescore_as(token_rescore_mse_top_lp_kernel, s.final, p.top_t, a.cw);   // MSE under top_t: top_t, then c
         else if (p.top_t) token_rescore_as(token_rescore_top_lp_kernel, s.final, p.top_t);      // the TOPT kernels take top_t last
-        else if (mse) token_rescore_as(token_rescore_mse_lp_kernel, s.final, a.cw);                 // the MSE kernels take c last
+        else if (mse) token_rescore_as(token_rescore_mse_lp_kernel, s.final, a.cw);                 // the MSE kernels (mean's too) take c last
         else token_rescore_as(token_rescore_lp_kernel, s.final);
     }
     if (rows)
@@ -3167,4 +3364,86 @@ extern "C" int skyemb_distance_topk_tokens_prefiltered_pq(const float *c, const 
     return search(request(SKYEMB_PF_TOKENS, bank_of(dtype), Q, N_padded, P, 2 * D, k, key_combine, 0, 0.f, thr0),
                   {t, nullptr, nullptr, nullptr, bank16, dtype, nullptr, nullptr, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo, stream,
                    nullptr, N, who, c, image});
+}
+
+// ---- weighted MSE under combine 'mean' ("Weighted MSE under combine 'mean'" above): the pooled image, its constants, the search -----------
+#define TOKEN_MSE_MEAN_PREFILTER_MSG "many-query weighted-MSE patch-token search, combine mean: needs P a divisor of 64, D %% 32 == 0, " \
+                                     "128 <= D <= 4096, 1 <= k <= %d, k <= N, N >= 2048 images, N * P < 2^31 rows and Q >= 1 " \
+                                     "(Q=%d N=%lld P=%d D=%d k=%d)"
+extern "C" int skyemb_token_mse_mean_prefilter_applicable(int Q, int64_t N, int P, int D, int k) {
+    const bool ok = pfplan::mean_shape_ok(Q, N, P, D, k);
+    if (!ok) skyemb_set_error(TOKEN_MSE_MEAN_PREFILTER_MSG, TOK_KMAX, Q, (long long)N, P, D, k);
+    return ok ? 1 : 0;
+}
+
+extern "C" double skyemb_token_mse_mean_prefilter_eps(int D, int lo, int dtype) { return eps_mse_mean_of(D, lo != 0, dtype == SKYEMB_BF16); }
+
+extern "C" double skyemb_token_mse_mean_prefilter_gamma(int D, int P) { return gamma_mse_mean_of(D, P); }
+
+namespace {
+int mse_mean_shape(const char *who, int dtype, int64_t N, int P, int D) {
+    SKY_CHECK_ARG(sky_is_lp(dtype), "%s: dtype " RESIDENT_DTYPE_MSG, who, dtype);
+    SKY_CHECK_ARG(N > 0 && P >= 1 && P <= 64 && 64 % P == 0 && D % BK == 0 && D >= BK && D <= 4096 && N * P < (1ll << 31),
+                  "%s: expected P a divisor of 64, D %% 32 == 0, D <= 4096 and fewer than 2^31 token rows (N=%lld P=%d D=%d)", who,
+                  (long long)N, P, D);
+    return 0;
+}
+}  // namespace
+
+extern "C" int skyemb_token_mse_mean_pool(const void *bank16, int dtype, int64_t N, int P, int D, void *pooled16, float *paux, void *tail,
+                                          void *stream) {
+    const char *who = "skyemb_token_mse_mean_pool";
+    if (mse_mean_shape(who, dtype, N, P, D)) return 1;
+    SKY_CHECK_ARG(bank16 && pooled16 && paux, "%s: null argument", who);
+    SKY_CHECK_ARG(N % BT == 0 || tail, "%s: N = %lld is no whole number of %d-image tiles: a tail tile [%d, D] is needed", who, (long long)N,
+                  BT, BT);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(pooled16) && aligned16(tail), "%s: the bank, the pooled image and the tail tile must be "
+                  "16-byte aligned", who);
+    const int64_t padded = skyemb_bank16_rowp_rows(N);
+    const bool bf = dtype == SKYEMB_BF16;
+    // one image serves both variants: the smaller eps_m (hi + lo) gives the larger, always valid, pooling term
+    const float kfac = (float)(kappa_mse_mean_of(P) / eps_m_of(D, true, bf) * (1.0 + 1e-6));
+    const dim3 grid((unsigned)(padded / 2));
+#define POOL_ARGS (const unsigned short *)bank16, N, P, D, (unsigned short *)pooled16, (float2 *)paux, padded, \
+                  N % BT ? (unsigned short *)tail : nullptr, N / BT * BT, kfac
+    if (bf) hipLaunchKernelGGL(token_mse_mean_pool_kernel<true>, grid, dim3(128), 0, (hipStream_t)stream, POOL_ARGS);
+    else hipLaunchKernelGGL(token_mse_mean_pool_kernel<false>, grid, dim3(128), 0, (hipStream_t)stream, POOL_ARGS);
+#undef POOL_ARGS
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+extern "C" int skyemb_token_mse_mean_rowp(const void *bank16, int dtype, const float *c, const float *paux, int64_t N, int P, int D,
+                                          float *rowp, void *stream) {
+    const char *who = "skyemb_token_mse_mean_rowp";
+    if (mse_mean_shape(who, dtype, N, P, D)) return 1;
+    SKY_CHECK_ARG(bank16 && c && paux && rowp, "%s: null argument", who);
+    SKY_CHECK_ARG(aligned16(bank16) && aligned16(c), "%s: the bank and c must be 16-byte aligned", who);
+    const int64_t padded = skyemb_bank16_rowp_rows(N);
+    const dim3 grid((unsigned)(padded / 4));
+#define ROWP_ARGS (const unsigned short *)bank16, c, (const float2 *)paux, N, P, D, (float4 *)rowp, padded
+    if (dtype == SKYEMB_BF16) hipLaunchKernelGGL(token_mse_mean_rowp_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, ROWP_ARGS);
+    else hipLaunchKernelGGL(token_mse_mean_rowp_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, ROWP_ARGS);
+#undef ROWP_ARGS
+    SKY_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// (pooled16 and tail are those of skyemb_token_mse_mean_pool, rowp that of skyemb_token_mse_mean_rowp under the same c; out_s holds keys =
+// -distance.  The request plans as the cosine mean's: {SKYEMB_PF_TOKENS_MEAN, the bank's format, D}, eps = 0)
+extern "C" int skyemb_distance_topk_tokens_mean_prefiltered(const float *c, const float *t, int Q, const void *bank16, int dtype,
+                                                            const void *pooled16, const void *tail, const float *rowp, int64_t N, int P,
+                                                            int D, int k, int64_t idx_offset, const float *thr0, void *ws, int64_t ws_bytes,
+                                                            float *out_s, int64_t *out_i, int *redo, void *stream) {
+    const char *who = "skyemb_distance_topk_tokens_mean_prefiltered";
+    SKY_CHECK_ARG(c && aligned16(c) && aligned16(t), "%s: c and t must be given and 16-byte aligned", who);
+    if (!skyemb_token_mse_mean_prefilter_applicable(Q, N, P, D, k)) {
+        char why[512];
+        snprintf(why, sizeof why, "%s", skyemb_last_error());
+        skyemb_set_error("%s: %s", who, why);
+        return 1;
+    }
+    return search(request(SKYEMB_PF_TOKENS_MEAN, bank_of(dtype), Q, N, P, D, k, SKYEMB_COMBINE_MEAN, 0, 0.f, thr0),
+                  {t, nullptr, nullptr, nullptr, bank16, dtype, tail, pooled16, rowp, nullptr, idx_offset, thr0, ws, ws_bytes, out_s, out_i, redo,
+                   stream, nullptr, 0, who, c});
 }

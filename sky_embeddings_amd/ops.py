@@ -775,6 +775,72 @@ def distance_topk_tokens_prefiltered_pq(c, t, tokens, image, rowp, k, combine, i
     return ws
 
 
+def token_mse_mean_prefilter_refusal(Q, N, P, D, k):
+    """None when the two-stage weighted-MSE token search under combine mean takes the shape (N >= 2048 images: stage 1 walks the
+    pooled image), else the library's own statement of its limits.  Host arithmetic only."""
+    L = lib()
+    return None if L.skyemb_token_mse_mean_prefilter_applicable(Q, N, P, D, k) else L.skyemb_last_error().decode()
+
+
+def token_mse_mean_prefilter_eps(D, dtype, lo=True):
+    """eps of stage 1 of the weighted-MSE search under combine mean over a ``dtype`` bank: the pooled image's eps_m + 2^-22 (host
+    arithmetic only; include/skyemb.h)."""
+    return lib().skyemb_token_mse_mean_prefilter_eps(D, int(lo), resident_dtype_code(dtype, "token_mse_mean_prefilter_eps"))
+
+
+def token_mse_mean_prefilter_gamma(D, P):
+    """gamma of that search: ``token_mse_prefilter_gamma(D)`` widened for the mean's own P - 1 rounded additions (host arithmetic
+    only; include/skyemb.h)."""
+    return lib().skyemb_token_mse_mean_prefilter_gamma(D, P)
+
+
+def token_mse_mean_pool(tokens):
+    """(pooled, tail, aux) of ``skyemb_token_mse_mean_pool`` over a resident 16-bit token bank ``tokens`` [N, P, D]: the pooled
+    image [N, D] in the bank's dtype -- the fp32 sum of each image's tokens in token order, scaled exactly by 1 / P and by the
+    image's power of two 2^-e, rounded once --, its zero-padded tail tile (None when N % 256 == 0) and aux f32
+    [ceil(N / 256) * 256, 2] = {R1, 2^-e}, the bank's share of the row constants.  One pass over the bank; nothing depends on the
+    weights."""
+    N, P, D = tokens.shape
+    code = resident_dtype_code(tokens.dtype, "token_mse_mean_pool")
+    assert tokens.is_contiguous()
+    _check_aligned16(tokens, "token_mse_mean_pool", "the 16-bit", "must be")
+    rows = lib().skyemb_bank16_rowp_rows(N)
+    pooled = torch.empty(N, D, device=tokens.device, dtype=tokens.dtype)
+    aux = torch.empty(rows, 2, device=tokens.device, dtype=torch.float32)
+    tail = torch.empty(256, D, device=tokens.device, dtype=tokens.dtype) if rows != N else None
+    check(lib().skyemb_token_mse_mean_pool(_p(tokens), code, N, P, D, _p(pooled), _p(aux), _p(tail), _stream()),
+          "skyemb_token_mse_mean_pool")
+    return pooled, tail, aux
+
+
+def token_mse_mean_rowp(tokens, c, aux):
+    """rowp f32 [ceil(N / 256) * 256, 4] of the weighted-MSE search under combine mean: the row constants of the pooled image of
+    ``tokens`` [N, P, D] under the weights ``c`` [D] (``prepare_distance_weights``), from ``aux`` of ``token_mse_mean_pool``.  One
+    more pass over the bank per (bank, c)."""
+    N, P, D = tokens.shape
+    code = resident_dtype_code(tokens.dtype, "token_mse_mean_rowp")
+    assert tokens.is_contiguous() and c.dtype == torch.float32 and c.is_contiguous() and tuple(c.shape) == (D,)
+    rows = lib().skyemb_bank16_rowp_rows(N)
+    assert aux.dtype == torch.float32 and aux.is_contiguous() and tuple(aux.shape) == (rows, 2)
+    rowp = torch.empty(rows, 4, device=tokens.device, dtype=torch.float32)
+    check(lib().skyemb_token_mse_mean_rowp(_p(tokens), code, _p(c), _p(aux), N, P, D, _p(rowp), _stream()), "skyemb_token_mse_mean_rowp")
+    return rowp
+
+
+def distance_topk_tokens_mean_prefiltered(c, t, tokens, pooled, tail, rowp, k, idx_offset, out_s, out_i, redo, thr0=None, ws=None):
+    """The two-stage many-query weighted-MSE search under combine mean over a resident 16-bit token bank ``tokens`` [N, P, D], the
+    (pooled, tail) of ``token_mse_mean_pool`` and the rowp of ``token_mse_mean_rowp`` under the same ``c``.  ``out_s`` receives
+    keys = -distance (include/skyemb.h)."""
+    Q, D = t.shape
+    N, P = tokens.shape[:2]
+    code = resident_dtype_code(tokens.dtype, "distance_topk_tokens_mean_prefiltered")
+    ws = _workspace(ws, lib().skyemb_token_mean_prefilter_ws_bytes(Q, D, k), t.device)
+    check(lib().skyemb_distance_topk_tokens_mean_prefiltered(_p(c), _p(t), Q, _p(tokens), code, _p(pooled), _p(tail), _p(rowp), N, P, D, k,
+                                                             idx_offset, _p(thr0), _p(ws), ws.numel(), _p(out_s), _p(out_i), _p(redo),
+                                                             _stream()), "skyemb_distance_topk_tokens_mean_prefiltered")
+    return ws
+
+
 def token_mean_prefilter_refusal(Q, N, P, D, k):
     """None when the two-stage token search with combine mean takes the shape, else the library's own statement of its limits."""
     L = lib()

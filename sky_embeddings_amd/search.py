@@ -451,6 +451,8 @@ class TokenBank:
         self._stage1_mse = None                            # (c, tail tile, rowp) of the weighted-MSE route, for the last c seen
         self._mse_top_t = False                            # True: asked to take that route under top_t too (prepare_mse_top_t)
         self._mse_pq = None                                # (image [x ; x o x], rowp) of that route with per-query weights (prepare_mse_per_query)
+        self._mse_mean = None                              # (pooled image, its tail tile, aux) of that route under combine 'mean' (prepare_mse_mean)
+        self._stage1_mse_mean = None                       # (c, rowp) of it, for the last c seen
         self._version = 0                                  # counts set_weights calls: what depends on the norms checks it
         self.set_weights(weights)
 
@@ -524,6 +526,32 @@ class TokenBank:
         if self._mse_pq is None:
             self._mse_pq = ops.token_mse_pq_image(self.bank)
         return self
+
+    def prepare_mse_mean(self):
+        """Ask this resident bank to take the two-stage weighted-MSE route of ``distance_topk_tokens`` under ``combine='mean'``, and
+        build what that route reads: the pooled 16-bit image [N, D] of the bank -- each image's tokens summed in fp32 in token order,
+        scaled exactly by 1 / P and by the image's own power of two, rounded once to the bank's dtype --, its 256-row tail tile and
+        the bank's share of the row constants (``ops.token_mse_mean_pool``: one pass over the bank, 2 N D + 8 N bytes beside the
+        bank's 2 N P D).  None of it depends on the weights, so ``set_weights`` keeps it; the weights' share (``stage1_mse_mean``) is
+        one more pass per weight vector.  A bank never asked answers 'mean' by the grouped route, as it always has.  Returns
+        ``self``: ``TokenBank.resident(bank).prepare_mse_mean()``."""
+        if not self._resident:
+            raise ValueError("TokenBank.prepare_mse_mean: the bank must be made by TokenBank.resident")
+        if self._mse_mean is None:
+            self._mse_mean = ops.token_mse_mean_pool(self.bank)
+        return self
+
+    def stage1_mse_mean(self, c):
+        """(pooled, tail, rowp) of the two-stage weighted-MSE route under combine 'mean' and the distance weights ``c`` [D]: the
+        pooled image and tail tile of ``prepare_mse_mean`` and the row constants of ``ops.token_mse_mean_rowp``, kept for the last
+        ``c`` seen as ``stage1_mse`` keeps its own (keyed by the vector itself)."""
+        if self._mse_mean is None:
+            raise ValueError("TokenBank.stage1_mse_mean: the bank was not asked (TokenBank.prepare_mse_mean)")
+        pooled, tail, aux = self._mse_mean
+        held = self._stage1_mse_mean
+        if held is None or not torch.equal(held[0], c):
+            held = self._stage1_mse_mean = (c.clone(), ops.token_mse_mean_rowp(self.bank, c, aux))
+        return pooled, tail, held[1]
 
     def set_weights(self, weights):
         self._version += 1
@@ -1040,6 +1068,16 @@ TOKEN_MSE_SELECT_TOPT_PREFILTER_MIN_Q = 32
 # 1.58x but bf16, whose bound is the wider one (unit roundoff 2^-8), loses (0.89x - 0.91x), and one constant serves both dtypes.
 # Smaller banks are NOT MEASURED: TOKEN_MSE_PREFILTER_MIN_Q_SMALL, as above
 TOKEN_MSE_PQ_PREFILTER_MIN_Q = 128
+# ... under combine 'mean', by opt-in (TokenBank.prepare_mse_mean): stage 1 walks a pooled image of N rows, not N P.
+# tools/bench_mse_mean.py measures it against the grouped route on two banks of the size above, [15625, 64, 768] and [250000, 4, 768]
+# (Q in 16 .. 1024, k = 100, both dtypes, query preparation, the first-threshold sample and the row-constants launch included, the
+# one-off pooling pass -- 0.8 - 1.1 ms -- apart); the constant is the smallest Q of its grid from which the route is at least 10 %
+# faster in both of two runs, on every bank and dtype (profiles/mse_mean_crossover.json and its repeat).
+# Measured: 64, decided by the P = 64 bank -- 1.94x - 2.02x there (1.01x - 1.05x at 32, 0.58x - 0.59x at 16), 5.2x - 5.5x at 256,
+# 4.6x - 4.9x at 1024; the P = 4 bank wins from the grid's smallest point (2.5x at 16, 6.5x at 64, 12.6x - 12.9x at 1024): a call costs
+# about 2 ms there against about 9.5 ms on the P = 64 bank, whose candidates cost 64 token rows each.  Smaller banks are NOT MEASURED:
+# TOKEN_MSE_PREFILTER_MIN_Q_SMALL, as above
+TOKEN_MSE_MEAN_PREFILTER_MIN_Q = 64
 
 
 def _token_mse_prefilter_refusal(rq: TokenRequest):
@@ -1054,14 +1092,15 @@ def _token_mse_prefilter_refusal(rq: TokenRequest):
     asked = isinstance(sel, Selection) and held is not None and tb in held
     why = token_mse_route_refusal(rq.Q, rq.N, rq.P, rq.D, rq.k, name, rq.combine, rq.top_t, sel is not None, rq.per_query,
                                   top_t_prepared=bool(getattr(tb, "_mse_top_t", False)), select_prepared=asked,
-                                  selected=sel.count if asked else None, per_query_prepared=getattr(tb, "_mse_pq", None) is not None)
+                                  selected=sel.count if asked else None, per_query_prepared=getattr(tb, "_mse_pq", None) is not None,
+                                  mean_prepared=getattr(tb, "_mse_mean", None) is not None)
     if why == "select under a distance metric" and isinstance(sel, Selection):
         why += " without the masked row constants of this bank (opt in once per Selection and bank: Selection.prepare_mse)"
     return why
 
 
 def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=False, per_query=False, *, top_t_prepared=False,
-                            select_prepared=False, selected=None, per_query_prepared=False):
+                            select_prepared=False, selected=None, per_query_prepared=False, mean_prepared=False):
     """The same decision from the request's plain facts, for a caller that has not wrapped its bank yet (``similarity_search.py``
     builds a ``TokenBank.resident`` -- a norm pass over the bank -- only when this returns None): ``metric`` a name, ``combine`` a
     name or an ``ops.COMBINE_CODES`` code, ``top_t`` None / 0 for all tokens, ``select`` whether there is a selection.  The bank is
@@ -1075,12 +1114,33 @@ def token_mse_route_refusal(Q, N, P, D, k, metric, combine, top_t=0, select=Fals
     ``per_query_prepared`` (keyword only; False: the answers as they ever were): the caller will opt in by
     ``TokenBank.prepare_mse_per_query``, and a request with per-query weights is then decided by that route's rule -- no ``top_t`` and
     no ``select`` (with either the answer stays "per-query weights"), D % 32 == 0 and 128 <= D <= 2048 (stage 1 multiplies rows of
-    2 D), and ``TOKEN_MSE_PQ_PREFILTER_MIN_Q`` as the smallest Q."""
+    2 D), and ``TOKEN_MSE_PQ_PREFILTER_MIN_Q`` as the smallest Q.
+
+    ``mean_prepared`` (keyword only; False: the answers as they ever were): the caller will opt in by
+    ``TokenBank.prepare_mse_mean``, and ``combine='mean'`` is then decided by that route's rule -- no ``top_t``, no ``select`` and no
+    per-query weights (with any of them the answer stays "combine 'mean' under a distance metric"), P a divisor of 64, the switch on,
+    the library's shape rule with N >= 2048 IMAGES (stage 1 walks the pooled image), and ``TOKEN_MSE_MEAN_PREFILTER_MIN_Q`` as the
+    smallest Q."""
     combine = ops.COMBINE_CODES.get(combine, combine)
     if metric != 'MSE':
         return f"metric {metric} (a distance that is no dot product)"
     if combine == ops.COMBINE_CODES['mean']:
-        return "combine 'mean' under a distance metric"
+        if not mean_prepared or top_t or select or per_query:
+            return "combine 'mean' under a distance metric"
+        if P < 1 or 64 % P:
+            return f"P = {P} does not divide 64"
+        if not _prefilter_enabled():
+            return "SKYEMB_TOPK_PREFILTER=0"
+        why = ops.token_mse_mean_prefilter_refusal(Q, N, P, D, k)         # the library's shape rule first, then the smallest Q
+        if why is not None:
+            return why
+        if N * P * D >= TOKEN_MSE_PREFILTER_MIN_ELEMENTS:
+            if Q < TOKEN_MSE_MEAN_PREFILTER_MIN_Q:
+                return f"Q = {Q} < TOKEN_MSE_MEAN_PREFILTER_MIN_Q = {TOKEN_MSE_MEAN_PREFILTER_MIN_Q}"
+        elif Q < TOKEN_MSE_PREFILTER_MIN_Q_SMALL:
+            return (f"Q = {Q} < TOKEN_MSE_PREFILTER_MIN_Q_SMALL = {TOKEN_MSE_PREFILTER_MIN_Q_SMALL} (a bank of fewer than "
+                    f"TOKEN_MSE_PREFILTER_MIN_ELEMENTS = {TOKEN_MSE_PREFILTER_MIN_ELEMENTS} elements)")
+        return None
     if top_t and not top_t_prepared:
         return "top_t under a distance metric"
     if select and not select_prepared:
@@ -1416,11 +1476,17 @@ def _topk_tokens_mse_prefiltered(rq: TokenRequest, queries, prune, stats, proces
     every slice; flagged queries go through the grouped route, those queries only.  Everything runs in key space (key = -distance)
     until the result is negated on the way out.  Under ``top_t`` the sample is scored under it; under a selection the sample is of
     SELECTED images, stage 1 walks the live tiles of ``Selection.mse_prefilter`` and its first slice ends where ``cum`` says the
-    cosine driver's would (``_topk_tokens_prefiltered``); the re-run keeps both."""
+    cosine driver's would (``_topk_tokens_prefiltered``); the re-run keeps both.  Under ``combine='mean'`` (a bank asked by
+    ``TokenBank.prepare_mse_mean``; "Weighted MSE under combine 'mean'" there) stage 1 walks the pooled image of
+    ``TokenBank.stage1_mse_mean``; the sample is scored under 'mean' and the re-run keeps it."""
     tb, Q, k, dev, sel = rq.bank, rq.Q, rq.k, rq.tokens.device, rq.select
     q = queries.to(dev, torch.float32).contiguous()
     c = prepare_distance_weights(rq.weights, rq.D, dev)
-    tail, rowp = tb.stage1_mse(c)
+    mean = rq.combine == ops.COMBINE_CODES['mean']         # (no top_t and no selection reach here with it: token_mse_route_refusal)
+    if mean:
+        pooled, tail, rowp = tb.stage1_mse_mean(c)
+    else:
+        tail, rowp = tb.stage1_mse(c)
     # (a selection that reaches this driver holds at least 2048 token rows -- the route's shape rule on the selected images alone --,
     # and 7 whole 256-row tiles and a tail tile hold 2047 at most: it has SELECT_MIN_LIVE_TILES live whole tiles, nothing to check)
     prepared = None if sel is None else sel.mse_prefilter(tb, c)
@@ -1436,6 +1502,8 @@ def _topk_tokens_mse_prefiltered(rq: TokenRequest, queries, prune, stats, proces
         ops.kth_largest_floor(keys[:g].neg_(), k, thr0[lo:lo + g])
 
     def launch(*out):                                      # ``top_t`` follows ``combine`` in the calls that take it
+        if mean:
+            return ops.distance_topk_tokens_mean_prefiltered(c, q, tb.bank, pooled, tail, rowp, k, rq.idx_offset, *out, thr0)
         if sel is None and rq.top_t == 0:
             return ops.distance_topk_tokens_prefiltered(c, q, tb.bank, tail, rowp, k, rq.combine, rq.idx_offset, *out, thr0)
         if sel is None:
@@ -1547,9 +1615,19 @@ def distance_topk_tokens(queries: torch.Tensor, bank, k: int, metric: str = 'MAE
     divisor of 64, D % 32 == 0 and 128 <= D <= 2048, the shape rule above on (N, P, 2 D, k), at least
     ``TOKEN_MSE_PQ_PREFILTER_MIN_Q`` queries (smaller banks: ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``); ``stats`` gains
     ``per_query_weights``.  A negative, NaN or above-2^10 weight sends back only the queries whose own row holds it; a query with
-    c_q o t_q = 0 is re-run as well.  Out of scope for the two-stage route, served by the grouped route as ever: metric 'MAE' (no dot
-    product), ``combine`` 'mean', per-query weights over a bank never asked or together with ``top_t`` or ``select``, fp32 banks, P
-    not dividing 64, a bool-tensor ``select``.  (Cosine with per-query weights, ``cosine_topk_tokens``, stays on the grouped route as
+    c_q o t_q = 0 is re-run as well.  ``combine`` 'mean' takes the route BY OPT-IN as well:
+    ``TokenBank.resident(bank).prepare_mse_mean()`` builds a pooled 16-bit image [N, D] of the bank -- each image's tokens summed in
+    fp32 in token order, scaled exactly by 1 / P and by the image's own power of two, rounded once (2 N D + 8 N bytes, one pass,
+    independent of the weights and kept across ``set_weights``) --; D mean_p dist = A_q + Bbar_i - 2 (c o t) . m_i is exactly linear
+    in the tokens, so stage 1 walks N rows instead of N P (its row constants: ``TokenBank.stage1_mse_mean``, one more pass per bank
+    and weight vector) and stage 2 re-scores every candidate image's tokens and folds them in token order -- bit for bit the grouped
+    route.  Its rule: metric 'MSE', 'mean', shared weights, no ``top_t`` and no ``select`` (with either the request keeps the grouped
+    route), P a divisor of 64, D % 32 == 0, 128 <= D <= 4096, N >= 2048 images, k <= 256, at least
+    ``TOKEN_MSE_MEAN_PREFILTER_MIN_Q`` queries (smaller banks: ``TOKEN_MSE_PREFILTER_MIN_Q_SMALL``); the first threshold comes from
+    the same sample scored under 'mean', a re-run keeps it.  Out of scope for the two-stage route, served by the grouped route as
+    ever: metric 'MAE' (no dot product), ``combine`` 'mean' over a bank never asked or together with ``top_t``, ``select`` or
+    per-query weights, per-query weights over a bank never asked or together with ``top_t`` or ``select``, fp32 banks, P not dividing
+    64, a bool-tensor ``select``.  (Cosine with per-query weights, ``cosine_topk_tokens``, stays on the grouped route as
     well: its row norm sum w_qd x_d^2 sits under a square root in the denominator, so stage 1's candidate test is no longer one
     linear instruction.)
 
